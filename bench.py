@@ -462,7 +462,33 @@ def parse_args(argv=None):
     ap.add_argument("--no-val-acc", action="store_true",
                     help="skip the short val-acc parity run (scripts/val_acc_parity.py: the same batches trained on the "
                          "device and on the oracle's torch-CPU twin, val_acc next to val_acc_cpu); N=1 only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the model's parameters, BN moving "
+                         "statistics, gradients and RMSprop slots, and the metric rows of the timed steps) as DIR/<name>.npy, "
+                         "float32, so that two builds can be compared output for output (rank 0 only)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, net, metrics_rows, write=True):
+    """The arrays a caller of the timed path receives after its last step: the updated parameters and BN moving statistics,
+    the gradients and optimizer slots that produced the update, and the metric row (loss sum, correct count, ...) of every
+    timed step.  Copied to the host outside the timed region; returns the names written.  Every rank calls it (write=False
+    off rank 0), so that an output over the size limit ends all ranks at the same point, before the next collective."""
+    arrays = [("params", net.params), ("bn_state", net.state), ("grads", net.grads), ("rmsprop_slots", net.slots),
+              ("metrics_per_step", metrics_rows)]
+    total = sum(4 * t.numel() for _, t in arrays)                    # written as float32
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    if not write:
+        return None
+    arrays = [(name, t.detach().float().cpu().numpy()) for name, t in arrays]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return [name for name, _ in arrays]
 
 
 def visible_gpu_count():
@@ -678,8 +704,11 @@ def launch_ranks(args, json_out):
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"),
                KWS_BENCH_CHILD="1")
+    argv = sys.argv[1:]
+    if args.dump_outputs:    # the ranks run in ROOT: a relative DIR is the caller's (argparse keeps the last occurrence)
+        argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv
     child = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, cwd=ROOT)
     out_b, _ = child.communicate()
     lines = [l for l in out_b.decode().splitlines() if l.lstrip().startswith("{")]
@@ -828,6 +857,9 @@ def main():
     dt, dt_own = timed_steps(args.warmup, args.steps)
     clips = B * world * args.steps
     ms = ring[args.warmup:args.warmup + args.steps].cpu().numpy()
+    dumped = None
+    if args.dump_outputs:                   # before the profiled and A/B steps below train the model further
+        dumped = dump_outputs(args.dump_outputs, model.net, ring[args.warmup:args.warmup + args.steps], write=(rank == 0))
     # every rank's own wall time per step (a straggler shows here) and the seed its sampler drew from (ranks must not train on
     # the same clips)
     per_rank_ms = gather_per_rank(dist, 1e3 * dt_own / args.steps, world, device)
@@ -1225,6 +1257,7 @@ def main():
             "configs": configs,
             "kernels": prof,
             "skipped_legs": skipped,
+            "dumped_outputs": dumped,
         }
     if dist:
         dist.barrier()

@@ -192,3 +192,37 @@ def test_bench_single_gpu_line_carries_the_round4_keys():
     assert err["clips"] == 16
     assert err["log_mel"]["max_abs_err_vs_f64"] < 1e-3 and err["mfcc"]["max_abs_err_vs_f64"] < 2e-3     # the test-suite bars
     assert err["spectrogram"]["max_abs_err_vs_f64"] < 2e-5 * max(1.0, err["spectrogram"]["max_abs_value"])
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR (relative: the caller's directory) writes the state right after the timed steps: the profiled steps that
+    follow do not reach it, one more timed step does, its metric rows are the timed steps' own (the line's train_loss_first_last),
+    and under bench.py's own rank launcher the relative DIR still lands in the caller's directory."""
+    import numpy as np
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KWS_BENCH_ONE_DEVICE"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "2", "--bank", "8192", "--batch", "256", "--no-cpu-baseline",
+            "--no-ab", "--no-configs", "--no-val-acc"]
+
+    def run(name, steps, profile_steps, extra=(), run_env=env):
+        cmd = base + ["--steps", str(steps), "--profile-steps", str(profile_steps), "--dump-outputs", name] + list(extra)
+        res = subprocess.run(cmd, cwd=str(tmp_path), env=run_env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
+        assert res.returncode == 0, res.stderr.decode()[-2000:]
+        out = json.loads([l for l in res.stdout.decode().splitlines() if l.strip()][-1])
+        names = out["dumped_outputs"]
+        assert names == ["params", "bn_state", "grads", "rmsprop_slots", "metrics_per_step"]
+        return out, {n: np.load(str(tmp_path / name / (n + ".npy"))) for n in names}
+
+    out_a, a = run("a", 3, 0)
+    _, b = run("b", 3, 2)                                  # two profiled steps train the model further after the dump
+    _, c = run("c", 4, 0)                                  # one more timed step
+    for n in ("params", "bn_state", "grads", "rmsprop_slots", "metrics_per_step"):
+        assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
+    assert a["metrics_per_step"].shape == (3, 4) and c["metrics_per_step"].shape == (4, 4)
+    assert np.array_equal(c["metrics_per_step"][:3], a["metrics_per_step"])
+    assert not np.array_equal(a["params"], c["params"])
+    first, last = out_a["train_loss_first_last"]
+    assert np.isclose(a["metrics_per_step"][0, 0] / 256, first) and np.isclose(a["metrics_per_step"][-1, 0] / 256, last)
+    _, d = run("d", 3, 0, ["--gpus", "2"], dict(env, KWS_BENCH_ONE_DEVICE="1"))
+    assert d["metrics_per_step"].shape == (3, 4) and d["params"].shape == a["params"].shape

@@ -21,6 +21,12 @@ def _free_port():
     return p
 
 
+def _cpu_barrier():
+    """dist.barrier() first asks torch for the machine's accelerator, which opens the GPU on a box that has one (eight CPU ranks
+    would then hold it at once); an all-reduce of a CPU tensor waits for every rank the same way without touching it."""
+    torch.distributed.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, out_dir):
     os.environ.update(WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
@@ -55,7 +61,7 @@ def _worker(rank, world, port, out_dir):
     np.save(os.path.join(out_dir, "r%d.npy" % rank),
             np.stack([local.numpy(), flat.numpy(), new_p]))
     np.save(os.path.join(out_dir, "seed%d.npy" % rank), np.array([parallel.rank_seed(1234), lo, hi]))
-    torch.distributed.barrier()
+    _cpu_barrier()
     torch.distributed.destroy_process_group()
 
 
@@ -99,7 +105,7 @@ def _worker8(rank, world, port, out_dir):
     per_rank = bench.gather_per_rank(dist, 4.0 + 0.25 * rank, world, torch.device("cpu"))     # bench.py's per_rank_ms
     seeds = bench.gather_per_rank(dist, float(parallel.rank_seed(1234)), world, torch.device("cpu"))
     np.save(os.path.join(out_dir, "w8_r%d.npy" % rank), np.array([lo, hi, t_lo, t_hi] + per_rank + seeds))
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
