@@ -276,6 +276,37 @@ int kws_gemm_tn_gather_f32(const float* X, const kws_gather_t* g, const float* G
 int kws_transpose_f32(const float* in, float* out, int rows, int cols, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouped Conv1D (VALID, no bias) on f32 MFMA: the g Keras Conv1D layers of the reference's _grouped_reduce_conv /
+ * _grouped_context_conv (model.py:651-693, 1258-1300), each reading the slice x[:, :, q*gs : (q+1)*gs] of one input and
+ * concatenated in group order.  Input X [B, L, C]; output [B, Lout, F = g*Ng], group q at columns q*Ng.  Kernel of group q:
+ * [k, gs, Ng] (Keras layout) at W + q * w_group_stride (0 = k*gs*Ng: the groups back to back).  Channels >= g*gs are never
+ * read.  One launch covers all groups; results are bit-identical from run to run (no atomics).
+ *   fwd    Y[b,t,q*Ng+n] = sum_{j,c} act(X[b, stride*t + j, q*gs + c]) * W_q[j,c,n]; act = relu6(scale*x + shift) of the
+ *          producer's BatchNorm tables bn [C / bn_group][4][bn_group] (scale|shift|mean|rstd per BN layer of bn_group
+ *          channels), or identity when bn is NULL.  stats_part (may be NULL): [kws_gconv_stats_rows][2][F] column sums
+ *          (sum y, sum y^2) per 128-row tile for kws_bn_stats_finalize-style folding.
+ *   dgrad  dX[b,tau,q*gs+c] = sum over s*t + j = tau of sum_n dY[b,t,q*Ng+n] * W_q[j,c,n]: the gradient wrt the INPUT of
+ *          the convolution (wrt act(X) when the forward applied a table).  Every element of dX is written: rows no
+ *          window covers and channels >= g*gs are exact zeros.
+ *   wgrad  dW_q[j,c,n] = sum_{b,t} act(X[b, stride*t+j, q*gs+c]) * dY[b,t,q*Ng+n], written at dW + q * w_group_stride;
+ *          workspace >= kws_gconv_wgrad_workspace_floats floats (fixed-order split over B*Lout).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, L, C;     /* input [B, L, C] */
+  int Lout;        /* output rows per clip: stride*(Lout-1) + k <= L */
+  int k, stride;   /* taps, time stride */
+  int g, gs, Ng;   /* groups, input channels per group, filters per group */
+  int64_t w_group_stride;
+} kws_gconv_t;
+int kws_gconv_stats_rows(const kws_gconv_t* d);
+int kws_gconv_fwd_f32(const float* X, const float* bn, int bn_group, const float* W, float* Y, float* stats_part,
+                      const kws_gconv_t* d, void* stream);
+int kws_gconv_dgrad_f32(const float* dY, const float* W, float* dX, const kws_gconv_t* d, void* stream);
+int64_t kws_gconv_wgrad_workspace_floats(const kws_gconv_t* d);
+int kws_gconv_wgrad_f32(const float* X, const float* bn, int bn_group, const float* dY, float* dW, float* workspace,
+                        const kws_gconv_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -347,6 +378,12 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *   KWS_NET_RESIDUAL:     conv_1d_residual_model, reference model.py:841-908 (raw input; filter_mult honoured)
  *   KWS_NET_MFCC_AND_RAW: conv_1d_mfcc_and_raw_model, reference model.py:1563-1660; the two Keras inputs arrive as ONE
  *                         row [mfcc spectrogram_length*num_features | raw samples], input_size = the row length
+ *   KWS_NET_CONV_1D_FAST: conv_1d_fast_model, reference model.py:642-713 (raw input; Keras model name 'conv_1d_learned_spec')
+ *   KWS_NET_CONV_1D_SPEC: conv_1d_spec_model, reference model.py:1249-1323 (input: the 'spec' output, fixed [98 * 257];
+ *                         input_size is ignored).  Both: grouped Conv1D blocks (kws_gconv_*), each group its own Conv1D and
+ *                         BatchNormalization layer; kws_net_debug_view what 0 = pre-BN output of conv layer `index` (0 = the
+ *                         first, per grouped BLOCK: the groups concatenated [B, Lout, F]), what 2 = the table [4][Ng] of
+ *                         batch_normalization_{index+1}.
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -356,6 +393,8 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_STEFFE 3
 #define KWS_NET_RESIDUAL 4
 #define KWS_NET_MFCC_AND_RAW 5
+#define KWS_NET_CONV_1D_FAST 6
+#define KWS_NET_CONV_1D_SPEC 7
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

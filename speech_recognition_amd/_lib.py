@@ -17,6 +17,8 @@ KWS_NET_LOG_MFCC = 2
 KWS_NET_STEFFE = 3
 KWS_NET_RESIDUAL = 4
 KWS_NET_MFCC_AND_RAW = 5
+KWS_NET_CONV_1D_FAST = 6
+KWS_NET_CONV_1D_SPEC = 7
 
 
 class KwsError(RuntimeError):
@@ -27,6 +29,13 @@ class GatherDesc(ctypes.Structure):
     _fields_ = [("L_out", ctypes.c_int), ("cin", ctypes.c_int), ("taps", ctypes.c_int),
                 ("stride_t", ctypes.c_int), ("stride_j", ctypes.c_int), ("base_off", ctypes.c_int),
                 ("x_len", ctypes.c_int), ("x_batch_stride", ctypes.c_int64)]
+
+
+class GconvDesc(ctypes.Structure):
+    """kws_gconv_t: grouped Conv1D over [B, L, C] -> [B, Lout, g * Ng]."""
+    _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("C", ctypes.c_int), ("Lout", ctypes.c_int),
+                ("k", ctypes.c_int), ("stride", ctypes.c_int), ("g", ctypes.c_int), ("gs", ctypes.c_int),
+                ("Ng", ctypes.c_int), ("w_group_stride", ctypes.c_int64)]
 
 
 class SamplerSet(ctypes.Structure):
@@ -124,6 +133,11 @@ SIGNATURES = {
     "kws_gemm_tn_workspace_floats": (_I64, [_I64, _I, _I]),
     "kws_gemm_tn_f32": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
     "kws_gemm_tn_gather_f32": (_I, [_P, ctypes.POINTER(GatherDesc), _P, _P, _I, _I, _P, _P]),
+    "kws_gconv_stats_rows": (_I, [ctypes.POINTER(GconvDesc)]),
+    "kws_gconv_fwd_f32": (_I, [_P, _P, _I, _P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
+    "kws_gconv_dgrad_f32": (_I, [_P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
+    "kws_gconv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(GconvDesc)]),
+    "kws_gconv_wgrad_f32": (_I, [_P, _P, _I, _P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
     "kws_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
     "kws_bn_stats_finalize": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "kws_bn_infer_prepare": (_I, [_P, _P, _P, _P, _F, _I, _P, _P]),

@@ -85,6 +85,34 @@ struct SlabBatch {
 };
 extern "C" int kws_slab_batch_fill(SlabBatch* b, const float* const* ws, float* const* out, const int64_t* n, const int* S, int count,
                                    int* blocks_out, double* bytes_out);
+// gconv.hip: grouped BatchNorm bookkeeping of the grouped-Conv1D programs (net_grouped.hip).  Each group's BN is its own Keras
+// layer: gamma of group q at gamma + q * pstride, beta at + boff; moving mean at mm + q * sstride, moving variance at + voff;
+// its table scale|shift|mean|rstd is bn + q * 4 * Ng.
+struct kws_gbn_refs {
+  const float* gamma;
+  int64_t pstride, boff;
+  float* mm;
+  int64_t sstride, voff;
+  int g, Ng;
+};
+// stats rows [rows][2][g*Ng] -> tables + moving statistics (r->mm NULL: no update)
+int kws_gbn_finalize(const float* part, int rows, int64_t count, const kws_gbn_refs* r, float eps, float momentum, float* bn,
+                     hipStream_t st);
+int kws_gbn_infer(const kws_gbn_refs* r, float eps, float* bn, hipStream_t st);
+// backward of relu6 o BN over [M, g*Ng], in place on dA (-> dy); part: kws_gbn_bwd_rows(M) * 2 * F floats, coef 2 * F floats;
+// dgamma / dbeta land at dgamma0 + q * pstride (+ boff)
+int kws_gbn_bwd_rows(int64_t M);
+int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, int Ng, float* part, float* coef, float* dgamma0,
+                int64_t pstride, int64_t boff, hipStream_t st);
+// Flatten -> Dropout -> Dense(bias) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F
+struct kws_flat_tail_args {
+  const float* y; const float* bn; int Ng;
+  const float* Wd; const float* bd; const float* labels;
+  float* probs; float* fd; float* dl; float* dA; float* per_loss; float* per_correct;
+  int B, D, F, NC;
+  uint64_t seed; uint32_t step; float keep_prob; int loss_batch; int64_t row_offset;
+};
+int kws_flat_tail_launch(const kws_flat_tail_args* a, int training, hipStream_t st);
 #ifdef __HIPCC__
 __device__ __forceinline__ void kws_add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 __device__ __forceinline__ void kws_reduce_slabs_batch_body(const SlabBatch& b, int bid, float4 (*red)[64]) {

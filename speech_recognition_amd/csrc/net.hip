@@ -287,12 +287,15 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     rc = residual_build(n);
   } else if (cfg->kind == KWS_NET_MFCC_AND_RAW) {
     rc = mfcc_raw_build(n);
+  } else if (cfg->kind == KWS_NET_CONV_1D_FAST || cfg->kind == KWS_NET_CONV_1D_SPEC) {
+    rc = gc_build(n);
   } else {
     kws_set_error("net_create: kind %d not supported", cfg->kind);
     rc = KWS_E_INVALID;
   }
   if (rc != KWS_OK) {
     lm_free(n);
+    gc_free(n);
     delete n;
     return rc;
   }
@@ -303,6 +306,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
 int kws_net_destroy(kws_net_t* net) {
   if (net) {
     lm_free(net);
+    gc_free(net);
   }
   delete net;
   return KWS_OK;
@@ -320,6 +324,7 @@ int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) 
 
 int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
   if (!net || max_batch <= 0) return 0;
+  if (net->gc) return gc_workspace_bytes(net, max_batch, training);
   if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
        net->cfg.kind == KWS_NET_MFCC_AND_RAW)) return lm_workspace_bytes(net, max_batch, training);
   Layout lo;
@@ -330,6 +335,7 @@ int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int trainin
 int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, int index, int64_t* offset_floats,
                        int64_t* count) {
   KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
+  if (net->gc) return gc_debug_view(net, batch, training, what, index, offset_floats, count);
   if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
        net->cfg.kind == KWS_NET_MFCC_AND_RAW)) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
   Layout lo;
@@ -362,6 +368,7 @@ int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, 
 int kws_net_predict(const kws_net_t* net, const float* params, const float* state, const float* x, int B,
                     float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
   KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
+  if (net->gc) return gc_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
        net->cfg.kind == KWS_NET_MFCC_AND_RAW))
     return lm_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
@@ -679,6 +686,9 @@ int kws_net_train_fwd_bwd(const kws_net_t* net, const float* params, float* stat
   KWS_REQUIRE(net && params && state && x && y_onehot && grads && probs && metrics && workspace && B > 0,
               "net_train_fwd_bwd: bad arguments");
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd: loss_batch %d < B %d", loss_batch, B);
+  if (net->gc)
+    return gc_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
+                    workspace_bytes, (hipStream_t)stream);
   if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
        net->cfg.kind == KWS_NET_MFCC_AND_RAW))
     return lm_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch,

@@ -1,0 +1,324 @@
+// Network programs of the two grouped-Conv1D models:
+//   KWS_NET_CONV_1D_FAST  conv_1d_fast_model (reference model.py:642-713): raw waveform -> Conv1D(252, 479, strides=160, VALID,
+//                         no bias, l2 1e-4) with no BN and no activation -> grouped reduce blocks (300, k15, g6 on 252 channels),
+//                         (360, k7, g5 on 300) -> Flatten -> Dropout(.3) -> Dense + softmax; RMSprop(3e-3), categorical CE
+//   KWS_NET_CONV_1D_SPEC  conv_1d_spec_model (model.py:1249-1323): the 'spec' output [98, 257] -> four reduce / context pairs,
+//                         k 3, reduce g 4 stride 2, context g 3 -> Flatten -> Dropout(.3) -> Dense + softmax; RMSprop(2e-3)
+// A grouped block is g Keras Conv1D layers over the slices x[:, :, q*gs : (q+1)*gs] (gs from the block's num_channels
+// argument: channels past g*gs are never read), each followed by its own BatchNormalization and relu6, concatenated.
+// On the device a block is one kws_gconv_fwd_f32 launch (BN partial sums in its epilogue) and one grouped BN finalise; the
+// normalise + ReLU6 is applied on load by the next block (or the tail), the project's convention.  The 479-tap front
+// convolution is the gathered GEMM on ONE tap of 480 samples against a kernel padded with a zero row (as steffeNet pads 75
+// to 76).
+#include "net_internal.h"
+
+struct GcBlock {
+  kws_gconv_t d;            // B filled in per call
+  int F;
+  int64_t w0;               // group 0's kernel (params); group q's at + q * pstride
+  int64_t gamma0, beta_off; // group 0's gamma (params); beta at gamma + beta_off
+  int64_t mm0, mv_off;      // group 0's moving mean (state); variance at mm + mv_off
+  int64_t pstride, sstride;
+  int bn_idx0;              // 0-based Keras index of group 0's BatchNormalization
+};
+
+struct GcProgram {
+  bool front = false;       // conv_1d_fast: the 479-tap front convolution
+  int L_in = 0, C_in = 0;   // the input seen as [L_in, C_in]
+  int64_t conv0 = 0;
+  int K0 = 0, K0p = 0, L0 = 0, C0 = 0;
+  kws_gather_t g0{};
+  std::vector<GcBlock> blocks;
+  int64_t dk = 0, db = 0;
+  int D = 0, NC = 0;
+  float keep = 0.7f;
+};
+
+void gc_free(kws_net* n) {
+  delete n->gc;
+  n->gc = nullptr;
+}
+
+namespace {
+
+constexpr float GC_DROP_KEEP = 0.7f;      // Dropout(0.3), model.py:710 / 1318
+constexpr float GC_FRONT_L2 = 1e-4f;      // kernel_regularizer=l2(0.0001), model.py:700
+
+int add_block(kws_net* n, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride, int* conv_idx,
+              int* bn_idx) {
+  KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C, "net: grouped block F=%d g=%d num_channels=%d C=%d", F, g,
+              num_channels, C);
+  GcBlock b;
+  memset(&b, 0, sizeof(b));
+  b.d.L = L; b.d.C = C; b.d.k = k; b.d.stride = stride; b.d.g = g; b.d.gs = num_channels / g; b.d.Ng = F / g;
+  KWS_REQUIRE(L >= k, "net: grouped block input length %d < %d taps", L, k);
+  b.d.Lout = (L - k) / stride + 1;
+  b.F = F;
+  b.bn_idx0 = *bn_idx;
+  const int gs = b.d.gs, Ng = b.d.Ng;
+  int64_t prev_w = 0, prev_m = 0;
+  for (int q = 0; q < g; ++q) {
+    const int64_t w = kws_net_add_tensor(n, "conv1d_" + std::to_string((*conv_idx)++) + "/kernel", {k, gs, Ng}, false, 0.f, k * gs,
+                                         k * Ng, 0.f);
+    const BnRef r = kws_net_add_bn(n, ++(*bn_idx), Ng);
+    if (q == 0) {
+      b.w0 = w; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
+    } else {
+      // every group has the same tensors in the same order: one stride per buffer
+      if (q == 1) {
+        b.pstride = w - prev_w;
+        b.sstride = r.mm - prev_m;
+      }
+      KWS_REQUIRE(w - prev_w == b.pstride && r.mm - prev_m == b.sstride && r.gamma - w == b.gamma0 - b.w0,
+                  "net: grouped block layout is not uniform");
+    }
+    prev_w = w;
+    prev_m = r.mm;
+  }
+  if (g == 1) {
+    b.pstride = (int64_t)k * gs * Ng;
+    b.sstride = 0;
+  }
+  b.d.w_group_stride = b.pstride;
+  p->blocks.push_back(b);
+  return KWS_OK;
+}
+
+struct GcLayout {
+  int64_t total = 0;
+  int64_t w0p = 0, y0 = 0;
+  std::vector<int64_t> y, bn;
+  int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, tnws = 0, dw0p = 0;
+  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+};
+
+void gc_layout(const kws_net* n, int B, bool training, GcLayout* lo) {
+  const GcProgram& p = *n->gc;
+  Bump bp;
+  const int nb = (int)p.blocks.size();
+  int64_t max_act = 64, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64;
+  if (p.front) {
+    lo->w0p = bp.take((int64_t)p.K0p * p.C0);
+    lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
+    max_act = std::max(max_act, (int64_t)B * p.L0 * p.C0);
+  }
+  lo->y.assign(nb, 0);
+  lo->bn.assign(nb, 0);
+  for (int i = 0; i < nb; ++i) {
+    kws_gconv_t d = p.blocks[i].d;
+    d.B = B;
+    const int64_t M = (int64_t)B * d.Lout;
+    lo->y[i] = bp.take(M * p.blocks[i].F);
+    lo->bn[i] = bp.take((int64_t)4 * p.blocks[i].F);
+    max_act = std::max(max_act, std::max(M * p.blocks[i].F, (int64_t)B * d.L * d.C));
+    max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&d) * 2 * p.blocks[i].F);
+    max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * p.blocks[i].F);
+    max_coef = std::max(max_coef, (int64_t)2 * p.blocks[i].F);
+    max_wws = std::max(max_wws, kws_gconv_wgrad_workspace_floats(&d));
+  }
+  lo->stats = bp.take(max_stats);
+  if (training) {
+    lo->dA[0] = bp.take(max_act);
+    lo->dA[1] = bp.take(max_act);
+    lo->part = bp.take(max_part);
+    lo->coef = bp.take(max_coef);
+    lo->wws = bp.take(max_wws);
+    if (p.front) {
+      lo->tnws = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * p.L0, p.K0p, p.C0));
+      lo->dw0p = bp.take((int64_t)p.K0p * p.C0);
+    }
+    lo->fd = bp.take((int64_t)B * p.D);
+    lo->dl = bp.take((int64_t)B * p.NC);
+    lo->per_loss = bp.take(B);
+    lo->per_correct = bp.take(B);
+    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.D * p.NC);
+  }
+  lo->total = bp.cur * 4;
+}
+
+kws_gbn_refs refs_of(const GcBlock& b, const float* params, float* state) {
+  kws_gbn_refs r;
+  r.gamma = params + b.gamma0; r.pstride = b.pstride; r.boff = b.beta_off;
+  r.mm = state ? state + b.mm0 : nullptr; r.sstride = b.sstride; r.voff = b.mv_off;
+  r.g = b.d.g; r.Ng = b.d.Ng;
+  return r;
+}
+
+// forward through the blocks; training: batch statistics (moving averages updated), else the moving statistics
+int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+               hipStream_t st) {
+  const GcProgram& p = *n->gc;
+  if (p.front) {
+    KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
+    KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
+    KWS_TRY(kws_gemm_gather_f32(x, &p.g0, ws + lo.w0p, ws + lo.y0, B, p.C0, nullptr, st));
+  }
+  for (size_t i = 0; i < p.blocks.size(); ++i) {
+    const GcBlock& b = p.blocks[i];
+    kws_gconv_t d = b.d;
+    d.B = B;
+    const float* in = i ? ws + lo.y[i - 1] : (p.front ? ws + lo.y0 : x);
+    const float* bn_in = i ? ws + lo.bn[i - 1] : nullptr;
+    const int bg = i ? p.blocks[i - 1].d.Ng : 0;
+    const kws_gbn_refs r = refs_of(b, params, state);
+    if (training) {
+      KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], ws + lo.stats, &d, st));
+      KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&d), (int64_t)B * d.Lout, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
+                               ws + lo.bn[i], st));
+    } else {
+      KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], nullptr, &d, st));
+      KWS_TRY(kws_gbn_infer(&r, KWS_BN_EPS, ws + lo.bn[i], st));
+    }
+  }
+  return KWS_OK;
+}
+
+kws_flat_tail_args tail_args(const kws_net* n, const GcLayout& lo, const float* params, float* ws, int B, float* probs) {
+  const GcProgram& p = *n->gc;
+  const GcBlock& last = p.blocks.back();
+  kws_flat_tail_args t;
+  memset(&t, 0, sizeof(t));
+  t.y = ws + lo.y.back(); t.bn = ws + lo.bn.back(); t.Ng = last.d.Ng;
+  t.Wd = params + p.dk; t.bd = params + p.db;
+  t.probs = probs;
+  t.B = B; t.D = p.D; t.F = last.F; t.NC = p.NC;
+  t.keep_prob = p.keep;
+  return t;
+}
+
+}  // namespace
+
+int gc_build(kws_net* n) {
+  const kws_net_config_t& c = n->cfg;
+  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
+  GcProgram* p = new GcProgram();
+  n->gc = p;
+  p->NC = c.num_classes;
+  p->keep = GC_DROP_KEEP;
+  int conv_idx = 1, bn_idx = 0;
+  if (c.kind == KWS_NET_CONV_1D_FAST) {
+    KWS_REQUIRE(c.input_size >= 479 && c.input_size % 2 == 0, "net: conv_1d_fast input_size %d (even, >= 479)", c.input_size);
+    p->front = true;
+    p->K0 = 479; p->K0p = 480; p->C0 = 252;
+    p->L0 = (c.input_size - p->K0) / 160 + 1;
+    p->conv0 = kws_net_add_tensor(n, "conv1d_" + std::to_string(conv_idx++) + "/kernel", {p->K0, 1, p->C0}, false, GC_FRONT_L2, p->K0,
+                                  p->K0 * p->C0, 0.f);
+    // ONE tap of 480 samples (the 480th weight is a zero row): window t starts at 160 t and ends at 160 t + 479 < input_size
+    p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
+    p->g0.x_len = c.input_size; p->g0.x_batch_stride = c.input_size;
+    p->L_in = c.input_size; p->C_in = 1;
+    KWS_TRY(add_block(n, p, p->L0, p->C0, 300, 15, 6, 252, 2, &conv_idx, &bn_idx));
+    const GcBlock& b1 = p->blocks.back();
+    KWS_TRY(add_block(n, p, b1.d.Lout, b1.F, 360, 7, 5, 300, 2, &conv_idx, &bn_idx));
+  } else {
+    p->L_in = 98; p->C_in = 257;   // Input(shape=[98 * 257]) -> Reshape([98, 257]); input_size is not consulted
+    struct { int F, g, nch, stride; } spec[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
+                                                 {420, 4, 360, 2}, {420, 3, 360, 1}, {480, 4, 420, 2}, {480, 3, 480, 1}};
+    int L = p->L_in, C = p->C_in;
+    for (int i = 0; i < 8; ++i) {
+      KWS_TRY(add_block(n, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride, &conv_idx, &bn_idx));
+      L = p->blocks.back().d.Lout;
+      C = p->blocks.back().F;
+    }
+  }
+  const GcBlock& last = p->blocks.back();
+  p->D = last.d.Lout * last.F;
+  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->D, p->NC}, false, 0.f, p->D, p->NC, 0.f);
+  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  return KWS_OK;
+}
+
+int64_t gc_workspace_bytes(const kws_net* n, int B, int training) {
+  GcLayout lo;
+  gc_layout(n, B, training != 0, &lo);
+  return lo.total;
+}
+
+int gc_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) {
+  const GcProgram& p = *n->gc;
+  GcLayout lo;
+  gc_layout(n, B, training != 0, &lo);
+  const int nb = (int)p.blocks.size();
+  if (what == 0) {   // pre-BN output of conv stage `index` (conv_1d_fast: 0 = the front convolution)
+    const int i = index - (p.front ? 1 : 0);
+    KWS_REQUIRE(index >= 0 && i < nb, "net_debug_view: y index %d", index);
+    if (i < 0) {
+      *offset_floats = lo.y0;
+      *count = (int64_t)B * p.L0 * p.C0;
+    } else {
+      *offset_floats = lo.y[i];
+      *count = (int64_t)B * p.blocks[i].d.Lout * p.blocks[i].F;
+    }
+  } else if (what == 2) {   // table of batch_normalization_{index+1}
+    for (int i = 0; i < nb; ++i) {
+      const GcBlock& b = p.blocks[i];
+      if (index >= b.bn_idx0 && index < b.bn_idx0 + b.d.g) {
+        *offset_floats = lo.bn[i] + (int64_t)(index - b.bn_idx0) * 4 * b.d.Ng;
+        *count = 4 * b.d.Ng;
+        return KWS_OK;
+      }
+    }
+    kws_set_error("net_debug_view: bn index %d", index);
+    return KWS_E_INVALID;
+  } else {
+    kws_set_error("net_debug_view: unknown view %d", what);
+    return KWS_E_INVALID;
+  }
+  return KWS_OK;
+}
+
+int gc_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
+               int64_t ws_bytes, hipStream_t st) {
+  GcLayout lo;
+  gc_layout(n, B, false, &lo);
+  if (lo.total > ws_bytes) {
+    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
+    return KWS_E_WORKSPACE;
+  }
+  KWS_TRY(gc_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, st));
+  kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
+  return kws_flat_tail_launch(&t, 0, st);
+}
+
+int gc_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
+             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
+             int64_t ws_bytes, hipStream_t st) {
+  const GcProgram& p = *n->gc;
+  GcLayout lo;
+  gc_layout(n, B, true, &lo);
+  if (lo.total > ws_bytes) {
+    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
+    return KWS_E_WORKSPACE;
+  }
+  KWS_TRY(gc_forward(n, lo, params, state, x, B, true, ws, st));
+  int cur = 0;
+  kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
+  t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = ws + lo.dA[cur];
+  t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct;
+  t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
+  KWS_TRY(kws_flat_tail_launch(&t, 1, st));
+  KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
+  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.D, p.NC, ws + lo.swg, st));
+  for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
+    const GcBlock& b = p.blocks[i];
+    kws_gconv_t d = b.d;
+    d.B = B;
+    const int64_t M = (int64_t)B * d.Lout;
+    float* dy = ws + lo.dA[cur];
+    KWS_TRY(kws_gbn_bwd(dy, ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part, ws + lo.coef, grads + b.gamma0, b.pstride,
+                        b.beta_off, st));
+    const float* in = i ? ws + lo.y[i - 1] : (p.front ? ws + lo.y0 : x);
+    const float* bn_in = i ? ws + lo.bn[i - 1] : nullptr;
+    const int bg = i ? p.blocks[i - 1].d.Ng : 0;
+    KWS_TRY(kws_gconv_wgrad_f32(in, bn_in, bg, dy, grads + b.w0, ws + lo.wws, &d, st));
+    if (i > 0 || p.front) {
+      KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.dA[cur ^ 1], &d, st));
+      cur ^= 1;
+    }
+  }
+  if (p.front) {   // dA[cur] = gradient wrt the front convolution's output (no BN, no activation in between)
+    KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, ws + lo.dA[cur], ws + lo.dw0p, B, p.C0, ws + lo.tnws, st));
+    KWS_HIP(hipMemcpyAsync(grads + p.conv0, ws + lo.dw0p, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
+  }
+  return KWS_OK;
+}

@@ -26,6 +26,7 @@ struct Block {
 };
 
 struct LmProgram;  // conv_1d_log_mfcc layer table (net_logmfcc.hip)
+struct GcProgram;  // conv_1d_fast / conv_1d_spec layer table (net_grouped.hip)
 
 struct kws_net {
   kws_net_config_t cfg;
@@ -44,6 +45,8 @@ struct kws_net {
   int K1f = 0;            // folded K
   // LOG_MFCC
   LmProgram* lm = nullptr;
+  // CONV_1D_FAST / CONV_1D_SPEC
+  GcProgram* gc = nullptr;
   // arithmetic of the pointwise GEMMs (kws_net_set_gemm_mode): 0 = f32 MFMA, 2 = fp16 x 2 split products (A/B arm)
   std::atomic<int> gemm_mode{0};
 };
@@ -75,6 +78,17 @@ int lm_predict(const kws_net* n, const float* params, const float* state, const 
 int lm_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B,
              float* grads, float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset,
              int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st);
+
+// ---- grouped-Conv1D programs (net_grouped.hip) ------------------------------------------------------------------------
+int gc_build(kws_net* n);
+void gc_free(kws_net* n);
+int64_t gc_workspace_bytes(const kws_net* n, int B, int training);
+int gc_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
+int gc_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
+               int64_t ws_bytes, hipStream_t st);
+int gc_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
+             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
+             int64_t ws_bytes, hipStream_t st);
 
 // ---- residual-block / log-mfcc tail launchers (resblock.hip) ------------------------------------------
 // o = maxpool_P(relu6(bn(y))) + (res_bn ? res_bn.scale*res + res_bn.shift : res)

@@ -6,7 +6,8 @@ from . import _lib
 from .keras_api import Model, RMSprop
 from .net import DeviceNet
 
-ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw')
+ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
+               'conv_1d_fast', 'conv_1d_spec')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -132,6 +133,23 @@ def conv_1d_mfcc_and_raw_model(input_size=16000, num_classes=11, *args, **kwargs
     return Model(net, RMSprop(lr=5e-4), name='conv_1d_mfcc_and_raw', loss='cce')
 
 
+def conv_1d_fast_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:642-713: raw waveform -> Conv1D(252, 479, strides=160, l2 1e-4; no BN, no activation) -> two
+    grouped reduce blocks (300 filters, k 15, 6 groups over 252 channels; 360, k 7, 5 groups over 300), each group its
+    own Conv1D + BatchNormalization + relu6 -> Flatten -> Dropout(.3) -> Dense; RMSprop(3e-3), categorical CE.  The
+    reference names the Keras model 'conv_1d_learned_spec'."""
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_FAST, num_classes, input_size=input_size)
+    return Model(net, RMSprop(lr=3e-3), name='conv_1d_learned_spec', loss='cce')
+
+
+def conv_1d_spec_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:1249-1323: the generator's 'spec' output as [98, 257] (the reference fixes Input(shape=[98 * 257])
+    and ignores input_size) -> four grouped reduce (k 3, stride 2, 4 groups) / context (k 3, 3 groups) pairs of 300 ... 480
+    filters -> Flatten -> Dropout(.3) -> Dense; RMSprop(2e-3), categorical CE."""
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_SPEC, num_classes, input_size=98 * 257)
+    return Model(net, RMSprop(lr=2e-3), name='conv_1d_spec', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -145,6 +163,10 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_residual_model(input_size, num_classes)
     if model_type == 'conv_1d_mfcc_and_raw':
         return conv_1d_mfcc_and_raw_model(input_size, num_classes, *args, **kwargs)
+    if model_type == 'conv_1d_fast':
+        return conv_1d_fast_model(input_size, num_classes)
+    if model_type == 'conv_1d_spec':
+        return conv_1d_spec_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"

@@ -1,0 +1,164 @@
+"""The grouped Conv1D primitive (kws_gconv_fwd_f32 / kws_gconv_dgrad_f32 / kws_gconv_wgrad_f32) against float64 NumPy at
+the ten grouped layer shapes of conv_1d_fast / conv_1d_spec and at edge cases (g = 1, k = 1, strides 1 / 2 / 3 > k, group
+widths that are no multiple of 4, channels no group reads, B = 1 and B = 1024).  Every output is a window of a guarded
+allocation (the method of test_guards_gpu.py); kernels with a gap between groups (w_group_stride > k*gs*Ng) must leave the
+gaps alone; two runs must agree bit for bit."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from grouped_oracle import gconv_bwd, gconv_fwd
+from speech_recognition_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 4096
+SENT = 0x7FC0DEAD
+
+# (B, L, C, k, stride, g, gs, Ng, bn_group or 0, gap)
+LAYERS = [
+    (4, 98, 252, 15, 2, 6, 42, 50, 0, 0),        # conv_1d_fast block 1 (its input is the un-normalised front convolution)
+    (4, 42, 300, 7, 2, 5, 60, 72, 50, 0),        # conv_1d_fast block 2
+    (4, 98, 257, 3, 2, 4, 63, 75, 0, 0),         # conv_1d_spec: 257 bins, 252 read
+    (4, 48, 300, 3, 1, 3, 100, 100, 75, 0),
+    (4, 46, 300, 3, 2, 4, 75, 90, 100, 0),
+    (4, 22, 360, 3, 1, 3, 120, 120, 90, 0),
+    (4, 20, 360, 3, 2, 4, 90, 105, 120, 0),
+    (4, 9, 420, 3, 1, 3, 120, 140, 105, 0),      # 420 channels, 360 read
+    (4, 7, 420, 3, 2, 4, 105, 120, 140, 0),
+    (4, 3, 480, 3, 1, 3, 160, 160, 120, 0),      # one output row
+]
+EDGES = [
+    (3, 20, 37, 5, 3, 1, 37, 13, 0, 0),          # g = 1, odd widths, stride 3
+    (2, 10, 9, 1, 1, 2, 4, 6, 3, 5),             # k = 1, one channel unread, gap between the groups' kernels
+    (2, 11, 7, 2, 3, 2, 3, 5, 7, 3),             # stride > k: phase 2 has no taps (exact zeros)
+    (1, 98, 257, 3, 2, 4, 63, 75, 257, 0),       # B = 1
+    (1024, 98, 257, 3, 2, 4, 63, 75, 0, 0),      # B = 1024
+    (5, 33, 130, 4, 2, 2, 65, 33, 65, 11),       # tiles past 64 columns on both sides, gaps
+]
+
+
+class Guarded(object):
+    def __init__(self, n):
+        self.buf = torch.empty(n + 2 * GUARD, dtype=torch.int32, device="cuda")
+        self.buf.fill_(SENT)
+        self.view = self.buf[GUARD:GUARD + n].view(torch.float32)
+
+    def check(self, what, holes=None):
+        torch.cuda.synchronize()
+        assert bool((self.buf[:GUARD] == SENT).all()) and bool((self.buf[-GUARD:] == SENT).all()), \
+            "%s wrote outside its output" % what
+        inner = self.view.view(torch.int32).cpu().numpy()
+        written = inner != SENT
+        if holes is None:
+            assert written.all(), "%s left output elements unwritten" % what
+        else:
+            assert (written == ~holes).all(), "%s wrote into a gap / left an element unwritten" % what
+
+
+def _desc(B, L, C, k, s, g, gs, Ng, gap):
+    Lout = (L - k) // s + 1
+    return _lib.GconvDesc(B, L, C, Lout, k, s, g, gs, Ng, (k * gs * Ng + gap) if gap else 0), Lout
+
+
+def _act(x, bn, bg):
+    if bn is None:
+        return x
+    t = bn.reshape(-1, 4, bg)
+    sc, sh = t[:, 0].reshape(-1), t[:, 1].reshape(-1)
+    return np.clip(x * sc + sh, 0, 6)
+
+
+def _run(d, X, bn, bg, W, dY, Bsz):
+    lib = _lib.load()
+    S = _lib.stream_ptr()
+    F = d.g * d.Ng
+    rows = lib.kws_gconv_stats_rows(ctypes.byref(d))
+    Y = Guarded(Bsz * d.Lout * F)
+    st = Guarded(rows * 2 * F)
+    dX = Guarded(Bsz * d.L * d.C)
+    ws_n = int(lib.kws_gconv_wgrad_workspace_floats(ctypes.byref(d)))
+    assert ws_n > 0
+    ws = torch.empty(ws_n, dtype=torch.float32, device="cuda")
+    stride = d.w_group_stride or d.k * d.gs * d.Ng
+    dW = Guarded(d.g * stride)
+    bnp = _lib.ptr(bn) if bn is not None else None
+    _lib.call("kws_gconv_fwd_f32", _lib.ptr(X), bnp, bg, _lib.ptr(W), _lib.ptr(Y.view), _lib.ptr(st.view), ctypes.byref(d), S)
+    _lib.call("kws_gconv_dgrad_f32", _lib.ptr(dY), _lib.ptr(W), _lib.ptr(dX.view), ctypes.byref(d), S)
+    _lib.call("kws_gconv_wgrad_f32", _lib.ptr(X), bnp, bg, _lib.ptr(dY), _lib.ptr(dW.view), _lib.ptr(ws), ctypes.byref(d), S)
+    torch.cuda.synchronize()
+    return Y, st, dX, dW, rows
+
+
+@pytest.mark.parametrize("case", LAYERS + EDGES)
+def test_grouped_conv_matches_float64(case):
+    B, L, C, k, s, g, gs, Ng, bg, gap = case
+    d, Lout = _desc(B, L, C, k, s, g, gs, Ng, gap)
+    F = g * Ng
+    rng = np.random.RandomState(L * 31 + C + k)
+    x = rng.randn(B, L, C).astype(np.float32)
+    stride = k * gs * Ng + gap
+    Wflat = np.zeros(g * stride, np.float32)
+    Ws = []
+    for q in range(g):
+        w = (rng.randn(k, gs, Ng) / np.sqrt(k * gs)).astype(np.float32)
+        Wflat[q * stride:q * stride + w.size] = w.reshape(-1)
+        Ws.append(w.astype(np.float64))
+    dy = rng.randn(B, Lout, F).astype(np.float32)
+    bn = None
+    if bg:
+        bn = np.zeros((C // bg, 4, bg), np.float32)
+        bn[:, 0] = 0.5 + rng.rand(C // bg, bg)
+        bn[:, 1] = 0.5 * rng.randn(C // bg, bg)
+        bn = bn.reshape(-1)
+    tX, tW, tdY = (torch.from_numpy(a).cuda() for a in (x, Wflat, dy))
+    tbn = torch.from_numpy(bn).cuda() if bn is not None else None
+    Y, st, dX, dW, rows = _run(d, tX, tbn, bg, tW, tdY, B)
+    holes = np.zeros(g * stride, bool)
+    for q in range(g):
+        holes[q * stride + k * gs * Ng:(q + 1) * stride] = True
+    Y.check("gconv_fwd")
+    st.check("gconv_fwd stats")
+    dX.check("gconv_dgrad")
+    dW.check("gconv_wgrad", holes)
+
+    a = _act(x.astype(np.float64), bn.astype(np.float64) if bn is not None else None, bg)
+    y_ref = gconv_fwd(a, Ws, k, s, gs)
+    dx_ref, dW_ref = gconv_bwd(dy.astype(np.float64), a, Ws, k, s, gs)
+
+    def rel(got, ref):
+        return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
+    y = Y.view.cpu().numpy().reshape(B, Lout, F)
+    assert rel(y, y_ref) < 1e-5
+    part = st.view.cpu().numpy().astype(np.float64).reshape(rows, 2, F).sum(0)
+    y2 = y_ref.reshape(-1, F)
+    assert (np.abs(part[0] - y2.sum(0)) <= 1e-5 * np.abs(y2).sum(0) + 1e-30).all()
+    assert (np.abs(part[1] - (y2 * y2).sum(0)) <= 1e-5 * (y2 * y2).sum(0) + 1e-30).all()
+    got_dx = dX.view.cpu().numpy().reshape(B, L, C)
+    assert rel(got_dx, dx_ref) < 1e-5
+    assert (got_dx[:, :, g * gs:] == 0).all()                           # channels no group reads
+    covered = np.zeros(L, bool)
+    for t in range(Lout):
+        covered[s * t:s * t + k] = True
+    assert (got_dx[:, ~covered] == 0).all()                              # rows no window covers
+    got_dw = dW.view.cpu().numpy()
+    for q in range(g):
+        assert rel(got_dw[q * stride:q * stride + k * gs * Ng].reshape(k, gs, Ng), dW_ref[q]) < 1e-5, q
+
+    # run to run: bit for bit
+    Y2, st2, dX2, dW2, _ = _run(d, tX, tbn, bg, tW, tdY, B)
+    for a1, a2, what in ((Y, Y2, "fwd"), (st, st2, "stats"), (dX, dX2, "dgrad"), (dW, dW2, "wgrad")):
+        assert torch.equal(a1.buf, a2.buf), what
+
+
+def test_bad_descriptors_are_refused():
+    lib = _lib.load()
+    bad = [_lib.GconvDesc(2, 10, 8, 5, 3, 2, 2, 4, 4, 0),     # windows past L
+           _lib.GconvDesc(2, 10, 8, 4, 3, 2, 3, 5, 4, 0),     # groups wider than C
+           _lib.GconvDesc(2, 10, 8, 4, 3, 2, 2, 4, 4, 5)]     # w_group_stride < one kernel
+    x = torch.zeros(1024, device="cuda")
+    for d in bad:
+        rc = lib.kws_gconv_dgrad_f32(_lib.ptr(x), _lib.ptr(x), _lib.ptr(x), ctypes.byref(d), _lib.stream_ptr())
+        assert rc == -1
