@@ -9,6 +9,10 @@ both arms of the A/B) -> forward + backward of the raw-waveform net -> [RCCL all
 Batches are produced by the AudioProcessor generator on a background thread with a depth-10 queue,
 exactly like Keras fit_generator drives it.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline.  Every other leg (profiled
+steps and roofline objects, A/B arms, the N>1 all-reduce measurements, other configs, the epoch anchor, checks against the
+oracle, CPU baselines, val-acc parity) runs only with --full, after the timed steps.
+
 Prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 """
 from __future__ import division, print_function
@@ -444,6 +448,10 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--bank", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg beyond the headline: profiled steps and roofline objects, "
+                         "A/B arms, the N>1 all-reduce measurements, configs, epoch anchor, oracle checks, CPU baselines and val-acc "
+                         "parity (each still subject to the --no-* options below); a plain run measures the headline alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=5)
     ap.add_argument("--no-ab", action="store_true",
@@ -457,8 +465,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` legs (BASELINE configs[2] C3 and configs[4] C5 on this one GPU; N=1 only)")
     ap.add_argument("--wall-budget", type=float, default=360.0,
-                    help="seconds after which the remaining CHECKER legs (A/B arms, configs, epoch anchor, val-acc parity) report "
-                         "{'skipped': 'budget'} instead of starting; the timed region, its roofline and cpu_baseline always run")
+                    help="seconds after which the remaining CHECKER legs of a --full run (A/B arms, configs, epoch anchor, val-acc "
+                         "parity) report {'skipped': 'budget'} instead of starting; its roofline and cpu_baseline always run")
     ap.add_argument("--no-val-acc", action="store_true",
                     help="skip the short val-acc parity run (scripts/val_acc_parity.py: the same batches trained on the "
                          "device and on the oracle's torch-CPU twin, val_acc next to val_acc_cpu); N=1 only")
@@ -466,7 +474,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the last timed step computed (the model's parameters, BN moving "
                          "statistics, gradients and RMSprop slots, and the metric rows of the timed steps) as DIR/<name>.npy, "
                          "float32, so that two builds can be compared output for output (rank 0 only)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:        # a plain run: the headline alone (the profiled steps and the N>1 legs check args.full themselves)
+        args.no_cpu_baseline = args.no_ab = args.no_configs = args.no_val_acc = True
+    return args
 
 
 DUMP_LIMIT_BYTES = 64 << 20
@@ -870,7 +881,7 @@ def main():
     roof = None
     stages = []
     used = args.warmup + args.steps
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         # EVERY rank runs the profiled steps (each step contains the gradient all-reduce: a rank that skipped them
         # would leave the others waiting in the collective); only rank 0 records and reports the kernel times.
         # The profiler is a handle: this thread attaches to it, the generator thread through proc.profiler.
@@ -906,7 +917,7 @@ def main():
     # ---- N > 1: what the gradient exchange costs, and the split-overlap form of the same step -----
     exchange = None
     ab = {}
-    if dist:
+    if dist and args.full:
         n_grad = int(model.net.n_params)
         buf = torch.zeros(n_grad, dtype=torch.float32, device=device)
         for _ in range(5):
@@ -1258,6 +1269,7 @@ def main():
             "kernels": prof,
             "skipped_legs": skipped,
             "dumped_outputs": dumped,
+            "full": args.full,
         }
     if dist:
         dist.barrier()

@@ -45,6 +45,20 @@ def test_watchdog_covers_the_rendezvous_too_and_is_silent_when_all_is_well():
     assert res.returncode == 5 and not res.stdout.strip()
 
 
+def test_plain_run_turns_every_leg_beyond_the_headline_off():
+    """Without --full the checker legs are off whatever else is asked; --full runs them unless a --no-* option says otherwise."""
+    code = ("import sys, json; sys.argv = ['bench.py']; import bench\n"
+            "keys = ('full', 'no_cpu_baseline', 'no_ab', 'no_configs', 'no_val_acc', 'profile_steps')\n"
+            "for argv in ([], ['--profile-steps', '3'], ['--full'], ['--full', '--no-ab']):\n"
+            "    a = bench.parse_args(argv)\n"
+            "    print(json.dumps([getattr(a, k) for k in keys]))\n")
+    res = _run(code)
+    assert res.returncode == 0, res.stderr.decode()[-2000:]
+    got = [json.loads(l) for l in res.stdout.decode().split("\n") if l.strip()]
+    assert got == [[False, True, True, True, True, 5], [False, True, True, True, True, 3],
+                   [True, False, False, False, False, 5], [True, False, True, False, False, 5]]
+
+
 def test_dump_outputs_writes_float32_arrays_of_the_last_step(tmp_path):
     """--dump-outputs: one DIR/<name>.npy per array the timed path hands back, float32, values unchanged."""
     code = ("import sys, types, json, torch; d = sys.argv[1]; sys.argv = ['bench.py']; import bench\n"

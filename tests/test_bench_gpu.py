@@ -19,7 +19,7 @@ def test_bench_two_ranks_print_one_json_line():
     env = dict(os.environ, KWS_BENCH_ONE_DEVICE="1", KWS_BENCH_TRACE="240", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--bank", "8192", "--batch", "256"]
+           "--warmup", "2", "--bank", "8192", "--batch", "256", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -57,7 +57,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--bank", "8192",
-           "--batch", "256", "--no-cpu-baseline", "--allreduce-split", "3", "--n1-value", "100000"]
+           "--batch", "256", "--full", "--no-cpu-baseline", "--allreduce-split", "3", "--n1-value", "100000"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -79,7 +79,7 @@ def test_bench_four_ranks_on_one_device_rehearsal():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "2", "--bank", "512",
-           "--batch", "64", "--no-cpu-baseline", "--n1-value", "50000"]
+           "--batch", "64", "--full", "--no-cpu-baseline", "--n1-value", "50000"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=500)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -174,7 +174,7 @@ def test_bench_single_gpu_line_carries_the_round4_keys():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KWS_BENCH_ONE_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3", "--bank", "8192", "--batch", "256",
-           "--no-val-acc", "--no-configs", "--profile-steps", "1"]
+           "--full", "--no-val-acc", "--no-configs", "--profile-steps", "1"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -192,6 +192,29 @@ def test_bench_single_gpu_line_carries_the_round4_keys():
     assert err["clips"] == 16
     assert err["log_mel"]["max_abs_err_vs_f64"] < 1e-3 and err["mfcc"]["max_abs_err_vs_f64"] < 2e-3     # the test-suite bars
     assert err["spectrogram"]["max_abs_err_vs_f64"] < 2e-5 * max(1.0, err["spectrogram"]["max_abs_value"])
+
+
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the line carries the headline and nothing that needs steps or runs of its own: no profiled steps, A/B arms,
+    configs, epoch anchor, oracle check, CPU baseline or val-acc parity."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KWS_BENCH_ONE_DEVICE"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--bank", "8192", "--batch", "256"]
+    res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert res.returncode == 0, res.stderr.decode()[-2000:]
+    lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 2
+    assert out["metric"] == "1s 16kHz clips/sec training throughput" and out["unit"] == "clips/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and abs(out["value"] - 256 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"] and out["dtype"] == "f32"
+    assert out["train_loss_first_last"][1] == out["train_loss_first_last"][1]
+    assert out["kernels"] is None and out["roofline"] is None and out["roofline_stages"] == []
+    for k in ("ab_gemm_f16x2", "ab_features", "ab_fit_generator", "ab_bwd_pair", "configs", "epoch_anchor", "vs_baseline",
+              "stft_mel_error", "allreduce_only", "ab_allreduce_split"):
+        assert out[k] is None, k
+    assert "cpu_baseline" not in out and "val_acc_parity" not in out and out["skipped_legs"] == []
 
 
 def test_dump_outputs_hold_the_last_timed_step(tmp_path):
@@ -215,7 +238,7 @@ def test_dump_outputs_hold_the_last_timed_step(tmp_path):
         return out, {n: np.load(str(tmp_path / name / (n + ".npy"))) for n in names}
 
     out_a, a = run("a", 3, 0)
-    _, b = run("b", 3, 2)                                  # two profiled steps train the model further after the dump
+    _, b = run("b", 3, 2, ["--full"])                      # two profiled steps train the model further after the dump
     _, c = run("c", 4, 0)                                  # one more timed step
     for n in ("params", "bn_state", "grads", "rmsprop_slots", "metrics_per_step"):
         assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
