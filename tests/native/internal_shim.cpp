@@ -1,0 +1,72 @@
+// Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip).
+// libkws_hip.so builds them with hidden visibility; tests/test_resblock_kernels_gpu.py links this file with the library's own
+// objects into a separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them.  No kernels live here.
+//
+// Every forwarder has exactly the parameter list of the declaration it forwards to: KWST_FORWARD static_asserts that the two
+// function types are the same, so a changed declaration fails this build instead of being cast into a wrong call.
+#include <type_traits>
+
+#include "net_internal.h"
+
+#define KWST_API extern "C" __attribute__((visibility("default")))
+#define KWST_FORWARD(RET, NAME, PARAMS, ARGS)                                                                        \
+  KWST_API RET kwst_##NAME PARAMS { return kws_##NAME ARGS; }                                                         \
+  static_assert(std::is_same<decltype(kwst_##NAME), decltype(kws_##NAME)>::value,                                     \
+                "kwst_" #NAME " does not match the declaration of kws_" #NAME)
+
+// ---- residual-block joins (resblock.hip) ----
+KWST_FORWARD(int, block_out_fwd,
+             (const float* y, const float* bn, const float* res, const float* res_bn, float* o, int B, int L, int C, int pool,
+              hipStream_t st),
+             (y, bn, res, res_bn, o, B, L, C, pool, st));
+KWST_FORWARD(int, block_out_dw_fwd,
+             (const float* y, const float* bn, const float* res, const float* res_bn, const float* w, float* o, float* z, int B,
+              int L, int C, int pool, hipStream_t st),
+             (y, bn, res, res_bn, w, o, z, B, L, C, pool, st));
+KWST_FORWARD(int64_t, block_out_bwd_part_floats, (int B, int L, int C, int pool), (B, L, C, pool));
+KWST_FORWARD(int, block_out_bwd,
+             (const float* dO, const float* y, const float* bn, float* g, float* part, int B, int L, int C, int pool, int relu,
+              hipStream_t st),
+             (dO, y, bn, g, part, B, L, C, pool, relu, st));
+KWST_FORWARD(int, block_join_bwd_parts, (int B, int L, int C, int pool), (B, L, C, pool));
+KWST_FORWARD(int, block_join_bwd,
+             (const float* dO, const float* y, const float* bn, const float* gamma, const float* coef, float* out, float* part,
+              int pass, int B, int L, int C, int pool, int relu, hipStream_t st),
+             (dO, y, bn, gamma, coef, out, part, pass, B, L, C, pool, relu, st));
+KWST_FORWARD(int, block_out3_fwd,
+             (const float* y, const float* bn, const float* res, const float* res_bn, float* o, int B, int L, int Lo, int C,
+              int stride, int pad_l, hipStream_t st),
+             (y, bn, res, res_bn, o, B, L, Lo, C, stride, pad_l, st));
+KWST_FORWARD(int64_t, block_out3_bwd_part_floats, (int B, int L, int C), (B, L, C));
+KWST_FORWARD(int, block_out3_bwd,
+             (const float* dO, const float* y, const float* bn, float* g, float* part, int B, int L, int Lo, int C, int stride,
+              int pad_l, hipStream_t st),
+             (dO, y, bn, g, part, B, L, Lo, C, stride, pad_l, st));
+
+// ---- adds and the depthwise backward with an added gradient (resblock.hip, dwconv.hip) ----
+KWST_FORWARD(int, add_f32, (const float* a, const float* b, float* out, int64_t n, hipStream_t st), (a, b, out, n, st));
+KWST_FORWARD(int, add_strided_f32, (float* out, const float* in, int B, int L_out, int L_in, int C, int stride, hipStream_t st),
+             (out, in, B, L_out, L_in, C, stride, st));
+KWST_FORWARD(int, dwconv_bwd_acc_f32,
+             (const float* dz, const float* y, const float* w, const float* add, float* g, float* part, int B, int L_in,
+              int L_out, int C, int stride, int pad_l, hipStream_t st),
+             (dz, y, w, add, g, part, B, L_in, L_out, C, stride, pad_l, st));
+KWST_FORWARD(int, dwconv_bwd_acc_strided_f32,
+             (const float* dz, const float* y, const float* w, const float* add, int add_stride, int add_len, float* g,
+              float* part, int B, int L_in, int L_out, int C, int stride, int pad_l, hipStream_t st),
+             (dz, y, w, add, add_stride, add_len, g, part, B, L_in, L_out, C, stride, pad_l, st));
+
+// ---- strided GEMMs and slab sums (gemm.hip) ----
+KWST_FORWARD(bool, gather_strided_rows, (const kws_gather_t* g, int* lda), (g, lda));
+KWST_FORWARD(int, gemm_nn_strided_f32,
+             (const float* A, int lda, const float* W, float* C, int64_t M, int K, int N, float* stats_part, hipStream_t stream),
+             (A, lda, W, C, M, K, N, stats_part, stream));
+KWST_FORWARD(int, gemm_tn_slabs_strided_f32,
+             (const float* A, int lda, const float* G, int64_t M, int K, int N, float* workspace, int* S, hipStream_t stream),
+             (A, lda, G, M, K, N, workspace, S, stream));
+KWST_FORWARD(int, gemm_tn_slabs_f32,
+             (const float* A, const float* G, int64_t M, int K, int N, float* workspace, int* S, hipStream_t stream),
+             (A, G, M, K, N, workspace, S, stream));
+KWST_FORWARD(int, reduce_slabs_batch,
+             (const float* const* ws, float* const* out, const int64_t* n, const int* S, int count, hipStream_t stream),
+             (ws, out, n, S, count, stream));
