@@ -49,6 +49,27 @@ BnRef kws_net_add_bn(kws_net* n, int idx, int C) {
   return r;
 }
 
+void kws_same_pad(int L, int k, int s, int* Lout, int* pl) {
+  *Lout = (L + s - 1) / s;
+  int p = (*Lout - 1) * s + k - L;
+  if (p < 0) p = 0;
+  *pl = p / 2;  // TF: extra padding goes to the right
+}
+
+int64_t KerasNames::conv(int k, int cin, int cout, float l2) {
+  return kws_net_add_tensor(n, "conv1d_" + std::to_string(++n_conv) + "/kernel", {k, cin, cout}, false, l2, k * cin, k * cout,
+                            0.f);
+}
+BnRef KerasNames::bn(int C, int* idx) {
+  ++n_bn;
+  if (idx) *idx = n_bn;
+  return kws_net_add_bn(n, n_bn, C);
+}
+int64_t KerasNames::dw(int C) {
+  return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(++n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
+                            KWS_L2_COEF, 3 * C, 3, 0.f);
+}
+
 namespace {
 
 constexpr float BN_EPS = KWS_BN_EPS;
@@ -57,33 +78,20 @@ constexpr float L2_COEF = KWS_L2_COEF;
 constexpr float DROP_KEEP = 0.6f;     // Dropout(0.4), model.py:819,828
 constexpr float LABEL_SMOOTH = 0.1f;  // model.py:835-836
 
-inline int64_t add_tensor(kws_net* n, const std::string& name, std::vector<int64_t> shape, bool is_state, float l2,
-                          int fan_in, int fan_out, float init) {
-  return kws_net_add_tensor(n, name, shape, is_state, l2, fan_in, fan_out, init);
-}
-inline BnRef add_bn(kws_net* n, int idx, int C) { return kws_net_add_bn(n, idx, C); }
-
-void same_pad(int L, int k, int s, int* Lout, int* pl) {
-  *Lout = (L + s - 1) / s;
-  int p = (*Lout - 1) * s + k - L;
-  if (p < 0) p = 0;
-  *pl = p / 2;  // TF: extra padding goes to the right
-}
-
 int build_ts_attention(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   KWS_REQUIRE(c.filter_mult >= 1 && c.filter_mult <= 2, "net: filter_mult %d unsupported", c.filter_mult);
   KWS_REQUIRE(c.input_size >= 1600 && c.input_size % 4 == 0, "net: input_size %d unsupported", c.input_size);
   const int fm = c.filter_mult;
   n->L_in = c.input_size;
   // overlapping_time_slice_stack(x, 40, 20) SAME (model.py:805) fused with Conv1D(128,3,strides=2) (model.py:807)
   int Lf, plf;
-  same_pad(n->L_in, 40, 20, &Lf, &plf);
+  kws_same_pad(n->L_in, 40, 20, &Lf, &plf);
   n->L1 = (Lf - 3) / 2 + 1;
   n->C1 = 128 * fm;
-  n->conv1 = add_tensor(n, "conv1d_1/kernel", {3, 40, n->C1}, false, L2_COEF, 3 * 40, 3 * n->C1, 0.f);
-  n->bn1 = add_bn(n, 1, n->C1);
+  KerasNames kn{n};
+  n->conv1 = kn.conv(3, 40, n->C1, L2_COEF);
+  n->bn1 = kn.bn(n->C1);
   kws_gather_t g;
   g.L_out = n->L1; g.cin = 40; g.taps = 3; g.stride_t = 2 * 20; g.stride_j = 20; g.base_off = -plf;
   g.x_len = n->L_in; g.x_batch_stride = n->L_in;
@@ -104,17 +112,15 @@ int build_ts_attention(kws_net* n) {
     b.cout = spec[i][1] * fm;
     b.Lin = L;
     if (b.stride == 2) {
-      same_pad(L, 3, 2, &b.Lout, &b.pad_l);  // _reduce_conv: padding='same'
+      kws_same_pad(L, 3, 2, &b.Lout, &b.pad_l);  // _reduce_conv: padding='same'
     } else {
       b.Lout = L - 2;  // _context_conv: padding='valid'
       b.pad_l = 0;
     }
     KWS_REQUIRE(b.Lout >= 1, "net: input too short for block %d", i);
-    b.dw = add_tensor(n, "depthwise_conv2d_" + std::to_string(i + 1) + "/depthwise_kernel", {1, 3, cin, 1}, false,
-                      L2_COEF, 3 * cin, 3, 0.f);
-    b.pw = add_tensor(n, "conv1d_" + std::to_string(i + 2) + "/kernel", {1, cin, b.cout}, false, L2_COEF, cin,
-                      b.cout, 0.f);
-    b.bn = add_bn(n, i + 2, b.cout);
+    b.dw = kn.dw(cin);
+    b.pw = kn.conv(1, cin, b.cout, L2_COEF);
+    b.bn = kn.bn(b.cout);
     n->blocks.push_back(b);
     L = b.Lout;
     cin = b.cout;
@@ -123,9 +129,9 @@ int build_ts_attention(kws_net* n) {
   n->C = cin;
   n->NC = c.num_classes;
   KWS_REQUIRE(n->T <= 16, "net: %d time steps at the tail (max 16)", n->T);
-  n->d1k = add_tensor(n, "dense_1/kernel", {(int64_t)n->T * n->C, n->T}, false, L2_COEF, n->T * n->C, n->T, 0.f);
-  n->d1b = add_tensor(n, "dense_1/bias", {n->T}, false, 0.f, 0, 0, 0.f);
-  n->d2k = add_tensor(n, "dense_2/kernel", {2 * n->C, n->NC}, false, L2_COEF, 2 * n->C, n->NC, 0.f);
+  n->d1k = kws_net_add_tensor(n, "dense_1/kernel", {(int64_t)n->T * n->C, n->T}, false, L2_COEF, n->T * n->C, n->T, 0.f);
+  n->d1b = kws_net_add_tensor(n, "dense_1/bias", {n->T}, false, 0.f, 0, 0, 0.f);
+  n->d2k = kws_net_add_tensor(n, "dense_2/kernel", {2 * n->C, n->NC}, false, L2_COEF, 2 * n->C, n->NC, 0.f);
   return KWS_OK;
 }
 
@@ -274,24 +280,21 @@ extern "C" {
 
 int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
   KWS_REQUIRE(cfg && out, "net_create: NULL pointer");
+  KWS_REQUIRE(cfg->num_classes >= 2 && cfg->num_classes <= 64, "net: num_classes %d out of range", cfg->num_classes);
   kws_net* n = new kws_net();
   n->cfg = *cfg;
   int rc;
-  if (cfg->kind == KWS_NET_TS_ATTENTION) {
-    rc = build_ts_attention(n);
-  } else if (cfg->kind == KWS_NET_LOG_MFCC) {
-    rc = lm_build(n);
-  } else if (cfg->kind == KWS_NET_STEFFE) {
-    rc = steffe_build(n);
-  } else if (cfg->kind == KWS_NET_RESIDUAL) {
-    rc = residual_build(n);
-  } else if (cfg->kind == KWS_NET_MFCC_AND_RAW) {
-    rc = mfcc_raw_build(n);
-  } else if (cfg->kind == KWS_NET_CONV_1D_FAST || cfg->kind == KWS_NET_CONV_1D_SPEC) {
-    rc = gc_build(n);
-  } else {
-    kws_set_error("net_create: kind %d not supported", cfg->kind);
-    rc = KWS_E_INVALID;
+  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc tell
+    case KWS_NET_TS_ATTENTION: rc = build_ts_attention(n); break;
+    case KWS_NET_LOG_MFCC: rc = lm_build(n); break;
+    case KWS_NET_STEFFE: rc = steffe_build(n); break;
+    case KWS_NET_RESIDUAL: rc = residual_build(n); break;
+    case KWS_NET_MFCC_AND_RAW: rc = mfcc_raw_build(n); break;
+    case KWS_NET_CONV_1D_FAST:
+    case KWS_NET_CONV_1D_SPEC: rc = gc_build(n); break;
+    default:
+      kws_set_error("net_create: kind %d not supported", cfg->kind);
+      rc = KWS_E_INVALID;
   }
   if (rc != KWS_OK) {
     lm_free(n);
@@ -325,8 +328,7 @@ int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) 
 int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
   if (!net || max_batch <= 0) return 0;
   if (net->gc) return gc_workspace_bytes(net, max_batch, training);
-  if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
-       net->cfg.kind == KWS_NET_MFCC_AND_RAW)) return lm_workspace_bytes(net, max_batch, training);
+  if (net->lm) return lm_workspace_bytes(net, max_batch, training);
   Layout lo;
   make_layout(net, max_batch, training != 0, &lo);
   return lo.total;
@@ -336,8 +338,7 @@ int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, 
                        int64_t* count) {
   KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
   if (net->gc) return gc_debug_view(net, batch, training, what, index, offset_floats, count);
-  if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
-       net->cfg.kind == KWS_NET_MFCC_AND_RAW)) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
+  if (net->lm) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
   Layout lo;
   make_layout(net, batch, training != 0, &lo);
   const int nb = (int)net->blocks.size();
@@ -369,8 +370,7 @@ int kws_net_predict(const kws_net_t* net, const float* params, const float* stat
                     float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
   KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
   if (net->gc) return gc_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
-       net->cfg.kind == KWS_NET_MFCC_AND_RAW))
+  if (net->lm)
     return lm_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   Layout lo;
   make_layout(net, B, false, &lo);
@@ -689,8 +689,7 @@ int kws_net_train_fwd_bwd(const kws_net_t* net, const float* params, float* stat
   if (net->gc)
     return gc_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
                     workspace_bytes, (hipStream_t)stream);
-  if ((net->cfg.kind == KWS_NET_LOG_MFCC || net->cfg.kind == KWS_NET_STEFFE || net->cfg.kind == KWS_NET_RESIDUAL ||
-       net->cfg.kind == KWS_NET_MFCC_AND_RAW))
+  if (net->lm)
     return lm_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch,
                     (float*)workspace, workspace_bytes, (hipStream_t)stream);
   return ts_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, workspace,

@@ -44,8 +44,7 @@ namespace {
 constexpr float GC_DROP_KEEP = 0.7f;      // Dropout(0.3), model.py:710 / 1318
 constexpr float GC_FRONT_L2 = 1e-4f;      // kernel_regularizer=l2(0.0001), model.py:700
 
-int add_block(kws_net* n, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride, int* conv_idx,
-              int* bn_idx) {
+int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride) {
   KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C, "net: grouped block F=%d g=%d num_channels=%d C=%d", F, g,
               num_channels, C);
   GcBlock b;
@@ -54,13 +53,12 @@ int add_block(kws_net* n, GcProgram* p, int L, int C, int F, int k, int g, int n
   KWS_REQUIRE(L >= k, "net: grouped block input length %d < %d taps", L, k);
   b.d.Lout = (L - k) / stride + 1;
   b.F = F;
-  b.bn_idx0 = *bn_idx;
+  b.bn_idx0 = kn.n_bn;
   const int gs = b.d.gs, Ng = b.d.Ng;
   int64_t prev_w = 0, prev_m = 0;
   for (int q = 0; q < g; ++q) {
-    const int64_t w = kws_net_add_tensor(n, "conv1d_" + std::to_string((*conv_idx)++) + "/kernel", {k, gs, Ng}, false, 0.f, k * gs,
-                                         k * Ng, 0.f);
-    const BnRef r = kws_net_add_bn(n, ++(*bn_idx), Ng);
+    const int64_t w = kn.conv(k, gs, Ng, 0.f);
+    const BnRef r = kn.bn(Ng);
     if (q == 0) {
       b.w0 = w; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
     } else {
@@ -190,33 +188,31 @@ kws_flat_tail_args tail_args(const kws_net* n, const GcLayout& lo, const float* 
 
 int gc_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   GcProgram* p = new GcProgram();
   n->gc = p;
   p->NC = c.num_classes;
   p->keep = GC_DROP_KEEP;
-  int conv_idx = 1, bn_idx = 0;
+  KerasNames kn{n};
   if (c.kind == KWS_NET_CONV_1D_FAST) {
     KWS_REQUIRE(c.input_size >= 479 && c.input_size % 2 == 0, "net: conv_1d_fast input_size %d (even, >= 479)", c.input_size);
     p->front = true;
     p->K0 = 479; p->K0p = 480; p->C0 = 252;
     p->L0 = (c.input_size - p->K0) / 160 + 1;
-    p->conv0 = kws_net_add_tensor(n, "conv1d_" + std::to_string(conv_idx++) + "/kernel", {p->K0, 1, p->C0}, false, GC_FRONT_L2, p->K0,
-                                  p->K0 * p->C0, 0.f);
+    p->conv0 = kn.conv(p->K0, 1, p->C0, GC_FRONT_L2);
     // ONE tap of 480 samples (the 480th weight is a zero row): window t starts at 160 t and ends at 160 t + 479 < input_size
     p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
     p->g0.x_len = c.input_size; p->g0.x_batch_stride = c.input_size;
     p->L_in = c.input_size; p->C_in = 1;
-    KWS_TRY(add_block(n, p, p->L0, p->C0, 300, 15, 6, 252, 2, &conv_idx, &bn_idx));
+    KWS_TRY(add_block(kn, p, p->L0, p->C0, 300, 15, 6, 252, 2));
     const GcBlock& b1 = p->blocks.back();
-    KWS_TRY(add_block(n, p, b1.d.Lout, b1.F, 360, 7, 5, 300, 2, &conv_idx, &bn_idx));
+    KWS_TRY(add_block(kn, p, b1.d.Lout, b1.F, 360, 7, 5, 300, 2));
   } else {
     p->L_in = 98; p->C_in = 257;   // Input(shape=[98 * 257]) -> Reshape([98, 257]); input_size is not consulted
     struct { int F, g, nch, stride; } spec[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
                                                  {420, 4, 360, 2}, {420, 3, 360, 1}, {480, 4, 420, 2}, {480, 3, 480, 1}};
     int L = p->L_in, C = p->C_in;
     for (int i = 0; i < 8; ++i) {
-      KWS_TRY(add_block(n, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride, &conv_idx, &bn_idx));
+      KWS_TRY(add_block(kn, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride));
       L = p->blocks.back().d.Lout;
       C = p->blocks.back().F;
     }

@@ -1,5 +1,6 @@
-// Shared between the two network programs (net.hip: conv_1d_time_sliced_with_attention,
-// net_logmfcc.hip: conv_1d_log_mfcc).  Not part of the public C ABI.
+// Shared between the three network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
+// residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
+// net_grouped.hip: conv_1d_fast, conv_1d_spec).  Not part of the public C ABI.
 #pragma once
 #include <string.h>
 
@@ -25,7 +26,7 @@ struct Block {
   BnRef bn;        // BN after the pointwise conv
 };
 
-struct LmProgram;  // conv_1d_log_mfcc layer table (net_logmfcc.hip)
+struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
 struct GcProgram;  // conv_1d_fast / conv_1d_spec layer table (net_grouped.hip)
 
 struct kws_net {
@@ -43,7 +44,7 @@ struct kws_net {
   kws_gather_t gather1;   // the reference's view: 3 taps of 40 samples, taps 20 samples apart (K = 120)
   kws_gather_t gather1f;  // folded view used by the GEMMs: ONE tap of 80 contiguous samples (see net.hip fold_taps_kernel)
   int K1f = 0;            // folded K
-  // LOG_MFCC
+  // LOG_MFCC / STEFFE / RESIDUAL / MFCC_AND_RAW
   LmProgram* lm = nullptr;
   // CONV_1D_FAST / CONV_1D_SPEC
   GcProgram* gc = nullptr;
@@ -55,6 +56,18 @@ struct kws_net {
 int64_t kws_net_add_tensor(kws_net* n, const std::string& name, std::vector<int64_t> shape, bool is_state, float l2,
                            int fan_in, int fan_out, float init);
 BnRef kws_net_add_bn(kws_net* n, int idx, int C);
+// Keras padding='same': output length and left padding of a k-wide window at stride s (TF puts the odd sample on the right)
+void kws_same_pad(int L, int k, int s, int* Lout, int* pl);
+
+// Keras names a layer by its class and a per-class counter in creation order, and those names are the checkpoint format.
+// One KerasNames per table: the builders create their layers through it, in model.py's order.
+struct KerasNames {
+  kws_net* n;
+  int n_conv = 0, n_bn = 0, n_dw = 0;
+  int64_t conv(int k, int cin, int cout, float l2);  // conv1d_<n>/kernel [k, cin, cout]
+  BnRef bn(int C, int* idx = nullptr);               // batch_normalization_<n>/...; *idx = n
+  int64_t dw(int C);                                 // depthwise_conv2d_<n>/depthwise_kernel [1, 3, C, 1], l2
+};
 
 struct Bump {
   int64_t cur = 0;  // in floats
@@ -65,7 +78,7 @@ struct Bump {
   }
 };
 
-// ---- conv_1d_log_mfcc program -----------------------------------------------------------------------
+// ---- residual-block programs (net_logmfcc.hip) --------------------------------------------------------
 int lm_build(kws_net* n);
 int steffe_build(kws_net* n);
 int residual_build(kws_net* n);

@@ -1,12 +1,12 @@
 // Residual-block network programs.  One layer table (LmProgram) drives five reference models:
-//   style 0  conv_1d_log_mfcc_model (model.py:1400-1479) and conv_1d_spectrogram_model
-//            (model.py:1482-1561: the same program on 257-bin input, first convolution on re-pitched copies)
-//   style 1  steffeNet (model.py:1663-1726): stride in the block's first depthwise convolution, context block,
-//            global max ++ average pooling tail
-//   style 2  conv_1d_residual_model (model.py:841-908): 3-wide SAME max-pool joins, plain blocks after the stack,
-//            global-average tail
-//   style 3  conv_1d_mfcc_and_raw_model (model.py:1563-1660): two stems on packed [mfcc | raw] rows, concatenated
-// The original description of style 0 follows.
+//   LM_ATTENTION     conv_1d_log_mfcc_model (model.py:1400-1479) and conv_1d_spectrogram_model
+//                    (model.py:1482-1561: the same program on 257-bin input, first convolution on re-pitched copies)
+//   LM_STEFFE        steffeNet (model.py:1663-1726): stride in the block's first depthwise convolution, context block,
+//                    global max ++ average pooling tail
+//   LM_RESIDUAL      conv_1d_residual_model (model.py:841-908): 3-wide SAME max-pool joins, plain blocks after the
+//                    stack, global-average tail
+//   LM_MFCC_AND_RAW  conv_1d_mfcc_and_raw_model (model.py:1563-1660): two stems on packed [mfcc | raw] rows, concatenated
+// The original description of LM_ATTENTION follows.
 // Network program of conv_1d_log_mfcc_model (reference model.py:1400-1479; SURVEY 8a row a19, layer
 // table Appendix B.2): Conv1D(64,3)+BN+ReLU6 on [98,40] features, 10 residual blocks of
 // 2 x [depthwise k3 SAME -> pointwise -> BN -> ReLU6] + MaxPool1D(pool=stride) + Add (1x1 stride-2
@@ -19,10 +19,6 @@
 #include "net_internal.h"
 
 namespace {
-
-constexpr float DROP_KEEP = 0.8f;  // Dropout(0.2), model.py:1471
-constexpr float STEFFE_DROP_KEEP = 0.5f;     // Dropout(0.5), model.py:1716
-constexpr float STEFFE_LABEL_SMOOTH = 0.1f;  // model.py:1722-1724
 
 struct LmBlock {
   int nf, stride, cin, Lin, Lout;
@@ -49,33 +45,43 @@ struct LmPlain {
   int bn_idx, cin, cout, stride, pad_l, Lin, Lout;
 };
 
+// which model the table was built for; forward / backward ask it only for structure no field below describes
+enum LmStyle { LM_ATTENTION, LM_STEFFE, LM_RESIDUAL, LM_MFCC_AND_RAW };
+
 struct LmProgram {
+  LmStyle style = LM_ATTENTION;
   int T0, F, C0, L0;
   int Fp;  // F rounded up to the 16-byte vectors of the gathered GEMM (spectrogram input: 257 -> 260)
   int64_t conv1;
   BnRef bn0;
   kws_gather_t g0;
   std::vector<LmBlock> blocks;
-  int T, C, NC;
-  int64_t att_dw, att_pw, dk, db;
+  int T, C, NC;   // [T, C]: the running activation while the table is built, the tail's input afterwards
+  int64_t att_dw, att_pw, dk, db = 0;
   BnRef att_bn;
   int att_bn_idx;
   int n_bn;
-  int maxC;
-  // steffeNet (style 1): raw input, first convolution of K0 = 75 taps on one channel (gathered as ONE tap of
+  int maxC;       // widest BatchNormalization of the table
+  // the dense layer and, for every style but LM_ATTENTION (softmax-over-time attention), the global-pooling tail in front of it
+  bool has_bias = true;    // dense_1/bias
+  bool pool_max = false;   // GlobalMaxPooling1D ++ GlobalAveragePooling1D (else the average alone)
+  int feat = 0;            // width of the dense layer's input: 2 C with pool_max, else C
+  int loss_kind = 1;       // kws_gp_tail_args::loss_kind: 0 = label-smoothed CE, 1 = keras categorical_crossentropy
+  float label_smoothing = 0.f;
+  float drop_keep = 0.5f;
+  // steffeNet: raw input, first convolution of K0 = 75 taps on one channel (gathered as ONE tap of
   // K0p = 76 samples against a zero-padded kernel), a context block between the first convolution and the
   // residual stack, global max ++ average pooling tail
-  int style = 0, K0 = 0, K0p = 0;
-  // conv_1d_residual (style 2): raw input through the time-slice gather, 3-wide max-pool joins, plain blocks after the
+  int K0 = 0, K0p = 0;
+  // conv_1d_residual: raw input through the time-slice gather, 3-wide max-pool joins, plain blocks after the
   // residual stack, global average pooling tail with bias and plain CE
   std::vector<LmPlain> plain;
-  // conv_1d_mfcc_and_raw (style 3): input rows are [mfcc T0*F | raw L_raw]; two first convolutions (Cm + Cr = C0
-  // channels, concatenated after BN + ReLU6), style-2 blocks, global-average tail
+  // conv_1d_mfcc_and_raw: input rows are [mfcc T0*F | raw L_raw]; two first convolutions (Cm + Cr = C0
+  // channels, concatenated after BN + ReLU6), conv_1d_residual's blocks, global-average tail
   int Cm = 0, Cr = 0, Din = 0;
   int64_t conv1r = 0;
   BnRef bn0r;
   kws_gather_t g0r;
-  float drop_keep = 0.5f;
   int64_t ctx_dw = 0, ctx_pw = 0;
   BnRef ctx_bn;
   int ctx_bn_idx = 0;
@@ -92,11 +98,11 @@ struct LmLayout {
   int64_t dwq = 0, dwq_floats = 0;         // partial rows of the depthwise weight gradients folded by one launch (DwFinQueue)
   int64_t dOa = 0, dOb = 0, G = 0, DZ = 0, DXS = 0;
   int64_t u = 0, fd = 0, dl = 0, gu = 0, coef2 = 0, per_loss = 0, per_correct = 0, att = 0;
-  int64_t xpad = 0, wpad = 0, gwpad = 0;  // only when Fp != F (style 0) / always (style 1: padded first kernel)
+  int64_t xpad = 0, wpad = 0, gwpad = 0;  // only when Fp != F (spectrogram input) / always (steffeNet: padded first kernel)
   int64_t zc = 0, yc = 0, ac = 0;          // steffeNet context block
-  std::vector<int64_t> pz, py;             // plain blocks (style 2)
+  std::vector<int64_t> pz, py;             // plain blocks (conv_1d_residual)
   int64_t alast = 0;
-  int64_t a0m = 0, a0r = 0;                // style 3: activated branch outputs before the concatenation
+  int64_t a0m = 0, a0r = 0;                // conv_1d_mfcc_and_raw: activated branch outputs before the concatenation
   std::vector<int64_t> wt_pw1, wt_pw2, wt_ws, wt_plain;   // transposed pointwise kernels for the dgrad GEMMs
   int64_t wt_ctx = 0;
 };
@@ -122,14 +128,14 @@ void lm_layout(const kws_net* n, int B, LmLayout* lo) {
     upd_gemm(M, K, N);
     sum_tnq += (kws_gemm_tn_workspace_floats(M, K, N) + 63) / 64 * 64;
   };
-  upd_pw((int64_t)B * p.L0, p.style == 1 ? p.K0p : 3 * p.Fp, p.C0);     // (gathered weight gradients queue their slabs too: round 5)
-  if (p.style == 3) {
+  upd_pw((int64_t)B * p.L0, p.g0.taps * p.g0.cin, p.C0);    // (gathered weight gradients queue their slabs too: round 5)
+  if (p.style == LM_MFCC_AND_RAW) {
     upd_pw((int64_t)B * p.L0, p.g0r.taps * p.g0r.cin, p.Cr);
     lo->a0m = bp.take((int64_t)B * p.L0 * p.Cm);
     lo->a0r = bp.take((int64_t)B * p.L0 * p.Cr);
   }
   max_part = std::max(max_part, kws_block_out_bwd_part_floats(B, p.L0, p.C0, 1));
-  if (p.style == 1) {
+  if (p.style == LM_STEFFE) {
     lo->zc = bp.take((int64_t)B * p.L0 * p.C0);
     lo->yc = bp.take((int64_t)B * p.L0 * p.C0);
     lo->ac = bp.take((int64_t)B * p.L0 * p.C0);
@@ -175,7 +181,6 @@ void lm_layout(const kws_net* n, int B, LmLayout* lo) {
   }
   if (!p.plain.empty()) lo->alast = bp.take((int64_t)B * p.T * p.C);
   max_part = std::max(max_part, (int64_t)B * 5 * p.C);
-  const int feat = p.style == 1 ? 2 * p.C : p.C;   // width of the dense layer's input
   lo->bn_stride = 4 * p.maxC;
   lo->bn = bp.take(lo->bn_stride * (p.n_bn + 1));
   lo->part = bp.take(max_part);
@@ -190,27 +195,27 @@ void lm_layout(const kws_net* n, int B, LmLayout* lo) {
     if (b.has_short) lo->wt_ws[i] = bp.take((int64_t)b.cin * b.nf);
   }
   for (size_t j = 0; j < p.plain.size(); ++j) lo->wt_plain[j] = bp.take((int64_t)p.plain[j].cin * p.plain[j].cout);
-  if (p.style == 1) lo->wt_ctx = bp.take((int64_t)p.C0 * p.C0);
+  if (p.style == LM_STEFFE) lo->wt_ctx = bp.take((int64_t)p.C0 * p.C0);
   lo->tn = bp.take(max_tn);
   lo->tnq_floats = sum_tnq;
   lo->tnq = bp.take(sum_tnq);
   lo->dwq_floats = sum_dwq;
   lo->dwq = bp.take(sum_dwq);
-  lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * feat * p.NC);
+  lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.feat * p.NC);
   lo->dOa = bp.take(max_o);
   lo->dOb = bp.take(max_o);
   lo->G = bp.take(max_y);
   lo->DZ = bp.take(max_z);
   lo->DXS = bp.take(max_xs);
   lo->u = bp.take((int64_t)B * 16);
-  lo->fd = bp.take((int64_t)B * feat);
+  lo->fd = bp.take((int64_t)B * p.feat);
   lo->dl = bp.take((int64_t)B * p.NC);
   lo->gu = bp.take((int64_t)B * 16);
   lo->coef2 = bp.take(4);
   lo->per_loss = bp.take(B);
   lo->per_correct = bp.take(B);
   lo->att = bp.take((int64_t)B * 16);
-  if (p.style == 1) {
+  if (p.style == LM_STEFFE) {
     lo->wpad = bp.take((int64_t)p.K0p * p.C0);
     lo->gwpad = bp.take((int64_t)p.K0p * p.C0);
   } else if (p.Fp != p.F) {
@@ -286,7 +291,7 @@ int pad_first_conv(const Ctx& c, const float* x, const float** x_used, const flo
   const LmProgram& p = *c.p;
   *x_used = x;
   *w_used = c.params + p.conv1;
-  if (p.style == 1) {  // [75, 1, C0] kernel + one zero row: the gather reads 76 samples per output row
+  if (p.style == LM_STEFFE) {  // [75, 1, C0] kernel + one zero row: the gather reads 76 samples per output row
     float* wp = c.ws + c.lo.wpad;
     KWS_HIP(hipMemcpyAsync(wp, c.params + p.conv1, (size_t)p.K0 * p.C0 * 4, hipMemcpyDeviceToDevice, c.st));
     KWS_HIP(hipMemsetAsync(wp + (size_t)p.K0 * p.C0, 0, (size_t)(p.K0p - p.K0) * p.C0 * 4, c.st));
@@ -316,7 +321,7 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
   const int B = c.B;
   float* stats = c.training ? ws + lo.part : nullptr;
   bool z1_first = false;      // the first block's first depthwise output already written (see below)
-  if (p.style == 3) {  // two stems on the packed [mfcc | raw] rows, concatenated after BN + ReLU6
+  if (p.style == LM_MFCC_AND_RAW) {  // two stems on the packed [mfcc | raw] rows, concatenated after BN + ReLU6
     const int64_t M = (int64_t)B * p.L0;
     float* y0m = ws + lo.y0;
     float* y0r = ws + lo.y0 + M * p.Cm;
@@ -335,7 +340,7 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
   KWS_TRY(bn_table(c, p.bn0, 1, (int64_t)B * p.L0, kws_gemm_gather_stats_rows((int64_t)B * p.L0)));
   // the first convolution's activation - and, where the first block starts with a k 3 / stride 1 / 'same' depthwise convolution over it
   // (conv_1d_log_mfcc), that convolution's output in the same pass (round 6, kws_block_out_dw_fwd without a residual: bit-identical)
-  if (p.style == 0 && !p.blocks.empty() && kws_net_get_gemm_mode(c.n) != 1) {
+  if (p.style == LM_ATTENTION && !p.blocks.empty() && kws_net_get_gemm_mode(c.n) != 1) {
     const LmBlock& b0 = p.blocks[0];
     if (b0.s1 == 1 && b0.pad1 == 1 && b0.Lmid == b0.Lin && b0.Lin == p.L0 && b0.cin == p.C0) {
       KWS_TRY(kws_block_out_dw_fwd(ws + lo.y0, c.bn_at(1), nullptr, nullptr, c.params + b0.dw1, ws + lo.a0, ws + lo.z1[0], B, p.L0, p.C0, 1, c.st));
@@ -345,7 +350,7 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
   if (!z1_first) KWS_TRY(kws_bn_relu6_apply(ws + lo.y0, c.bn_at(1), ws + lo.a0, (int64_t)B * p.L0, p.C0, 1, c.st));
   }
   const float* xin = ws + lo.a0;
-  if (p.style == 1) {  // _context_conv(x, 256, 3, 'same'): depthwise -> pointwise -> BN -> ReLU6, materialised
+  if (p.style == LM_STEFFE) {  // _context_conv(x, 256, 3, 'same'): depthwise -> pointwise -> BN -> ReLU6, materialised
     const int64_t M = (int64_t)B * p.L0;
     KWS_TRY(kws_dwconv_fwd_f32(xin, nullptr, c.params + p.ctx_dw, ws + lo.zc, B, p.L0, p.L0, p.C0, 1, 1, c.st));
     KWS_TRY(kws_gemm_nn_f32(ws + lo.zc, c.params + p.ctx_pw, ws + lo.yc, M, p.C0, p.C0, stats, c.st));
@@ -419,273 +424,235 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
   }
   memset(t, 0, sizeof(*t));
   t->x = xin;
-  if (p.style != 0) return KWS_OK;  // the caller sets up the global-pooling tail
-  t->x = xin; t->wa = c.params + p.att_dw; t->Wa = c.params + p.att_pw;
+  if (p.style != LM_ATTENTION) return KWS_OK;  // the caller sets up the global-pooling tail
+  t->wa = c.params + p.att_dw; t->Wa = c.params + p.att_pw;
   t->bn_gamma = c.params + p.att_bn.gamma; t->bn_beta = c.params + p.att_bn.beta;
   t->mm = c.state + p.att_bn.mm; t->mv = c.state + p.att_bn.mv;
   t->Wd = c.params + p.dk; t->bd = c.params + p.db;
   t->u = ws + lo.u; t->bn = c.bn_at(p.att_bn_idx);
-  t->B = B; t->T = p.T; t->C = p.C; t->NC = p.NC; t->keep_prob = c.training ? DROP_KEEP : 1.f; t->loss_batch = 1;
+  t->B = B; t->T = p.T; t->C = p.C; t->NC = p.NC; t->keep_prob = c.training ? p.drop_keep : 1.f; t->loss_batch = 1;
   return KWS_OK;
+}
+
+// Where a residual block's stride sits (LmBlock::s1 / pool / Lmid / pad1 / pool3 / ppad follow from it)
+enum LmStridePlace {
+  LM_POOL_AFTER,   // MaxPool1D(stride, stride) after the second pointwise convolution (conv_1d_log_mfcc)
+  LM_STRIDED_DW,   // the block's first depthwise convolution is strided, 'same' (steffeNet)
+  LM_POOL3_SAME,   // MaxPool1D(3, stride, 'same') after the second pointwise (conv_1d_residual, conv_1d_mfcc_and_raw)
+};
+
+LmProgram* lm_new(kws_net* n, LmStyle style, float drop_keep) {
+  LmProgram* p = new LmProgram();
+  n->lm = p;   // kws_net_create frees it when the builder fails
+  p->style = style;
+  p->drop_keep = drop_keep;
+  return p;
+}
+
+// The stem is done: the running activation is [L0, C0]
+void lm_begin_stack(LmProgram* p) {
+  p->T = p->L0;
+  p->C = p->C0;
+  p->maxC = p->C0;
+}
+
+// Appends one residual block of nf filters over the running activation [p->T, p->C] and moves that on to the block's
+// output.  Keras creation order: shortcut Conv1D + BN (strided blocks only), then 2 x (depthwise, pointwise, BN).
+int lm_add_block(KerasNames& kn, LmProgram* p, LmStridePlace place, int nf, int stride) {
+  const int cin = p->C, L = p->T;
+  LmBlock b{};
+  b.nf = nf; b.stride = stride; b.cin = cin; b.Lin = L;
+  b.s1 = 1; b.pool = stride; b.Lmid = L; b.pad1 = 1;
+  b.Lout = (L + stride - 1) / stride;   // Keras 'same' whichever layer carries the stride: ceil(L / stride)
+  if (place == LM_STRIDED_DW) {
+    kws_same_pad(L, 3, stride, &b.Lout, &b.pad1);
+    b.s1 = stride; b.pool = 1; b.Lmid = b.Lout;
+  } else if (place == LM_POOL3_SAME) {
+    b.pool3 = 1;
+    kws_same_pad(L, 3, stride, &b.Lout, &b.ppad);
+  }
+  b.has_short = stride != 1;
+  if (b.has_short) {
+    b.ws = kn.conv(1, cin, nf, 0.f);  // the shortcut Conv1D(nf, 1, strides) has no kernel_regularizer (model.py:1431-1432, 1692-1693)
+    b.bns = kn.bn(nf, &b.bns_idx);
+    b.gs.L_out = b.Lout; b.gs.cin = cin; b.gs.taps = 1; b.gs.stride_t = stride * cin; b.gs.stride_j = 0;
+    b.gs.base_off = 0; b.gs.x_len = L * cin; b.gs.x_batch_stride = (int64_t)L * cin;
+  } else {
+    KWS_REQUIRE(cin == nf, "net: identity shortcut needs cin == nf");
+  }
+  b.dw1 = kn.dw(cin);
+  b.pw1 = kn.conv(1, cin, nf, KWS_L2_COEF);
+  b.bn1 = kn.bn(nf, &b.bn1_idx);
+  b.dw2 = kn.dw(nf);
+  b.pw2 = kn.conv(1, nf, nf, KWS_L2_COEF);
+  b.bn2 = kn.bn(nf, &b.bn2_idx);
+  p->blocks.push_back(b);
+  p->C = nf;
+  p->T = b.Lout;
+  p->maxC = std::max(p->maxC, nf);
+  return KWS_OK;
+}
+
+// Appends a depthwise block without a residual: _reduce_conv (strides 2, 'same') or _context_conv ('valid')
+int lm_add_plain(KerasNames& kn, LmProgram* p, int cout, int stride) {
+  LmPlain q;
+  q.cin = p->C; q.cout = cout; q.Lin = p->T; q.stride = stride;
+  if (stride == 1) { q.pad_l = 0; q.Lout = q.Lin - 2; }
+  else kws_same_pad(q.Lin, 3, stride, &q.Lout, &q.pad_l);
+  KWS_REQUIRE(q.Lout >= 1, "net: conv_1d_residual input too short");
+  q.dw = kn.dw(q.cin);
+  q.pw = kn.conv(1, q.cin, cout, KWS_L2_COEF);
+  q.bn = kn.bn(cout, &q.bn_idx);
+  p->plain.push_back(q);
+  p->C = cout;
+  p->T = q.Lout;
+  p->maxC = std::max(p->maxC, cout);
+  return KWS_OK;
+}
+
+// Dense(num_classes) over the pooled features of the running activation; closes the table
+void lm_add_dense(KerasNames& kn, LmProgram* p) {
+  p->NC = kn.n->cfg.num_classes;
+  p->feat = p->pool_max ? 2 * p->C : p->C;
+  p->dk = kws_net_add_tensor(kn.n, "dense_1/kernel", {p->feat, p->NC}, false, KWS_L2_COEF, p->feat, p->NC, 0.f);
+  if (p->has_bias) p->db = kws_net_add_tensor(kn.n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->n_bn = kn.n_bn;
+}
+
+// Depthwise backward kernels that leave ONLY a weight gradient behind (a block's first depthwise convolution, the context
+// block's, the first plain block's: their input is a materialised activation, no BatchNorm in front): nothing on the
+// dependency chain needs the fold of their partial rows, so the rows stay in regions of their own and one launch folds up to
+// KWS_DW_FIN_BATCH layers at the end of the pass (round 4: one small launch per block off the chain).
+struct DwFinQueue {
+  const float* part[KWS_DW_FIN_BATCH];
+  float* dw[KWS_DW_FIN_BATCH];
+  int n_parts[KWS_DW_FIN_BATCH], C[KWS_DW_FIN_BATCH];
+  int count = 0;
+  float* base = nullptr;
+  int64_t used = 0, cap = 0;
+  hipStream_t st = nullptr;
+  int flush() {
+    if (count == 0) return KWS_OK;
+    const int rc = kws_dw_grad_finalize_batch(part, n_parts, C, dw, count, st);
+    count = 0;
+    used = 0;
+    return rc;
+  }
+  // a region for the rows of one depthwise backward launch (floats = kws_dwconv_bwd_part_floats) whose fold writes dW
+  int take(int64_t floats, int Cc, float* dW, float** out) {
+    const int64_t need = (floats + 63) / 64 * 64;
+    if (count == KWS_DW_FIN_BATCH || used + need > cap) KWS_TRY(flush());
+    if (need > cap) return KWS_E_WORKSPACE;
+    *out = base + used;
+    part[count] = base + used; dw[count] = dW; n_parts[count] = (int)(floats / (5 * Cc)); C[count] = Cc;
+    used += need;
+    ++count;
+    return KWS_OK;
+  }
+};
+
+// The global-pooling tail's arguments as the program fixes them (inference as it stands; training adds its buffers and the
+// dropout draw)
+kws_gp_tail_args gp_tail_args(const Ctx& c, const float* x, float* probs) {
+  const LmProgram& p = *c.p;
+  kws_gp_tail_args g;
+  memset(&g, 0, sizeof(g));
+  g.x = x; g.Wd = c.params + p.dk; g.bd = p.has_bias ? c.params + p.db : nullptr; g.probs = probs;
+  g.B = c.B; g.T = p.T; g.C = p.C; g.NC = p.NC;
+  g.pool_max = p.pool_max; g.loss_kind = p.loss_kind; g.label_smoothing = p.label_smoothing;
+  g.keep_prob = 1.f; g.loss_batch = 1;
+  return g;
 }
 
 }  // namespace
 
 int lm_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   KWS_REQUIRE(c.spectrogram_length >= 19 && c.num_features >= 4 &&
                   c.input_size == c.spectrogram_length * c.num_features,
               "net: log-mfcc input %d != %d x %d", c.input_size, c.spectrogram_length, c.num_features);
-  // any length >= 3: the strided blocks are Keras 'same' layers - MaxPool1D(2, 2) and Conv1D(nf, 1, strides=2) both give
-  // ceil(L / 2), e.g. the function's own default spectrogram_length = 65 -> 63 -> 32 -> 16 -> 8 (model.py:1410)
-  KWS_REQUIRE(c.spectrogram_length >= 3, "net: spectrogram_length %d is too short", c.spectrogram_length);
-  LmProgram* p = new LmProgram();
-  n->lm = p;
-  int n_conv = 0, n_bn = 0, n_dw = 0;
-  auto conv = [&](int k, int cin, int cout, bool l2) {
-    ++n_conv;
-    return kws_net_add_tensor(n, "conv1d_" + std::to_string(n_conv) + "/kernel", {k, cin, cout}, false,
-                              l2 ? KWS_L2_COEF : 0.f, k * cin, k * cout, 0.f);
-  };
-  auto bn = [&](int C, int* idx) {
-    ++n_bn;
-    *idx = n_bn;
-    return kws_net_add_bn(n, n_bn, C);
-  };
-  auto dw = [&](int C) {
-    ++n_dw;
-    return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
-                              KWS_L2_COEF, 3 * C, 3, 0.f);
-  };
+  LmProgram* p = lm_new(n, LM_ATTENTION, 0.8f);  // Dropout(0.2), model.py:1471
+  KerasNames kn{n};
   p->T0 = c.spectrogram_length; p->F = c.num_features; p->C0 = 64; p->L0 = p->T0 - 2;
-  p->conv1 = conv(3, p->F, p->C0, true);
-  int idx0;
-  p->bn0 = bn(p->C0, &idx0);
+  p->conv1 = kn.conv(3, p->F, p->C0, KWS_L2_COEF);
+  p->bn0 = kn.bn(p->C0);
   kws_gather_t g0;
   p->Fp = (p->F + 3) & ~3;
   g0.L_out = p->L0; g0.cin = p->Fp; g0.taps = 3; g0.stride_t = p->Fp; g0.stride_j = p->Fp; g0.base_off = 0;
   g0.x_len = p->T0 * p->Fp; g0.x_batch_stride = p->T0 * p->Fp;
   p->g0 = g0;
+  // any length: the strided blocks are Keras 'same' layers - MaxPool1D(2, 2) and Conv1D(nf, 1, strides=2) both give
+  // ceil(L / 2), e.g. the function's own default spectrogram_length = 65 -> 63 -> 32 -> 16 -> 8 (model.py:1410)
   static const int spec[10][2] = {{64, 1}, {64, 1}, {128, 2}, {128, 1}, {192, 2}, {192, 1}, {192, 1}, {256, 2},
                                   {256, 1}, {256, 1}};  // model.py:1453-1462
-  int cin = p->C0, L = p->L0;
-  for (int i = 0; i < 10; ++i) {
-    LmBlock b;
-    b.nf = spec[i][0]; b.stride = spec[i][1]; b.cin = cin; b.Lin = L; b.Lout = (L + b.stride - 1) / b.stride;
-    b.has_short = b.stride != 1;
-    b.s1 = 1; b.pool = b.stride; b.Lmid = b.Lin; b.pad1 = 1;
-    b.ws = 0; b.bns_idx = 0;
-    memset(&b.gs, 0, sizeof(b.gs));
-    if (b.has_short) {
-      b.ws = conv(1, cin, b.nf, false);  // shortcut Conv1D has no kernel_regularizer (model.py:1431-1432)
-      b.bns = bn(b.nf, &b.bns_idx);
-      b.gs.L_out = b.Lout; b.gs.cin = cin; b.gs.taps = 1; b.gs.stride_t = b.stride * cin; b.gs.stride_j = 0;
-      b.gs.base_off = 0; b.gs.x_len = L * cin; b.gs.x_batch_stride = (int64_t)L * cin;
-    } else {
-      KWS_REQUIRE(cin == b.nf, "net: identity shortcut needs cin == nf");
-    }
-    b.dw1 = dw(cin);
-    b.pw1 = conv(1, cin, b.nf, true);
-    b.bn1 = bn(b.nf, &b.bn1_idx);
-    b.dw2 = dw(b.nf);
-    b.pw2 = conv(1, b.nf, b.nf, true);
-    b.bn2 = bn(b.nf, &b.bn2_idx);
-    p->blocks.push_back(b);
-    cin = b.nf;
-    L = b.Lout;
-  }
-  p->T = L; p->C = cin; p->NC = c.num_classes;
+  lm_begin_stack(p);
+  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL_AFTER, s[0], s[1]));
   KWS_REQUIRE(p->T <= 16, "net: %d time steps at the tail (max 16)", p->T);
-  p->att_dw = dw(cin);
-  p->att_pw = conv(1, cin, 1, true);
-  p->att_bn = bn(1, &p->att_bn_idx);
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {cin, p->NC}, false, KWS_L2_COEF, cin, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
-  p->n_bn = n_bn;
-  p->maxC = 256;
+  p->att_dw = kn.dw(p->C);
+  p->att_pw = kn.conv(1, p->C, 1, KWS_L2_COEF);
+  p->att_bn = kn.bn(1, &p->att_bn_idx);
+  lm_add_dense(kn, p);
   return KWS_OK;
 }
 
 // steffeNet, reference model.py:1663-1726
 int steffe_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   KWS_REQUIRE(c.input_size >= 3200 && c.input_size % 2 == 0, "net: steffeNet input_size %d", c.input_size);
-  LmProgram* p = new LmProgram();
-  n->lm = p;
-  p->style = 1;
-  p->drop_keep = STEFFE_DROP_KEEP;
-  int n_conv = 0, n_bn = 0, n_dw = 0;
-  auto conv = [&](int k, int cin, int cout, bool l2) {
-    ++n_conv;
-    return kws_net_add_tensor(n, "conv1d_" + std::to_string(n_conv) + "/kernel", {k, cin, cout}, false,
-                              l2 ? KWS_L2_COEF : 0.f, k * cin, k * cout, 0.f);
-  };
-  auto bn = [&](int C, int* idx) {
-    ++n_bn;
-    *idx = n_bn;
-    return kws_net_add_bn(n, n_bn, C);
-  };
-  auto dw = [&](int C) {
-    ++n_dw;
-    return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
-                              KWS_L2_COEF, 3 * C, 3, 0.f);
-  };
-  auto same = [](int L, int k, int stride, int* Lout, int* pad_l) {   // TF 'SAME'
-    *Lout = (L + stride - 1) / stride;
-    const int pad = std::max((*Lout - 1) * stride + k - L, 0);
-    *pad_l = pad / 2;
-  };
+  LmProgram* p = lm_new(n, LM_STEFFE, 0.5f);     // Dropout(0.5), model.py:1716
+  p->pool_max = true; p->has_bias = false;       // GlobalMaxPooling1D ++ GlobalAveragePooling1D -> Dense(use_bias=False), model.py:1712-1718
+  p->loss_kind = 0; p->label_smoothing = 0.1f;   // model.py:1722-1724
+  KerasNames kn{n};
   // Conv1D(256, 75, strides=50, padding='same', use_bias=False): no kernel_regularizer (model.py:1705)
   p->K0 = 75; p->K0p = 76; p->C0 = 256; p->T0 = c.input_size; p->F = 1; p->Fp = 1;
   int pl0;
-  same(c.input_size, p->K0, 50, &p->L0, &pl0);
+  kws_same_pad(c.input_size, p->K0, 50, &p->L0, &pl0);
   KWS_REQUIRE(pl0 % 2 == 0, "net: steffeNet left padding %d must be even (8-byte gather loads)", pl0);
-  p->conv1 = conv(p->K0, 1, p->C0, false);
-  int idx0;
-  p->bn0 = bn(p->C0, &idx0);
+  p->conv1 = kn.conv(p->K0, 1, p->C0, 0.f);
+  p->bn0 = kn.bn(p->C0);
   kws_gather_t g0;
   g0.L_out = p->L0; g0.cin = p->K0p; g0.taps = 1; g0.stride_t = 50; g0.stride_j = 0; g0.base_off = -pl0;
   g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
   p->g0 = g0;
-  p->ctx_dw = dw(p->C0);                                  // _context_conv(x, 256, 3, padding='same'), model.py:1708
-  p->ctx_pw = conv(1, p->C0, p->C0, true);
-  p->ctx_bn = bn(p->C0, &p->ctx_bn_idx);
+  p->ctx_dw = kn.dw(p->C0);                                  // _context_conv(x, 256, 3, padding='same'), model.py:1708
+  p->ctx_pw = kn.conv(1, p->C0, p->C0, KWS_L2_COEF);
+  p->ctx_bn = kn.bn(p->C0, &p->ctx_bn_idx);
   static const int widths[6] = {320, 384, 512, 768, 1024, 1536};  // model.py:1709
-  int cin = p->C0, L = p->L0;
-  p->maxC = p->C0;
-  for (int wi = 0; wi < 6; ++wi) {
-    for (int stride = 2; stride >= 1; --stride) {
-      LmBlock b;
-      b.nf = widths[wi]; b.stride = stride; b.cin = cin; b.Lin = L;
-      same(L, 3, stride, &b.Lout, &b.pad1);
-      b.s1 = stride; b.pool = 1; b.Lmid = b.Lout;
-      b.has_short = stride != 1;
-      b.ws = 0; b.bns_idx = 0;
-      memset(&b.gs, 0, sizeof(b.gs));
-      if (b.has_short) {
-        b.ws = conv(1, cin, b.nf, false);                 // Conv1D(nh, 1, strides, 'same', no bias), model.py:1692-1693
-        b.bns = bn(b.nf, &b.bns_idx);
-        b.gs.L_out = b.Lout; b.gs.cin = cin; b.gs.taps = 1; b.gs.stride_t = stride * cin; b.gs.stride_j = 0;
-        b.gs.base_off = 0; b.gs.x_len = L * cin; b.gs.x_batch_stride = (int64_t)L * cin;
-      } else {
-        KWS_REQUIRE(cin == b.nf, "net: identity shortcut needs cin == nf");
-      }
-      b.dw1 = dw(cin);
-      b.pw1 = conv(1, cin, b.nf, true);
-      b.bn1 = bn(b.nf, &b.bn1_idx);
-      b.dw2 = dw(b.nf);
-      b.pw2 = conv(1, b.nf, b.nf, true);
-      b.bn2 = bn(b.nf, &b.bn2_idx);
-      p->blocks.push_back(b);
-      cin = b.nf;
-      L = b.Lout;
-      p->maxC = std::max(p->maxC, b.nf);
-    }
-  }
-  p->T = L; p->C = cin; p->NC = c.num_classes;
+  lm_begin_stack(p);
+  for (int nf : widths)
+    for (int stride = 2; stride >= 1; --stride) KWS_TRY(lm_add_block(kn, p, LM_STRIDED_DW, nf, stride));
   KWS_REQUIRE(p->T >= 1 && p->T <= 64, "net: %d time steps at the tail", p->T);
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {2 * cin, p->NC}, false, KWS_L2_COEF, 2 * cin, p->NC, 0.f);
-  p->n_bn = n_bn;
+  lm_add_dense(kn, p);
   return KWS_OK;
 }
 
 // conv_1d_residual_model, reference model.py:841-908
 int residual_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   KWS_REQUIRE(c.input_size >= 4000 && c.input_size % 2 == 0, "net: conv_1d_residual input_size %d", c.input_size);
   const int fm = c.filter_mult > 0 ? c.filter_mult : 1;
-  LmProgram* p = new LmProgram();
-  n->lm = p;
-  p->style = 2;
-  p->drop_keep = 0.5f;                           // Dropout(0.5), model.py:899
-  int n_conv = 0, n_bn = 0, n_dw = 0;
-  auto conv = [&](int k, int cin, int cout, bool l2) {
-    ++n_conv;
-    return kws_net_add_tensor(n, "conv1d_" + std::to_string(n_conv) + "/kernel", {k, cin, cout}, false,
-                              l2 ? KWS_L2_COEF : 0.f, k * cin, k * cout, 0.f);
-  };
-  auto bn = [&](int C, int* idx) {
-    ++n_bn;
-    *idx = n_bn;
-    return kws_net_add_bn(n, n_bn, C);
-  };
-  auto dw = [&](int C) {
-    ++n_dw;
-    return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
-                              KWS_L2_COEF, 3 * C, 3, 0.f);
-  };
-  auto same = [](int L, int k, int stride, int* Lout, int* pad_l) {   // TF 'SAME'
-    *Lout = (L + stride - 1) / stride;
-    const int pad = std::max((*Lout - 1) * stride + k - L, 0);
-    *pad_l = pad / 2;
-  };
+  LmProgram* p = lm_new(n, LM_RESIDUAL, 0.5f);   // Dropout(0.5), model.py:899
+  KerasNames kn{n};
   // overlapping_time_slice_stack(x, 40, 20) SAME fused with Conv1D(64, 3, strides=2) (model.py:881-884), as the
   // raw-waveform net's first convolution
   int Lf, plf;
-  same(c.input_size, 40, 20, &Lf, &plf);
+  kws_same_pad(c.input_size, 40, 20, &Lf, &plf);
   p->T0 = c.input_size; p->F = 40; p->Fp = 40; p->C0 = 64 * fm; p->L0 = (Lf - 3) / 2 + 1;
-  p->conv1 = conv(3, 40, p->C0, true);
-  int idx0;
-  p->bn0 = bn(p->C0, &idx0);
+  p->conv1 = kn.conv(3, 40, p->C0, KWS_L2_COEF);
+  p->bn0 = kn.bn(p->C0);
   kws_gather_t g0;
   g0.L_out = p->L0; g0.cin = 40; g0.taps = 3; g0.stride_t = 2 * 20; g0.stride_j = 20; g0.base_off = -plf;
   g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
   p->g0 = g0;
   static const int spec[13][2] = {{128, 2}, {256, 2}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1},
                                   {256, 1}, {256, 1}, {512, 2}, {728, 2}, {728, 2}};  // model.py:888-894
-  int cin = p->C0, L = p->L0;
-  p->maxC = p->C0;
-  for (int i = 0; i < 13; ++i) {
-    LmBlock b;
-    b.nf = spec[i][0] * fm; b.stride = spec[i][1]; b.cin = cin; b.Lin = L;
-    b.s1 = 1; b.pool = b.stride; b.Lmid = L; b.pad1 = 1; b.pool3 = 1;
-    same(L, 3, b.stride, &b.Lout, &b.ppad);
-    b.has_short = b.stride != 1;
-    b.ws = 0; b.bns_idx = 0;
-    memset(&b.gs, 0, sizeof(b.gs));
-    if (b.has_short) {
-      b.ws = conv(1, cin, b.nf, false);
-      b.bns = bn(b.nf, &b.bns_idx);
-      b.gs.L_out = b.Lout; b.gs.cin = cin; b.gs.taps = 1; b.gs.stride_t = b.stride * cin; b.gs.stride_j = 0;
-      b.gs.base_off = 0; b.gs.x_len = L * cin; b.gs.x_batch_stride = (int64_t)L * cin;
-    } else {
-      KWS_REQUIRE(cin == b.nf, "net: identity shortcut needs cin == nf");
-    }
-    b.dw1 = dw(cin);
-    b.pw1 = conv(1, cin, b.nf, true);
-    b.bn1 = bn(b.nf, &b.bn1_idx);
-    b.dw2 = dw(b.nf);
-    b.pw2 = conv(1, b.nf, b.nf, true);
-    b.bn2 = bn(b.nf, &b.bn2_idx);
-    p->blocks.push_back(b);
-    cin = b.nf;
-    L = b.Lout;
-    p->maxC = std::max(p->maxC, b.nf);
-  }
+  lm_begin_stack(p);
+  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0] * fm, s[1]));
   // _reduce_block(x, 1024, 3): _reduce_conv (strides 2, 'same') then _context_conv ('valid'), model.py:895
-  const int cr = 1024 * fm;
-  for (int j = 0; j < 2; ++j) {
-    LmPlain q;
-    q.cin = cin; q.cout = cr; q.Lin = L;
-    if (j == 0) { q.stride = 2; same(L, 3, 2, &q.Lout, &q.pad_l); }
-    else { q.stride = 1; q.pad_l = 0; q.Lout = L - 2; }
-    KWS_REQUIRE(q.Lout >= 1, "net: conv_1d_residual input too short");
-    q.dw = dw(cin);
-    q.pw = conv(1, cin, cr, true);
-    q.bn = bn(cr, &q.bn_idx);
-    p->plain.push_back(q);
-    cin = cr;
-    L = q.Lout;
-    p->maxC = std::max(p->maxC, cr);
-  }
-  p->T = L; p->C = cin; p->NC = c.num_classes;
+  KWS_TRY(lm_add_plain(kn, p, 1024 * fm, 2));
+  KWS_TRY(lm_add_plain(kn, p, 1024 * fm, 1));
   KWS_REQUIRE(p->T <= 64, "net: %d time steps at the tail", p->T);
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {cin, p->NC}, false, KWS_L2_COEF, cin, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
-  p->n_bn = n_bn;
+  lm_add_dense(kn, p);
   return KWS_OK;
 }
 
@@ -693,44 +660,19 @@ int residual_build(kws_net* n) {
 int mfcc_raw_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   const int T = c.spectrogram_length, F = c.num_features;
-  KWS_REQUIRE(c.num_classes >= 2 && c.num_classes <= 64, "net: num_classes %d out of range", c.num_classes);
   KWS_REQUIRE(T >= 19 && F >= 4 && F % 4 == 0 && c.input_size > T * F, "net: mfcc_and_raw input %d, features %d x %d",
               c.input_size, T, F);
   const int Lraw = c.input_size - T * F;
   const int frame_len = 480, frame_step = 160;   // window_size_samples / window_stride_samples of prepare_model_settings
   KWS_REQUIRE(1 + (Lraw - frame_len) / frame_step == T && (T * F) % 4 == 0 && Lraw % 2 == 0,
               "net: mfcc_and_raw needs 1 + (raw %d - 480) / 160 == spectrogram_length %d", Lraw, T);
-  LmProgram* p = new LmProgram();
-  n->lm = p;
-  p->style = 3;
-  p->drop_keep = 0.7f;                           // Dropout(0.3), model.py:1648
-  int n_conv = 0, n_bn = 0, n_dw = 0;
-  auto conv = [&](int k, int cin, int cout, bool l2) {
-    ++n_conv;
-    return kws_net_add_tensor(n, "conv1d_" + std::to_string(n_conv) + "/kernel", {k, cin, cout}, false,
-                              l2 ? KWS_L2_COEF : 0.f, k * cin, k * cout, 0.f);
-  };
-  auto bn = [&](int C, int* idx) {
-    ++n_bn;
-    *idx = n_bn;
-    return kws_net_add_bn(n, n_bn, C);
-  };
-  auto dw = [&](int C) {
-    ++n_dw;
-    return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
-                              KWS_L2_COEF, 3 * C, 3, 0.f);
-  };
-  auto same = [](int L, int k, int stride, int* Lout, int* pad_l) {
-    *Lout = (L + stride - 1) / stride;
-    const int pad = std::max((*Lout - 1) * stride + k - L, 0);
-    *pad_l = pad / 2;
-  };
+  LmProgram* p = lm_new(n, LM_MFCC_AND_RAW, 0.7f);   // Dropout(0.3), model.py:1648
+  KerasNames kn{n};
   p->T0 = T; p->F = F; p->Fp = F; p->Cm = 64; p->Cr = 96; p->C0 = p->Cm + p->Cr; p->L0 = T - 2; p->Din = c.input_size;
-  int idx;
-  p->conv1 = conv(3, F, p->Cm, true);            // model.py:1615
-  p->bn0 = bn(p->Cm, &idx);
-  p->conv1r = conv(3, frame_len, p->Cr, true);   // model.py:1625
-  p->bn0r = bn(p->Cr, &idx);
+  p->conv1 = kn.conv(3, F, p->Cm, KWS_L2_COEF);            // model.py:1615
+  p->bn0 = kn.bn(p->Cm);
+  p->conv1r = kn.conv(3, frame_len, p->Cr, KWS_L2_COEF);   // model.py:1625
+  p->bn0r = kn.bn(p->Cr);
   kws_gather_t g;
   g.L_out = p->L0; g.cin = F; g.taps = 3; g.stride_t = F; g.stride_j = F; g.base_off = 0;
   g.x_len = T * F; g.x_batch_stride = p->Din;
@@ -740,39 +682,9 @@ int mfcc_raw_build(kws_net* n) {
   p->g0r = g;
   static const int spec[10][2] = {{160, 1}, {160, 1}, {192, 2}, {192, 1}, {256, 2}, {256, 1}, {320, 2}, {320, 1},
                                   {384, 2}, {384, 1}};  // model.py:1632-1641
-  int cin = p->C0, L = p->L0;
-  p->maxC = p->C0;
-  for (int i = 0; i < 10; ++i) {
-    LmBlock b;
-    b.nf = spec[i][0]; b.stride = spec[i][1]; b.cin = cin; b.Lin = L;
-    b.s1 = 1; b.pool = b.stride; b.Lmid = L; b.pad1 = 1; b.pool3 = 1;
-    same(L, 3, b.stride, &b.Lout, &b.ppad);
-    b.has_short = b.stride != 1;
-    b.ws = 0; b.bns_idx = 0;
-    memset(&b.gs, 0, sizeof(b.gs));
-    if (b.has_short) {
-      b.ws = conv(1, cin, b.nf, false);
-      b.bns = bn(b.nf, &b.bns_idx);
-      b.gs.L_out = b.Lout; b.gs.cin = cin; b.gs.taps = 1; b.gs.stride_t = b.stride * cin; b.gs.stride_j = 0;
-      b.gs.base_off = 0; b.gs.x_len = L * cin; b.gs.x_batch_stride = (int64_t)L * cin;
-    } else {
-      KWS_REQUIRE(cin == b.nf, "net: identity shortcut needs cin == nf");
-    }
-    b.dw1 = dw(cin);
-    b.pw1 = conv(1, cin, b.nf, true);
-    b.bn1 = bn(b.nf, &b.bn1_idx);
-    b.dw2 = dw(b.nf);
-    b.pw2 = conv(1, b.nf, b.nf, true);
-    b.bn2 = bn(b.nf, &b.bn2_idx);
-    p->blocks.push_back(b);
-    cin = b.nf;
-    L = b.Lout;
-    p->maxC = std::max(p->maxC, b.nf);
-  }
-  p->T = L; p->C = cin; p->NC = c.num_classes;
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {cin, p->NC}, false, KWS_L2_COEF, cin, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
-  p->n_bn = n_bn;
+  lm_begin_stack(p);
+  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0], s[1]));
+  lm_add_dense(kn, p);
   return KWS_OK;
 }
 
@@ -806,7 +718,7 @@ int lm_debug_view(const kws_net* n, int B, int training, int what, int index, in
   if (what == 4) { *offset_floats = lo.u; *count = (int64_t)B * p.T; return KWS_OK; }
   if (what == 5) { *offset_floats = lo.o[nb - 1]; *count = (int64_t)B * p.T * p.C; return KWS_OK; }
   if (what == 0) {
-    if (p.style == 3 && index <= 2) {
+    if (p.style == LM_MFCC_AND_RAW && index <= 2) {
       *offset_floats = lo.y0 + (index == 2 ? (int64_t)B * p.L0 * p.Cm : 0);
       *count = (int64_t)B * p.L0 * (index == 2 ? p.Cr : p.Cm);
       return KWS_OK;
@@ -814,7 +726,7 @@ int lm_debug_view(const kws_net* n, int B, int training, int what, int index, in
     if (index == 1) { *offset_floats = lo.y0; *count = (int64_t)B * p.L0 * p.C0; return KWS_OK; }
     for (size_t j = 0; j < p.plain.size(); ++j)
       if (index == p.plain[j].bn_idx) { *offset_floats = lo.py[j]; *count = (int64_t)B * p.plain[j].Lout * p.plain[j].cout; return KWS_OK; }
-    if (p.style == 1 && index == p.ctx_bn_idx) { *offset_floats = lo.yc; *count = (int64_t)B * p.L0 * p.C0; return KWS_OK; }
+    if (p.style == LM_STEFFE && index == p.ctx_bn_idx) { *offset_floats = lo.yc; *count = (int64_t)B * p.L0 * p.C0; return KWS_OK; }
     for (int i = 0; i < nb; ++i) {
       const LmBlock& b = p.blocks[i];
       if (b.has_short && index == b.bns_idx) { *offset_floats = lo.ys[i]; *count = (int64_t)B * b.Lout * b.nf; return KWS_OK; }
@@ -839,12 +751,8 @@ int lm_predict(const kws_net* n, const float* params, const float* state, const 
   }
   kws_lm_tail_args t;
   KWS_TRY(forward(c, x, &t));
-  if (n->lm->style != 0) {
-    kws_gp_tail_args g;
-    memset(&g, 0, sizeof(g));
-    g.x = t.x; g.Wd = params + n->lm->dk; g.probs = probs; g.B = B; g.T = n->lm->T; g.C = n->lm->C; g.NC = n->lm->NC;
-    g.keep_prob = 1.f; g.loss_batch = 1; g.pool_max = n->lm->style == 1;
-    g.bd = n->lm->style >= 2 ? params + n->lm->db : nullptr;
+  if (c.p->style != LM_ATTENTION) {
+    const kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
     return kws_gp_tail_launch(&g, 0, st);
   }
   t.probs = probs;
@@ -881,7 +789,7 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
       if (b.has_short) add(b.ws, lo.wt_ws[i], b.cin, b.nf);
     }
     for (size_t j = 0; j < p.plain.size(); ++j) add(p.plain[j].pw, lo.wt_plain[j], p.plain[j].cin, p.plain[j].cout);
-    if (p.style == 1) add(p.ctx_pw, lo.wt_ctx, p.C0, p.C0);
+    if (p.style == LM_STEFFE) add(p.ctx_pw, lo.wt_ctx, p.C0, p.C0);
     for (size_t o = 0; o < tin.size(); o += KWS_TRANSPOSE_BATCH) {
       const int nbat = (int)std::min<size_t>(KWS_TRANSPOSE_BATCH, tin.size() - o);
       KWS_TRY(kws_transpose_batch_f32(tin.data() + o, tout.data() + o, trows.data() + o, tcols.data() + o, nbat, st));
@@ -897,37 +805,7 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
   KwsSlabQueue sq;
   sq.base = ws + lo.tnq; sq.cap = lo.tnq_floats;
   sq.allow_pair = kws_net_get_gemm_mode(n) != 1;    // mode 1: the A/B reference schedule (separate input- / weight-gradient launches)
-  // Depthwise backward kernels that leave ONLY a weight gradient behind (a block's first depthwise convolution, the context
-  // block's, the first plain block's: their input is a materialised activation, no BatchNorm in front): nothing on the
-  // dependency chain needs the fold of their partial rows, so the rows stay in regions of their own and one launch folds up to
-  // KWS_DW_FIN_BATCH layers at the end of the pass (round 4: one small launch per block off the chain).
-  struct DwFinQueue {
-    const float* part[KWS_DW_FIN_BATCH];
-    float* dw[KWS_DW_FIN_BATCH];
-    int n_parts[KWS_DW_FIN_BATCH], C[KWS_DW_FIN_BATCH];
-    int count = 0;
-    float* base = nullptr;
-    int64_t used = 0, cap = 0;
-    hipStream_t st = nullptr;
-    int flush() {
-      if (count == 0) return KWS_OK;
-      const int rc = kws_dw_grad_finalize_batch(part, n_parts, C, dw, count, st);
-      count = 0;
-      used = 0;
-      return rc;
-    }
-    // a region for the rows of one depthwise backward launch (floats = kws_dwconv_bwd_part_floats) whose fold writes dW
-    int take(int64_t floats, int Cc, float* dW, float** out) {
-      const int64_t need = (floats + 63) / 64 * 64;
-      if (count == KWS_DW_FIN_BATCH || used + need > cap) KWS_TRY(flush());
-      if (need > cap) return KWS_E_WORKSPACE;
-      *out = base + used;
-      part[count] = base + used; dw[count] = dW; n_parts[count] = (int)(floats / (5 * Cc)); C[count] = Cc;
-      used += need;
-      ++count;
-      return KWS_OK;
-    }
-  } dq;
+  DwFinQueue dq;
   dq.base = ws + lo.dwq; dq.cap = lo.dwq_floats; dq.st = st;
   // join backward + BatchNorm backward in two passes (round 4): reductions, fold (dgamma, dbeta, c1 | c2), then the masked /
   // pool-routed gradient is recomputed and dy written directly - 5 tensor passes instead of the 6 of "kws_block_out_bwd,
@@ -939,20 +817,24 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
                                 grads + r.beta, coef, red, st));
     return kws_block_join_bwd(dOin, yv, c.bn_at(bn_idx), params + r.gamma, coef, outp, nullptr, 2, B, L, C, pool, relu, st);
   };
+  // a strided block's shortcut branch: its BN (no mask, in place), the 1 x 1 convolution's weight gradient (slabs queued: summed
+  // with the pass's other weight gradients) and its input gradient on the Lout strided rows, left in DXS
+  auto short_bwd = [&](int i, const float* xin) -> int {
+    const LmBlock& b = p.blocks[i];
+    KWS_TRY(join_bwd(dO, ws + lo.ys[i], b.bns, b.bns_idx, dO, b.Lout, b.nf, 1, 0));
+    KWS_TRY(sq.gemm_gather(xin, &b.gs, dO, grads + b.ws, B, b.nf, st));
+    return kws_gemm_nn_f32(dO, ws + lo.wt_ws[i], ws + lo.DXS, (int64_t)B * b.Lout, b.nf, b.cin, nullptr, st);
+  };
   // ---- tail forward + backward ----
-  if (p.style != 0) {
-    kws_gp_tail_args g;
-    memset(&g, 0, sizeof(g));
-    g.x = t.x; g.Wd = params + p.dk; g.labels = y_onehot; g.probs = probs; g.dX = dO; g.fd = ws + lo.fd; g.dl = ws + lo.dl;
-    g.per_loss = ws + lo.per_loss; g.per_correct = ws + lo.per_correct; g.B = B; g.T = p.T; g.C = p.C; g.NC = p.NC;
-    g.pool_max = p.style == 1; g.loss_kind = p.style == 1 ? 0 : 1;
-    g.bd = p.style >= 2 ? params + p.db : nullptr;
-    g.seed = seed; g.step = step; g.keep_prob = p.drop_keep; g.label_smoothing = STEFFE_LABEL_SMOOTH;
-    g.loss_batch = loss_batch; g.row_offset = row_offset;
+  if (p.style != LM_ATTENTION) {
+    kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
+    g.labels = y_onehot; g.dX = dO; g.fd = ws + lo.fd; g.dl = ws + lo.dl;
+    g.per_loss = ws + lo.per_loss; g.per_correct = ws + lo.per_correct;
+    g.seed = seed; g.step = step; g.keep_prob = p.drop_keep; g.loss_batch = loss_batch; g.row_offset = row_offset;
     KWS_TRY(kws_gp_tail_launch(&g, 1, st));
     KWS_TRY(kws_metrics_launch(g.per_loss, g.per_correct, B, metrics, st));
-    KWS_TRY(kws_small_wgrad_launch(g.fd, g.dl, grads + p.dk, p.style >= 2 ? grads + p.db : nullptr, B,
-                                   p.style == 1 ? 2 * p.C : p.C, p.NC, ws + lo.swg, st));
+    KWS_TRY(kws_small_wgrad_launch(g.fd, g.dl, grads + p.dk, p.has_bias ? grads + p.db : nullptr, B, p.feat, p.NC, ws + lo.swg,
+                                   st));
     // ---- plain blocks after the residual stack, last to first: dO is the gradient wrt the materialised activation
     for (int j = (int)p.plain.size() - 1; j >= 0; --j) {
       const LmPlain& q = p.plain[j];
@@ -993,7 +875,7 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
   for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
     const LmBlock& b = p.blocks[i];
     const int64_t M = (int64_t)B * b.Lmid;
-    const float* xin = i == 0 ? (p.style == 1 ? ws + lo.ac : ws + lo.a0) : ws + lo.o[i - 1];
+    const float* xin = i == 0 ? (p.style == LM_STEFFE ? ws + lo.ac : ws + lo.a0) : ws + lo.o[i - 1];
     // main branch: join backward (maxpool routing + ReLU6 mask) -> BN2 -> pointwise 2
     int np;
     if (b.pool3) {   // the 3-wide SAME join keeps the one-pass form (an input position collects up to three windows)
@@ -1022,26 +904,19 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
     // add_strided pass afterwards; gemm mode 1 (the A/B reference schedule) keeps the order and the launches of rounds 3 - 5
     const bool short_first = b.has_short && sq.allow_pair && b.stride >= 2 && (int64_t)(b.Lout - 1) * b.stride < b.Lin;
     if (b.has_short && short_first) {
-      const int64_t Mo = (int64_t)B * b.Lout;
-      KWS_TRY(join_bwd(dO, ws + lo.ys[i], b.bns, b.bns_idx, dO, b.Lout, b.nf, 1, 0));   // the shortcut's BN: no mask, in place
-      KWS_TRY(sq.gemm_gather(xin, &b.gs, dO, grads + b.ws, B, b.nf, st));
-      KWS_TRY(kws_gemm_nn_f32(dO, ws + lo.wt_ws[i], ws + lo.DXS, Mo, b.nf, b.cin, nullptr, st));
+      KWS_TRY(short_bwd(i, xin));
       KWS_TRY(kws_dwconv_bwd_acc_strided_f32(DZ, xin, params + b.dw1, ws + lo.DXS, b.stride, b.Lout, dX, dpart, B, b.Lin, b.Lmid, b.cin,
                                              b.s1, b.pad1, st));
     } else if (!b.has_short) {   // identity shortcut: the join's other gradient is added while the depthwise input gradient is written
       KWS_TRY(kws_dwconv_bwd_acc_f32(DZ, xin, params + b.dw1, dO, dX, dpart, B, b.Lin, b.Lmid, b.cin, b.s1, b.pad1, st));
     } else {
       KWS_TRY(kws_dwconv_bwd_f32(DZ, xin, nullptr, params + b.dw1, dX, dpart, B, b.Lin, b.Lmid, b.cin, b.s1, b.pad1, st));
-      // residual branch
-      const int64_t Mo = (int64_t)B * b.Lout;
-      KWS_TRY(join_bwd(dO, ws + lo.ys[i], b.bns, b.bns_idx, dO, b.Lout, b.nf, 1, 0));   // the shortcut's BN: no mask, in place
-      KWS_TRY(sq.gemm_gather(xin, &b.gs, dO, grads + b.ws, B, b.nf, st));   // slabs queued: summed with the pass's other weight gradients
-      KWS_TRY(kws_gemm_nn_f32(dO, ws + lo.wt_ws[i], ws + lo.DXS, Mo, b.nf, b.cin, nullptr, st));
+      KWS_TRY(short_bwd(i, xin));   // residual branch
       KWS_TRY(kws_add_strided_f32(dX, ws + lo.DXS, B, b.Lin, b.Lout, b.cin, b.stride, st));
     }
     std::swap(dO, dX);
   }
-  if (p.style == 1) {  // ---- context block: dO is the gradient wrt its activated output ----
+  if (p.style == LM_STEFFE) {  // ---- context block: dO is the gradient wrt its activated output ----
     const int64_t M = (int64_t)B * p.L0;
     KWS_TRY(join_bwd(dO, ws + lo.yc, p.ctx_bn, p.ctx_bn_idx, G, p.L0, p.C0, 1, 1));
     KWS_TRY(sq.pair(G, ws + lo.wt_ctx, DZ, ws + lo.zc, grads + p.ctx_pw, M, p.C0, p.C0, st));
@@ -1050,7 +925,7 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
     KWS_TRY(kws_dwconv_bwd_f32(DZ, ws + lo.a0, nullptr, params + p.ctx_dw, dX, dpart, B, p.L0, p.L0, p.C0, 1, 1, st));
     std::swap(dO, dX);
   }
-  if (p.style == 3) {  // ---- the two stems: split the gradient of the concatenation, then each like a first convolution
+  if (p.style == LM_MFCC_AND_RAW) {  // ---- the two stems: split the gradient of the concatenation, then each like a first convolution
     const int64_t M = (int64_t)B * p.L0;
     float* dOm = dX;
     float* dOr = dX + M * p.Cm;
@@ -1071,12 +946,12 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
   // ---- first convolution ----
   {
     KWS_TRY(join_bwd(dO, ws + lo.y0, p.bn0, 1, G, p.L0, p.C0, 1, 1));
-    if (p.style != 1 && p.Fp == p.F) {   // its gradient is written in place: the slabs join the pass's batched sum
+    if (p.style != LM_STEFFE && p.Fp == p.F) {   // its gradient is written in place: the slabs join the pass's batched sum
       KWS_TRY(sq.gemm_gather(x, &p.g0, G, grads + p.conv1, B, p.C0, st));
       return sq.flush(st);
     }
     KWS_TRY(sq.flush(st));   // the pointwise weight gradients of the whole pass: one sum (two past 16 layers)
-    if (p.style == 1) {  // gradient of the zero-padded [76, C0] kernel; its first 75 rows are the kernel's
+    if (p.style == LM_STEFFE) {  // gradient of the zero-padded [76, C0] kernel; its first 75 rows are the kernel's
       float* gw = ws + lo.gwpad;
       KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, G, gw, B, p.C0, ws + lo.tn, st));
       KWS_HIP(hipMemcpyAsync(grads + p.conv1, gw, (size_t)p.K0 * p.C0 * 4, hipMemcpyDeviceToDevice, st));

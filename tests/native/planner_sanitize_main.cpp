@@ -1,7 +1,9 @@
 // Host-side planners of libkws_hip under AddressSanitizer + UBSan.  The library's sources are built
 // HOST-ONLY (hipcc --offload-host-only: kernels become launch stubs that are never called here) with -fsanitize=address,undefined and
 // this driver walks everything that does pointer / offset arithmetic on the host without touching a GPU:
-//   * the layer tables of all five net kinds (kws_net_create, kws_net_tensor_info): tensors inside their buffers, no overlap;
+//   * the layer tables of all seven net kinds (kws_net_create, kws_net_tensor_info): tensors inside their buffers, no overlap;
+//   * the error path of every builder: configs that must be refused come back KWS_E_INVALID with a null handle, and what the
+//     builder had allocated by then is freed (LeakSanitizer reports at exit);
 //   * the workspace layouts behind kws_net_workspace_bytes for awkward batches (1, 3, 70, 384, 1024, 2048), both modes, and every
 //     debug view into them (inside the reported size, pairwise disjoint);
 //   * the GEMM planners over every pointwise shape of the nets and those batches: kws_gemm_nn_stats_rows, kws_gemm_num_row_tiles,
@@ -109,13 +111,27 @@ int main() {
   walk_net(KWS_NET_TS_ATTENTION, 32, 2, 16000, 0, 0, "ts_attention/32 x2");
   walk_net(KWS_NET_LOG_MFCC, 32, 1, 98 * 40, 98, 40, "log_mfcc/32 98x40");
   walk_net(KWS_NET_LOG_MFCC, 12, 1, 65 * 40, 65, 40, "log_mfcc/12 65x40");
+  walk_net(KWS_NET_LOG_MFCC, 12, 1, 98 * 257, 98, 257, "spectrogram");
   walk_net(KWS_NET_STEFFE, 12, 1, 16000, 0, 0, "steffe");
   walk_net(KWS_NET_RESIDUAL, 12, 1, 16000, 0, 0, "residual");
+  walk_net(KWS_NET_RESIDUAL, 12, 2, 16000, 0, 0, "residual x2");
   walk_net(KWS_NET_MFCC_AND_RAW, 12, 1, 98 * 40 + 16000, 98, 40, "mfcc_and_raw");
-  // a config that must be refused, not walked
-  kws_net_config_t cfg = {99, 12, 1, 16000, 0, 0};
-  kws_net_t* net = nullptr;
-  CHECK(kws_net_create(&cfg, &net) != KWS_OK && net == nullptr, "unknown kind accepted");
+  walk_net(KWS_NET_CONV_1D_FAST, 12, 1, 16000, 0, 0, "conv_1d_fast");
+  walk_net(KWS_NET_CONV_1D_SPEC, 12, 1, 98 * 257, 0, 0, "conv_1d_spec");
+  // configs that must be refused, not walked: class counts out of range, an input that is not T x F, lengths a stem or
+  // the stack cannot take, a raw part that does not give T frames, an unknown kind
+  static const kws_net_config_t REFUSED[] = {
+      {KWS_NET_LOG_MFCC, 1, 1, 3920, 98, 40},      {KWS_NET_LOG_MFCC, 65, 1, 3920, 98, 40},
+      {KWS_NET_LOG_MFCC, 12, 1, 3921, 98, 40},     {KWS_NET_STEFFE, 12, 1, 3198, 0, 0},
+      {KWS_NET_STEFFE, 12, 1, 16001, 0, 0},        {KWS_NET_RESIDUAL, 12, 1, 3998, 0, 0},
+      {KWS_NET_MFCC_AND_RAW, 12, 1, 19921, 98, 40}, {KWS_NET_MFCC_AND_RAW, 12, 1, 18920, 98, 40},
+      {KWS_NET_TS_ATTENTION, 1, 1, 16000, 0, 0},   {KWS_NET_CONV_1D_FAST, 65, 1, 16000, 0, 0},
+      {99, 12, 1, 16000, 0, 0}};
+  for (const kws_net_config_t& cfg : REFUSED) {
+    kws_net_t* net = nullptr;
+    CHECK(kws_net_create(&cfg, &net) == KWS_E_INVALID && net == nullptr, "config (%d, %d, %d, %d, %d, %d) accepted", cfg.kind,
+          cfg.num_classes, cfg.filter_mult, cfg.input_size, cfg.spectrogram_length, cfg.num_features);
+  }
   // tn_plan's memo (std::map under a mutex) from four threads at once, fresh shapes
   std::vector<std::thread> th;
   for (int t = 0; t < 4; ++t)

@@ -23,9 +23,9 @@ def _golden(name):
         return json.load(f)[name]
 
 
-def _native_table(kind, nc=12, input_size=16000):
+def _native_table(kind, nc=12, input_size=16000, filter_mult=1, spectrogram_length=0, num_features=0):
     lib = _lib.load()
-    cfg = _lib.NetConfig(kind, nc, 1, input_size, 0, 0)
+    cfg = _lib.NetConfig(kind, nc, filter_mult, input_size, spectrogram_length, num_features)
     h = ctypes.c_void_p()
     _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
     out = []
