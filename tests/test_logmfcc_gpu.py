@@ -14,22 +14,14 @@ from oracle.net import LogMfccNet
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
 
+from net_parity import check_step, perturb, relu_masks
+
 pytestmark = pytest.mark.gpu
 
 
 def _pair(num_classes=32, seed=11, F=40, T=98):
     ora = LogMfccNet(num_classes=num_classes, spectrogram_length=T, num_features=F, dtype=np.float64)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            ora.params[k] = (1.0 + 0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('beta') or k.endswith('bias'):
-            ora.params[k] = (0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    perturb(ora, seed)
     net = DeviceNet(_lib.KWS_NET_LOG_MFCC, num_classes, input_size=T * F, spectrogram_length=T, num_features=F)
     net.set_weights(dict(ora.params, **ora.state))
     return ora, net
@@ -47,26 +39,12 @@ def _decisions(net, ora, B):
     of the kernels: pre = fmaf(y, scale, shift))."""
     shapes = {ora.first[1]: (B, ora.T0 - 2, 64), ora.att[2]: (B, ora.T, 1)}
     pools = {}
-    for i, blk in enumerate(ora.blocks):
-        if 'short' in blk:
-            shapes[blk['short'][1]] = None                       # linear BN: no mask
+    for i, blk in enumerate(ora.blocks):                         # a shortcut's BN is linear: no mask
         shapes[blk['bn1']] = (B, blk['Lin'], blk['nf'])
         shapes[blk['bn2']] = (B, blk['Lin'], blk['nf'])
         if blk['stride'] != 1:
             pools[i] = blk['bn2']
-    masks, pre_of = {}, {}
-    for idx, shp in shapes.items():
-        if shp is None:
-            continue
-        C = shp[2]
-        bn = net.debug_view(B, 2, idx)
-        if idx == ora.att[2]:
-            y = net.debug_view(B, 4, 0).reshape(shp)
-        else:
-            y = net.debug_view(B, 0, idx).reshape(shp)
-        pre = (y.astype(np.float64) * bn[:C].astype(np.float64) + bn[C:2 * C].astype(np.float64)).astype(np.float32)
-        masks[idx] = ((pre > 0) & (pre <= 6)).astype(np.float64)
-        pre_of[idx] = pre
+    masks, pre_of = relu_masks(net, B, shapes, y_views={ora.att[2]: (4, 0)})    # the attention logit has a view of its own
     args = {}
     for i, idx in pools.items():
         a = np.minimum(np.maximum(pre_of[idx], np.float32(0)), np.float32(6))
@@ -106,25 +84,10 @@ def test_train_fwd_bwd_matches_oracle(B, nc, F):
     probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
     torch.cuda.synchronize()
     masks, args = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
-                                               relu_masks=masks, pool_args=args)
-    got = probs.cpu().numpy()
-    assert np.abs(got - p).max() < 2e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    m = net.metrics.cpu().numpy()
-    assert abs(m[0] / B - loss) < 5e-5
-    assert m[1] == (p.argmax(1) == y.argmax(1)).sum()
-    g = net.grads_dict()
-    for k, ref in grads.items():
-        if k in ora.l2_names:
-            ref = ref - 2e-5 * ora.params[k].astype(np.float64)
-        ref = ref.reshape(g[k].shape)
-        err = np.abs(g[k] - ref).max() / max(np.abs(ref).max(), 1e-7)
-        assert err < 1e-4, (k, err)
-    w = net.get_weights()
-    for idx, (mean, var) in cache['batch_stats'].items():
-        mm = ora.state['batch_normalization_%d/moving_mean' % idx].astype(np.float64)
-        np.testing.assert_allclose(w['batch_normalization_%d/moving_mean' % idx], mm - (mm - mean) * 0.01, atol=5e-6)
+    ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
+                             relu_masks=masks, pool_args=args)
+    check_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
+               moving_mean_atol=5e-6)
 
 
 def test_config_c3_features_net_head32to12():
@@ -208,17 +171,10 @@ def test_odd_lengths_pool_in_ceil_mode(T):
     probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=5, step=1)
     torch.cuda.synchronize()
     masks, args = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=5, step=1,
-                                               relu_masks=masks, pool_args=args)
-    got = probs.cpu().numpy()
-    assert np.abs(got - p).max() < 2e-5 and np.array_equal(got.argmax(1), p.argmax(1))
-    assert abs(net.metrics.cpu().numpy()[0] / B - loss) < 5e-5
-    g = net.grads_dict()
-    for k, ref in grads.items():
-        if k in ora.l2_names:
-            ref = ref - 2e-5 * ora.params[k].astype(np.float64)
-        ref = ref.reshape(g[k].shape)
-        assert np.abs(g[k] - ref).max() / max(np.abs(ref).max(), 1e-7) < 1e-4, k
+    ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=5, step=1,
+                             relu_masks=masks, pool_args=args)
+    check_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
+               moving_mean_atol=5e-6)
 
 
 def test_paired_backward_launches_are_bit_identical_for_the_residual_program():

@@ -9,33 +9,21 @@ from oracle.net import SteffeNet
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
 
+from net_parity import check_step, perturb, relu_masks, waveform_batch
+
 pytestmark = pytest.mark.gpu
 
 
 def _pair(nc=12, seed=5):
     ora = SteffeNet(num_classes=nc, dtype=np.float64)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            ora.params[k] = (1.0 + 0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    perturb(ora, seed)
     net = DeviceNet(_lib.KWS_NET_STEFFE, nc, input_size=16000)
     net.set_weights(dict(ora.params, **ora.state))
     return ora, net
 
 
 def _batch(B, nc, seed):
-    rng = np.random.RandomState(seed)
-    lab = rng.randint(0, nc, B)
-    t = np.arange(16000) / 16000.0
-    x = rng.randn(B, 16000) * 0.0774 + 0.05 * np.sin(2 * np.pi * 200.0 * (1 + lab)[:, None] * t[None, :])
-    return x.astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
+    return waveform_batch(B, nc, seed)
 
 
 def _decisions(net, ora, B):
@@ -43,13 +31,7 @@ def _decisions(net, ora, B):
     for blk in ora.blocks:
         shapes[blk['bn1']] = (B, blk['Lout'], blk['nf'])
         shapes[blk['bn2']] = (B, blk['Lout'], blk['nf'])
-    masks = {}
-    for idx, shp in shapes.items():
-        C = shp[2]
-        bn = net.debug_view(B, 2, idx)
-        y = net.debug_view(B, 0, idx).reshape(shp)
-        pre = (y.astype(np.float64) * bn[:C].astype(np.float64) + bn[C:2 * C].astype(np.float64)).astype(np.float32)
-        masks[idx] = ((pre > 0) & (pre <= 6)).astype(np.float64)
+    masks, _ = relu_masks(net, B, shapes)
     h = net.debug_view(B, 5, 0).reshape(B, ora.T, ora.C)
     ind = (h == h.max(axis=1, keepdims=True)).astype(np.float64)
     return masks, ind
@@ -79,25 +61,10 @@ def test_train_fwd_bwd_matches_oracle(B):
     probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
     torch.cuda.synchronize()
     masks, ind = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
-                                               relu_masks=masks, pool_ind=ind)
-    got = probs.cpu().numpy()
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    m = net.metrics.cpu().numpy()
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == y.argmax(1)).sum()
-    g = net.grads_dict()
-    for k, ref in grads.items():
-        if k in ora.l2_names:
-            ref = ref - 2e-5 * ora.params[k].astype(np.float64)
-        ref = ref.reshape(g[k].shape)
-        err = np.abs(g[k] - ref).max() / max(np.abs(ref).max(), 1e-7)
-        assert err < 2e-4, (k, err)
-    w = net.get_weights()
-    for idx, (mean, var) in cache['batch_stats'].items():
-        mm = ora.state['batch_normalization_%d/moving_mean' % idx].astype(np.float64)
-        np.testing.assert_allclose(w['batch_normalization_%d/moving_mean' % idx], mm - (mm - mean) * 0.01, atol=5e-6)
+    ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
+                             relu_masks=masks, pool_ind=ind)
+    check_step(ora, net, probs, y, ref, probs_atol=5e-5, loss_atol=1e-4, grad_rtol=2e-4,
+               moving_mean_atol=5e-6)
 
 
 def test_speech_model_trains():
