@@ -365,6 +365,11 @@ int kws_rmsprop_step(float* p, const float* grad, float* acc, const float* l2, i
                      float rho, float eps, float grad_scale, void* stream);
 int kws_sgd_momentum_step(float* p, const float* grad, float* vel, const float* l2, int64_t n,
                           float lr, float momentum, float grad_scale, void* stream);
+/* Keras 2.1.2 Adam (reference model.py:153,251,306,403,464): m' = beta1*m + (1-beta1)*g, v' = beta2*v + (1-beta2)*g^2,
+ * p' = p - lr_t*m'/(sqrt(v') + eps).  lr_t = lr*sqrt(1-beta2^t)/(1-beta1^t) with t = iterations + 1 is the CALLER's (one host
+ * value per step); eps is added to the un-corrected sqrt(v'), which is not torch.optim.Adam's rule.  m and v: n floats each. */
+int kws_adam_step(float* p, const float* grad, float* m, float* v, const float* l2, int64_t n, float lr_t,
+                  float beta1, float beta2, float eps, float grad_scale, void* stream);
 /* out[0] = sum_i l2[i]*p[i]^2 (Keras regularisation loss) */
 int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* stream);
 

@@ -150,6 +150,7 @@ SIGNATURES = {
     "kws_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _I64, _I, _P]),
     "kws_rmsprop_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P]),
     "kws_sgd_momentum_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _P]),
+    "kws_adam_step": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     "kws_l2_loss": (_I, [_P, _P, _I64, _P, _P]),
     "kws_net_create": (_I, [ctypes.POINTER(NetConfig), ctypes.POINTER(_P)]),
     "kws_net_destroy": (_I, [_P]),

@@ -2,6 +2,9 @@
 // Keras 2.1.2 semantics, constants pinned by the reference graph_def:
 //   RMSprop: a' = rho*a + (1-rho)*g^2 ; p' = p - lr*g / (sqrt(a') + eps)      (model.py:834)
 //   SGD    : v' = m*v - lr*g         ; p' = p + v'                            (model.py:96,110)
+//   Adam   : m' = b1*m + (1-b1)*g ; v' = b2*v + (1-b2)*g^2 ; p' = p - lr_t*m' / (sqrt(v') + eps)   (model.py:153,251,306,403,464)
+//            lr_t = lr*sqrt(1-b2^t)/(1-b1^t), t = iterations+1, comes from the host; eps sits beside the UN-corrected sqrt(v')
+//            (Keras 2.1.2 / the TensorFlow-1 rule, not torch's): 8 streams of n floats
 // g = grad*grad_scale + 2*l2[i]*p folds the kernel_regularizer=l2(1e-5) gradient (model.py:37,807)
 // and the data-parallel 1/world averaging into the same pass: 6 streams of n floats, HBM-bound.
 #include "common.h"
@@ -46,6 +49,41 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   const float v = mom * vel[i] - lr * g;
   vel[i] = v;
   p[i] = p[i] + v;
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ grad,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ l2, int64_t n, float lr_t, float b1, float b2,
+                                                   float eps, float gs) {
+  const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = i4 * 4;
+  if (i + 3 < n) {
+    float4 pv = reinterpret_cast<float4*>(p)[i4];
+    const float4 gv = reinterpret_cast<const float4*>(grad)[i4];
+    float4 mv = reinterpret_cast<float4*>(m)[i4];
+    float4 vv = reinterpret_cast<float4*>(v)[i4];
+    const float4 lv = reinterpret_cast<const float4*>(l2)[i4];
+    float g;
+#define KWS_ADAM(c)                                  \
+  g = fmaf(2.0f * lv.c, pv.c, gv.c * gs);            \
+  mv.c = b1 * mv.c + (1.0f - b1) * g;                \
+  vv.c = b2 * vv.c + (1.0f - b2) * g * g;            \
+  pv.c = pv.c - lr_t * mv.c / (sqrtf(fmaxf(vv.c, 0.0f)) + eps);
+    KWS_ADAM(x) KWS_ADAM(y) KWS_ADAM(z) KWS_ADAM(w)
+#undef KWS_ADAM
+    reinterpret_cast<float4*>(p)[i4] = pv;
+    reinterpret_cast<float4*>(m)[i4] = mv;
+    reinterpret_cast<float4*>(v)[i4] = vv;
+  } else {
+    for (int64_t j = i; j < n; ++j) {
+      const float g = fmaf(2.0f * l2[j], p[j], grad[j] * gs);
+      const float m2 = b1 * m[j] + (1.0f - b1) * g;
+      const float v2 = b2 * v[j] + (1.0f - b2) * g * g;
+      m[j] = m2;
+      v[j] = v2;
+      p[j] = p[j] - lr_t * m2 / (sqrtf(fmaxf(v2, 0.0f)) + eps);
+    }
+  }
 }
 
 __global__ __launch_bounds__(1024) void l2_loss_kernel(const float* __restrict__ p, const float* __restrict__ l2,
@@ -98,6 +136,17 @@ int kws_sgd_momentum_step(float* p, const float* grad, float* vel, const float* 
   hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, (hipStream_t)stream, p, grad, vel,
                      l2, n, lr, momentum, grad_scale);
   KWS_LAUNCH_CHECK("sgd_kernel");
+  return KWS_OK;
+}
+
+int kws_adam_step(float* p, const float* grad, float* m, float* v, const float* l2, int64_t n, float lr_t, float beta1,
+                  float beta2, float eps, float grad_scale, void* stream) {
+  KWS_REQUIRE(p && grad && m && v && l2 && n > 0 && m != v, "adam: bad arguments");
+  const int64_t n4 = ceil_div64(n, 4);
+  KwsProfScope prof("optimizer", 12.0 * n, 32.0 * n, (hipStream_t)stream);
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ceil_div64(n4, 256)), dim3(256), 0, (hipStream_t)stream, p, grad, m, v,
+                     l2, n, lr_t, beta1, beta2, eps, grad_scale);
+  KWS_LAUNCH_CHECK("adam_kernel");
   return KWS_OK;
 }
 

@@ -15,6 +15,7 @@ import queue
 import sys
 import threading
 import time
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -39,7 +40,7 @@ from .net import DeviceNet
 
 
 # ------------------------------------------------------------------------------------------------
-# optimizers (hyper-parameters only; the update itself is kws_rmsprop_step / kws_sgd_momentum_step)
+# optimizers (hyper-parameters only; the update itself is kws_rmsprop_step / kws_sgd_momentum_step / kws_adam_step)
 # ------------------------------------------------------------------------------------------------
 class _LrVar(object):
     """Stand-in for the Keras backend variable `optimizer.lr` (read/written by ReduceLROnPlateau
@@ -55,6 +56,17 @@ class _LrVar(object):
 class Optimizer(object):
     def __init__(self, lr):
         self.lr = _LrVar(lr)
+
+    # optimizer state beyond net.slots and lr, as everything that carries optimizer state sees it: extra device buffers
+    # (checkpointed and broadcast beside net.slots) and host scalars (checkpointed, broadcast from rank 0)
+    def extra_slots(self, net):
+        return []
+
+    def get_scalars(self):
+        return []
+
+    def set_scalars(self, values):
+        pass
 
 
 class RMSprop(Optimizer):
@@ -81,6 +93,37 @@ class SGD(Optimizer):
 
     def apply(self, net, grad_scale, stream=None):
         net.sgd_step(float(self.lr), self.momentum, grad_scale, stream)
+
+
+class Adam(Optimizer):
+    """keras.optimizers.Adam(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.) - reference model.py:153,251,306,
+    403,464.  Keras 2.1.2 rule: t = iterations + 1; lr_t = lr*sqrt(1 - beta_2^t)/(1 - beta_1^t); epsilon is added to the
+    un-corrected sqrt(v) (torch.optim.Adam puts it elsewhere).  First moment in net.slots, second in net.second_slots()."""
+
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.0, amsgrad=False):
+        Optimizer.__init__(self, lr)
+        self.beta_1, self.beta_2, self.epsilon, self.decay = beta_1, beta_2, epsilon, decay
+        self.iterations = 0
+        if decay or amsgrad:
+            raise NotImplementedError("Adam decay != 0 / amsgrad are not used by the reference")
+
+    def step_size(self):
+        """lr_t of the NEXT update, in float64 on the host (one float32 argument of the kernel)."""
+        t = self.iterations + 1
+        return float(self.lr) * np.sqrt(1.0 - float(self.beta_2) ** t) / (1.0 - float(self.beta_1) ** t)
+
+    def apply(self, net, grad_scale, stream=None):
+        net.adam_step(self.step_size(), self.beta_1, self.beta_2, self.epsilon, grad_scale, stream)
+        self.iterations += 1
+
+    def extra_slots(self, net):
+        return [net.second_slots()]
+
+    def get_scalars(self):
+        return [self.iterations]
+
+    def set_scalars(self, values):
+        self.iterations = int(values[0])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -364,7 +407,13 @@ class Model(object):
         """Weights + optimizer slots + lr under Keras variable names (.npz container)."""
         w = self.net.get_weights()
         blob = {k.replace('/', '|'): v for k, v in w.items()}
+        blob['__optimizer__'] = np.array(type(self.optimizer).__name__)
         blob['__optimizer_slots__'] = self.net.slots.cpu().numpy()
+        for i, buf in enumerate(self.optimizer.extra_slots(self.net)):       # Adam: the second moment ...
+            blob['__optimizer_slots_%d__' % (i + 2)] = buf.cpu().numpy()
+        scalars = self.optimizer.get_scalars()                               # ... and `iterations`
+        if scalars:
+            blob['__optimizer_scalars__'] = np.asarray(scalars, np.int64)
         blob['__lr__'] = np.float32(self.optimizer.lr.value)
         blob['__step__'] = np.int64(self._step)
         blob['__model_name__'] = np.array(self.name)
@@ -380,9 +429,33 @@ class Model(object):
             w = OrderedDict((k.replace('|', '/'), z[k]) for k in z.files if not k.startswith('__'))
             self.net.set_weights(w)
             if '__optimizer_slots__' in z.files:
-                self.net.slots.copy_(torch.from_numpy(z['__optimizer_slots__']))
-                self.optimizer.lr.value = np.float32(z['__lr__'])
                 self._step = int(z['__step__'])
+                mine = type(self.optimizer).__name__
+                saved = str(z['__optimizer__']) if '__optimizer__' in z.files else mine   # (files older than the key: trusted)
+                extra = self.optimizer.extra_slots(self.net)
+                if saved != mine:
+                    # Keras' own behaviour for optimizer state that does not fit: the weights load, the optimizer starts fresh.
+                    # One optimizer's slot is not another's (Adam's first moment is no RMSprop accumulator).
+                    warnings.warn("%s was saved under %s, this model trains with %s: weights loaded, optimizer state "
+                                  "starts fresh" % (filepath, saved, mine))
+                    for buf in [self.net.slots] + extra:
+                        buf.zero_()
+                    if self.optimizer.get_scalars():
+                        self.optimizer.set_scalars([0] * len(self.optimizer.get_scalars()))
+                else:
+                    keys = ['__optimizer_slots_%d__' % (i + 2) for i in range(len(extra))]
+                    if self.optimizer.get_scalars():
+                        keys.append('__optimizer_scalars__')
+                    missing = [k for k in keys if k not in z.files]
+                    if missing:
+                        raise ValueError("%s does not hold the state of a %s optimizer (no %s)" %
+                                         (filepath, mine, ', '.join(missing)))
+                    self.net.slots.copy_(torch.from_numpy(z['__optimizer_slots__']))
+                    for key, buf in zip(keys, extra):
+                        buf.copy_(torch.from_numpy(z[key]))
+                    if self.optimizer.get_scalars():
+                        self.optimizer.set_scalars([int(v) for v in z['__optimizer_scalars__']])
+                    self.optimizer.lr.value = np.float32(z['__lr__'])
         self.sync_replicas()
 
     def sync_replicas(self):
@@ -391,14 +464,18 @@ class Model(object):
         cannot drift apart through a one-rank load or through their rank-local BN statistics."""
         if not parallel.active():
             return
-        for buf in (self.net.params, self.net.state, self.net.slots):
+        for buf in [self.net.params, self.net.state, self.net.slots] + self.optimizer.extra_slots(self.net):
             parallel.broadcast_params(buf)
-        t = torch.tensor([float(self.optimizer.lr.value), float(self._step), float(self.stop_training)],
+        scalars = self.optimizer.get_scalars()      # Adam: `iterations` (exact in float64)
+        t = torch.tensor([float(self.optimizer.lr.value), float(self._step), float(self.stop_training)] +
+                         [float(v) for v in scalars],
                          dtype=torch.float64, device=self.device if parallel.dist.get_backend() == 'nccl' else 'cpu')
         parallel.dist.broadcast(t, src=0)
         self.optimizer.lr.value = np.float32(t[0].item())
         self._step = int(t[1].item())
         self.stop_training = bool(t[2].item())
+        if scalars:
+            self.optimizer.set_scalars([int(t[3 + i].item()) for i in range(len(scalars))])
 
     def summary(self):
         print("Model: %s" % self.name)

@@ -60,6 +60,7 @@ class DeviceNet(object):
             self.l2 = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
             self.metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
             self.reg_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.slots2 = None        # Adam's second moment: allocated by the first adam_step (RMSprop / SGD nets never pay for it)
         self._ws = None
         self._ws_key = None
         # arithmetic of the pointwise GEMMs, a property of THIS handle: 0 = f32 MFMA (the product path), 2 = the fp16 x 2
@@ -111,6 +112,8 @@ class DeviceNet(object):
         self.state.copy_(torch.from_numpy(st))
         self.l2.copy_(torch.from_numpy(l2))
         self.slots.zero_()
+        if self.slots2 is not None:
+            self.slots2.zero_()
         self.grads.zero_()
 
     def get_weights(self):
@@ -216,3 +219,16 @@ class DeviceNet(object):
     def sgd_step(self, lr, momentum=0.9, grad_scale=1.0, stream=None):
         _lib.call("kws_sgd_momentum_step", _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.slots),
                   _lib.ptr(self.l2), self.n_params, lr, momentum, grad_scale, _lib.stream_ptr(stream))
+
+    def second_slots(self):
+        """Adam's second-moment buffer (`slots` holds the first moment), zeros on first use."""
+        if self.slots2 is None:
+            with torch.cuda.device(self.device):
+                self.slots2 = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        return self.slots2
+
+    def adam_step(self, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, stream=None):
+        """One Adam update; lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) is the caller's (keras_api.Adam.step_size)."""
+        _lib.call("kws_adam_step", _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.slots),
+                  _lib.ptr(self.second_slots()), _lib.ptr(self.l2), self.n_params, lr_t, beta1, beta2, eps, grad_scale,
+                  _lib.stream_ptr(stream))
