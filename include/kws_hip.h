@@ -307,6 +307,24 @@ int kws_gconv_wgrad_f32(const float* X, const float* bn, int bn_group, const flo
                         const kws_gconv_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MaxPool1D(pool_size=3, strides=2, padding='valid') over relu6(bn(y)): the pool of the reference's _reduce_conv in
+ * conv_1d_time_stacked_model / conv_1d_heavy_model (model.py:271-277, 423-429).  y [B, L, C] is the RAW convolution output,
+ * bn its table scale|shift|mean|rstd [4][C]; C % 4 == 0, C <= 1024, L >= 3.
+ *   fwd  z[b,t,c] = max_{j<3} relu6(scale[c] * y[b, 2t+j, c] + shift[c]), t < kws_pool3s2_out_len(L) = (L - 3) / 2 + 1.  The
+ *        activation is applied BEFORE the maximum (a scale may be negative).  With an even L the last row is in no window.
+ *   bwd  g[b,u,c] = relu6'(bn(y[b,u,c])) * sum of dz[b,t,c] over the windows t that row u won; the FIRST maximum of a window wins
+ *        (TF MaxPoolGrad).  Every element of g [B, L, C] is written once (rows no window covers: exact 0).  part receives
+ *        kws_pool3s2_bwd_part_rows() rows [2][C] of (sum g, sum g * xhat), xhat = (y - mean) * rstd: the BatchNorm backward's
+ *        reductions, to be added over the rows in a fixed order.  No atomics: results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int kws_pool3s2_out_len(int L);
+int kws_pool3s2_fwd_f32(const float* y, const float* bn, float* z, int B, int L, int C, void* stream);
+int kws_pool3s2_bwd_part_rows(int B, int L, int C);
+int64_t kws_pool3s2_bwd_part_floats(int B, int L, int C);
+int kws_pool3s2_bwd_f32(const float* dz, const float* y, const float* bn, float* g, float* part, int B, int L, int C,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -389,6 +407,13 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         BatchNormalization layer; kws_net_debug_view what 0 = pre-BN output of conv layer `index` (0 = the
  *                         first, per grouped BLOCK: the groups concatenated [B, Lout, F]), what 2 = the table [4][Ng] of
  *                         batch_normalization_{index+1}.
+ *   KWS_NET_CONV_1D_TIME_STACKED: conv_1d_time_stacked_model, reference model.py:257-309 (raw input, input_size must be 16000:
+ *                         the reference reshapes to [800, 20])
+ *   KWS_NET_CONV_1D_HEAVY: conv_1d_heavy_model, reference model.py:409-467 (raw input as [1600, 10]; Keras model name
+ *                         'conv_1d_time_stacked' too).  Both: a ladder of dense VALID Conv1D (kws_gconv_* with one group) +
+ *                         BatchNormalization + relu6, every second layer followed by kws_pool3s2_*; debug views as for the
+ *                         grouped nets (what 0 = raw output of conv1d_{index+1}, conv_1d_heavy's Conv1D(128, 5) head included;
+ *                         what 2 = table of batch_normalization_{index+1}).
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -400,6 +425,8 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_MFCC_AND_RAW 5
 #define KWS_NET_CONV_1D_FAST 6
 #define KWS_NET_CONV_1D_SPEC 7
+#define KWS_NET_CONV_1D_TIME_STACKED 8
+#define KWS_NET_CONV_1D_HEAVY 9
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

@@ -19,6 +19,8 @@ KWS_NET_RESIDUAL = 4
 KWS_NET_MFCC_AND_RAW = 5
 KWS_NET_CONV_1D_FAST = 6
 KWS_NET_CONV_1D_SPEC = 7
+KWS_NET_CONV_1D_TIME_STACKED = 8
+KWS_NET_CONV_1D_HEAVY = 9
 
 
 class KwsError(RuntimeError):
@@ -138,6 +140,11 @@ SIGNATURES = {
     "kws_gconv_dgrad_f32": (_I, [_P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
     "kws_gconv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(GconvDesc)]),
     "kws_gconv_wgrad_f32": (_I, [_P, _P, _I, _P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
+    "kws_pool3s2_out_len": (_I, [_I]),
+    "kws_pool3s2_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "kws_pool3s2_bwd_part_rows": (_I, [_I, _I, _I]),
+    "kws_pool3s2_bwd_part_floats": (_I64, [_I, _I, _I]),
+    "kws_pool3s2_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "kws_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
     "kws_bn_stats_finalize": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "kws_bn_infer_prepare": (_I, [_P, _P, _P, _P, _F, _I, _P, _P]),

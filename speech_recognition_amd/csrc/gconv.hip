@@ -493,7 +493,8 @@ __global__ __launch_bounds__(256) void gbn_bwd_apply_kernel(float* __restrict__ 
 
 // ---- Flatten -> Dropout -> Dense(bias) -> softmax -> keras categorical_crossentropy (conv_1d_fast / conv_1d_spec) ------
 // One workgroup per clip.  Features are relu6(bn(y)) of the last grouped block in Keras Flatten order (t * F + f); the
-// dropout element index of row r is r * D + i (layer_id 1), as in the other tails.  Training also writes the dropped
+// dropout element index of row r is r * D + i (layer_id 1 unless the caller names another), as in the other tails.  bd may
+// be NULL (conv_1d_heavy's Conv1D(num_classes, 1, use_bias=False) head over its [B, 1, 128] features).  Training also writes the dropped
 // features fd [B, D], dlogits dl [B, NC] and the gradient wrt the activated block output dA [B, D].
 constexpr int FT_MAXD = 8192, FT_MAXNC = 64;
 struct FtArgs {
@@ -527,7 +528,10 @@ __global__ __launch_bounds__(256) void flat_tail_kernel(FtArgs a) {
       for (int i = sl; i < D; i += 4) s = fmaf(s_feat[i], a.Wd[(int64_t)i * NC + k], s);
     s_red[sl][k] = s;
     __syncthreads();
-    if (tid < NC) s_p[tid] = (((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid]) + a.bd[tid];
+    if (tid < NC) {
+      const float dot = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+      s_p[tid] = a.bd ? dot + a.bd[tid] : dot;
+    }
     __syncthreads();
     if (tid == 0) {
       float mx = s_p[0];
@@ -602,23 +606,35 @@ int kws_gbn_infer(const kws_gbn_refs* r, float eps, float* bn, hipStream_t st) {
 
 int kws_gbn_bwd_rows(int64_t M) { return (int)ceil_div64(M, GBWD_ROWS); }
 
+static int gbn_bwd_finish_launch(float* gbuf, const float* y, const float* bn, int64_t M, int g, int Ng, const float* part, int rows,
+                                 float* coef, float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st) {
+  const int F = g * Ng;
+  hipLaunchKernelGGL(gbn_bwd_fin_kernel, dim3((unsigned)ceil_div(F, GFIN_CG)), dim3(256), 0, st, part, rows, 1.0 / (double)M, g, Ng,
+                     dgamma0, pstride, boff, coef);
+  KWS_LAUNCH_CHECK("gbn_bwd_fin_kernel");
+  const int64_t n_el = M * F;
+  hipLaunchKernelGGL(gbn_bwd_apply_kernel, dim3((unsigned)ceil_div64(n_el, 256)), dim3(256), 0, st, gbuf, y, bn, coef, n_el, g, Ng);
+  KWS_LAUNCH_CHECK("gbn_bwd_apply_kernel");
+  return KWS_OK;
+}
+
 int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, int Ng, float* part, float* coef, float* dgamma0,
                 int64_t pstride, int64_t boff, hipStream_t st) {
   const int F = g * Ng, rows = kws_gbn_bwd_rows(M);
   KwsProfScope prof("gbn_bwd", 0.0, 4.0 * 5.0 * (double)M * F, st);
   hipLaunchKernelGGL(gbn_bwd_part_kernel, dim3((unsigned)rows, (unsigned)ceil_div(F, 256)), dim3(256), 0, st, dA, y, bn, M, g, Ng, part);
   KWS_LAUNCH_CHECK("gbn_bwd_part_kernel");
-  hipLaunchKernelGGL(gbn_bwd_fin_kernel, dim3((unsigned)ceil_div(F, GFIN_CG)), dim3(256), 0, st, part, rows, 1.0 / (double)M, g, Ng,
-                     dgamma0, pstride, boff, coef);
-  KWS_LAUNCH_CHECK("gbn_bwd_fin_kernel");
-  const int64_t n_el = M * F;
-  hipLaunchKernelGGL(gbn_bwd_apply_kernel, dim3((unsigned)ceil_div64(n_el, 256)), dim3(256), 0, st, dA, y, bn, coef, n_el, g, Ng);
-  KWS_LAUNCH_CHECK("gbn_bwd_apply_kernel");
-  return KWS_OK;
+  return gbn_bwd_finish_launch(dA, y, bn, M, g, Ng, part, rows, coef, dgamma0, pstride, boff, st);
+}
+
+int kws_gbn_bwd_finish(float* gbuf, const float* y, const float* bn, int64_t M, int g, int Ng, const float* part, int rows, float* coef,
+                       float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st) {
+  KwsProfScope prof("gbn_bwd_finish", 0.0, 4.0 * 3.0 * (double)M * g * Ng, st);
+  return gbn_bwd_finish_launch(gbuf, y, bn, M, g, Ng, part, rows, coef, dgamma0, pstride, boff, st);
 }
 
 int kws_flat_tail_launch(const kws_flat_tail_args* t, int training, hipStream_t st) {
-  KWS_REQUIRE(t && t->y && t->bn && t->Wd && t->bd && t->probs && t->B > 0 && t->D > 0 && t->D <= FT_MAXD && t->F > 0 &&
+  KWS_REQUIRE(t && t->y && t->bn && t->Wd && t->probs && t->B > 0 && t->D > 0 && t->D <= FT_MAXD && t->F > 0 &&
                   t->D % t->F == 0 && t->Ng > 0 && t->F % t->Ng == 0 && t->NC > 0 && t->NC <= FT_MAXNC,
               "flat_tail: bad arguments (D=%d F=%d NC=%d)", t ? t->D : 0, t ? t->F : 0, t ? t->NC : 0);
   KWS_REQUIRE(!training || (t->labels && t->fd && t->dl && t->dA && t->per_loss && t->per_correct),
@@ -627,7 +643,7 @@ int kws_flat_tail_launch(const kws_flat_tail_args* t, int training, hipStream_t 
   a.y = t->y; a.bn = t->bn; a.Ng = t->Ng; a.Wd = t->Wd; a.bd = t->bd; a.labels = t->labels;
   a.probs = t->probs; a.fd = t->fd; a.dl = t->dl; a.dA = t->dA; a.per_loss = t->per_loss; a.per_correct = t->per_correct;
   a.B = t->B; a.D = t->D; a.F = t->F; a.NC = t->NC;
-  a.key = kws_dropout_key(t->seed, t->step, 1);
+  a.key = kws_dropout_key(t->seed, t->step, t->layer_id ? t->layer_id : 1);
   a.thresh = kws_dropout_threshold(t->keep_prob);
   a.inv_keep = (float)(1.0 / (double)t->keep_prob);
   a.inv_loss_batch = 1.0f / (float)(t->loss_batch > 0 ? t->loss_batch : 1);

@@ -104,13 +104,18 @@ int kws_gbn_infer(const kws_gbn_refs* r, float eps, float* bn, hipStream_t st);
 int kws_gbn_bwd_rows(int64_t M);
 int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, int Ng, float* part, float* coef, float* dgamma0,
                 int64_t pstride, int64_t boff, hipStream_t st);
-// Flatten -> Dropout -> Dense(bias) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F
+// its last two passes alone, for a producer that wrote the gated gradient g and `rows` partial rows [2][F] of (sum g, sum g xhat)
+// itself (pool.hip kws_pool3s2_bwd_f32): dgamma / dbeta / coef from the rows, then dy in place on g
+int kws_gbn_bwd_finish(float* g, const float* y, const float* bn, int64_t M, int groups, int Ng, const float* part, int rows, float* coef,
+                       float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
+// Flatten -> Dropout -> Dense(bias or none: bd NULL) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F;
+// layer_id: the dropout layer's id (0 = 1)
 struct kws_flat_tail_args {
   const float* y; const float* bn; int Ng;
   const float* Wd; const float* bd; const float* labels;
   float* probs; float* fd; float* dl; float* dA; float* per_loss; float* per_correct;
   int B, D, F, NC;
-  uint64_t seed; uint32_t step; float keep_prob; int loss_batch; int64_t row_offset;
+  uint64_t seed; uint32_t step; float keep_prob; int loss_batch; int64_t row_offset; uint32_t layer_id;
 };
 int kws_flat_tail_launch(const kws_flat_tail_args* a, int training, hipStream_t st);
 #ifdef __HIPCC__

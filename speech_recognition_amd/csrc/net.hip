@@ -291,7 +291,9 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     case KWS_NET_RESIDUAL: rc = residual_build(n); break;
     case KWS_NET_MFCC_AND_RAW: rc = mfcc_raw_build(n); break;
     case KWS_NET_CONV_1D_FAST:
-    case KWS_NET_CONV_1D_SPEC: rc = gc_build(n); break;
+    case KWS_NET_CONV_1D_SPEC:
+    case KWS_NET_CONV_1D_TIME_STACKED:
+    case KWS_NET_CONV_1D_HEAVY: rc = gc_build(n); break;
     default:
       kws_set_error("net_create: kind %d not supported", cfg->kind);
       rc = KWS_E_INVALID;

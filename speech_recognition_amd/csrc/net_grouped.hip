@@ -10,6 +10,17 @@
 // normalise + ReLU6 is applied on load by the next block (or the tail), the project's convention.  The 479-tap front
 // convolution is the gathered GEMM on ONE tap of 480 samples against a kernel padded with a zero row (as steffeNet pads 75
 // to 76).
+// The same program runs the reference's plain dense-Conv1D ladders, a block with ONE group and, on every second layer, a
+// MaxPool1D(3, strides=2, 'valid') behind the activation (kws_pool3s2_*: the pooled tensor is materialised ACTIVATED, the next
+// block reads it without a table):
+//   KWS_NET_CONV_1D_TIME_STACKED  conv_1d_time_stacked_model (model.py:257-309): raw waveform as [800, 20] -> Conv1D(32, 1) ->
+//                         six reduce (k 3, pooled) / context (k 3) pairs of 48 ... 256 filters, l2 1e-5 -> Dropout(.3) ->
+//                         Conv1D(num_classes, 5, softmax, bias) over the 5 remaining steps = the flat tail with D = 1280; Adam(3e-4)
+//   KWS_NET_CONV_1D_HEAVY conv_1d_heavy_model (model.py:409-467): [1600, 10], seven pairs up to 320 filters -> Dropout(.3) ->
+//                         Conv1D(128, 5, no bias) -> BatchNormalization (over the B rows) + relu6 -> Dropout(.1) ->
+//                         Conv1D(num_classes, 1, softmax, no bias).  The 1600 -> 128 product is one more block of this program
+//                         whose input is the materialised dropped features; what follows it is the flat tail with D = 128,
+//                         dropout layer 2 and no bias.
 #include "net_internal.h"
 
 struct GcBlock {
@@ -20,6 +31,8 @@ struct GcBlock {
   int64_t mm0, mv_off;      // group 0's moving mean (state); variance at mm + mv_off
   int64_t pstride, sstride;
   int bn_idx0;              // 0-based Keras index of group 0's BatchNormalization
+  bool pool;                // MaxPool1D(3, strides=2, 'valid') behind the activation: Lp rows per clip leave the block
+  int Lp;
 };
 
 struct GcProgram {
@@ -32,6 +45,9 @@ struct GcProgram {
   int64_t dk = 0, db = 0;
   int D = 0, NC = 0;
   float keep = 0.7f;
+  bool head2 = false;       // conv_1d_heavy: the last block is the Conv1D(128, 5) head over the dropped features [B, Dd]
+  int Dd = 0;
+  float keep2 = 1.f;        // Dropout(0.1) between that block and the softmax convolution (dropout layer 2)
 };
 
 void gc_free(kws_net* n) {
@@ -43,8 +59,10 @@ namespace {
 
 constexpr float GC_DROP_KEEP = 0.7f;      // Dropout(0.3), model.py:710 / 1318
 constexpr float GC_FRONT_L2 = 1e-4f;      // kernel_regularizer=l2(0.0001), model.py:700
+constexpr float GC_HEAD2_KEEP = 0.9f;     // Dropout(0.1), model.py:458
 
-int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride) {
+int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride, float l2 = 0.f,
+              bool pool = false) {
   KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C, "net: grouped block F=%d g=%d num_channels=%d C=%d", F, g,
               num_channels, C);
   GcBlock b;
@@ -53,11 +71,14 @@ int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, i
   KWS_REQUIRE(L >= k, "net: grouped block input length %d < %d taps", L, k);
   b.d.Lout = (L - k) / stride + 1;
   b.F = F;
+  b.pool = pool;
+  KWS_REQUIRE(!pool || (g == 1 && b.d.Lout >= 3), "net: pooled block needs one group and >= 3 rows (g=%d Lout=%d)", g, b.d.Lout);
+  b.Lp = pool ? kws_pool3s2_out_len(b.d.Lout) : b.d.Lout;
   b.bn_idx0 = kn.n_bn;
   const int gs = b.d.gs, Ng = b.d.Ng;
   int64_t prev_w = 0, prev_m = 0;
   for (int q = 0; q < g; ++q) {
-    const int64_t w = kn.conv(k, gs, Ng, 0.f);
+    const int64_t w = kn.conv(k, gs, Ng, l2);
     const BnRef r = kn.bn(Ng);
     if (q == 0) {
       b.w0 = w; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
@@ -85,7 +106,8 @@ int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, i
 struct GcLayout {
   int64_t total = 0;
   int64_t w0p = 0, y0 = 0;
-  std::vector<int64_t> y, bn;
+  std::vector<int64_t> y, bn, z;   // z: the pooled activated output of a pooled block
+  int64_t fa = 0, fd1 = 0;         // head2: activated / dropped features [B, Dd]
   int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, tnws = 0, dw0p = 0;
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
 };
@@ -102,12 +124,17 @@ void gc_layout(const kws_net* n, int B, bool training, GcLayout* lo) {
   }
   lo->y.assign(nb, 0);
   lo->bn.assign(nb, 0);
+  lo->z.assign(nb, 0);
   for (int i = 0; i < nb; ++i) {
     kws_gconv_t d = p.blocks[i].d;
     d.B = B;
     const int64_t M = (int64_t)B * d.Lout;
     lo->y[i] = bp.take(M * p.blocks[i].F);
     lo->bn[i] = bp.take((int64_t)4 * p.blocks[i].F);
+    if (p.blocks[i].pool) {
+      lo->z[i] = bp.take((int64_t)B * p.blocks[i].Lp * p.blocks[i].F);
+      max_part = std::max(max_part, kws_pool3s2_bwd_part_floats(B, d.Lout, p.blocks[i].F));
+    }
     max_act = std::max(max_act, std::max(M * p.blocks[i].F, (int64_t)B * d.L * d.C));
     max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&d) * 2 * p.blocks[i].F);
     max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * p.blocks[i].F);
@@ -116,6 +143,10 @@ void gc_layout(const kws_net* n, int B, bool training, GcLayout* lo) {
   }
   lo->stats = bp.take(max_stats);
   if (training) {
+    if (p.head2) {
+      lo->fa = bp.take((int64_t)B * p.Dd);
+      lo->fd1 = bp.take((int64_t)B * p.Dd);
+    }
     lo->dA[0] = bp.take(max_act);
     lo->dA[1] = bp.take(max_act);
     lo->part = bp.take(max_part);
@@ -142,9 +173,23 @@ kws_gbn_refs refs_of(const GcBlock& b, const float* params, float* state) {
   return r;
 }
 
+// what block i convolves: the raw output of the block before it with that block's table (applied on load), its pooled
+// activated output without one, the network input, or (head2's last block, training) the dropped features
+struct GcInput {
+  const float* in;
+  const float* bn;
+  int bg;
+};
+GcInput gc_input(const GcProgram& p, const GcLayout& lo, int i, const float* x, const float* ws, bool training) {
+  if (i == 0) return {p.front ? ws + lo.y0 : x, nullptr, 0};
+  if (p.head2 && training && i + 1 == (int)p.blocks.size()) return {ws + lo.fd1, nullptr, 0};
+  if (p.blocks[i - 1].pool) return {ws + lo.z[i - 1], nullptr, 0};
+  return {ws + lo.y[i - 1], ws + lo.bn[i - 1], p.blocks[i - 1].d.Ng};
+}
+
 // forward through the blocks; training: batch statistics (moving averages updated), else the moving statistics
 int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-               hipStream_t st) {
+               uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
   const GcProgram& p = *n->gc;
   if (p.front) {
     KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
@@ -155,11 +200,17 @@ int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float*
     const GcBlock& b = p.blocks[i];
     kws_gconv_t d = b.d;
     d.B = B;
-    const float* in = i ? ws + lo.y[i - 1] : (p.front ? ws + lo.y0 : x);
-    const float* bn_in = i ? ws + lo.bn[i - 1] : nullptr;
-    const int bg = i ? p.blocks[i - 1].d.Ng : 0;
+    const GcInput gi = gc_input(p, lo, (int)i, x, ws, training);
+    const float* in = gi.in;
+    const float* bn_in = gi.bn;
+    const int bg = gi.bg;
     const kws_gbn_refs r = refs_of(b, params, state);
     if (training) {
+      if (p.head2 && i + 1 == p.blocks.size()) {   // Dropout(.3) over the activated ladder output, materialised for the head's GEMMs
+        const GcBlock& pb = p.blocks[i - 1];
+        KWS_TRY(kws_bn_relu6_apply(ws + lo.y[i - 1], ws + lo.bn[i - 1], ws + lo.fa, (int64_t)B * pb.d.Lout, pb.F, 1, st));
+        KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.Dd, p.keep, seed, step, 1, row_offset, st));
+      }
       KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], ws + lo.stats, &d, st));
       KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&d), (int64_t)B * d.Lout, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
                                ws + lo.bn[i], st));
@@ -167,6 +218,7 @@ int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float*
       KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], nullptr, &d, st));
       KWS_TRY(kws_gbn_infer(&r, KWS_BN_EPS, ws + lo.bn[i], st));
     }
+    if (b.pool) KWS_TRY(kws_pool3s2_fwd_f32(ws + lo.y[i], ws + lo.bn[i], ws + lo.z[i], B, d.Lout, b.F, st));
   }
   return KWS_OK;
 }
@@ -177,10 +229,11 @@ kws_flat_tail_args tail_args(const kws_net* n, const GcLayout& lo, const float* 
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
   t.y = ws + lo.y.back(); t.bn = ws + lo.bn.back(); t.Ng = last.d.Ng;
-  t.Wd = params + p.dk; t.bd = params + p.db;
+  t.Wd = params + p.dk; t.bd = p.db >= 0 ? params + p.db : nullptr;
   t.probs = probs;
   t.B = B; t.D = p.D; t.F = last.F; t.NC = p.NC;
-  t.keep_prob = p.keep;
+  t.keep_prob = p.head2 ? p.keep2 : p.keep;
+  t.layer_id = p.head2 ? 2 : 1;
   return t;
 }
 
@@ -206,6 +259,35 @@ int gc_build(kws_net* n) {
     KWS_TRY(add_block(kn, p, p->L0, p->C0, 300, 15, 6, 252, 2));
     const GcBlock& b1 = p->blocks.back();
     KWS_TRY(add_block(kn, p, b1.d.Lout, b1.F, 360, 7, 5, 300, 2));
+  } else if (c.kind == KWS_NET_CONV_1D_TIME_STACKED || c.kind == KWS_NET_CONV_1D_HEAVY) {
+    const bool heavy = c.kind == KWS_NET_CONV_1D_HEAVY;
+    KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_%s input_size %d (the reference reshapes 16000 samples)",
+                heavy ? "heavy" : "time_stacked", c.input_size);
+    p->L_in = heavy ? 1600 : 800; p->C_in = heavy ? 10 : 20;   // Reshape([800, 20]) / Reshape([1600, 10])
+    KWS_TRY(add_block(kn, p, p->L_in, p->C_in, 32, 1, 1, p->C_in, 1, KWS_L2_COEF));
+    const int widths[7] = {48, 96, 128, 160, 192, 256, 320};
+    for (int i = 0; i < (heavy ? 7 : 6); ++i)
+      for (int half = 0; half < 2; ++half) {   // _reduce_conv (pooled; its strides argument goes to the pool only), _context_conv
+        const GcBlock& pb = p->blocks.back();
+        KWS_TRY(add_block(kn, p, pb.Lp, pb.F, widths[i], 3, 1, pb.F, 1, KWS_L2_COEF, half == 0));
+      }
+    const GcBlock& top = p->blocks.back();
+    KWS_REQUIRE(top.d.Lout == 5, "net: ladder ends with %d rows, the head convolves 5", top.d.Lout);
+    if (heavy) {
+      p->head2 = true;
+      p->Dd = top.d.Lout * top.F;
+      p->keep2 = GC_HEAD2_KEEP;
+      KWS_TRY(add_block(kn, p, top.d.Lout, top.F, 128, 5, 1, top.F, 1));
+      const GcBlock& head = p->blocks.back();
+      p->D = head.F;
+      p->dk = kn.conv(1, head.F, p->NC, 0.f);
+      p->db = -1;
+    } else {
+      p->D = top.d.Lout * top.F;
+      p->dk = kn.conv(top.d.Lout, top.F, p->NC, 0.f);   // [5, 256, NC] = the Dense kernel [1280, NC] over the t-major flatten
+      p->db = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+    }
+    return KWS_OK;
   } else {
     p->L_in = 98; p->C_in = 257;   // Input(shape=[98 * 257]) -> Reshape([98, 257]); input_size is not consulted
     struct { int F, g, nch, stride; } spec[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
@@ -271,7 +353,7 @@ int gc_predict(const kws_net* n, const float* params, const float* state, const 
     kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
     return KWS_E_WORKSPACE;
   }
-  KWS_TRY(gc_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, st));
+  KWS_TRY(gc_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
   kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
   return kws_flat_tail_launch(&t, 0, st);
 }
@@ -286,7 +368,7 @@ int gc_train(const kws_net* n, const float* params, float* state, const float* x
     kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
     return KWS_E_WORKSPACE;
   }
-  KWS_TRY(gc_forward(n, lo, params, state, x, B, true, ws, st));
+  KWS_TRY(gc_forward(n, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   int cur = 0;
   kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
   t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = ws + lo.dA[cur];
@@ -294,20 +376,29 @@ int gc_train(const kws_net* n, const float* params, float* state, const float* x
   t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
   KWS_TRY(kws_flat_tail_launch(&t, 1, st));
   KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.D, p.NC, ws + lo.swg, st));
+  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, p.db >= 0 ? grads + p.db : nullptr, B, p.D, p.NC, ws + lo.swg,
+                                 st));
   for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
     const GcBlock& b = p.blocks[i];
     kws_gconv_t d = b.d;
     d.B = B;
     const int64_t M = (int64_t)B * d.Lout;
+    if (b.pool) {   // dA[cur] = gradient wrt the pooled output: route it to the winners, gate it, BN sums in the same pass
+      KWS_TRY(kws_pool3s2_bwd_f32(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], ws + lo.dA[cur ^ 1], ws + lo.part, B, d.Lout, b.F, st));
+      cur ^= 1;
+      KWS_TRY(kws_gbn_bwd_finish(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part,
+                                 kws_pool3s2_bwd_part_rows(B, d.Lout, b.F), ws + lo.coef, grads + b.gamma0, b.pstride, b.beta_off, st));
+    } else {
+      KWS_TRY(kws_gbn_bwd(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part, ws + lo.coef, grads + b.gamma0,
+                          b.pstride, b.beta_off, st));
+    }
     float* dy = ws + lo.dA[cur];
-    KWS_TRY(kws_gbn_bwd(dy, ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part, ws + lo.coef, grads + b.gamma0, b.pstride,
-                        b.beta_off, st));
-    const float* in = i ? ws + lo.y[i - 1] : (p.front ? ws + lo.y0 : x);
-    const float* bn_in = i ? ws + lo.bn[i - 1] : nullptr;
-    const int bg = i ? p.blocks[i - 1].d.Ng : 0;
-    KWS_TRY(kws_gconv_wgrad_f32(in, bn_in, bg, dy, grads + b.w0, ws + lo.wws, &d, st));
-    if (i > 0 || p.front) {
+    const GcInput gi = gc_input(p, lo, i, x, ws, true);
+    KWS_TRY(kws_gconv_wgrad_f32(gi.in, gi.bn, gi.bg, dy, grads + b.w0, ws + lo.wws, &d, st));
+    if (p.head2 && i + 1 == (int)p.blocks.size()) {   // back through Dropout(.3): the gradient wrt the activated ladder output
+      KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.fa, &d, st));
+      KWS_TRY(kws_dropout_bwd(ws + lo.fa, ws + lo.dA[cur], B, p.Dd, p.keep, seed, step, 1, row_offset, st));
+    } else if (i > 0 || p.front) {
       KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.dA[cur ^ 1], &d, st));
       cur ^= 1;
     }

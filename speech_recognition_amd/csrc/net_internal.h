@@ -1,6 +1,6 @@
 // Shared between the three network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
 // residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
-// net_grouped.hip: conv_1d_fast, conv_1d_spec).  Not part of the public C ABI.
+// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy).  Not part of the public C ABI.
 #pragma once
 #include <string.h>
 
@@ -27,7 +27,7 @@ struct Block {
 };
 
 struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
-struct GcProgram;  // conv_1d_fast / conv_1d_spec layer table (net_grouped.hip)
+struct GcProgram;  // conv_1d_fast / conv_1d_spec / conv_1d_time_stacked / conv_1d_heavy layer table (net_grouped.hip)
 
 struct kws_net {
   kws_net_config_t cfg;
@@ -46,7 +46,7 @@ struct kws_net {
   int K1f = 0;            // folded K
   // LOG_MFCC / STEFFE / RESIDUAL / MFCC_AND_RAW
   LmProgram* lm = nullptr;
-  // CONV_1D_FAST / CONV_1D_SPEC
+  // CONV_1D_FAST / CONV_1D_SPEC / CONV_1D_TIME_STACKED / CONV_1D_HEAVY
   GcProgram* gc = nullptr;
   // arithmetic of the pointwise GEMMs (kws_net_set_gemm_mode): 0 = f32 MFMA, 2 = fp16 x 2 split products (A/B arm)
   std::atomic<int> gemm_mode{0};

@@ -3,11 +3,11 @@ dispatch (reference model.py:1729-1781), `prepare_model_settings` (model.py:1785
 symbols checkpoints name as custom objects (`relu6` model.py:30-31, `overlapping_time_slice_stack`
 model.py:67-76).  The layer graphs themselves are native network programs in csrc/net.hip."""
 from . import _lib
-from .keras_api import Model, RMSprop
+from .keras_api import Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
-               'conv_1d_fast', 'conv_1d_spec')
+               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -150,6 +150,29 @@ def conv_1d_spec_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, RMSprop(lr=2e-3), name='conv_1d_spec', loss='cce')
 
 
+def _raw_16000(model_type, input_size):
+    if int(input_size) != 16000:
+        raise ValueError("%s: input_size %s - the reference reshapes exactly 16000 samples" % (model_type, input_size))
+
+
+def conv_1d_time_stacked_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:257-309: raw waveform as [800, 20] -> Conv1D(32, 1) -> six pairs of Conv1D(F, 3, VALID, l2 1e-5) +
+    BatchNormalization + relu6, the first of a pair followed by MaxPool1D(3, strides=2, 'valid') (F = 48 ... 256) -> Dropout(.3)
+    -> Conv1D(num_classes, 5, softmax); Adam(3e-4), categorical CE."""
+    _raw_16000('conv_1d_time_stacked', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_TIME_STACKED, num_classes, input_size=16000)
+    return Model(net, Adam(lr=3e-4), name='conv_1d_time_stacked', loss='cce')
+
+
+def conv_1d_heavy_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:409-467: raw waveform as [1600, 10], the conv_1d_time_stacked ladder with a seventh pair (320) ->
+    Dropout(.3) -> Conv1D(128, 5) + BatchNormalization + relu6 -> Dropout(.1) -> Conv1D(num_classes, 1, softmax, no bias);
+    Adam(3e-4), categorical CE.  The reference names this Keras model 'conv_1d_time_stacked' as well."""
+    _raw_16000('conv_1d_heavy', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_HEAVY, num_classes, input_size=16000)
+    return Model(net, Adam(lr=3e-4), name='conv_1d_time_stacked', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -167,6 +190,10 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_fast_model(input_size, num_classes)
     if model_type == 'conv_1d_spec':
         return conv_1d_spec_model(input_size, num_classes)
+    if model_type == 'conv_1d_time_stacked':
+        return conv_1d_time_stacked_model(input_size, num_classes)
+    if model_type == 'conv_1d_heavy':
+        return conv_1d_heavy_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"
