@@ -375,6 +375,40 @@ int kws_bn_bwd_apply(float* g, const float* y, const float* bn, const float* gam
                      const float* coef, int64_t rows, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DepthwiseConv2D((1, k), strides=s) on [B,1,L,C] with any tap count and stride, reference model.py:34-44 as the raw-waveform
+ * models call it (conv_1d_gru_model, model.py:470-512: k 63 / 31 / 15 / 7 / 5 / 8 at strides 16 / 4 / 4 / 4 / 2 / 1): the general
+ * form of kws_dwconv_*.  Channels-last [B, L, C], kernel w [k, C], the producer's BN+ReLU6 applied on load (bn may be NULL: the
+ * input is used as is, no gate, and the first two rows of a part block are zero).  Zero padding applies to the ACTIVATION.
+ *   fwd   z[b,t,c] = sum_{j<k} w[j,c] * act(y[b, s*t + j - pad_l, c])      (0 outside [0, L_in))
+ *   bwd   g[b,u,c] = relu6'(bn(y[b,u,c])) * sum over j with s | (u + pad_l - j) and 0 <= t = (u + pad_l - j)/s < L_out of
+ *                    w[j,c] * dz[b,t,c].  Every element of g [B, L_in, C] is written once; rows no window reaches are exact 0.
+ *         part     = kws_dwconvk_bwd_part_rows() blocks [2 + k][C] of (sum g, sum g*xhat, dw_0 .. dw_{k-1}),
+ *                    dw_j = sum_{b,t} act(y[b, s*t + j - pad_l, c]) * dz[b,t,c]
+ *   finalize       part -> dw [k, C] (may be NULL), dgamma, dbeta (may be NULL), coef [2C] = (c1 | c2) for kws_bn_bwd_apply
+ *                  (may be NULL); count = B * L_in
+ * Domain: 1 <= k <= 64, 1 <= s <= 16, 0 <= pad_l < k, s*(L_out-1) + k - pad_l <= L_in + (k-1), C = 1 or C % 4 == 0 with
+ * C <= 1024.  No atomics: results are bit-identical from run to run.
+ * kws_dwconvk_pw1_*: the pointwise convolution 1 -> N behind a one-channel depthwise layer (K = 1 is outside kws_gemm_nn_f32):
+ *   fwd   y[m,n] = z[m] * p[n]; stats_part (may be NULL): kws_dwconvk_pw1_stats_rows(M) rows [2][N] of (sum y, sum y^2) for
+ *         kws_bn_stats_finalize
+ *   bwd   dz[m] = sum_n dy[m,n] * p[n], dp[n] = sum_m z[m] * dy[m,n] (fixed order); workspace >=
+ *         kws_dwconvk_pw1_bwd_workspace_floats(M, N) floats.  N: a power of two, 4 .. 256.
+ * ---------------------------------------------------------------------------------------- */
+int kws_dwconvk_fwd_f32(const float* y, const float* bn, const float* w, float* z, int B, int L_in, int L_out, int C,
+                        int k, int stride, int pad_l, void* stream);
+int kws_dwconvk_bwd_part_rows(int B, int L_in, int C, int k, int stride);
+int64_t kws_dwconvk_bwd_part_floats(int B, int L_in, int C, int k, int stride);
+int kws_dwconvk_bwd_f32(const float* dz, const float* y, const float* bn, const float* w, float* g, float* part, int B,
+                        int L_in, int L_out, int C, int k, int stride, int pad_l, void* stream);
+int kws_dwconvk_bwd_finalize(const float* part, int n_parts, int64_t count, int C, int k, float* dw, float* dgamma,
+                             float* dbeta, float* coef, void* stream);
+int kws_dwconvk_pw1_stats_rows(int64_t M);
+int kws_dwconvk_pw1_fwd_f32(const float* z, const float* p, float* y, int64_t M, int N, float* stats_part, void* stream);
+int64_t kws_dwconvk_pw1_bwd_workspace_floats(int64_t M, int N);
+int kws_dwconvk_pw1_bwd_f32(const float* dy, const float* z, const float* p, float* dz, float* dp, int64_t M, int N,
+                            float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a14  optimizers on one flat parameter buffer, reference model.py:834 (RMSprop(lr=1e-3)) and
  *      model.py:96,110 (SGD momentum); constants SURVEY D.5.  g_eff = grad*grad_scale + 2*l2[i]*p
  *      (l2[i] = per-element kernel_regularizer coefficient, 0 for BN/bias).
@@ -414,6 +448,12 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         BatchNormalization + relu6, every second layer followed by kws_pool3s2_*; debug views as for the
  *                         grouped nets (what 0 = raw output of conv1d_{index+1}, conv_1d_heavy's Conv1D(128, 5) head included;
  *                         what 2 = table of batch_normalization_{index+1}).
+ *   KWS_NET_CONV_1D_GRU:  conv_1d_gru_model, reference model.py:470-512 (raw input, input_size must be 16000; Keras model name
+ *                         'conv_1d_bigru'; no recurrent layer): six depthwise blocks of kws_dwconvk_* + pointwise convolution +
+ *                         BatchNormalization + relu6 (SAME k 63 / 31 / 15 / 7 / 5 at strides 16 / 4 / 4 / 4 / 2, VALID k 8) ->
+ *                         Flatten -> Dropout(.3) -> Dense(256) + relu6 -> Dropout(.3) -> Dense + softmax.  Debug views: what 0 =
+ *                         raw pointwise output of block `index` (0 .. 5), what 1 = depthwise output of block `index`, what 2 =
+ *                         table of batch_normalization_{index+1}, what 4 = the hidden Dense layer's output before its bias.
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -427,6 +467,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_SPEC 7
 #define KWS_NET_CONV_1D_TIME_STACKED 8
 #define KWS_NET_CONV_1D_HEAVY 9
+#define KWS_NET_CONV_1D_GRU 10
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

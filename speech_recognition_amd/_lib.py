@@ -21,6 +21,7 @@ KWS_NET_CONV_1D_FAST = 6
 KWS_NET_CONV_1D_SPEC = 7
 KWS_NET_CONV_1D_TIME_STACKED = 8
 KWS_NET_CONV_1D_HEAVY = 9
+KWS_NET_CONV_1D_GRU = 10
 
 
 class KwsError(RuntimeError):
@@ -145,6 +146,15 @@ SIGNATURES = {
     "kws_pool3s2_bwd_part_rows": (_I, [_I, _I, _I]),
     "kws_pool3s2_bwd_part_floats": (_I64, [_I, _I, _I]),
     "kws_pool3s2_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_dwconvk_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "kws_dwconvk_bwd_part_rows": (_I, [_I, _I, _I, _I, _I]),
+    "kws_dwconvk_bwd_part_floats": (_I64, [_I, _I, _I, _I, _I]),
+    "kws_dwconvk_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "kws_dwconvk_bwd_finalize": (_I, [_P, _I, _I64, _I, _I, _P, _P, _P, _P, _P]),
+    "kws_dwconvk_pw1_stats_rows": (_I, [_I64]),
+    "kws_dwconvk_pw1_fwd_f32": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
+    "kws_dwconvk_pw1_bwd_workspace_floats": (_I64, [_I64, _I]),
+    "kws_dwconvk_pw1_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I, _P, _P]),
     "kws_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
     "kws_bn_stats_finalize": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "kws_bn_infer_prepare": (_I, [_P, _P, _P, _P, _F, _I, _P, _P]),

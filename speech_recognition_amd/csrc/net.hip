@@ -284,7 +284,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
   kws_net* n = new kws_net();
   n->cfg = *cfg;
   int rc;
-  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc tell
+  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc / net->dk tell
     case KWS_NET_TS_ATTENTION: rc = build_ts_attention(n); break;
     case KWS_NET_LOG_MFCC: rc = lm_build(n); break;
     case KWS_NET_STEFFE: rc = steffe_build(n); break;
@@ -294,6 +294,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     case KWS_NET_CONV_1D_SPEC:
     case KWS_NET_CONV_1D_TIME_STACKED:
     case KWS_NET_CONV_1D_HEAVY: rc = gc_build(n); break;
+    case KWS_NET_CONV_1D_GRU: rc = dk_build(n); break;
     default:
       kws_set_error("net_create: kind %d not supported", cfg->kind);
       rc = KWS_E_INVALID;
@@ -301,6 +302,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
   if (rc != KWS_OK) {
     lm_free(n);
     gc_free(n);
+    dk_free(n);
     delete n;
     return rc;
   }
@@ -312,6 +314,7 @@ int kws_net_destroy(kws_net_t* net) {
   if (net) {
     lm_free(net);
     gc_free(net);
+    dk_free(net);
   }
   delete net;
   return KWS_OK;
@@ -329,6 +332,7 @@ int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) 
 
 int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
   if (!net || max_batch <= 0) return 0;
+  if (net->dk) return dk_workspace_bytes(net, max_batch, training);
   if (net->gc) return gc_workspace_bytes(net, max_batch, training);
   if (net->lm) return lm_workspace_bytes(net, max_batch, training);
   Layout lo;
@@ -339,6 +343,7 @@ int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int trainin
 int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, int index, int64_t* offset_floats,
                        int64_t* count) {
   KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
+  if (net->dk) return dk_debug_view(net, batch, training, what, index, offset_floats, count);
   if (net->gc) return gc_debug_view(net, batch, training, what, index, offset_floats, count);
   if (net->lm) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
   Layout lo;
@@ -371,6 +376,7 @@ int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, 
 int kws_net_predict(const kws_net_t* net, const float* params, const float* state, const float* x, int B,
                     float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
   KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
+  if (net->dk) return dk_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (net->gc) return gc_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (net->lm)
     return lm_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
@@ -688,6 +694,9 @@ int kws_net_train_fwd_bwd(const kws_net_t* net, const float* params, float* stat
   KWS_REQUIRE(net && params && state && x && y_onehot && grads && probs && metrics && workspace && B > 0,
               "net_train_fwd_bwd: bad arguments");
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd: loss_batch %d < B %d", loss_batch, B);
+  if (net->dk)
+    return dk_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
+                    workspace_bytes, (hipStream_t)stream);
   if (net->gc)
     return gc_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
                     workspace_bytes, (hipStream_t)stream);

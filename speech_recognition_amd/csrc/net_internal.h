@@ -1,6 +1,7 @@
-// Shared between the three network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
+// Shared between the four network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
 // residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
-// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy).  Not part of the public C ABI.
+// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru).  Not part of
+// the public C ABI.
 #pragma once
 #include <string.h>
 
@@ -28,6 +29,7 @@ struct Block {
 
 struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
 struct GcProgram;  // conv_1d_fast / conv_1d_spec / conv_1d_time_stacked / conv_1d_heavy layer table (net_grouped.hip)
+struct DkProgram;  // conv_1d_gru layer table (net_dwk.hip)
 
 struct kws_net {
   kws_net_config_t cfg;
@@ -48,6 +50,8 @@ struct kws_net {
   LmProgram* lm = nullptr;
   // CONV_1D_FAST / CONV_1D_SPEC / CONV_1D_TIME_STACKED / CONV_1D_HEAVY
   GcProgram* gc = nullptr;
+  // CONV_1D_GRU
+  DkProgram* dk = nullptr;
   // arithmetic of the pointwise GEMMs (kws_net_set_gemm_mode): 0 = f32 MFMA, 2 = fp16 x 2 split products (A/B arm)
   std::atomic<int> gemm_mode{0};
 };
@@ -67,6 +71,7 @@ struct KerasNames {
   int64_t conv(int k, int cin, int cout, float l2);  // conv1d_<n>/kernel [k, cin, cout]
   BnRef bn(int C, int* idx = nullptr);               // batch_normalization_<n>/...; *idx = n
   int64_t dw(int C);                                 // depthwise_conv2d_<n>/depthwise_kernel [1, 3, C, 1], l2
+  int64_t dwk(int k, int C);                         // depthwise_conv2d_<n>/depthwise_kernel [1, k, C, 1], l2 (net_dwk.hip)
 };
 
 struct Bump {
@@ -100,6 +105,17 @@ int gc_debug_view(const kws_net* n, int B, int training, int what, int index, in
 int gc_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
                int64_t ws_bytes, hipStream_t st);
 int gc_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
+             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
+             int64_t ws_bytes, hipStream_t st);
+
+// ---- general depthwise ladder (net_dwk.hip) ------------------------------------------------------------------------------
+int dk_build(kws_net* n);
+void dk_free(kws_net* n);
+int64_t dk_workspace_bytes(const kws_net* n, int B, int training);
+int dk_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
+int dk_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
+               int64_t ws_bytes, hipStream_t st);
+int dk_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
              float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
              int64_t ws_bytes, hipStream_t st);
 

@@ -7,7 +7,7 @@ from .keras_api import Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
-               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy')
+               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -173,6 +173,16 @@ def conv_1d_heavy_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, Adam(lr=3e-4), name='conv_1d_time_stacked', loss='cce')
 
 
+def conv_1d_gru_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:470-512: raw waveform as [16000, 1] -> six depthwise blocks (DepthwiseConv2D((1, k), strides=s) ->
+    Conv1D(F, 1) -> BatchNormalization -> relu6, l2 1e-5): k 63 / 31 / 15 / 7 / 5 SAME at strides 16 / 4 / 4 / 4 / 2, then k 8
+    VALID; F = 128 ... 512 -> Flatten -> Dropout(.3) -> Dense(256) + relu6 -> Dropout(.3) -> Dense; RMSprop(1e-3), categorical
+    CE.  No recurrent layer, despite the name; the reference names the Keras model 'conv_1d_bigru'."""
+    _raw_16000('conv_1d_gru', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_GRU, num_classes, input_size=16000)
+    return Model(net, RMSprop(lr=1e-3), name='conv_1d_bigru', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -194,6 +204,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_time_stacked_model(input_size, num_classes)
     if model_type == 'conv_1d_heavy':
         return conv_1d_heavy_model(input_size, num_classes)
+    if model_type == 'conv_1d_gru':
+        return conv_1d_gru_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"
