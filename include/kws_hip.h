@@ -325,6 +325,24 @@ int kws_pool3s2_bwd_f32(const float* dz, const float* y, const float* bn, float*
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MaxPool1D(pool_size=3, strides=2, padding='same') over relu6(bn(y)): the pool of the reference's _reduce_conv in
+ * conv_1d_multi_time_sliced_model (model.py:1093-1097).  The contract of kws_pool3s2_* with TensorFlow's SAME geometry:
+ * kws_pool3s2_same_out_len(L) = ceil(L / 2) windows, pad_left = 0 for an even L and 1 for an odd L; window t covers the rows
+ * 2t - pad_left + j, j < 3, that exist (padding never wins; the middle row always exists).  C % 4 == 0, C <= 1024, L >= 2.
+ *   fwd  z[b,t,c] = max over the window's valid rows of relu6(scale[c] * y[b,r,c] + shift[c]): the activation BEFORE the maximum.
+ *   bwd  g[b,u,c] = relu6'(bn(y[b,u,c])) * sum of dz[b,t,c] over the windows t that row u won; the FIRST maximum among a window's
+ *        valid rows wins (TF MaxPoolGrad).  Every element of g [B, L, C] is written once.  part receives
+ *        kws_pool3s2_same_bwd_part_rows() rows [2][C] of (sum g, sum g * xhat) for the BatchNorm backward, to be added in a fixed
+ *        order.  No atomics: results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int kws_pool3s2_same_out_len(int L);
+int kws_pool3s2_same_fwd_f32(const float* y, const float* bn, float* z, int B, int L, int C, void* stream);
+int kws_pool3s2_same_bwd_part_rows(int B, int L, int C);
+int64_t kws_pool3s2_same_bwd_part_floats(int B, int L, int C);
+int kws_pool3s2_same_bwd_f32(const float* dz, const float* y, const float* bn, float* g, float* part, int B, int L, int C,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -409,6 +427,24 @@ int kws_dwconvk_pw1_bwd_f32(const float* dy, const float* z, const float* p, flo
                             float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The first _depthwise_conv_block of a narrow raw-waveform view (conv_1d_multi_time_sliced_model, model.py:1105-1140: the samples
+ * as [4000, 4], [3200, 5], [640, 25]): DepthwiseConv2D((1, 3), VALID, stride 1) and the pointwise Conv1D(N, 1) in ONE kernel, for
+ * channel counts outside kws_dwconvk_* and the GEMMs.  x [B, L, C] (the raw input, used as is), w [3, C], p [C, N]; C = 1 .. 32,
+ * N % 4 == 0 with N <= 64, L >= 3.  The depthwise output is never written; the backward recomputes it.
+ *   fwd   y[b,t,n] = sum_c p[c,n] * (sum_{j<3} w[j,c] * x[b,t+j,c]), t < L - 2; stats_part (may be NULL): kws_stem_stats_rows(B, L)
+ *         rows [2][N] of (sum y, sum y^2) for kws_bn_stats_finalize
+ *   bwd   dp[c,n] = sum_{b,t} z[b,t,c] * dy[b,t,n], dw[j,c] = sum_{b,t} x[b,t+j,c] * sum_n dy[b,t,n] p[c,n] (fixed-order partial rows
+ *         and a fold: bit-identical from run to run); workspace >= kws_stem_bwd_workspace_floats(B, L, C, N) floats.  No gradient
+ *         leaves the input.
+ * ---------------------------------------------------------------------------------------- */
+int kws_stem_stats_rows(int B, int L);
+int kws_stem_fwd_f32(const float* x, const float* w, const float* p, float* y, int B, int L, int C, int N, float* stats_part,
+                     void* stream);
+int64_t kws_stem_bwd_workspace_floats(int B, int L, int C, int N);
+int kws_stem_bwd_f32(const float* dy, const float* x, const float* w, const float* p, float* dw, float* dp, int B, int L, int C,
+                     int N, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a14  optimizers on one flat parameter buffer, reference model.py:834 (RMSprop(lr=1e-3)) and
  *      model.py:96,110 (SGD momentum); constants SURVEY D.5.  g_eff = grad*grad_scale + 2*l2[i]*p
  *      (l2[i] = per-element kernel_regularizer coefficient, 0 for BN/bias).
@@ -454,6 +490,13 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         Flatten -> Dropout(.3) -> Dense(256) + relu6 -> Dropout(.3) -> Dense + softmax.  Debug views: what 0 =
  *                         raw pointwise output of block `index` (0 .. 5), what 1 = depthwise output of block `index`, what 2 =
  *                         table of batch_normalization_{index+1}, what 4 = the hidden Dense layer's output before its bias.
+ *   KWS_NET_CONV_1D_MULTI_TIME_SLICED: conv_1d_multi_time_sliced_model, reference model.py:1080-1156 (raw input, input_size must
+ *                         be 16000): the samples viewed as [4000, 4], [3200, 5] and [640, 25], each view a ladder of depthwise blocks
+ *                         (k 3 VALID; a _reduce_conv adds kws_pool3s2_same_*), the first block of a view on kws_stem_*; five one-step
+ *                         branch ends of 64 channels (two of them tapped off a tensor the ladder goes on from) concatenated ->
+ *                         Dropout(.1) -> a one-tap depthwise block (128) -> Dropout(.1) -> Conv1D(num_classes, 1, softmax, bias).
+ *                         32 blocks in the reference's creation order; debug views: what 0 = raw pointwise output of block `index`
+ *                         (0 .. 31), what 2 = table of batch_normalization_{index+1}.
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -468,6 +511,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_TIME_STACKED 8
 #define KWS_NET_CONV_1D_HEAVY 9
 #define KWS_NET_CONV_1D_GRU 10
+#define KWS_NET_CONV_1D_MULTI_TIME_SLICED 11
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

@@ -22,6 +22,7 @@ KWS_NET_CONV_1D_SPEC = 7
 KWS_NET_CONV_1D_TIME_STACKED = 8
 KWS_NET_CONV_1D_HEAVY = 9
 KWS_NET_CONV_1D_GRU = 10
+KWS_NET_CONV_1D_MULTI_TIME_SLICED = 11
 
 
 class KwsError(RuntimeError):
@@ -146,6 +147,15 @@ SIGNATURES = {
     "kws_pool3s2_bwd_part_rows": (_I, [_I, _I, _I]),
     "kws_pool3s2_bwd_part_floats": (_I64, [_I, _I, _I]),
     "kws_pool3s2_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_pool3s2_same_out_len": (_I, [_I]),
+    "kws_pool3s2_same_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "kws_pool3s2_same_bwd_part_rows": (_I, [_I, _I, _I]),
+    "kws_pool3s2_same_bwd_part_floats": (_I64, [_I, _I, _I]),
+    "kws_pool3s2_same_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_stem_stats_rows": (_I, [_I, _I]),
+    "kws_stem_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "kws_stem_bwd_workspace_floats": (_I64, [_I, _I, _I, _I]),
+    "kws_stem_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "kws_dwconvk_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "kws_dwconvk_bwd_part_rows": (_I, [_I, _I, _I, _I, _I]),
     "kws_dwconvk_bwd_part_floats": (_I64, [_I, _I, _I, _I, _I]),

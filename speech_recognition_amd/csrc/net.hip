@@ -284,7 +284,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
   kws_net* n = new kws_net();
   n->cfg = *cfg;
   int rc;
-  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc / net->dk tell
+  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc / net->dk / net->mt tell
     case KWS_NET_TS_ATTENTION: rc = build_ts_attention(n); break;
     case KWS_NET_LOG_MFCC: rc = lm_build(n); break;
     case KWS_NET_STEFFE: rc = steffe_build(n); break;
@@ -295,6 +295,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     case KWS_NET_CONV_1D_TIME_STACKED:
     case KWS_NET_CONV_1D_HEAVY: rc = gc_build(n); break;
     case KWS_NET_CONV_1D_GRU: rc = dk_build(n); break;
+    case KWS_NET_CONV_1D_MULTI_TIME_SLICED: rc = mt_build(n); break;
     default:
       kws_set_error("net_create: kind %d not supported", cfg->kind);
       rc = KWS_E_INVALID;
@@ -303,6 +304,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     lm_free(n);
     gc_free(n);
     dk_free(n);
+    mt_free(n);
     delete n;
     return rc;
   }
@@ -315,6 +317,7 @@ int kws_net_destroy(kws_net_t* net) {
     lm_free(net);
     gc_free(net);
     dk_free(net);
+    mt_free(net);
   }
   delete net;
   return KWS_OK;
@@ -332,6 +335,7 @@ int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) 
 
 int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
   if (!net || max_batch <= 0) return 0;
+  if (net->mt) return mt_workspace_bytes(net, max_batch, training);
   if (net->dk) return dk_workspace_bytes(net, max_batch, training);
   if (net->gc) return gc_workspace_bytes(net, max_batch, training);
   if (net->lm) return lm_workspace_bytes(net, max_batch, training);
@@ -343,6 +347,7 @@ int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int trainin
 int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, int index, int64_t* offset_floats,
                        int64_t* count) {
   KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
+  if (net->mt) return mt_debug_view(net, batch, training, what, index, offset_floats, count);
   if (net->dk) return dk_debug_view(net, batch, training, what, index, offset_floats, count);
   if (net->gc) return gc_debug_view(net, batch, training, what, index, offset_floats, count);
   if (net->lm) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
@@ -376,6 +381,7 @@ int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, 
 int kws_net_predict(const kws_net_t* net, const float* params, const float* state, const float* x, int B,
                     float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
   KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
+  if (net->mt) return mt_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (net->dk) return dk_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (net->gc) return gc_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (net->lm)
@@ -694,6 +700,9 @@ int kws_net_train_fwd_bwd(const kws_net_t* net, const float* params, float* stat
   KWS_REQUIRE(net && params && state && x && y_onehot && grads && probs && metrics && workspace && B > 0,
               "net_train_fwd_bwd: bad arguments");
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd: loss_batch %d < B %d", loss_batch, B);
+  if (net->mt)
+    return mt_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
+                    workspace_bytes, (hipStream_t)stream);
   if (net->dk)
     return dk_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
                     workspace_bytes, (hipStream_t)stream);

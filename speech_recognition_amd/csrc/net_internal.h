@@ -1,7 +1,7 @@
-// Shared between the four network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
+// Shared between the five network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
 // residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
-// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru).  Not part of
-// the public C ABI.
+// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru; net_mts.hip:
+// conv_1d_multi_time_sliced).  Not part of the public C ABI.
 #pragma once
 #include <string.h>
 
@@ -30,6 +30,7 @@ struct Block {
 struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
 struct GcProgram;  // conv_1d_fast / conv_1d_spec / conv_1d_time_stacked / conv_1d_heavy layer table (net_grouped.hip)
 struct DkProgram;  // conv_1d_gru layer table (net_dwk.hip)
+struct MtProgram;  // conv_1d_multi_time_sliced layer table (net_mts.hip)
 
 struct kws_net {
   kws_net_config_t cfg;
@@ -52,6 +53,8 @@ struct kws_net {
   GcProgram* gc = nullptr;
   // CONV_1D_GRU
   DkProgram* dk = nullptr;
+  // CONV_1D_MULTI_TIME_SLICED
+  MtProgram* mt = nullptr;
   // arithmetic of the pointwise GEMMs (kws_net_set_gemm_mode): 0 = f32 MFMA, 2 = fp16 x 2 split products (A/B arm)
   std::atomic<int> gemm_mode{0};
 };
@@ -116,6 +119,17 @@ int dk_debug_view(const kws_net* n, int B, int training, int what, int index, in
 int dk_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
                int64_t ws_bytes, hipStream_t st);
 int dk_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
+             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
+             int64_t ws_bytes, hipStream_t st);
+
+// ---- three-branch raw-waveform net (net_mts.hip) -------------------------------------------------------------------------
+int mt_build(kws_net* n);
+void mt_free(kws_net* n);
+int64_t mt_workspace_bytes(const kws_net* n, int B, int training);
+int mt_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
+int mt_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
+               int64_t ws_bytes, hipStream_t st);
+int mt_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
              float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
              int64_t ws_bytes, hipStream_t st);
 

@@ -7,7 +7,7 @@ from .keras_api import Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
-               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru')
+               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -183,6 +183,16 @@ def conv_1d_gru_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, RMSprop(lr=1e-3), name='conv_1d_bigru', loss='cce')
 
 
+def conv_1d_multi_time_sliced_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:1080-1156: raw waveform viewed as [4000, 4], [3200, 5] and [640, 25], each view a ladder of depthwise
+    blocks (DepthwiseConv2D((1, k), VALID) -> Conv1D(F, 1) -> BatchNormalization -> relu6, l2 1e-5), a reduce block followed by
+    MaxPool1D(3, strides=2, 'same'); five one-step branch ends of 64 channels concatenated -> Dropout(.1) -> a one-tap block (128)
+    -> Dropout(.1) -> Conv1D(num_classes, 1, softmax); RMSprop(3e-3), categorical CE."""
+    _raw_16000('conv_1d_multi_time_sliced', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, num_classes, input_size=16000)
+    return Model(net, RMSprop(lr=3e-3), name='conv_1d_multi_time_sliced', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -206,6 +216,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_heavy_model(input_size, num_classes)
     if model_type == 'conv_1d_gru':
         return conv_1d_gru_model(input_size, num_classes)
+    if model_type == 'conv_1d_multi_time_sliced':
+        return conv_1d_multi_time_sliced_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"

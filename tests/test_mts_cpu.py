@@ -1,0 +1,259 @@
+"""CPU checks of conv_1d_multi_time_sliced: the structure recorded from the reference (tests/golden/mts_models.json, made by
+tests/golden/make_golden_mts.py) against the ladders the model is specified by, the native tensor table and the float64 oracle
+(tests/mts_oracle.py) against that fixture, the oracle against torch autograd (tests/mts_torch.py), its SAME pool against
+F.max_pool1d over TensorFlow's padding, and the speech_model surface."""
+import ctypes
+import json
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+from speech_recognition_amd import _lib
+from mts_oracle import (GOLDEN, MODEL, MtsNet, load_structure, pool_same_argmax, pool_same_bwd, pool_same_fwd, pool_same_geometry)
+from mts_torch import same_pool, torch_step
+
+# (length after the block's convolution, length after its pool) of every reduce block, then the context / tap lengths
+XS4 = [(3998, 1999), (1997, 999), (997, 499), (497, 249), (247, 124), (122, 61), (59, 30)]
+XS5 = [(3198, 1599), (1597, 799), (797, 399), (397, 199), (197, 99), (97, 49), (47, 24)]
+XS25 = [(638, 319), (317, 159), (157, 79), (77, 39), (37, 19)]
+WIDE = [16, 32, 48, 64, 96, 128, 160]
+
+
+def _gold():
+    with open(GOLDEN) as f:
+        return json.load(f)[MODEL]
+
+
+def _expected_blocks():
+    """(k, C, F, L_in, L_conv, L_pool or None) of the 32 blocks, from the model's specification."""
+    out = []
+    for view, ladder, tap_k, tail_k in (((4000, 4), XS4, 28, 11), ((3200, 5), XS5, 22, 8)):
+        L, C = view
+        for F, (lc, lp) in zip(WIDE, ladder):
+            out.append((3, C, F, L, lc, lp))
+            L, C = lp, F
+        out.append((3, 160, 160, L, L - 2, None))            # context(160, 3): the tensor with two consumers
+        fork = L - 2
+        assert fork == tap_k
+        out.append((tap_k, 160, 64, fork, 1, None))          # tap a
+        lp = -(-(fork - 2) // 2)
+        out.append((3, 160, 192, fork, fork - 2, lp))        # reduce(192, 3)
+        out.append((3, 192, 192, lp, lp - 2, None))          # context(192, 3)
+        assert lp - 2 == tail_k
+        out.append((tail_k, 192, 64, tail_k, 1, None))       # tap b
+    L, C = 640, 25
+    for F, (lc, lp) in zip([32, 48, 64, 96, 128], XS25):
+        out.append((3, C, F, L, lc, lp))
+        L, C = lp, F
+    out.append((3, 128, 128, 19, 17, None))
+    out.append((17, 128, 64, 17, 1, None))
+    out.append((1, 320, 128, 1, 1, None))                    # the head's one-tap block
+    return out
+
+
+def test_kind_constant():
+    assert _lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED == 11
+
+
+def test_fixture_has_the_expected_structure():
+    gold = _gold()
+    assert (gold['model_name'], gold['optimizer'], gold['lr'], gold['loss']) == \
+        ('conv_1d_multi_time_sliced', 'RMSprop', 3e-3, 'categorical_crossentropy')
+    assert gold['input_size'] == 16000 and gold['output_shape'] == [gold['num_classes']] == [12]
+    blocks, ends, _ = load_structure()
+    exp = _expected_blocks()
+    assert len(blocks) == len(exp) == 32
+    for b, (k, C, F, L, lc, lp) in zip(blocks, exp):
+        assert (b['k'], b['C'], b['F'], b['L'], b['Lout']) == (k, C, F, L, lc), b['idx']
+        assert (b['pool'] is None) == (lp is None), b['idx']
+        if lp is not None:
+            assert b['pool']['Lp'] == lp == -(-lc // 2), b['idx']
+            assert b['pool']['pad_l'] == lc % 2, b['idx']                   # 0 for an even input length, 1 for an odd one
+            assert b['pool']['pad_total'] == 2 * (lp - 1) + 3 - lc
+    assert {b['pool']['pad_l'] for b in blocks if b['pool']} == {0, 1}        # the ladders exercise both
+    layers = gold['layers']
+    assert sum(l['class'] == 'Conv1D' for l in layers) == 33 and sum(l['class'] == 'DepthwiseConv2D' for l in layers) == 32
+    assert [l['output'] for l in layers if l['class'] == 'Reshape'] == [[4000, 4], [3200, 5], [640, 25], [12]]
+    # the three views read the raw input, the two forks have two consumers each
+    assert [b['src'] for b in blocks if b['src'][0] == 'raw'] == [('raw', 4000, 4), ('raw', 3200, 5), ('raw', 640, 25)]
+    readers = {}
+    for b in blocks:
+        if b['src'][0] == 'act':
+            readers.setdefault(b['src'][1], []).append(b['idx'])
+    assert {k: v for k, v in readers.items() if len(v) > 1} == {8: [9, 10], 20: [21, 22]}
+    assert (blocks[7]['Lout'], blocks[19]['Lout']) == (28, 22)
+    # the concatenation: five one-step ends of 64 channels, in this order
+    cat = [l for l in layers if l['class'] == 'Concatenate'][0]
+    assert ends == [9, 12, 21, 24, 31] and cat['inputs'] == [[1, 64]] * 5 and cat['output'] == [1, 320] and cat['axis'] == -1
+    assert [l['rate'] for l in layers if l['class'] == 'Dropout'] == [0.1, 0.1]
+    assert blocks[-1]['src'] == ('concat',)
+    # every block layer without bias and with l2 1e-5, the classifier with bias, softmax and no l2
+    convs = [l for l in layers if l['class'] == 'Conv1D']
+    assert all(not c['use_bias'] and c['activation'] is None for c in convs[:-1])
+    assert convs[-1]['use_bias'] and convs[-1]['activation'] == 'softmax' and convs[-1]['kernel'] == [1, 128, 12]
+    l2 = {w['name']: w['l2'] for w in gold['weights']}
+    assert all(l2[n] == 1e-5 for n in l2 if n.endswith('depthwise_kernel') or (n.endswith('/kernel') and not n.startswith('conv1d_33')))
+    assert l2['conv1d_33/kernel'] == 0.0 and l2['conv1d_33/bias'] == 0.0
+
+
+def test_oracle_matches_the_fixture():
+    gold = _gold()
+    ora = MtsNet(num_classes=gold['num_classes'])
+    assert list(ora.params) == [w['name'] for w in gold['weights'] if not w.get('state')]
+    assert list(ora.state) == [w['name'] for w in gold['weights'] if w.get('state')]
+    for w in gold['weights']:
+        v = ora.state[w['name']] if w.get('state') else ora.params[w['name']]
+        assert list(v.shape) == w['shape'], w['name']
+    assert ora.count_params() == sum(int(np.prod(w['shape'])) for w in gold['weights'])
+    assert set(ora.l2_names) == {w['name'] for w in gold['weights'] if w['l2'] > 0}
+    assert ora.forks == [8, 20] and ora.keep == [0.9, 0.9]
+    assert MtsNet(num_classes=30).params['conv1d_33/kernel'].shape == (1, 128, 30)
+
+
+def test_native_tensor_table_matches_the_fixture():
+    gold = _gold()
+    lib = _lib.load()
+    cfg = _lib.NetConfig(_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, gold['num_classes'], 1, 16000, 0, 0)
+    h = ctypes.c_void_p()
+    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
+    try:
+        table = []
+        for i in range(lib.kws_net_num_tensors(h)):
+            ti = _lib.TensorInfo()
+            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
+            table.append(ti)
+    finally:
+        lib.kws_net_destroy(h)
+    assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
+    for t, w in zip(table, gold['weights']):
+        assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']
+        assert bool(t.is_state) == bool(w.get('state', False)), w['name']
+        assert t.l2 == np.float32(w['l2']), w['name']
+    cfg = _lib.NetConfig(_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 12, 1, 8000, 0, 0)
+    assert lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)) != 0
+    assert b'input_size' in lib.kws_last_error()
+
+
+def _perturbed(seed=5, negative=True):
+    ora = MtsNet(num_classes=12)
+    rng = np.random.RandomState(seed)
+    for k in ora.params:
+        if k.endswith('gamma'):
+            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
+            if negative:        # a third of the scales negative
+                g = g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)
+            ora.params[k] = g.astype(np.float32)
+        if k.endswith('beta'):
+            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+        if k.endswith('bias'):
+            ora.params[k] = (0.05 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    return ora
+
+
+def _batch(B, seed):
+    rng = np.random.RandomState(seed)
+    return (rng.randn(B, 16000) * 0.3).astype(np.float32), np.eye(12, dtype=np.float32)[rng.randint(0, 12, B)]
+
+
+@pytest.fixture(scope='module')
+def step3():
+    """One oracle step and its torch twin at batch 3, a third of the BN scales negative: shared, left unchanged."""
+    ora = _perturbed()
+    x, y = _batch(3, 7)
+    return ora, x, y, ora.loss_and_grads(x, y, seed=3, step=5), torch_step(ora, x, y, seed=3, step=5)
+
+
+def _assert_matches_torch(ref, tor):
+    loss, p, grads, _ = ref
+    tl, tp, tg, _ = tor
+    assert abs(loss - tl) < 1e-10
+    np.testing.assert_allclose(p, tp, atol=1e-12)
+    for k, g in grads.items():
+        scale = max(np.abs(tg[k]).max(), 1e-12)
+        assert np.abs(g - tg[k].reshape(g.shape)).max() / scale < 1e-9, k
+
+
+def test_oracle_gradients_match_torch_autograd_with_negative_scales(step3):
+    ora, x, y, ref, tor = step3
+    assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
+    _assert_matches_torch(ref, tor)
+
+
+def test_oracle_gradients_match_torch_autograd_with_positive_scales():
+    ora = _perturbed(seed=6, negative=False)
+    x, y = _batch(3, 8)
+    _assert_matches_torch(ora.loss_and_grads(x, y, seed=1, step=2), torch_step(ora, x, y, seed=1, step=2))
+
+
+@pytest.mark.parametrize("L", [2, 3, 4, 5, 20, 37])
+def test_oracle_pool_matches_torch_max_pool1d_with_same_padding(L):
+    rng = np.random.RandomState(L)
+    a = np.clip(rng.randn(3, L, 8) * 3.0, 0, 6)       # saturated 0 / 6 values: plenty of ties
+    Lp, pad_l = pool_same_geometry(L)
+    assert (Lp, pad_l) == ((L + 1) // 2, L % 2)
+    ind = pool_same_argmax(a, pad_l)
+    z = pool_same_fwd(a, ind, pad_l)
+    ta = torch.tensor(a, requires_grad=True)
+    tz = same_pool(ta.permute(0, 2, 1), pad_l).permute(0, 2, 1)
+    assert tz.shape[1] == Lp
+    np.testing.assert_array_equal(z, tz.detach().numpy())
+    dz = rng.randn(*z.shape)
+    tz.backward(torch.tensor(dz))
+    np.testing.assert_allclose(pool_same_bwd(dz, ind, L, pad_l), ta.grad.numpy(), atol=1e-15)   # torch: the first maximum too
+    # tied values: the first maximum wins, the last-maximum variant differs
+    q = rng.randint(1, 4, size=(3, L, 8)).astype(np.float64)
+    first, last = pool_same_argmax(q, pad_l), pool_same_argmax(q, pad_l, last=True)
+    assert (first <= last).all() and (first < last).any()
+    tq = torch.tensor(q, requires_grad=True)
+    same_pool(tq.permute(0, 2, 1), pad_l).permute(0, 2, 1).backward(torch.tensor(dz))
+    np.testing.assert_allclose(pool_same_bwd(dz, first, L, pad_l), tq.grad.numpy(), atol=1e-15)
+
+
+def test_pool_comparison_excludes_little():
+    """The GPU pool test compares g only away from the ReLU6 kinks (1e-5) and from ties (the window's two largest activations
+    more than 1e-6 apart): on its cases and seeds that leaves out less than 0.1 %, by the oracle alone."""
+    from mts_cases import POOL_CASES, pool_excluded_share, pool_inputs
+    for case in POOL_CASES:
+        assert pool_excluded_share(*pool_inputs(*case)) < 1e-3, case
+
+
+@pytest.mark.parametrize("mutate", ['drop_fork', 'pool_pad_side'])
+def test_mutated_oracle_breaks_the_gradient_bar(step3, mutate):
+    """Negative control on the oracle itself: each wrong variant moves the gradients far past the relative bar the GPU tests
+    apply."""
+    ora, x, y, ref, _ = step3
+    good = ref[2]
+    bad = ora.loss_and_grads(x, y, seed=3, step=5, mutate=mutate)[2]
+    err = max(np.abs(bad[k] - good[k]).max() / max(np.abs(good[k]).max(), 1e-12) for k in good)
+    assert err > 1e-2, err
+    if mutate == 'drop_fork':      # only what lies upstream of a fork moves
+        assert np.array_equal(bad['conv1d_12/kernel'], good['conv1d_12/kernel'])
+        assert np.abs(bad['conv1d_8/kernel'] - good['conv1d_8/kernel']).max() > 0
+
+
+def test_speech_model_surface(monkeypatch):
+    """speech_model('conv_1d_multi_time_sliced', ...) asks for kind 11 with RMSprop(3e-3), the reference's model name and the
+    categorical CE (the device net itself replaced: no GPU here); other input sizes are refused."""
+    from speech_recognition_amd import keras_api, model as M
+
+    class FakeNet(object):
+        def __init__(self, kind, num_classes, **kw):
+            self.kind, self.num_classes, self.kw = kind, num_classes, kw
+
+    captured = {}
+
+    def fake_model(net, optimizer, name=None, loss=None):
+        captured.update(net=net, optimizer=optimizer, name=name, loss=loss)
+        return captured
+
+    monkeypatch.setattr(M, 'DeviceNet', FakeNet)
+    monkeypatch.setattr(M, 'Model', fake_model)
+    assert 'conv_1d_multi_time_sliced' in M.ACCELERATED
+    M.speech_model('conv_1d_multi_time_sliced', 16000, 12)
+    assert captured['net'].kind == 11 and captured['net'].num_classes == 12 and captured['net'].kw['input_size'] == 16000
+    assert captured['name'] == 'conv_1d_multi_time_sliced' and captured['loss'] == 'cce'
+    assert isinstance(captured['optimizer'], keras_api.RMSprop) and abs(float(captured['optimizer'].lr) - 3e-3) < 1e-9
+    with pytest.raises(ValueError):
+        M.speech_model('conv_1d_multi_time_sliced', 8000, 12)
