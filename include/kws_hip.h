@@ -445,6 +445,44 @@ int kws_stem_bwd_f32(const float* dy, const float* x, const float* w, const floa
                      int N, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bidirectional(GRU(H, dropout, recurrent_dropout)) of Keras 2.1.2 (GRUCell, implementation=1, return_sequences=False,
+ * merge_mode='concat'), reference model.py:148 (conv_1d_simple_model) and the GRU of xception_with_attention.  Per direction d
+ * (0: t = 0 .. T-1, 1: t = T-1 .. 0, h = 0 before the first step), gates g in (z, r, h) = column blocks of kernel [I, 3H]:
+ *   a_g = (x * mx_g) W_g + bias_g;  z = hs(a_z + (h * mh_z) U_z);  r = hs(a_r + (h * mh_r) U_r);  hs(v) = clip(0.2 v + 0.5, 0, 1)
+ *   c = tanh(a_h + (r * h * mh_h) U_h)  (r before the product);  h' = z h + (1 - z) c;  out [B, 2H] = [h_fwd(T-1) | h_bwd(0)]
+ * x [B, T, I]; W_d [I, 3H], U_d [H, 3H], bias_d [3H]; mx [2][3][B][I] and mh [2][3][B][H] hold 0 or 1 / keep per batch row (either
+ * may be NULL: no mask).  kws_gru_masks draws them from the counter RNG of kws_dropout_fwd: layer id 16 + 6 d + g for mx_g and
+ * 16 + 6 d + 3 + g for mh_g, element counter (row_offset + b) * n + i.
+ *   kws_gru_seq_fwd_f32  the recurrence alone, ONE launch for all steps and both directions.  Pre-activation (d, g, b, t, j) is
+ *                        read at a + d * dir_stride + g * gate_stride + (b * T + t) * row_stride + j (bias NOT included).  save
+ *                        (NULL in inference): kws_gru_save_floats() floats [2][4: z, r, c, h][B, T, H].
+ *   kws_gru_seq_bwd_f32  the same against time.  UT [2][3][H][H] with UT[d][g][k][j] = U_d[j][g H + k]; writes the pre-activation
+ *                        gradients da [2][3][B T][H] (gate-major) and the left operands of U, lop [2][3][B T][H] =
+ *                        (h_prev mh_z | h_prev mh_r | r h_prev mh_h), whose products with da are the gradients of U.
+ *   kws_gru_fwd_f32      input projections (kws_gemm_nn_f32: one [B T, I] x [I, 3H] product per direction without mx, one per
+ *                        gate on the materialised masked views of x with it) + the recurrence.
+ *   kws_gru_bwd_f32      recurrence backward + dW, dU (kws_gemm_tn_f32), dbias (fixed-order column sums) per direction and
+ *                        dx = sum_{d,g} (da_g W_g^T) * mx_g (dx may be NULL).  workspace: kws_gru_workspace_floats(.., backward)
+ *                        floats; the backward needs nothing the forward left in it but `save`.
+ * Domain: B >= 1, 1 <= T <= 1024, H % 16 == 0 with 16 <= H <= 256, I % 4 == 0.  No atomics: bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int64_t kws_gru_save_floats(int B, int T, int H);
+int64_t kws_gru_workspace_floats(int B, int T, int I, int H, int backward);
+int kws_gru_masks(float* mx, float* mh, int B, int I, int H, float keep_prob, uint64_t seed, uint32_t step, int64_t row_offset,
+                  void* stream);
+int kws_gru_seq_fwd_f32(const float* a, int64_t dir_stride, int64_t gate_stride, int row_stride, const float* U0, const float* U1,
+                        const float* bias0, const float* bias1, const float* mh, float* out, float* save, int B, int T, int H,
+                        void* stream);
+int kws_gru_seq_bwd_f32(const float* dout, const float* UT, const float* mh, const float* save, float* da, float* lop, int B, int T,
+                        int H, void* stream);
+int kws_gru_fwd_f32(const float* x, const float* W0, const float* U0, const float* bias0, const float* W1, const float* U1,
+                    const float* bias1, const float* mx, const float* mh, float* out, float* save, float* workspace, int B, int T,
+                    int I, int H, void* stream);
+int kws_gru_bwd_f32(const float* dout, const float* x, const float* W0, const float* U0, const float* W1, const float* U1,
+                    const float* mx, const float* mh, const float* save, float* dx, float* dW0, float* dU0, float* dbias0, float* dW1,
+                    float* dU1, float* dbias1, float* workspace, int B, int T, int I, int H, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a14  optimizers on one flat parameter buffer, reference model.py:834 (RMSprop(lr=1e-3)) and
  *      model.py:96,110 (SGD momentum); constants SURVEY D.5.  g_eff = grad*grad_scale + 2*l2[i]*p
  *      (l2[i] = per-element kernel_regularizer coefficient, 0 for BN/bias).
@@ -497,6 +535,12 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         Dropout(.1) -> a one-tap depthwise block (128) -> Dropout(.1) -> Conv1D(num_classes, 1, softmax, bias).
  *                         32 blocks in the reference's creation order; debug views: what 0 = raw pointwise output of block `index`
  *                         (0 .. 31), what 2 = table of batch_normalization_{index+1}.
+ *   KWS_NET_CONV_1D_SIMPLE: conv_1d_simple_model, reference model.py:116-156 (raw input, input_size must be 16000; Keras model
+ *                         name 'conv_1d_time_stacked'): fourteen VALID depthwise blocks on the ladder of KWS_NET_CONV_1D_GRU (k 31 at
+ *                         stride 16 on one channel, then k 3 at strides 1, 2, 1, ...; F = 32, 32, 64, 64 .. 224, 224) ending at
+ *                         [B, 10, 224] -> Bidirectional(GRU(128, dropout=.2, recurrent_dropout=.2)) (kws_gru_*) -> Dense + softmax.
+ *                         Debug views: what 0 / 1 / 2 as for KWS_NET_CONV_1D_GRU (block `index` 0 .. 13), what 5 = the GRU's saved
+ *                         steps [2 directions][4: z, r, c, h][B, 10, 128] (training), what 6 = the GRU output [B, 256].
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -512,6 +556,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_HEAVY 9
 #define KWS_NET_CONV_1D_GRU 10
 #define KWS_NET_CONV_1D_MULTI_TIME_SLICED 11
+#define KWS_NET_CONV_1D_SIMPLE 12
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

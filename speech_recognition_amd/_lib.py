@@ -23,6 +23,7 @@ KWS_NET_CONV_1D_TIME_STACKED = 8
 KWS_NET_CONV_1D_HEAVY = 9
 KWS_NET_CONV_1D_GRU = 10
 KWS_NET_CONV_1D_MULTI_TIME_SLICED = 11
+KWS_NET_CONV_1D_SIMPLE = 12
 
 
 class KwsError(RuntimeError):
@@ -165,6 +166,13 @@ SIGNATURES = {
     "kws_dwconvk_pw1_fwd_f32": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
     "kws_dwconvk_pw1_bwd_workspace_floats": (_I64, [_I64, _I]),
     "kws_dwconvk_pw1_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I, _P, _P]),
+    "kws_gru_save_floats": (_I64, [_I, _I, _I]),
+    "kws_gru_workspace_floats": (_I64, [_I, _I, _I, _I, _I]),
+    "kws_gru_masks": (_I, [_P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_uint32, _I64, _P]),
+    "kws_gru_seq_fwd_f32": (_I, [_P, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_gru_seq_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_gru_fwd_f32": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),
+    "kws_gru_bwd_f32": (_I, [_P] * 17 + [_I, _I, _I, _I, _P]),
     "kws_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
     "kws_bn_stats_finalize": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "kws_bn_infer_prepare": (_I, [_P, _P, _P, _P, _F, _I, _P, _P]),

@@ -504,18 +504,24 @@ struct FtArgs {
   int B, D, F, NC;
   uint32_t key, thresh; float inv_keep, inv_loss_batch; int64_t row_offset;
 };
-template <bool TRAIN>
+// RAW (conv_1d_simple's head behind the GRU): the features are y as it is - signed, no table, no dropout
+template <bool TRAIN, bool RAW = false>
 __global__ __launch_bounds__(256) void flat_tail_kernel(FtArgs a) {
   __shared__ float s_feat[FT_MAXD], s_red[4][FT_MAXNC], s_p[FT_MAXNC], s_dl[FT_MAXNC];
   const int b = blockIdx.x, tid = threadIdx.x, D = a.D, NC = a.NC;
   const uint32_t row = (uint32_t)(a.row_offset + b);
   const float* yb = a.y + (int64_t)b * D;
   for (int i = tid; i < D; i += 256) {
-    const int c = i % a.F, grp = c / a.Ng, n = c - grp * a.Ng;
-    const float* t = a.bn + (int64_t)grp * 4 * a.Ng;
-    float f = relu6f(fmaf(yb[i], t[n], t[a.Ng + n]));
+    float f;
+    if (RAW) {
+      f = yb[i];
+    } else {
+      const int c = i % a.F, grp = c / a.Ng, n = c - grp * a.Ng;
+      const float* t = a.bn + (int64_t)grp * 4 * a.Ng;
+      f = relu6f(fmaf(yb[i], t[n], t[a.Ng + n]));
+    }
     if (TRAIN) {
-      f = kws_keep(row * (uint32_t)D + (uint32_t)i, a.key, a.thresh) ? f * a.inv_keep : 0.f;
+      if (!RAW) f = kws_keep(row * (uint32_t)D + (uint32_t)i, a.key, a.thresh) ? f * a.inv_keep : 0.f;
       a.fd[(int64_t)b * D + i] = f;
     }
     s_feat[i] = f;
@@ -580,7 +586,7 @@ __global__ __launch_bounds__(256) void flat_tail_kernel(FtArgs a) {
   for (int i = tid; i < D; i += 256) {
     float dv = 0.f;
     for (int q = 0; q < NC; ++q) dv = fmaf(a.Wd[(int64_t)i * NC + q], s_dl[q], dv);
-    a.dA[(int64_t)b * D + i] = kws_keep(row * (uint32_t)D + (uint32_t)i, a.key, a.thresh) ? dv * a.inv_keep : 0.f;
+    a.dA[(int64_t)b * D + i] = RAW ? dv : kws_keep(row * (uint32_t)D + (uint32_t)i, a.key, a.thresh) ? dv * a.inv_keep : 0.f;
   }
 }
 
@@ -634,7 +640,7 @@ int kws_gbn_bwd_finish(float* gbuf, const float* y, const float* bn, int64_t M, 
 }
 
 int kws_flat_tail_launch(const kws_flat_tail_args* t, int training, hipStream_t st) {
-  KWS_REQUIRE(t && t->y && t->bn && t->Wd && t->probs && t->B > 0 && t->D > 0 && t->D <= FT_MAXD && t->F > 0 &&
+  KWS_REQUIRE(t && t->y && (t->bn || t->raw) && t->Wd && t->probs && t->B > 0 && t->D > 0 && t->D <= FT_MAXD && t->F > 0 &&
                   t->D % t->F == 0 && t->Ng > 0 && t->F % t->Ng == 0 && t->NC > 0 && t->NC <= FT_MAXNC,
               "flat_tail: bad arguments (D=%d F=%d NC=%d)", t ? t->D : 0, t ? t->F : 0, t ? t->NC : 0);
   KWS_REQUIRE(!training || (t->labels && t->fd && t->dl && t->dA && t->per_loss && t->per_correct),
@@ -649,7 +655,9 @@ int kws_flat_tail_launch(const kws_flat_tail_args* t, int training, hipStream_t 
   a.inv_loss_batch = 1.0f / (float)(t->loss_batch > 0 ? t->loss_batch : 1);
   a.row_offset = t->row_offset;
   KwsProfScope prof("flat_tail", 2.0 * t->B * t->D * t->NC * (training ? 2.0 : 1.0), 4.0 * (double)t->B * t->D * (training ? 3.0 : 1.0), st);
-  if (training) hipLaunchKernelGGL((flat_tail_kernel<true>), dim3((unsigned)t->B), dim3(256), 0, st, a);
+  if (t->raw && training) hipLaunchKernelGGL((flat_tail_kernel<true, true>), dim3((unsigned)t->B), dim3(256), 0, st, a);
+  else if (t->raw) hipLaunchKernelGGL((flat_tail_kernel<false, true>), dim3((unsigned)t->B), dim3(256), 0, st, a);
+  else if (training) hipLaunchKernelGGL((flat_tail_kernel<true>), dim3((unsigned)t->B), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((flat_tail_kernel<false>), dim3((unsigned)t->B), dim3(256), 0, st, a);
   KWS_LAUNCH_CHECK("flat_tail_kernel");
   return KWS_OK;

@@ -109,13 +109,15 @@ int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, in
 int kws_gbn_bwd_finish(float* g, const float* y, const float* bn, int64_t M, int groups, int Ng, const float* part, int rows, float* coef,
                        float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
 // Flatten -> Dropout -> Dense(bias or none: bd NULL) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F;
-// layer_id: the dropout layer's id (0 = 1)
+// layer_id: the dropout layer's id (0 = 1).  raw != 0: the features are y itself (signed, bn unused, no dropout): Dense + softmax
+// behind conv_1d_simple's GRU
 struct kws_flat_tail_args {
   const float* y; const float* bn; int Ng;
   const float* Wd; const float* bd; const float* labels;
   float* probs; float* fd; float* dl; float* dA; float* per_loss; float* per_correct;
   int B, D, F, NC;
   uint64_t seed; uint32_t step; float keep_prob; int loss_batch; int64_t row_offset; uint32_t layer_id;
+  int raw;
 };
 int kws_flat_tail_launch(const kws_flat_tail_args* a, int training, hipStream_t st);
 #ifdef __HIPCC__

@@ -1,9 +1,15 @@
-// Network program of the general depthwise ladder:
+// Network programs of the general depthwise ladder:
 //   KWS_NET_CONV_1D_GRU  conv_1d_gru_model (reference model.py:470-512; Keras model name 'conv_1d_bigru', no recurrent layer):
 //                        raw waveform as [16000, 1] -> six _depthwise_conv_block (DepthwiseConv2D((1, k), strides=s, l2 1e-5) ->
 //                        Conv1D(F, 1, l2 1e-5) -> BatchNormalization -> relu6) with k 63 / 31 / 15 / 7 / 5 SAME at strides
 //                        16 / 4 / 4 / 4 / 2 and k 8 VALID, F = 128 / 256 / 384 / 448 / 512 / 512 -> Flatten (one time step) ->
 //                        Dropout(.3) -> Dense(256) -> relu6 -> Dropout(.3) -> Dense + softmax; RMSprop(1e-3), categorical CE
+//   KWS_NET_CONV_1D_SIMPLE  conv_1d_simple_model (reference model.py:116-156; Keras model name 'conv_1d_time_stacked'): raw waveform as
+//                        [16000, 1] -> fourteen such blocks, all VALID: k 31 at stride 16, then k 3 at strides 1, 2, 1, 2, 1, ...;
+//                        F = 32, 32, 64, 64, 96, 96 .. 224, 224; ends at [B, 10, 224] -> Bidirectional(GRU(128, dropout=.2,
+//                        recurrent_dropout=.2)) (gru.hip) -> Dense + softmax; Adam(1e-3), categorical CE.  No l2 on the GRU or the Dense
+//                        layer.  The activated ladder output is materialised for the GRU's GEMMs (kws_bn_relu6_apply), its masked
+//                        views by kws_gru_fwd_f32; the head is the flat tail's raw arm over the signed [B, 256] GRU output.
 // Data flow per block l (training), as in net.hip:
 //   z_l = dwk_l( relu6(bn_{l-1}(y_{l-1})) )     kws_dwconvk_fwd_f32, BN + ReLU6 applied on load
 //   y_l = z_l W_l                               f32 MFMA GEMM with the BN statistics in its epilogue
@@ -25,6 +31,10 @@ struct DkProgram {
   int NC = 0, D = 0, H = 0;          // features into the head, hidden width
   int64_t d1k = 0, d1b = -1, d2k = 0, d2b = 0;
   float keep = 0.7f;
+  // KWS_NET_CONV_1D_SIMPLE: the ladder ends in gT steps of D channels, a bidirectional GRU of gH units follows (H = 0: no hidden Dense)
+  bool gru = false;
+  int gT = 0, gH = 0;
+  int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
 };
 
 void dk_free(kws_net* n) {
@@ -37,6 +47,8 @@ namespace {
 constexpr float DK_DROP_KEEP = 0.7f;   // Dropout(0.3), model.py:502, 504
 constexpr int DK_HIDDEN = 256;         // Dense(256), model.py:503
 constexpr int DK_BIAS_SLICES = 32;
+constexpr int DK_GRU_UNITS = 128;      // GRU(128, ...), model.py:148
+constexpr float DK_GRU_KEEP = 0.8f;    // dropout=0.2, recurrent_dropout=0.2
 
 // tab [4][n] = 1 | bias (0 without one) | 0 | 1: what the flat tail reads as a BatchNorm table
 __global__ __launch_bounds__(256) void dk_bias_table_kernel(const float* __restrict__ bias, int n, float* __restrict__ tab) {
@@ -97,6 +109,7 @@ struct DkLayout {
   int64_t stats = 0, red = 0, fa = 0, fd1 = 0, h = 0, tab = 0;
   int64_t G[2] = {0, 0}, DZ = 0, part = 0, coef = 0, tn = 0, WT = 0, pw1ws = 0;
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0, bpart = 0;
+  int64_t gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;   // KWS_NET_CONV_1D_SIMPLE
 };
 
 void dk_layout(const kws_net* n, int B, bool training, DkLayout* lo) {
@@ -123,6 +136,36 @@ void dk_layout(const kws_net* n, int B, bool training, DkLayout* lo) {
       max_tn = std::max(max_tn, kws_gemm_tn_workspace_floats(M, b.cin, b.cout));
       max_w = std::max(max_w, (int64_t)b.cin * b.cout);
     }
+  }
+  if (p.gru) {
+    const int T = p.gT, I = p.D, H = p.gH;
+    max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows((int64_t)B * T) * 2 * I);
+    lo->stats = bp.take(max_stats);
+    lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 2 * maxC);
+    lo->fa = bp.take((int64_t)B * T * I);
+    lo->gout = bp.take((int64_t)B * 2 * H);
+    lo->gws = bp.take(kws_gru_workspace_floats(B, T, I, H, training ? 1 : 0));
+    if (training) {
+      lo->gmx = bp.take((int64_t)6 * B * I);
+      lo->gmh = bp.take((int64_t)6 * B * H);
+      lo->gsave = bp.take(kws_gru_save_floats(B, T, H));
+      lo->gdout = bp.take((int64_t)B * 2 * H);
+      lo->G[0] = bp.take(max_y);
+      lo->G[1] = bp.take(max_y);
+      lo->DZ = bp.take(max_z);
+      lo->part = bp.take(max_part);
+      lo->coef = bp.take((int64_t)2 * maxC);
+      lo->tn = bp.take(max_tn);
+      lo->WT = bp.take(max_w);
+      lo->pw1ws = bp.take(kws_dwconvk_pw1_bwd_workspace_floats((int64_t)B * p.blocks[0].Lout, p.blocks[0].cout));
+      lo->fd = bp.take((int64_t)B * 2 * H);
+      lo->dl = bp.take((int64_t)B * p.NC);
+      lo->per_loss = bp.take(B);
+      lo->per_correct = bp.take(B);
+      lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * 2 * H * p.NC);
+    }
+    lo->total = bp.cur * 4;
+    return;
   }
   max_stats = std::max(max_stats, (int64_t)2 * p.H * kws_gemm_num_row_tiles(B));
   max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(B) * 2 * p.D);
@@ -180,6 +223,14 @@ int dk_forward(const kws_net* n, const DkLayout& lo, const float* params, float*
       KWS_TRY(kws_bn_infer_prepare(params + b.bn.gamma, params + b.bn.beta, state + b.bn.mm, state + b.bn.mv, KWS_BN_EPS, b.cout,
                                    ws + lo.bn[i], st));
   }
+  if (p.gru) {   // the activated ladder output [B, T, I] is materialised for the GRU's GEMMs; masks only in training
+    const int T = p.gT, I = p.D, H = p.gH;
+    KWS_TRY(kws_bn_relu6_apply(ws + lo.y[nb - 1], ws + lo.bn[nb - 1], ws + lo.fa, (int64_t)B * T, I, 1, st));
+    if (training) KWS_TRY(kws_gru_masks(ws + lo.gmx, ws + lo.gmh, B, I, H, DK_GRU_KEEP, seed, step, row_offset, st));
+    return kws_gru_fwd_f32(ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gb[0], params + p.gW[1], params + p.gU[1],
+                           params + p.gb[1], training ? ws + lo.gmx : nullptr, training ? ws + lo.gmh : nullptr, ws + lo.gout,
+                           training ? ws + lo.gsave : nullptr, ws + lo.gws, B, T, I, H, st);
+  }
   // Flatten (one time step) -> Dropout -> Dense(H): the features are materialised for the GEMMs
   KWS_TRY(kws_bn_relu6_apply(ws + lo.y[nb - 1], ws + lo.bn[nb - 1], ws + lo.fa, B, p.D, 1, st));
   const float* feat = ws + lo.fa;
@@ -199,6 +250,14 @@ kws_flat_tail_args dk_tail_args(const kws_net* n, const DkLayout& lo, const floa
   const DkProgram& p = *n->dk;
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
+  if (p.gru) {   // Dense + softmax over the signed GRU output: the raw arm
+    t.y = ws + lo.gout; t.Ng = 2 * p.gH; t.raw = 1;
+    t.Wd = params + p.d2k; t.bd = params + p.d2b;
+    t.probs = probs;
+    t.B = B; t.D = 2 * p.gH; t.F = 2 * p.gH; t.NC = p.NC;
+    t.keep_prob = 1.f;
+    return t;
+  }
   t.y = ws + lo.h; t.bn = ws + lo.tab; t.Ng = p.H;
   t.Wd = params + p.d2k; t.bd = params + p.d2b;
   t.probs = probs;
@@ -215,8 +274,50 @@ int64_t KerasNames::dwk(int k, int C) {
                             k * C, k, 0.f);
 }
 
+// conv_1d_simple: _reduce_conv(x, 32, 31, strides=16), _context_conv(x, 32, 3), then for F in 64 .. 224: _reduce_conv(x, F, 3) (stride 2),
+// _context_conv(x, F, 3), all padding='valid' (model.py:142-146) -> Bidirectional(GRU(128)) -> Dense
+static int dk_build_simple(kws_net* n) {
+  const kws_net_config_t& c = n->cfg;
+  KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_simple input_size %d (the reference's ladder ends in 10 time steps for 16000 samples)",
+              c.input_size);
+  DkProgram* p = new DkProgram();
+  n->dk = p;
+  p->NC = c.num_classes;
+  p->gru = true;
+  KerasNames kn{n};
+  int L = c.input_size, cin = 1;
+  for (int i = 0; i < 14; ++i) {
+    DkBlock b;
+    b.Lin = L; b.k = i == 0 ? 31 : 3; b.stride = i == 0 ? 16 : (i % 2 == 0 ? 2 : 1); b.cin = cin; b.cout = i < 2 ? 32 : 32 * (i / 2 + 1);
+    KWS_REQUIRE(L >= b.k, "net: block %d input length %d < %d taps", i, L, b.k);
+    b.Lout = (L - b.k) / b.stride + 1;
+    b.pad_l = 0;
+    b.dw = kn.dwk(b.k, cin);
+    b.pw = kn.conv(1, cin, b.cout, KWS_L2_COEF);
+    b.bn = kn.bn(b.cout);
+    p->blocks.push_back(b);
+    L = b.Lout;
+    cin = b.cout;
+  }
+  KWS_REQUIRE(L == 10 && cin == 224, "net: conv_1d_simple ladder ends at [%d, %d], the GRU reads [10, 224]", L, cin);
+  p->D = cin;
+  p->gT = L;
+  p->gH = DK_GRU_UNITS;
+  const int H = p->gH;
+  for (int d = 0; d < 2; ++d) {   // recurrent_kernel: Keras's Orthogonal initialiser, drawn by the host (fan_in = 0 here)
+    const std::string base = std::string("bidirectional_1/") + (d ? "backward" : "forward") + "_gru_1/";
+    p->gW[d] = kws_net_add_tensor(n, base + "kernel", {p->D, 3 * H}, false, 0.f, p->D, 3 * H, 0.f);
+    p->gU[d] = kws_net_add_tensor(n, base + "recurrent_kernel", {H, 3 * H}, false, 0.f, 0, 0, 0.f);
+    p->gb[d] = kws_net_add_tensor(n, base + "bias", {3 * H}, false, 0.f, 0, 0, 0.f);
+  }
+  p->d2k = kws_net_add_tensor(n, "dense_1/kernel", {2 * H, p->NC}, false, 0.f, 2 * H, p->NC, 0.f);
+  p->d2b = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  return KWS_OK;
+}
+
 int dk_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
+  if (c.kind == KWS_NET_CONV_1D_SIMPLE) return dk_build_simple(n);
   KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_gru input_size %d (the reference's ladder ends in one time step for 16000 samples)",
               c.input_size);
   DkProgram* p = new DkProgram();
@@ -266,7 +367,18 @@ int dk_debug_view(const kws_net* n, int B, int training, int what, int index, in
   DkLayout lo;
   dk_layout(n, B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
-  if (what == 4) {   // the hidden Dense layer's output before its bias [B, H]
+  if (p.gru && what == 5) {   // the GRU's saved steps [2][4: z, r, c, h][B, T, H] (training)
+    KWS_REQUIRE(training, "net_debug_view: view 5 exists in training only");
+    *offset_floats = lo.gsave;
+    *count = kws_gru_save_floats(B, p.gT, p.gH);
+    return KWS_OK;
+  }
+  if (p.gru && what == 6) {   // the GRU output [B, 2H]
+    *offset_floats = lo.gout;
+    *count = (int64_t)B * 2 * p.gH;
+    return KWS_OK;
+  }
+  if (what == 4 && !p.gru) {   // the hidden Dense layer's output before its bias [B, H]
     *offset_floats = lo.h;
     *count = (int64_t)B * p.H;
     return KWS_OK;
@@ -324,18 +436,28 @@ int dk_train(const kws_net* n, const float* params, float* state, const float* x
   t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = G[0];
   t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct;
   t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
+  if (p.gru) t.dA = ws + lo.gdout;
   KWS_TRY(kws_flat_tail_launch(&t, 1, st));
   KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, p.H, p.NC, ws + lo.swg, st));
-  // G[0] = gradient wrt relu6(h + b1) [B, H] -> wrt h; dense_1's gradients; back through Dropout(.3) onto the activated features
-  KWS_TRY(dk_bias_relu6_bwd(G[0], ws + lo.h, p.d1b >= 0 ? params + p.d1b : nullptr, p.d1b >= 0 ? grads + p.d1b : nullptr, B, p.H,
-                            ws + lo.bpart, st));
-  KWS_TRY(kws_gemm_tn_f32(ws + lo.fd1, G[0], grads + p.d1k, B, p.D, p.H, ws + lo.tn, st));
-  KWS_TRY(kws_transpose_f32(params + p.d1k, ws + lo.WT, p.D, p.H, st));
-  KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, G[1], B, p.H, p.D, nullptr, st));
-  KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, seed, step, 1, row_offset, st));
-  int cur = 0;   // G[cur] = gradient wrt the activated output of the last block [B, 1, D]
-  {
+  int cur = 0;   // G[cur] = gradient wrt the activated output of the last block [B, T, D]
+  if (p.gru) {
+    const int T = p.gT, I = p.D, H = p.gH;
+    const DkBlock& b = p.blocks[nb - 1];
+    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, 2 * H, p.NC, ws + lo.swg, st));
+    KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
+                            ws + lo.gmh, ws + lo.gsave, G[0], grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
+                            grads + p.gU[1], grads + p.gb[1], ws + lo.gws, B, T, I, H, st));
+    KWS_TRY(kws_gbn_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], (int64_t)B * T, 1, b.cout, part, coef, grads + b.bn.gamma, 0,
+                        b.bn.beta - b.bn.gamma, st));
+  } else {
+    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, p.H, p.NC, ws + lo.swg, st));
+    // G[0] = gradient wrt relu6(h + b1) [B, H] -> wrt h; dense_1's gradients; back through Dropout(.3) onto the activated features
+    KWS_TRY(dk_bias_relu6_bwd(G[0], ws + lo.h, p.d1b >= 0 ? params + p.d1b : nullptr, p.d1b >= 0 ? grads + p.d1b : nullptr, B, p.H,
+                              ws + lo.bpart, st));
+    KWS_TRY(kws_gemm_tn_f32(ws + lo.fd1, G[0], grads + p.d1k, B, p.D, p.H, ws + lo.tn, st));
+    KWS_TRY(kws_transpose_f32(params + p.d1k, ws + lo.WT, p.D, p.H, st));
+    KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, G[1], B, p.H, p.D, nullptr, st));
+    KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, seed, step, 1, row_offset, st));
     const DkBlock& b = p.blocks[nb - 1];
     KWS_TRY(kws_gbn_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], B, 1, b.cout, part, coef, grads + b.bn.gamma, 0,
                         b.bn.beta - b.bn.gamma, st));

@@ -1,6 +1,6 @@
 // Shared between the five network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
 // residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
-// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru; net_mts.hip:
+// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru, conv_1d_simple; net_mts.hip:
 // conv_1d_multi_time_sliced).  Not part of the public C ABI.
 #pragma once
 #include <string.h>
@@ -29,7 +29,7 @@ struct Block {
 
 struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
 struct GcProgram;  // conv_1d_fast / conv_1d_spec / conv_1d_time_stacked / conv_1d_heavy layer table (net_grouped.hip)
-struct DkProgram;  // conv_1d_gru layer table (net_dwk.hip)
+struct DkProgram;  // conv_1d_gru / conv_1d_simple layer table (net_dwk.hip)
 struct MtProgram;  // conv_1d_multi_time_sliced layer table (net_mts.hip)
 
 struct kws_net {
@@ -51,7 +51,7 @@ struct kws_net {
   LmProgram* lm = nullptr;
   // CONV_1D_FAST / CONV_1D_SPEC / CONV_1D_TIME_STACKED / CONV_1D_HEAVY
   GcProgram* gc = nullptr;
-  // CONV_1D_GRU
+  // CONV_1D_GRU / CONV_1D_SIMPLE
   DkProgram* dk = nullptr;
   // CONV_1D_MULTI_TIME_SLICED
   MtProgram* mt = nullptr;

@@ -7,7 +7,7 @@ from .keras_api import Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
-               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced')
+               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -193,6 +193,16 @@ def conv_1d_multi_time_sliced_model(input_size=16000, num_classes=11, *args, **k
     return Model(net, RMSprop(lr=3e-3), name='conv_1d_multi_time_sliced', loss='cce')
 
 
+def conv_1d_simple_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:116-156: raw waveform as [16000, 1] -> fourteen VALID depthwise blocks (k 31 at stride 16, then k 3 at
+    strides 1, 2, 1, ...; F = 32, 32, 64, 64 ... 224, 224; l2 1e-5) ending at [10, 224] -> Bidirectional(GRU(128, dropout=.2,
+    recurrent_dropout=.2)) -> Dense; Adam() at the Keras defaults (lr 1e-3), categorical CE.  The reference names the Keras model
+    'conv_1d_time_stacked'."""
+    _raw_16000('conv_1d_simple', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_SIMPLE, num_classes, input_size=16000)
+    return Model(net, Adam(lr=1e-3), name='conv_1d_time_stacked', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -218,6 +228,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_gru_model(input_size, num_classes)
     if model_type == 'conv_1d_multi_time_sliced':
         return conv_1d_multi_time_sliced_model(input_size, num_classes)
+    if model_type == 'conv_1d_simple':
+        return conv_1d_simple_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"

@@ -94,14 +94,22 @@ class DeviceNet(object):
         return sum(s.size for s in self.tensors.values() if not s.is_state)
 
     def initialize(self, seed=87654321):
-        """Keras initialisers: glorot_uniform kernels, ones/zeros for BN, zeros bias."""
+        """Keras initialisers: glorot_uniform kernels, ones/zeros for BN, zeros bias; a GRU's `recurrent_kernel`
+        (fan_in = 0 in the native table, which has no field for an initialiser kind) is Keras's Orthogonal: the SVD factor of a
+        normal matrix of its shape, gain 1, drawn from a stream of its own so that every other tensor's draw stays what it was."""
         rng = np.random.RandomState(seed)
+        n_orth = 0
         p = np.zeros(self.n_params, np.float32)
         st = np.zeros(self.n_state, np.float32)
         l2 = np.zeros(self.n_params, np.float32)
         for s in self.tensors.values():
             dst = st if s.is_state else p
-            if s.fan_in > 0:
+            if s.name.endswith('/recurrent_kernel'):
+                n_orth += 1
+                orng = np.random.RandomState((int(seed) + 0x9E3779B1 * n_orth) & 0xFFFFFFFF)
+                u, _, v = np.linalg.svd(orng.normal(0.0, 1.0, s.shape), full_matrices=False)
+                dst[s.offset:s.offset + s.size] = (u if u.shape == tuple(s.shape) else v).astype(np.float32).reshape(-1)
+            elif s.fan_in > 0:
                 limit = np.sqrt(6.0 / (s.fan_in + s.fan_out))
                 dst[s.offset:s.offset + s.size] = rng.uniform(-limit, limit, size=s.size).astype(np.float32)
             else:
