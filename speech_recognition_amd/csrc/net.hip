@@ -1,6 +1,7 @@
 // Network programs: the forward / forward+backward of one model as a native sequence of kernel
 // launches on one HIP stream (no Python between layers, so the step can also be captured into a
-// hipGraph by the caller).  SURVEY 8a rows a7-a15.
+// hipGraph by the caller).  SURVEY 8a rows a7-a15.  This file holds the public net entry points, the
+// pieces every program shares, and the program of
 //
 //   KWS_NET_TS_ATTENTION  conv_1d_time_sliced_with_attention_model   reference model.py:775-838
 //
@@ -65,9 +66,26 @@ BnRef KerasNames::bn(int C, int* idx) {
   if (idx) *idx = n_bn;
   return kws_net_add_bn(n, n_bn, C);
 }
-int64_t KerasNames::dw(int C) {
-  return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(++n_dw) + "/depthwise_kernel", {1, 3, C, 1}, false,
-                            KWS_L2_COEF, 3 * C, 3, 0.f);
+int64_t KerasNames::dw(int C) { return dwk(3, C); }
+int64_t KerasNames::dwk(int k, int C) {
+  return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(++n_dw) + "/depthwise_kernel", {1, k, C, 1}, false, KWS_L2_COEF,
+                            k * C, k, 0.f);
+}
+
+int kws_workspace_check(const char* who, int64_t need_bytes, int64_t ws_bytes, int B) {
+  if (need_bytes <= ws_bytes) return KWS_OK;
+  kws_set_error("%s: workspace %lld B < %lld B needed for batch %d", who, (long long)ws_bytes, (long long)need_bytes, B);
+  return KWS_E_WORKSPACE;
+}
+
+int kws_flat_tail_train(kws_flat_tail_args* t, const float* labels, float* fd, float* dl, float* dA, float* per_loss,
+                        float* per_correct, uint64_t seed, uint32_t step, int loss_batch, int64_t row_offset, float* metrics,
+                        hipStream_t st) {
+  t->labels = labels; t->fd = fd; t->dl = dl; t->dA = dA;
+  t->per_loss = per_loss; t->per_correct = per_correct;
+  t->seed = seed; t->step = step; t->loss_batch = loss_batch; t->row_offset = row_offset;
+  KWS_TRY(kws_flat_tail_launch(t, 1, st));
+  return kws_metrics_launch(per_loss, per_correct, t->B, metrics, st);
 }
 
 namespace {
@@ -77,63 +95,6 @@ constexpr float BN_MOMENTUM = KWS_BN_MOMENTUM;
 constexpr float L2_COEF = KWS_L2_COEF;
 constexpr float DROP_KEEP = 0.6f;     // Dropout(0.4), model.py:819,828
 constexpr float LABEL_SMOOTH = 0.1f;  // model.py:835-836
-
-int build_ts_attention(kws_net* n) {
-  const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.filter_mult >= 1 && c.filter_mult <= 2, "net: filter_mult %d unsupported", c.filter_mult);
-  KWS_REQUIRE(c.input_size >= 1600 && c.input_size % 4 == 0, "net: input_size %d unsupported", c.input_size);
-  const int fm = c.filter_mult;
-  n->L_in = c.input_size;
-  // overlapping_time_slice_stack(x, 40, 20) SAME (model.py:805) fused with Conv1D(128,3,strides=2) (model.py:807)
-  int Lf, plf;
-  kws_same_pad(n->L_in, 40, 20, &Lf, &plf);
-  n->L1 = (Lf - 3) / 2 + 1;
-  n->C1 = 128 * fm;
-  KerasNames kn{n};
-  n->conv1 = kn.conv(3, 40, n->C1, L2_COEF);
-  n->bn1 = kn.bn(n->C1);
-  kws_gather_t g;
-  g.L_out = n->L1; g.cin = 40; g.taps = 3; g.stride_t = 2 * 20; g.stride_j = 20; g.base_off = -plf;
-  g.x_len = n->L_in; g.x_batch_stride = n->L_in;
-  n->gather1 = g;
-  // The three taps overlap (tap j covers samples 20 j .. 20 j + 39 of an 80-sample span): the convolution is a GEMM
-  // over the 80 DISTINCT samples with the kernel rows that hit the same sample added up front - 2/3 of the FLOPs.
-  n->K1f = g.stride_j * (g.taps - 1) + g.cin;
-  kws_gather_t gf = g;
-  gf.cin = n->K1f; gf.taps = 1; gf.stride_j = 0;
-  n->gather1f = gf;
-  static const int spec[11][2] = {{1, 128}, {2, 192}, {1, 192}, {2, 256}, {1, 256}, {2, 320},
-                                  {1, 320}, {2, 384}, {1, 384}, {2, 512}, {1, 512}};  // model.py:812-817
-  int L = n->L1, cin = n->C1;
-  for (int i = 0; i < 11; ++i) {
-    Block b;
-    b.stride = spec[i][0];
-    b.cin = cin;
-    b.cout = spec[i][1] * fm;
-    b.Lin = L;
-    if (b.stride == 2) {
-      kws_same_pad(L, 3, 2, &b.Lout, &b.pad_l);  // _reduce_conv: padding='same'
-    } else {
-      b.Lout = L - 2;  // _context_conv: padding='valid'
-      b.pad_l = 0;
-    }
-    KWS_REQUIRE(b.Lout >= 1, "net: input too short for block %d", i);
-    b.dw = kn.dw(cin);
-    b.pw = kn.conv(1, cin, b.cout, L2_COEF);
-    b.bn = kn.bn(b.cout);
-    n->blocks.push_back(b);
-    L = b.Lout;
-    cin = b.cout;
-  }
-  n->T = L;
-  n->C = cin;
-  n->NC = c.num_classes;
-  KWS_REQUIRE(n->T <= 16, "net: %d time steps at the tail (max 16)", n->T);
-  n->d1k = kws_net_add_tensor(n, "dense_1/kernel", {(int64_t)n->T * n->C, n->T}, false, L2_COEF, n->T * n->C, n->T, 0.f);
-  n->d1b = kws_net_add_tensor(n, "dense_1/bias", {n->T}, false, 0.f, 0, 0, 0.f);
-  n->d2k = kws_net_add_tensor(n, "dense_2/kernel", {2 * n->C, n->NC}, false, L2_COEF, 2 * n->C, n->NC, 0.f);
-  return KWS_OK;
-}
 
 // ---- first convolution with overlapping taps, folded -------------------------------------------------
 // Weff[s, n] = sum over taps j (ascending) with 0 <= s - hop*j < cin of W[j, s - hop*j, n]
@@ -159,23 +120,6 @@ __global__ __launch_bounds__(256) void unfold_taps_kernel(const float* __restric
   const int j = jc / cin, c = jc - j * cin;
   dW[i] = dWeff[(int64_t)(hop * j + c) * N + n];
 }
-int fold_conv1(const kws_net* net, const float* params, float* w1f, hipStream_t st) {
-  const kws_gather_t& g = net->gather1;
-  const int n = net->K1f * net->C1;
-  hipLaunchKernelGGL(fold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, params + net->conv1, w1f, g.taps, g.cin,
-                     g.stride_j, net->K1f, net->C1);
-  KWS_LAUNCH_CHECK("fold_taps_kernel");
-  return KWS_OK;
-}
-int unfold_conv1(const kws_net* net, const float* g1f, float* grads, hipStream_t st) {
-  const kws_gather_t& g = net->gather1;
-  const int n = g.taps * g.cin * net->C1;
-  hipLaunchKernelGGL(unfold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, g1f, grads + net->conv1, g.taps, g.cin,
-                     g.stride_j, net->C1);
-  KWS_LAUNCH_CHECK("unfold_taps_kernel");
-  return KWS_OK;
-}
-
 // ---- workspace layout ------------------------------------------------------------------------------
 struct Layout {
   int64_t total = 0;  // bytes
@@ -191,19 +135,132 @@ struct Layout {
   int64_t bn_stride = 0;
 };
 
-void make_layout(const kws_net* n, int B, bool training, Layout* lo) {
+struct Block {   // depthwise k 3 -> pointwise -> BN -> relu6
+  int stride, pad_l, cin, cout, Lin, Lout;
+  int64_t dw, pw;  // param offsets
+  BnRef bn;        // BN after the pointwise conv
+};
+
+// The layer table of the raw-waveform attention net and its launch sequences
+struct TsProgram : NetProgram {
+  const kws_net* net = nullptr;   // n_params, gemm_mode
+  int L_in = 0;        // samples per clip
+  int L1 = 0, C1 = 0;  // conv1 output
+  int64_t conv1 = 0;
+  BnRef bn1;
+  std::vector<Block> blocks;
+  int T = 0, C = 0, NC = 0;
+  int64_t d1k = 0, d1b = 0, d2k = 0;
+  kws_gather_t gather1;   // the reference's view: 3 taps of 40 samples, taps 20 samples apart (K = 120)
+  kws_gather_t gather1f;  // folded view used by the GEMMs: ONE tap of 80 contiguous samples (see fold_taps_kernel)
+  int K1f = 0;            // folded K
+
+  void make_layout(int B, bool training, Layout* lo) const;
+  int fold_conv1(const float* params, float* w1f, hipStream_t st) const;
+  int unfold_conv1(const float* g1f, float* grads, hipStream_t st) const;
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override {
+    return train_part(params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, ws, ws_bytes, st, 0, 0);
+  }
+  int train_part(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                 float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                 hipStream_t st, int phase, int split) const;
+};
+
+int ts_build(kws_net* n) {
+  TsProgram* p = new TsProgram();
+  n->program.reset(p);
+  p->net = n;
+  const kws_net_config_t& c = n->cfg;
+  KWS_REQUIRE(c.filter_mult >= 1 && c.filter_mult <= 2, "net: filter_mult %d unsupported", c.filter_mult);
+  KWS_REQUIRE(c.input_size >= 1600 && c.input_size % 4 == 0, "net: input_size %d unsupported", c.input_size);
+  const int fm = c.filter_mult;
+  p->L_in = c.input_size;
+  // overlapping_time_slice_stack(x, 40, 20) SAME (model.py:805) fused with Conv1D(128,3,strides=2) (model.py:807)
+  int Lf, plf;
+  kws_same_pad(p->L_in, 40, 20, &Lf, &plf);
+  p->L1 = (Lf - 3) / 2 + 1;
+  p->C1 = 128 * fm;
+  KerasNames kn{n};
+  p->conv1 = kn.conv(3, 40, p->C1, L2_COEF);
+  p->bn1 = kn.bn(p->C1);
+  kws_gather_t g;
+  g.L_out = p->L1; g.cin = 40; g.taps = 3; g.stride_t = 2 * 20; g.stride_j = 20; g.base_off = -plf;
+  g.x_len = p->L_in; g.x_batch_stride = p->L_in;
+  p->gather1 = g;
+  // The three taps overlap (tap j covers samples 20 j .. 20 j + 39 of an 80-sample span): the convolution is a GEMM
+  // over the 80 DISTINCT samples with the kernel rows that hit the same sample added up front - 2/3 of the FLOPs.
+  p->K1f = g.stride_j * (g.taps - 1) + g.cin;
+  kws_gather_t gf = g;
+  gf.cin = p->K1f; gf.taps = 1; gf.stride_j = 0;
+  p->gather1f = gf;
+  static const int spec[11][2] = {{1, 128}, {2, 192}, {1, 192}, {2, 256}, {1, 256}, {2, 320},
+                                  {1, 320}, {2, 384}, {1, 384}, {2, 512}, {1, 512}};  // model.py:812-817
+  int L = p->L1, cin = p->C1;
+  for (int i = 0; i < 11; ++i) {
+    Block b;
+    b.stride = spec[i][0];
+    b.cin = cin;
+    b.cout = spec[i][1] * fm;
+    b.Lin = L;
+    if (b.stride == 2) {
+      kws_same_pad(L, 3, 2, &b.Lout, &b.pad_l);  // _reduce_conv: padding='same'
+    } else {
+      b.Lout = L - 2;  // _context_conv: padding='valid'
+      b.pad_l = 0;
+    }
+    KWS_REQUIRE(b.Lout >= 1, "net: input too short for block %d", i);
+    b.dw = kn.dw(cin);
+    b.pw = kn.conv(1, cin, b.cout, L2_COEF);
+    b.bn = kn.bn(b.cout);
+    p->blocks.push_back(b);
+    L = b.Lout;
+    cin = b.cout;
+  }
+  p->T = L;
+  p->C = cin;
+  p->NC = c.num_classes;
+  KWS_REQUIRE(p->T <= 16, "net: %d time steps at the tail (max 16)", p->T);
+  p->d1k = kws_net_add_tensor(n, "dense_1/kernel", {(int64_t)p->T * p->C, p->T}, false, L2_COEF, p->T * p->C, p->T, 0.f);
+  p->d1b = kws_net_add_tensor(n, "dense_1/bias", {p->T}, false, 0.f, 0, 0, 0.f);
+  p->d2k = kws_net_add_tensor(n, "dense_2/kernel", {2 * p->C, p->NC}, false, L2_COEF, 2 * p->C, p->NC, 0.f);
+  return KWS_OK;
+}
+
+int TsProgram::fold_conv1(const float* params, float* w1f, hipStream_t st) const {
+  const kws_gather_t& g = gather1;
+  const int n = K1f * C1;
+  hipLaunchKernelGGL(fold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, params + conv1, w1f, g.taps, g.cin,
+                     g.stride_j, K1f, C1);
+  KWS_LAUNCH_CHECK("fold_taps_kernel");
+  return KWS_OK;
+}
+int TsProgram::unfold_conv1(const float* g1f, float* grads, hipStream_t st) const {
+  const kws_gather_t& g = gather1;
+  const int n = g.taps * g.cin * C1;
+  hipLaunchKernelGGL(unfold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, g1f, grads + conv1, g.taps, g.cin,
+                     g.stride_j, C1);
+  KWS_LAUNCH_CHECK("unfold_taps_kernel");
+  return KWS_OK;
+}
+
+void TsProgram::make_layout(int B, bool training, Layout* lo) const {
   Bump bp;
-  const int nb = (int)n->blocks.size();
+  const int nb = (int)blocks.size();
   lo->y.assign(nb + 1, 0);
   lo->z.assign(nb, 0);
-  int64_t max_y = (int64_t)B * n->L1 * n->C1, max_z = 0, max_part = 0, max_dwpart = 0, max_tn = 0;
-  int maxC = n->C1;
-  max_part = std::max((int64_t)kws_gemm_num_row_tiles((int64_t)B * n->L1), (int64_t)kws_conv1_stats_rows((int64_t)B * n->L1)) *
-             2 * n->C1;   // statistics rows of either first-convolution kernel
-  max_tn = std::max(kws_gemm_tn_workspace_floats((int64_t)B * n->L1, n->K1f, n->C1),
-                    kws_conv1_wgrad_workspace_floats((int64_t)B * n->L1));
+  int64_t max_y = (int64_t)B * L1 * C1, max_z = 0, max_part = 0, max_dwpart = 0, max_tn = 0;
+  int maxC = C1;
+  max_part = std::max((int64_t)kws_gemm_num_row_tiles((int64_t)B * L1), (int64_t)kws_conv1_stats_rows((int64_t)B * L1)) *
+             2 * C1;   // statistics rows of either first-convolution kernel
+  max_tn = std::max(kws_gemm_tn_workspace_floats((int64_t)B * L1, K1f, C1),
+                    kws_conv1_wgrad_workspace_floats((int64_t)B * L1));
   for (int i = 0; i < nb; ++i) {
-    const Block& b = n->blocks[i];
+    const Block& b = blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     if (M * b.cout > max_y) max_y = M * b.cout;
     if (M * b.cin > max_z) max_z = M * b.cin;
@@ -217,44 +274,44 @@ void make_layout(const kws_net* n, int B, bool training, Layout* lo) {
     if (b.cout > maxC) maxC = b.cout;
   }
   if (training) {
-    lo->y[0] = bp.take((int64_t)B * n->L1 * n->C1);
+    lo->y[0] = bp.take((int64_t)B * L1 * C1);
     for (int i = 0; i < nb; ++i) {
-      const Block& b = n->blocks[i];
+      const Block& b = blocks[i];
       lo->z[i] = bp.take((int64_t)B * b.Lout * b.cin);
       lo->y[i + 1] = bp.take((int64_t)B * b.Lout * b.cout);
     }
     lo->G = bp.take(max_y);
     lo->G2 = bp.take(max_y);
     lo->DZ = bp.take(max_z);
-    const int64_t tail_part = (int64_t)B * 5 * n->C;
+    const int64_t tail_part = (int64_t)B * 5 * C;
     lo->part = bp.take(std::max(std::max(max_part, max_dwpart), tail_part));
     lo->coef = bp.take(2 * maxC);
     lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * maxC);
     lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES *
-                      std::max((int64_t)n->T * n->C * n->T, (int64_t)2 * n->C * n->NC));
+                      std::max((int64_t)T * C * T, (int64_t)2 * C * NC));
     // round 4: the attention dense layer's slices keep a region of their own (both dense layers' slices wait for the call's slab sum)
-    lo->swg1 = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * n->T * n->C * n->T);
+    lo->swg1 = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * T * C * T);
     lo->WT.assign(nb, 0);
-    for (int i = 0; i < nb; ++i) lo->WT[i] = bp.take((int64_t)n->blocks[i].cin * n->blocks[i].cout);
+    for (int i = 0; i < nb; ++i) lo->WT[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
     lo->WPf.assign(nb, 0);
     lo->WPd.assign(nb, 0);
     for (int i = 0; i < nb; ++i) {                  // 2 fp16 per weight = 1 float; taken in every mode (1.2 M weights in all)
-      lo->WPf[i] = bp.take((int64_t)n->blocks[i].cin * n->blocks[i].cout);
-      lo->WPd[i] = bp.take((int64_t)n->blocks[i].cin * n->blocks[i].cout);
+      lo->WPf[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
+      lo->WPd[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
     }
     lo->amax = bp.take((int64_t)3 * nb * KWS_ABSMAX_WORDS);
     lo->tn = bp.take(max_tn);
     lo->tns.assign(nb, 0);
     for (int i = 0; i < nb; ++i)
-      lo->tns[i] = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * n->blocks[i].Lout, n->blocks[i].cin, n->blocks[i].cout));
-    lo->xd = bp.take((int64_t)B * n->T * n->C);
-    lo->fd = bp.take((int64_t)B * 2 * n->C);
-    lo->dl1 = bp.take((int64_t)B * n->T);
-    lo->dl2 = bp.take((int64_t)B * n->NC);
+      lo->tns[i] = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * blocks[i].Lout, blocks[i].cin, blocks[i].cout));
+    lo->xd = bp.take((int64_t)B * T * C);
+    lo->fd = bp.take((int64_t)B * 2 * C);
+    lo->dl1 = bp.take((int64_t)B * T);
+    lo->dl2 = bp.take((int64_t)B * NC);
     lo->per_loss = bp.take(B);
     lo->per_correct = bp.take(B);
     lo->att = bp.take((int64_t)B * 16);
-    lo->g1f = bp.take((int64_t)n->K1f * n->C1);
+    lo->g1f = bp.take((int64_t)K1f * C1);
   } else {
     // inference ping-pong: two y buffers and one z buffer
     const int64_t ya = bp.take(max_y), yb = bp.take(max_y), zz = bp.take(max_z);
@@ -265,113 +322,42 @@ void make_layout(const kws_net* n, int B, bool training, Layout* lo) {
     }
     lo->part = bp.take(64);
     lo->WPf.assign(nb, 0);                          // the split-GEMM arms in inference: forward planes and |x| maxima (W | z)
-    for (int i = 0; i < nb; ++i) lo->WPf[i] = bp.take((int64_t)n->blocks[i].cin * n->blocks[i].cout);
+    for (int i = 0; i < nb; ++i) lo->WPf[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
     lo->amax = bp.take((int64_t)2 * nb * KWS_ABSMAX_WORDS);
   }
-  lo->w1f = bp.take((int64_t)n->K1f * n->C1);
+  lo->w1f = bp.take((int64_t)K1f * C1);
   lo->bn_stride = (4 * maxC + 63) / 64 * 64;
   lo->bn = bp.take(lo->bn_stride * (nb + 1));
   lo->total = bp.cur * 4;
 }
 
-}  // namespace
-
-extern "C" {
-
-int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
-  KWS_REQUIRE(cfg && out, "net_create: NULL pointer");
-  KWS_REQUIRE(cfg->num_classes >= 2 && cfg->num_classes <= 64, "net: num_classes %d out of range", cfg->num_classes);
-  kws_net* n = new kws_net();
-  n->cfg = *cfg;
-  int rc;
-  switch (cfg->kind) {   // the one place that knows which program a kind runs on: afterwards net->lm / net->gc / net->dk / net->mt tell
-    case KWS_NET_TS_ATTENTION: rc = build_ts_attention(n); break;
-    case KWS_NET_LOG_MFCC: rc = lm_build(n); break;
-    case KWS_NET_STEFFE: rc = steffe_build(n); break;
-    case KWS_NET_RESIDUAL: rc = residual_build(n); break;
-    case KWS_NET_MFCC_AND_RAW: rc = mfcc_raw_build(n); break;
-    case KWS_NET_CONV_1D_FAST:
-    case KWS_NET_CONV_1D_SPEC:
-    case KWS_NET_CONV_1D_TIME_STACKED:
-    case KWS_NET_CONV_1D_HEAVY: rc = gc_build(n); break;
-    case KWS_NET_CONV_1D_GRU:
-    case KWS_NET_CONV_1D_SIMPLE: rc = dk_build(n); break;
-    case KWS_NET_CONV_1D_MULTI_TIME_SLICED: rc = mt_build(n); break;
-    default:
-      kws_set_error("net_create: kind %d not supported", cfg->kind);
-      rc = KWS_E_INVALID;
-  }
-  if (rc != KWS_OK) {
-    lm_free(n);
-    gc_free(n);
-    dk_free(n);
-    mt_free(n);
-    delete n;
-    return rc;
-  }
-  *out = n;
-  return KWS_OK;
-}
-
-int kws_net_destroy(kws_net_t* net) {
-  if (net) {
-    lm_free(net);
-    gc_free(net);
-    dk_free(net);
-    mt_free(net);
-  }
-  delete net;
-  return KWS_OK;
-}
-
-int64_t kws_net_num_params(const kws_net_t* net) { return net ? net->n_params : 0; }
-int64_t kws_net_num_state(const kws_net_t* net) { return net ? net->n_state : 0; }
-int kws_net_num_tensors(const kws_net_t* net) { return net ? (int)net->tensors.size() : 0; }
-
-int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) {
-  KWS_REQUIRE(net && info && idx >= 0 && idx < (int)net->tensors.size(), "net_tensor_info: bad index %d", idx);
-  *info = net->tensors[idx];
-  return KWS_OK;
-}
-
-int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
-  if (!net || max_batch <= 0) return 0;
-  if (net->mt) return mt_workspace_bytes(net, max_batch, training);
-  if (net->dk) return dk_workspace_bytes(net, max_batch, training);
-  if (net->gc) return gc_workspace_bytes(net, max_batch, training);
-  if (net->lm) return lm_workspace_bytes(net, max_batch, training);
+int64_t TsProgram::workspace_bytes(int B, int training) const {
   Layout lo;
-  make_layout(net, max_batch, training != 0, &lo);
+  make_layout(B, training != 0, &lo);
   return lo.total;
 }
 
-int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, int index, int64_t* offset_floats,
-                       int64_t* count) {
-  KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
-  if (net->mt) return mt_debug_view(net, batch, training, what, index, offset_floats, count);
-  if (net->dk) return dk_debug_view(net, batch, training, what, index, offset_floats, count);
-  if (net->gc) return gc_debug_view(net, batch, training, what, index, offset_floats, count);
-  if (net->lm) return lm_debug_view(net, batch, training, what, index, offset_floats, count);
+int TsProgram::debug_view(int batch, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   Layout lo;
-  make_layout(net, batch, training != 0, &lo);
-  const int nb = (int)net->blocks.size();
+  make_layout(batch, training != 0, &lo);
+  const int nb = (int)blocks.size();
   if (what == 0) {  // pre-BN output y[index], index 0..nb
     KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: y index %d", index);
     *offset_floats = lo.y[index];
-    *count = index == 0 ? (int64_t)batch * net->L1 * net->C1
-                        : (int64_t)batch * net->blocks[index - 1].Lout * net->blocks[index - 1].cout;
+    *count = index == 0 ? (int64_t)batch * L1 * C1
+                        : (int64_t)batch * blocks[index - 1].Lout * blocks[index - 1].cout;
   } else if (what == 1) {  // depthwise output z[index]
     KWS_REQUIRE(index >= 0 && index < nb, "net_debug_view: z index %d", index);
     *offset_floats = lo.z[index];
-    *count = (int64_t)batch * net->blocks[index].Lout * net->blocks[index].cin;
+    *count = (int64_t)batch * blocks[index].Lout * blocks[index].cin;
   } else if (what == 2) {  // bn table (scale|shift|mean|rstd) of BN index
     KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: bn index %d", index);
     *offset_floats = lo.bn + lo.bn_stride * index;
-    *count = 4 * (index == 0 ? net->C1 : net->blocks[index - 1].cout);
+    *count = 4 * (index == 0 ? C1 : blocks[index - 1].cout);
   } else if (what == 3) {  // attention weights [B, T] (training only)
     KWS_REQUIRE(training, "net_debug_view: att is a training-only view");
     *offset_floats = lo.att;
-    *count = (int64_t)batch * net->T;
+    *count = (int64_t)batch * T;
   } else {
     kws_set_error("net_debug_view: unknown view %d", what);
     return KWS_E_INVALID;
@@ -379,24 +365,12 @@ int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, 
   return KWS_OK;
 }
 
-int kws_net_predict(const kws_net_t* net, const float* params, const float* state, const float* x, int B,
-                    float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
-  KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
-  if (net->mt) return mt_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  if (net->dk) return dk_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  if (net->gc) return gc_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  if (net->lm)
-    return lm_predict(net, params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+int TsProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
   Layout lo;
-  make_layout(net, B, false, &lo);
-  if (lo.total > workspace_bytes) {
-    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)workspace_bytes,
-                  (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  float* ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const int nb = (int)net->blocks.size();
+  make_layout(B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  const int nb = (int)blocks.size();
   auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
   {  // the twelve inference tables in one launch (round 4: twelve 4.5 us launches per predict call before)
     KWS_REQUIRE(nb + 1 <= KWS_BN_INFER_BATCH, "net: %d blocks exceed the BatchNorm table batch", nb);
@@ -406,15 +380,15 @@ int kws_net_predict(const kws_net_t* net, const float* params, const float* stat
     auto put = [&](const BnRef& r, int l) {
       ga[l] = params + r.gamma; be[l] = params + r.beta; mm[l] = state + r.mm; mv[l] = state + r.mv; tb[l] = bn_at(l); Cs[l] = r.C;
     };
-    put(net->bn1, 0);
-    for (int i = 0; i < nb; ++i) put(net->blocks[i].bn, i + 1);
+    put(bn1, 0);
+    for (int i = 0; i < nb; ++i) put(blocks[i].bn, i + 1);
     KWS_TRY(kws_bn_infer_prepare_batch(ga, be, mm, mv, BN_EPS, Cs, tb, nb + 1, st));
   }
-  if (kws_conv1_supported(&net->gather1f, &net->gather1, net->C1)) {
-    KWS_TRY(kws_conv1_fwd(x, &net->gather1f, &net->gather1, params + net->conv1, ws + lo.y[0], B, net->C1, nullptr, st));
+  if (kws_conv1_supported(&gather1f, &gather1, C1)) {
+    KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, ws + lo.y[0], B, C1, nullptr, st));
   } else {
-    KWS_TRY(fold_conv1(net, params, ws + lo.w1f, st));
-    KWS_TRY(kws_gemm_gather_f32(x, &net->gather1f, ws + lo.w1f, ws + lo.y[0], B, net->C1, nullptr, st));
+    KWS_TRY(fold_conv1(params, ws + lo.w1f, st));
+    KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, ws + lo.y[0], B, C1, nullptr, st));
   }
   // the fp16 x 2 arithmetic arm (kws_net_set_gemm_mode) in inference: forward planes of the pointwise kernels, one launch;
   // a layer the arm's kernels cannot take (kws_gemm_nn_f16x2_supported) runs the f32 kernel
@@ -430,8 +404,8 @@ int kws_net_predict(const kws_net_t* net, const float* params, const float* stat
     int srows[24], scols[24], str[24];
     KWS_REQUIRE(nb <= 24, "net: %d blocks exceed the split batch", nb);
     for (int i = 0; i < nb; ++i) {
-      sin_[i] = params + net->blocks[i].pw; sout[i] = ws + lo.WPf[i]; ssl[i] = w_slots(i);
-      srows[i] = net->blocks[i].cin; scols[i] = net->blocks[i].cout; str[i] = 1;
+      sin_[i] = params + blocks[i].pw; sout[i] = ws + lo.WPf[i]; ssl[i] = w_slots(i);
+      srows[i] = blocks[i].cin; scols[i] = blocks[i].cout; str[i] = 1;
       wn[i] = (int64_t)srows[i] * scols[i];
     }
     KWS_TRY(kws_absmax_batch_f32(sin_, wn, w_slots(0), nb, st));
@@ -439,7 +413,7 @@ int kws_net_predict(const kws_net_t* net, const float* params, const float* stat
     KWS_TRY(kws_f16x2_split_batch(sin_, sout, srows, scols, str, ssl, nb, st));
   }
   for (int i = 0; i < nb; ++i) {
-    const Block& b = net->blocks[i];
+    const Block& b = blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     KWS_TRY(kws_dwconv_fwd_amax_f32(ws + lo.y[i], bn_at(i), params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.stride,
                                     b.pad_l, h2 ? z_slots(i) : nullptr, st));
@@ -450,39 +424,22 @@ int kws_net_predict(const kws_net_t* net, const float* params, const float* stat
   }
   kws_ts_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + net->d1k; t.b1 = params + net->d1b;
-  t.W2 = params + net->d2k; t.probs = probs; t.B = B; t.T = net->T; t.C = net->C; t.NC = net->NC;
+  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
+  t.W2 = params + d2k; t.probs = probs; t.B = B; t.T = T; t.C = C; t.NC = NC;
   t.keep_prob = 1.f; t.loss_batch = 1; t.train = 0;
   return kws_ts_tail_launch(&t, st);
-}
-
-// Arithmetic of the pointwise GEMMs of ONE net handle: 0 = f32 MFMA (the product path), 2 = power-of-two scaled fp16 x 2 split
-// products (A/B arm, gemm_f16x2.hip).  Kept on the handle (no process-wide switch); bench.py's A/B leg flips it between steps.
-extern "C" int kws_net_get_gemm_mode(const kws_net_t* net) { return net ? net->gemm_mode.load(std::memory_order_relaxed) : 0; }
-extern "C" int kws_net_set_gemm_mode(kws_net_t* net, int mode) {
-  KWS_REQUIRE(net != nullptr, "net_set_gemm_mode: NULL net");
-  KWS_REQUIRE(mode >= 0 && mode <= 2,
-              "net_set_gemm_mode: mode %d (0 = f32 MFMA, 1 = f32 MFMA with separate input- / weight-gradient launches, 2 = fp16 x 2 split)", mode);
-  net->gemm_mode.store(mode, std::memory_order_relaxed);
-  return KWS_OK;
 }
 
 // part 0: the whole step.  part 1: forward, tail and the backward pass down to block `split` (inclusive); part 2: the rest
 // of the backward pass (blocks split-1 .. 0 and the first convolution).  Parts 1 + 2 enqueue exactly the launches of
 // part 0 in the same order - every intermediate lives in the caller's workspace - so the gradients are bit-identical.
-static int ts_train(const kws_net_t* net, const float* params, float* state, const float* x, const float* y_onehot, int B,
-                    float* grads, float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset,
-                    int loss_batch, void* workspace, int64_t workspace_bytes, void* stream, int phase, int split) {
+int TsProgram::train_part(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                          float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                          hipStream_t st, int phase, int split) const {
   Layout lo;
-  make_layout(net, B, true, &lo);
-  if (lo.total > workspace_bytes) {
-    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)workspace_bytes,
-                  (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  float* ws = (float*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const int nb = (int)net->blocks.size();
+  make_layout(B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  const int nb = (int)blocks.size();
   auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
   float* part = ws + lo.part;
   float* DZ = ws + lo.DZ;
@@ -508,8 +465,8 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
     int trows[KWS_TRANSPOSE_BATCH], tcols[KWS_TRANSPOSE_BATCH];
     KWS_REQUIRE(nb <= KWS_TRANSPOSE_BATCH, "net: %d blocks exceed the transpose batch", nb);
     for (int i = 0; i < nb; ++i) {
-      tin[i] = params + net->blocks[i].pw; tout[i] = ws + lo.WT[i];
-      trows[i] = net->blocks[i].cin; tcols[i] = net->blocks[i].cout;
+      tin[i] = params + blocks[i].pw; tout[i] = ws + lo.WT[i];
+      trows[i] = blocks[i].cin; tcols[i] = blocks[i].cout;
     }
     return kws_transpose_batch_f32(tin, tout, trows, tcols, nb, st);
   };
@@ -527,11 +484,11 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
     int srows[24], scols[24], str[24];
     KWS_REQUIRE(2 * nb <= 24, "net: %d blocks exceed the split batch", nb);
     for (int i = 0; i < nb; ++i) {
-      win[i] = params + net->blocks[i].pw;
-      wn[i] = (int64_t)net->blocks[i].cin * net->blocks[i].cout;
-      sin_[2 * i] = sin_[2 * i + 1] = params + net->blocks[i].pw;
-      srows[2 * i] = srows[2 * i + 1] = net->blocks[i].cin;
-      scols[2 * i] = scols[2 * i + 1] = net->blocks[i].cout;
+      win[i] = params + blocks[i].pw;
+      wn[i] = (int64_t)blocks[i].cin * blocks[i].cout;
+      sin_[2 * i] = sin_[2 * i + 1] = params + blocks[i].pw;
+      srows[2 * i] = srows[2 * i + 1] = blocks[i].cin;
+      scols[2 * i] = scols[2 * i + 1] = blocks[i].cout;
       ssl[2 * i] = ssl[2 * i + 1] = w_slots(i);
       sout[2 * i] = ws + lo.WPf[i]; str[2 * i] = 1;
       sout[2 * i + 1] = ws + lo.WPd[i]; str[2 * i + 1] = 0;
@@ -542,20 +499,20 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
   }
   // ---------------- forward ----------------
   {
-    const int64_t M = (int64_t)B * net->L1;
-    if (kws_conv1_supported(&net->gather1f, &net->gather1, net->C1)) {
-      KWS_TRY(kws_conv1_fwd(x, &net->gather1f, &net->gather1, params + net->conv1, ws + lo.y[0], B, net->C1, part, st));
+    const int64_t M = (int64_t)B * L1;
+    if (kws_conv1_supported(&gather1f, &gather1, C1)) {
+      KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, ws + lo.y[0], B, C1, part, st));
     } else {
-      KWS_TRY(fold_conv1(net, params, ws + lo.w1f, st));
-      KWS_TRY(kws_gemm_gather_f32(x, &net->gather1f, ws + lo.w1f, ws + lo.y[0], B, net->C1, part, st));
+      KWS_TRY(fold_conv1(params, ws + lo.w1f, st));
+      KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, ws + lo.y[0], B, C1, part, st));
     }
-    const int rows1 = kws_conv1_supported(&net->gather1f, &net->gather1, net->C1) ? kws_conv1_stats_rows(M) : kws_gemm_gather_stats_rows(M);
-    KWS_TRY(kws_bn_stats_finalize(part, rows1, M, net->C1, params + net->bn1.gamma,
-                                  params + net->bn1.beta, BN_EPS, BN_MOMENTUM, state + net->bn1.mm, state + net->bn1.mv,
+    const int rows1 = kws_conv1_supported(&gather1f, &gather1, C1) ? kws_conv1_stats_rows(M) : kws_gemm_gather_stats_rows(M);
+    KWS_TRY(kws_bn_stats_finalize(part, rows1, M, C1, params + bn1.gamma,
+                                  params + bn1.beta, BN_EPS, BN_MOMENTUM, state + bn1.mm, state + bn1.mv,
                                   bn_at(0), red, st));
   }
   for (int i = 0; i < nb; ++i) {
-    const Block& b = net->blocks[i];
+    const Block& b = blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     KWS_TRY(kws_dwconv_fwd_amax_f32(ws + lo.y[i], bn_at(i), params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.stride,
                                     b.pad_l, h2 ? z_slots(i) : nullptr, st));
@@ -571,10 +528,10 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
                                   BN_EPS, BN_MOMENTUM, state + b.bn.mm, state + b.bn.mv, bn_at(i + 1), red, st));
   }
   // ---------------- tail forward + backward ----------------
-  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + net->d1k; t.b1 = params + net->d1b;
-  t.W2 = params + net->d2k; t.labels = y_onehot; t.probs = probs; t.g = ws + ((nb % 2) ? lo.G2 : lo.G); t.part = part; t.xd = ws + lo.xd;
+  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
+  t.W2 = params + d2k; t.labels = y_onehot; t.probs = probs; t.g = ws + ((nb % 2) ? lo.G2 : lo.G); t.part = part; t.xd = ws + lo.xd;
   t.fd = ws + lo.fd; t.dl1 = ws + lo.dl1; t.dl2 = ws + lo.dl2; t.per_loss = ws + lo.per_loss;
-  t.per_correct = ws + lo.per_correct; t.att = ws + lo.att; t.B = B; t.T = net->T; t.C = net->C; t.NC = net->NC; t.seed = seed;
+  t.per_correct = ws + lo.per_correct; t.att = ws + lo.att; t.B = B; t.T = T; t.C = C; t.NC = NC; t.seed = seed;
   t.step = step; t.keep_prob = DROP_KEEP; t.label_smoothing = LABEL_SMOOTH; t.loss_batch = loss_batch;
   t.row_offset = row_offset; t.train = 1;
   KWS_TRY(kws_ts_tail_launch(&t, st));
@@ -585,9 +542,9 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
   bool tail_fused = false;
   if (pair_bwd) {
     kws_tail_post_args tp;
-    tp.X2 = t.fd; tp.D2 = t.dl2; tp.ws2 = ws + lo.swg; tp.K2 = 2 * net->C; tp.N2 = net->NC;
-    tp.X1 = t.xd; tp.D1 = t.dl1; tp.ws1 = ws + lo.swg1; tp.K1 = net->T * net->C; tp.N1 = net->T;
-    tp.bias1 = grads + net->d1b; tp.per_loss = t.per_loss; tp.per_correct = t.per_correct; tp.metrics = metrics; tp.B = B;
+    tp.X2 = t.fd; tp.D2 = t.dl2; tp.ws2 = ws + lo.swg; tp.K2 = 2 * C; tp.N2 = NC;
+    tp.X1 = t.xd; tp.D1 = t.dl1; tp.ws1 = ws + lo.swg1; tp.K1 = T * C; tp.N1 = T;
+    tp.bias1 = grads + d1b; tp.per_loss = t.per_loss; tp.per_correct = t.per_correct; tp.metrics = metrics; tp.B = B;
     int S_tail = 0;
     const int rc = kws_tail_post_launch(&tp, &S_tail, st);
     if (rc < 0) return rc;
@@ -598,13 +555,13 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
   }
   if (!tail_fused) {
   KWS_TRY(kws_metrics_launch(t.per_loss, t.per_correct, B, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(t.fd, t.dl2, grads + net->d2k, nullptr, B, 2 * net->C, net->NC, ws + lo.swg, st));
-  KWS_TRY(kws_small_wgrad_launch(t.xd, t.dl1, grads + net->d1k, grads + net->d1b, B, net->T * net->C, net->T,
+  KWS_TRY(kws_small_wgrad_launch(t.fd, t.dl2, grads + d2k, nullptr, B, 2 * C, NC, ws + lo.swg, st));
+  KWS_TRY(kws_small_wgrad_launch(t.xd, t.dl1, grads + d1k, grads + d1b, B, T * C, T,
                                  ws + lo.swg, st));
   }
   {
-    const BnRef& r = net->blocks[nb - 1].bn;
-    KWS_TRY(kws_dw_bwd_finalize(part, B, (int64_t)B * net->T, r.C, nullptr, grads + r.gamma,
+    const BnRef& r = blocks[nb - 1].bn;
+    KWS_TRY(kws_dw_bwd_finalize(part, B, (int64_t)B * T, r.C, nullptr, grads + r.gamma,
                                 grads + r.beta, coef, red, st));
   }
   }  // run_head
@@ -622,12 +579,12 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
   int sl_S[KWS_SLAB_BATCH], n_sl = 0;
   KWS_REQUIRE(nb + 2 <= KWS_SLAB_BATCH, "net: %d blocks exceed the slab batch", nb);
   if (tail_S > 0) {   // (negative S: kws_small_wgrad_launch's summation order)
-    sl_ws[n_sl] = ws + lo.swg; sl_out[n_sl] = grads + net->d2k; sl_n[n_sl] = (int64_t)2 * net->C * net->NC; sl_S[n_sl] = -tail_S; ++n_sl;
-    sl_ws[n_sl] = ws + lo.swg1; sl_out[n_sl] = grads + net->d1k; sl_n[n_sl] = (int64_t)net->T * net->C * net->T; sl_S[n_sl] = -tail_S; ++n_sl;
+    sl_ws[n_sl] = ws + lo.swg; sl_out[n_sl] = grads + d2k; sl_n[n_sl] = (int64_t)2 * C * NC; sl_S[n_sl] = -tail_S; ++n_sl;
+    sl_ws[n_sl] = ws + lo.swg1; sl_out[n_sl] = grads + d1k; sl_n[n_sl] = (int64_t)T * C * T; sl_S[n_sl] = -tail_S; ++n_sl;
   }
   const int i_hi = phase == 2 ? split - 1 : nb - 1, i_lo = phase == 1 ? split : 0;
   for (int i = i_hi; i >= i_lo; --i) {
-    const Block& b = net->blocks[i];
+    const Block& b = blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     float* Gcur = Gb[(i + 1) % 2];
     float* Gnext = Gb[i % 2];
@@ -663,7 +620,7 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
       ++n_sl;
     }
     }
-    const BnRef& prev = (i == 0) ? net->bn1 : net->blocks[i - 1].bn;
+    const BnRef& prev = (i == 0) ? bn1 : blocks[i - 1].bn;
     // depthwise backward + BatchNorm backward of this block's input without materialising the masked
     // gradient: reduce, fold (dw, dgamma, dbeta, c1 | c2), recompute and write dy of the previous block
     KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y[i], bn_at(i), params + b.dw, nullptr, nullptr, part, 1, B, b.Lin, b.Lout,
@@ -677,20 +634,98 @@ static int ts_train(const kws_net_t* net, const float* params, float* state, con
   // the slab sums of this call's pointwise weight gradients: beside the first convolution's weight gradient in ONE launch when
   // that kernel runs in this call (round 4: conv1_wgrad_slabsum_kernel - the two are independent, one is MFMA / memory bound, the
   // other HBM bound), their own launch otherwise (a part's gradients are final when it returns)
-  const bool sum_with_conv1 = n_sl > 0 && phase != 1 && kws_conv1_supported(&net->gather1f, &net->gather1, net->C1) &&
+  const bool sum_with_conv1 = n_sl > 0 && phase != 1 && kws_conv1_supported(&gather1f, &gather1, C1) &&
                               kws_net_get_gemm_mode(net) != 1;
   if (n_sl > 0 && !sum_with_conv1) KWS_TRY(kws_reduce_slabs_batch(sl_ws, sl_out, sl_n, sl_S, n_sl, st));
   if (phase != 1) {
-    const int64_t M = (int64_t)B * net->L1;
+    const int64_t M = (int64_t)B * L1;
     (void)M;                                        // Gb[0] already holds dy of the first convolution
-    if (kws_conv1_supported(&net->gather1f, &net->gather1, net->C1)) {
-      KWS_TRY(kws_conv1_wgrad_slabs(x, &net->gather1f, &net->gather1, Gb[0], grads + net->conv1, B, net->C1, ws + lo.tn,
+    if (kws_conv1_supported(&gather1f, &gather1, C1)) {
+      KWS_TRY(kws_conv1_wgrad_slabs(x, &gather1f, &gather1, Gb[0], grads + conv1, B, C1, ws + lo.tn,
                                     sl_ws, sl_out, sl_n, sl_S, sum_with_conv1 ? n_sl : 0, st));
     } else {
-      KWS_TRY(kws_gemm_tn_gather_f32(x, &net->gather1f, Gb[0], ws + lo.g1f, B, net->C1, ws + lo.tn, st));
-      KWS_TRY(unfold_conv1(net, ws + lo.g1f, grads, st));
+      KWS_TRY(kws_gemm_tn_gather_f32(x, &gather1f, Gb[0], ws + lo.g1f, B, C1, ws + lo.tn, st));
+      KWS_TRY(unfold_conv1(ws + lo.g1f, grads, st));
     }
   }
+  return KWS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
+  KWS_REQUIRE(cfg && out, "net_create: NULL pointer");
+  KWS_REQUIRE(cfg->num_classes >= 2 && cfg->num_classes <= 64, "net: num_classes %d out of range", cfg->num_classes);
+  kws_net* n = new kws_net();
+  n->cfg = *cfg;
+  int rc;
+  switch (cfg->kind) {   // the one place that knows which program a kind runs on: its builder installs it as n->program
+    case KWS_NET_TS_ATTENTION: rc = ts_build(n); break;
+    case KWS_NET_LOG_MFCC: rc = lm_build(n); break;
+    case KWS_NET_STEFFE: rc = steffe_build(n); break;
+    case KWS_NET_RESIDUAL: rc = residual_build(n); break;
+    case KWS_NET_MFCC_AND_RAW: rc = mfcc_raw_build(n); break;
+    case KWS_NET_CONV_1D_FAST:
+    case KWS_NET_CONV_1D_SPEC:
+    case KWS_NET_CONV_1D_TIME_STACKED:
+    case KWS_NET_CONV_1D_HEAVY: rc = gc_build(n); break;
+    case KWS_NET_CONV_1D_GRU:
+    case KWS_NET_CONV_1D_SIMPLE: rc = dk_build(n); break;
+    case KWS_NET_CONV_1D_MULTI_TIME_SLICED: rc = mt_build(n); break;
+    default:
+      kws_set_error("net_create: kind %d not supported", cfg->kind);
+      rc = KWS_E_INVALID;
+  }
+  if (rc != KWS_OK) {
+    delete n;
+    return rc;
+  }
+  *out = n;
+  return KWS_OK;
+}
+
+int kws_net_destroy(kws_net_t* net) {
+  delete net;
+  return KWS_OK;
+}
+
+int64_t kws_net_num_params(const kws_net_t* net) { return net ? net->n_params : 0; }
+int64_t kws_net_num_state(const kws_net_t* net) { return net ? net->n_state : 0; }
+int kws_net_num_tensors(const kws_net_t* net) { return net ? (int)net->tensors.size() : 0; }
+
+int kws_net_tensor_info(const kws_net_t* net, int idx, kws_tensor_info_t* info) {
+  KWS_REQUIRE(net && info && idx >= 0 && idx < (int)net->tensors.size(), "net_tensor_info: bad index %d", idx);
+  *info = net->tensors[idx];
+  return KWS_OK;
+}
+
+int64_t kws_net_workspace_bytes(const kws_net_t* net, int max_batch, int training) {
+  if (!net || max_batch <= 0) return 0;
+  return net->program->workspace_bytes(max_batch, training);
+}
+
+int kws_net_debug_view(const kws_net_t* net, int batch, int training, int what, int index, int64_t* offset_floats,
+                       int64_t* count) {
+  KWS_REQUIRE(net && offset_floats && count && batch > 0, "net_debug_view: bad arguments");
+  return net->program->debug_view(batch, training, what, index, offset_floats, count);
+}
+
+int kws_net_predict(const kws_net_t* net, const float* params, const float* state, const float* x, int B,
+                    float* probs, void* workspace, int64_t workspace_bytes, void* stream) {
+  KWS_REQUIRE(net && params && state && x && probs && workspace && B > 0, "net_predict: bad arguments");
+  return net->program->predict(params, state, x, B, probs, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// Arithmetic of the pointwise GEMMs of ONE net handle: 0 = f32 MFMA (the product path), 2 = power-of-two scaled fp16 x 2 split
+// products (A/B arm, gemm_f16x2.hip).  Kept on the handle (no process-wide switch); bench.py's A/B leg flips it between steps.
+extern "C" int kws_net_get_gemm_mode(const kws_net_t* net) { return net ? net->gemm_mode.load(std::memory_order_relaxed) : 0; }
+extern "C" int kws_net_set_gemm_mode(kws_net_t* net, int mode) {
+  KWS_REQUIRE(net != nullptr, "net_set_gemm_mode: NULL net");
+  KWS_REQUIRE(mode >= 0 && mode <= 2,
+              "net_set_gemm_mode: mode %d (0 = f32 MFMA, 1 = f32 MFMA with separate input- / weight-gradient launches, 2 = fp16 x 2 split)", mode);
+  net->gemm_mode.store(mode, std::memory_order_relaxed);
   return KWS_OK;
 }
 
@@ -701,31 +736,26 @@ int kws_net_train_fwd_bwd(const kws_net_t* net, const float* params, float* stat
   KWS_REQUIRE(net && params && state && x && y_onehot && grads && probs && metrics && workspace && B > 0,
               "net_train_fwd_bwd: bad arguments");
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd: loss_batch %d < B %d", loss_batch, B);
-  if (net->mt)
-    return mt_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
-                    workspace_bytes, (hipStream_t)stream);
-  if (net->dk)
-    return dk_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
-                    workspace_bytes, (hipStream_t)stream);
-  if (net->gc)
-    return gc_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
-                    workspace_bytes, (hipStream_t)stream);
-  if (net->lm)
-    return lm_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch,
-                    (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  return ts_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, workspace,
-                  workspace_bytes, stream, 0, 0);
+  return net->program->train(params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
+                             workspace_bytes, (hipStream_t)stream);
+}
+
+// the raw-waveform attention net's program, NULL for every other kind (the split step exists for it alone)
+static const TsProgram* ts_program(const kws_net_t* net) {
+  return (net && net->cfg.kind == KWS_NET_TS_ATTENTION) ? static_cast<const TsProgram*>(net->program.get()) : nullptr;
 }
 
 int kws_net_num_blocks(const kws_net_t* net) {
-  return (net && net->cfg.kind == KWS_NET_TS_ATTENTION) ? (int)net->blocks.size() : 0;
+  const TsProgram* ts = ts_program(net);
+  return ts ? (int)ts->blocks.size() : 0;
 }
 
 int64_t kws_net_grad_ready_offset(const kws_net_t* net, int split_block) {
-  if (!net || net->cfg.kind != KWS_NET_TS_ATTENTION || split_block < 1 || split_block >= (int)net->blocks.size()) return -1;
+  const TsProgram* ts = ts_program(net);
+  if (!ts || split_block < 1 || split_block >= (int)ts->blocks.size()) return -1;
   // block `split_block`'s backward writes the gradients of the BatchNorm in front of it; everything from there to the end
   // of the flat buffer (Keras layer order) is final once part 1 has run
-  return net->blocks[split_block - 1].bn.gamma;
+  return ts->blocks[split_block - 1].bn.gamma;
 }
 
 int kws_net_train_fwd_bwd_part(const kws_net_t* net, const float* params, float* state, const float* x,
@@ -736,10 +766,11 @@ int kws_net_train_fwd_bwd_part(const kws_net_t* net, const float* params, float*
               "net_train_fwd_bwd_part: bad arguments");
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd_part: loss_batch %d < B %d", loss_batch, B);
   KWS_REQUIRE(net->cfg.kind == KWS_NET_TS_ATTENTION, "net_train_fwd_bwd_part: only the raw-waveform attention net is split");
-  KWS_REQUIRE((part == 1 || part == 2) && split_block >= 1 && split_block < (int)net->blocks.size(),
+  const TsProgram* ts = ts_program(net);
+  KWS_REQUIRE((part == 1 || part == 2) && split_block >= 1 && split_block < (int)ts->blocks.size(),
               "net_train_fwd_bwd_part: part %d split_block %d", part, split_block);
-  return ts_train(net, params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, workspace,
-                  workspace_bytes, stream, part, split_block);
+  return ts->train_part(params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
+                        workspace_bytes, (hipStream_t)stream, part, split_block);
 }
 
 }  // extern "C"

@@ -10,24 +10,17 @@
 //                        recurrent_dropout=.2)) (gru.hip) -> Dense + softmax; Adam(1e-3), categorical CE.  No l2 on the GRU or the Dense
 //                        layer.  The activated ladder output is materialised for the GRU's GEMMs (kws_bn_relu6_apply), its masked
 //                        views by kws_gru_fwd_f32; the head is the flat tail's raw arm over the signed [B, 256] GRU output.
-// Data flow per block l (training), as in net.hip:
-//   z_l = dwk_l( relu6(bn_{l-1}(y_{l-1})) )     kws_dwconvk_fwd_f32, BN + ReLU6 applied on load
-//   y_l = z_l W_l                               f32 MFMA GEMM with the BN statistics in its epilogue
-// Block 1 has one input channel: its depthwise layer is the C = 1 arm and its pointwise layer the outer product
-// kws_dwconvk_pw1_* (K = 1 is outside the GEMM).  The backward is the two-kernel form: kws_dwconvk_bwd_f32 materialises the gated
-// gradient g, kws_dwconvk_bwd_finalize folds its partial rows, kws_bn_bwd_apply turns g into dy in place.
+// The blocks and their data flow are net_sepblock.hip's.  Block 1 has one input channel: its depthwise layer is the C = 1 arm and
+// its pointwise layer the outer product kws_dwconvk_pw1_* (K = 1 is outside the GEMM).
 // The hidden Dense layer is a GEMM over the materialised dropped features; its bias, relu6 and Dropout run inside the flat tail,
 // which reads (h, table) with the table scale = 1 | shift = bias (fmaf(h, 1, b) = h + b exactly).
 #include "net_internal.h"
 
-struct DkBlock {
-  int Lin, Lout, k, stride, pad_l, cin, cout;
-  int64_t dw, pw;   // param offsets
-  BnRef bn;         // BN behind the pointwise convolution
-};
+namespace {
 
-struct DkProgram {
-  std::vector<DkBlock> blocks;
+struct DkProgram : NetProgram {
+  const kws_net* net = nullptr;
+  std::vector<SepBlock> blocks;
   int NC = 0, D = 0, H = 0;          // features into the head, hidden width
   int64_t d1k = 0, d1b = -1, d2k = 0, d2b = 0;
   float keep = 0.7f;
@@ -35,14 +28,14 @@ struct DkProgram {
   bool gru = false;
   int gT = 0, gH = 0;
   int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
+
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
-
-void dk_free(kws_net* n) {
-  delete n->dk;
-  n->dk = nullptr;
-}
-
-namespace {
 
 constexpr float DK_DROP_KEEP = 0.7f;   // Dropout(0.3), model.py:502, 504
 constexpr int DK_HIDDEN = 256;         // Dense(256), model.py:503
@@ -112,8 +105,7 @@ struct DkLayout {
   int64_t gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;   // KWS_NET_CONV_1D_SIMPLE
 };
 
-void dk_layout(const kws_net* n, int B, bool training, DkLayout* lo) {
-  const DkProgram& p = *n->dk;
+void dk_layout(const DkProgram& p, int B, bool training, DkLayout* lo) {
   Bump bp;
   const int nb = (int)p.blocks.size();
   int64_t max_y = 64, max_z = 64, max_stats = 64, max_part = 64, max_tn = 64, max_w = 64;
@@ -122,7 +114,7 @@ void dk_layout(const kws_net* n, int B, bool training, DkLayout* lo) {
   lo->y.assign(nb, 0);
   lo->bn.assign(nb, 0);
   for (int i = 0; i < nb; ++i) {
-    const DkBlock& b = p.blocks[i];
+    const SepBlock& b = p.blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     lo->z[i] = bp.take(M * b.cin);
     lo->y[i] = bp.take(M * b.cout);
@@ -197,31 +189,25 @@ void dk_layout(const kws_net* n, int B, bool training, DkLayout* lo) {
 }
 
 // forward through the blocks and the hidden Dense product; training: batch statistics (moving averages updated) and dropout
-int dk_forward(const kws_net* n, const DkLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
                uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
-  const DkProgram& p = *n->dk;
   const int nb = (int)p.blocks.size();
   for (int i = 0; i < nb; ++i) {
-    const DkBlock& b = p.blocks[i];
+    const SepBlock& b = p.blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     const float* in = i == 0 ? x : ws + lo.y[i - 1];
     const float* bn_in = i == 0 ? nullptr : ws + lo.bn[i - 1];
-    KWS_TRY(kws_dwconvk_fwd_f32(in, bn_in, params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.k, b.stride, b.pad_l, st));
     float* stats = training ? ws + lo.stats : nullptr;
     int rows;
     if (i == 0) {
+      KWS_TRY(kws_dwconvk_fwd_f32(in, bn_in, params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.k, b.stride, b.pad_l, st));
       KWS_TRY(kws_dwconvk_pw1_fwd_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i], M, b.cout, stats, st));
       rows = kws_dwconvk_pw1_stats_rows(M);
     } else {
-      KWS_TRY(kws_gemm_nn_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i], M, b.cin, b.cout, stats, st));
-      rows = kws_gemm_nn_stats_rows(M, b.cin, b.cout);
+      rows = kws_sep_fwd(b, params, in, bn_in, ws + lo.z[i], ws + lo.y[i], stats, B, st);
+      if (rows < 0) return rows;
     }
-    if (training)
-      KWS_TRY(kws_bn_stats_finalize(stats, rows, M, b.cout, params + b.bn.gamma, params + b.bn.beta, KWS_BN_EPS, KWS_BN_MOMENTUM,
-                                    state + b.bn.mm, state + b.bn.mv, ws + lo.bn[i], ws + lo.red, st));
-    else
-      KWS_TRY(kws_bn_infer_prepare(params + b.bn.gamma, params + b.bn.beta, state + b.bn.mm, state + b.bn.mv, KWS_BN_EPS, b.cout,
-                                   ws + lo.bn[i], st));
+    KWS_TRY(kws_sep_bn_table(b, params, state, stats, rows, M, training, ws + lo.bn[i], ws + lo.red, st));
   }
   if (p.gru) {   // the activated ladder output [B, T, I] is materialised for the GRU's GEMMs; masks only in training
     const int T = p.gT, I = p.D, H = p.gH;
@@ -246,8 +232,7 @@ int dk_forward(const kws_net* n, const DkLayout& lo, const float* params, float*
 }
 
 // bias + relu6 + Dropout (layer 2) of the hidden layer, Dense + softmax (+ loss and its backward): the flat tail over (h, table)
-kws_flat_tail_args dk_tail_args(const kws_net* n, const DkLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const DkProgram& p = *n->dk;
+kws_flat_tail_args dk_tail_args(const DkProgram& p, const DkLayout& lo, const float* params, float* ws, int B, float* probs) {
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
   if (p.gru) {   // Dense + softmax over the signed GRU output: the raw arm
@@ -267,27 +252,21 @@ kws_flat_tail_args dk_tail_args(const kws_net* n, const DkLayout& lo, const floa
   return t;
 }
 
-}  // namespace
-
-int64_t KerasNames::dwk(int k, int C) {
-  return kws_net_add_tensor(n, "depthwise_conv2d_" + std::to_string(++n_dw) + "/depthwise_kernel", {1, k, C, 1}, false, KWS_L2_COEF,
-                            k * C, k, 0.f);
-}
-
 // conv_1d_simple: _reduce_conv(x, 32, 31, strides=16), _context_conv(x, 32, 3), then for F in 64 .. 224: _reduce_conv(x, F, 3) (stride 2),
 // _context_conv(x, F, 3), all padding='valid' (model.py:142-146) -> Bidirectional(GRU(128)) -> Dense
-static int dk_build_simple(kws_net* n) {
+int dk_build_simple(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_simple input_size %d (the reference's ladder ends in 10 time steps for 16000 samples)",
               c.input_size);
   DkProgram* p = new DkProgram();
-  n->dk = p;
+  n->program.reset(p);
+  p->net = n;
   p->NC = c.num_classes;
   p->gru = true;
   KerasNames kn{n};
   int L = c.input_size, cin = 1;
   for (int i = 0; i < 14; ++i) {
-    DkBlock b;
+    SepBlock b;
     b.Lin = L; b.k = i == 0 ? 31 : 3; b.stride = i == 0 ? 16 : (i % 2 == 0 ? 2 : 1); b.cin = cin; b.cout = i < 2 ? 32 : 32 * (i / 2 + 1);
     KWS_REQUIRE(L >= b.k, "net: block %d input length %d < %d taps", i, L, b.k);
     b.Lout = (L - b.k) / b.stride + 1;
@@ -315,13 +294,16 @@ static int dk_build_simple(kws_net* n) {
   return KWS_OK;
 }
 
+}  // namespace
+
 int dk_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   if (c.kind == KWS_NET_CONV_1D_SIMPLE) return dk_build_simple(n);
   KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_gru input_size %d (the reference's ladder ends in one time step for 16000 samples)",
               c.input_size);
   DkProgram* p = new DkProgram();
-  n->dk = p;
+  n->program.reset(p);
+  p->net = n;
   p->NC = c.num_classes;
   p->keep = DK_DROP_KEEP;
   KerasNames kn{n};
@@ -330,7 +312,7 @@ int dk_build(kws_net* n) {
                                                              {448, 7, 4, true},   {512, 5, 2, true},  {512, 8, 1, false}};
   int L = c.input_size, cin = 1;
   for (int i = 0; i < 6; ++i) {
-    DkBlock b;
+    SepBlock b;
     b.Lin = L; b.k = spec[i].k; b.stride = spec[i].s; b.cin = cin; b.cout = spec[i].F;
     if (spec[i].same) {
       kws_same_pad(L, b.k, b.stride, &b.Lout, &b.pad_l);
@@ -356,16 +338,18 @@ int dk_build(kws_net* n) {
   return KWS_OK;
 }
 
-int64_t dk_workspace_bytes(const kws_net* n, int B, int training) {
+namespace {
+
+int64_t DkProgram::workspace_bytes(int B, int training) const {
   DkLayout lo;
-  dk_layout(n, B, training != 0, &lo);
+  dk_layout(*this, B, training != 0, &lo);
   return lo.total;
 }
 
-int dk_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) {
-  const DkProgram& p = *n->dk;
+int DkProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
+  const DkProgram& p = *this;
   DkLayout lo;
-  dk_layout(n, B, training != 0, &lo);
+  dk_layout(p, B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
   if (p.gru && what == 5) {   // the GRU's saved steps [2][4: z, r, c, h][B, T, H] (training)
     KWS_REQUIRE(training, "net_debug_view: view 5 exists in training only");
@@ -384,7 +368,7 @@ int dk_debug_view(const kws_net* n, int B, int training, int what, int index, in
     return KWS_OK;
   }
   KWS_REQUIRE(index >= 0 && index < nb, "net_debug_view: block index %d", index);
-  const DkBlock& b = p.blocks[index];
+  const SepBlock& b = p.blocks[index];
   if (what == 0) {          // raw pointwise output of block `index`
     *offset_floats = lo.y[index];
     *count = (int64_t)B * b.Lout * b.cout;
@@ -401,48 +385,38 @@ int dk_debug_view(const kws_net* n, int B, int training, int what, int index, in
   return KWS_OK;
 }
 
-int dk_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st) {
+int DkProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
   DkLayout lo;
-  dk_layout(n, B, false, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  KWS_TRY(dk_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = dk_tail_args(n, lo, params, ws, B, probs);
+  dk_layout(*this, B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  KWS_TRY(dk_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
+  kws_flat_tail_args t = dk_tail_args(*this, lo, params, ws, B, probs);
   return kws_flat_tail_launch(&t, 0, st);
 }
 
-int dk_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st) {
-  const DkProgram& p = *n->dk;
+int DkProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                     hipStream_t st) const {
+  const DkProgram& p = *this;
   DkLayout lo;
-  dk_layout(n, B, true, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
+  dk_layout(p, B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
   const int nb = (int)p.blocks.size();
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)n->n_params * 4, st));   // the padding behind a tensor of 63 taps stays zero
-  KWS_TRY(dk_forward(n, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
+  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));   // the padding behind a tensor of 63 taps stays zero
+  KWS_TRY(dk_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
-  float* DZ = ws + lo.DZ;
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
+  const SepBwdScratch scratch = {ws + lo.WT, ws + lo.DZ, ws + lo.tn, part, coef};
   // ---- head ----
-  kws_flat_tail_args t = dk_tail_args(n, lo, params, ws, B, probs);
-  t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = G[0];
-  t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct;
-  t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
-  if (p.gru) t.dA = ws + lo.gdout;
-  KWS_TRY(kws_flat_tail_launch(&t, 1, st));
-  KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
+  kws_flat_tail_args t = dk_tail_args(p, lo, params, ws, B, probs);
+  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, p.gru ? ws + lo.gdout : G[0], ws + lo.per_loss, ws + lo.per_correct,
+                              seed, step, loss_batch, row_offset, metrics, st));
   int cur = 0;   // G[cur] = gradient wrt the activated output of the last block [B, T, D]
   if (p.gru) {
     const int T = p.gT, I = p.D, H = p.gH;
-    const DkBlock& b = p.blocks[nb - 1];
+    const SepBlock& b = p.blocks[nb - 1];
     KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, 2 * H, p.NC, ws + lo.swg, st));
     KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
                             ws + lo.gmh, ws + lo.gsave, G[0], grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
@@ -458,33 +432,24 @@ int dk_train(const kws_net* n, const float* params, float* state, const float* x
     KWS_TRY(kws_transpose_f32(params + p.d1k, ws + lo.WT, p.D, p.H, st));
     KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, G[1], B, p.H, p.D, nullptr, st));
     KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, seed, step, 1, row_offset, st));
-    const DkBlock& b = p.blocks[nb - 1];
+    const SepBlock& b = p.blocks[nb - 1];
     KWS_TRY(kws_gbn_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], B, 1, b.cout, part, coef, grads + b.bn.gamma, 0,
                         b.bn.beta - b.bn.gamma, st));
   }
   // ---- blocks: G[cur] = dy of block i's pointwise output ----
   for (int i = nb - 1; i >= 1; --i) {
-    const DkBlock& b = p.blocks[i];
-    const DkBlock& pb = p.blocks[i - 1];
-    const int64_t M = (int64_t)B * b.Lout;
-    KWS_TRY(kws_transpose_f32(params + b.pw, ws + lo.WT, b.cin, b.cout, st));
-    KWS_TRY(kws_gemm_nn_f32(G[cur], ws + lo.WT, DZ, M, b.cout, b.cin, nullptr, st));
-    KWS_TRY(kws_gemm_tn_f32(ws + lo.z[i], G[cur], grads + b.pw, M, b.cin, b.cout, ws + lo.tn, st));
-    float* g = G[cur ^ 1];
-    KWS_TRY(kws_dwconvk_bwd_f32(DZ, ws + lo.y[i - 1], ws + lo.bn[i - 1], params + b.dw, g, part, B, b.Lin, b.Lout, b.cin, b.k, b.stride,
-                                b.pad_l, st));
-    KWS_TRY(kws_dwconvk_bwd_finalize(part, kws_dwconvk_bwd_part_rows(B, b.Lin, b.cin, b.k, b.stride), (int64_t)B * b.Lin, b.cin, b.k,
-                                     grads + b.dw, grads + pb.bn.gamma, grads + pb.bn.beta, coef, st));
-    KWS_TRY(kws_bn_bwd_apply(g, ws + lo.y[i - 1], ws + lo.bn[i - 1], params + pb.bn.gamma, coef, (int64_t)B * b.Lin, b.cin, st));
+    const SepBlock& b = p.blocks[i];
+    KWS_TRY(kws_sep_bwd(b, params, grads, G[cur], ws + lo.z[i], ws + lo.y[i - 1], ws + lo.bn[i - 1], &p.blocks[i - 1].bn, G[cur ^ 1],
+                        scratch, B, st));
     cur ^= 1;
   }
   {   // block 1: the outer product's backward, then the taps of the one-channel depthwise layer (no gradient leaves the input)
-    const DkBlock& b = p.blocks[0];
+    const SepBlock& b = p.blocks[0];
     const int64_t M = (int64_t)B * b.Lout;
-    KWS_TRY(kws_dwconvk_pw1_bwd_f32(G[cur], ws + lo.z[0], params + b.pw, DZ, grads + b.pw, M, b.cout, ws + lo.pw1ws, st));
-    KWS_TRY(kws_dwconvk_bwd_f32(DZ, x, nullptr, params + b.dw, G[cur ^ 1], part, B, b.Lin, b.Lout, b.cin, b.k, b.stride, b.pad_l, st));
-    KWS_TRY(kws_dwconvk_bwd_finalize(part, kws_dwconvk_bwd_part_rows(B, b.Lin, b.cin, b.k, b.stride), (int64_t)B * b.Lin, b.cin, b.k,
-                                     grads + b.dw, nullptr, nullptr, nullptr, st));
+    KWS_TRY(kws_dwconvk_pw1_bwd_f32(G[cur], ws + lo.z[0], params + b.pw, scratch.DZ, grads + b.pw, M, b.cout, ws + lo.pw1ws, st));
+    KWS_TRY(kws_sep_dw_bwd(b, params, grads, x, nullptr, nullptr, G[cur ^ 1], scratch, B, st));
   }
   return KWS_OK;
 }
+
+}  // namespace

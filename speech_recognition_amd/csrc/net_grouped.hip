@@ -23,6 +23,8 @@
 //                         dropout layer 2 and no bias.
 #include "net_internal.h"
 
+namespace {
+
 struct GcBlock {
   kws_gconv_t d;            // B filled in per call
   int F;
@@ -35,7 +37,7 @@ struct GcBlock {
   int Lp;
 };
 
-struct GcProgram {
+struct GcProgram : NetProgram {
   bool front = false;       // conv_1d_fast: the 479-tap front convolution
   int L_in = 0, C_in = 0;   // the input seen as [L_in, C_in]
   int64_t conv0 = 0;
@@ -48,14 +50,14 @@ struct GcProgram {
   bool head2 = false;       // conv_1d_heavy: the last block is the Conv1D(128, 5) head over the dropped features [B, Dd]
   int Dd = 0;
   float keep2 = 1.f;        // Dropout(0.1) between that block and the softmax convolution (dropout layer 2)
+
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
-
-void gc_free(kws_net* n) {
-  delete n->gc;
-  n->gc = nullptr;
-}
-
-namespace {
 
 constexpr float GC_DROP_KEEP = 0.7f;      // Dropout(0.3), model.py:710 / 1318
 constexpr float GC_FRONT_L2 = 1e-4f;      // kernel_regularizer=l2(0.0001), model.py:700
@@ -112,8 +114,7 @@ struct GcLayout {
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
 };
 
-void gc_layout(const kws_net* n, int B, bool training, GcLayout* lo) {
-  const GcProgram& p = *n->gc;
+void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
   Bump bp;
   const int nb = (int)p.blocks.size();
   int64_t max_act = 64, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64;
@@ -188,9 +189,8 @@ GcInput gc_input(const GcProgram& p, const GcLayout& lo, int i, const float* x, 
 }
 
 // forward through the blocks; training: batch statistics (moving averages updated), else the moving statistics
-int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
                uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
-  const GcProgram& p = *n->gc;
   if (p.front) {
     KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
     KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
@@ -223,8 +223,7 @@ int gc_forward(const kws_net* n, const GcLayout& lo, const float* params, float*
   return KWS_OK;
 }
 
-kws_flat_tail_args tail_args(const kws_net* n, const GcLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const GcProgram& p = *n->gc;
+kws_flat_tail_args tail_args(const GcProgram& p, const GcLayout& lo, const float* params, float* ws, int B, float* probs) {
   const GcBlock& last = p.blocks.back();
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
@@ -242,7 +241,7 @@ kws_flat_tail_args tail_args(const kws_net* n, const GcLayout& lo, const float* 
 int gc_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   GcProgram* p = new GcProgram();
-  n->gc = p;
+  n->program.reset(p);
   p->NC = c.num_classes;
   p->keep = GC_DROP_KEEP;
   KerasNames kn{n};
@@ -306,16 +305,18 @@ int gc_build(kws_net* n) {
   return KWS_OK;
 }
 
-int64_t gc_workspace_bytes(const kws_net* n, int B, int training) {
+namespace {
+
+int64_t GcProgram::workspace_bytes(int B, int training) const {
   GcLayout lo;
-  gc_layout(n, B, training != 0, &lo);
+  gc_layout(*this, B, training != 0, &lo);
   return lo.total;
 }
 
-int gc_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) {
-  const GcProgram& p = *n->gc;
+int GcProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
+  const GcProgram& p = *this;
   GcLayout lo;
-  gc_layout(n, B, training != 0, &lo);
+  gc_layout(p, B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
   if (what == 0) {   // pre-BN output of conv stage `index` (conv_1d_fast: 0 = the front convolution)
     const int i = index - (p.front ? 1 : 0);
@@ -345,37 +346,28 @@ int gc_debug_view(const kws_net* n, int B, int training, int what, int index, in
   return KWS_OK;
 }
 
-int gc_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st) {
+int GcProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
   GcLayout lo;
-  gc_layout(n, B, false, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  KWS_TRY(gc_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
+  gc_layout(*this, B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  KWS_TRY(gc_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
+  kws_flat_tail_args t = tail_args(*this, lo, params, ws, B, probs);
   return kws_flat_tail_launch(&t, 0, st);
 }
 
-int gc_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st) {
-  const GcProgram& p = *n->gc;
+int GcProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                     hipStream_t st) const {
+  const GcProgram& p = *this;
   GcLayout lo;
-  gc_layout(n, B, true, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  KWS_TRY(gc_forward(n, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
+  gc_layout(p, B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  KWS_TRY(gc_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   int cur = 0;
-  kws_flat_tail_args t = tail_args(n, lo, params, ws, B, probs);
-  t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = ws + lo.dA[cur];
-  t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct;
-  t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
-  KWS_TRY(kws_flat_tail_launch(&t, 1, st));
-  KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
+  kws_flat_tail_args t = tail_args(p, lo, params, ws, B, probs);
+  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.dA[cur], ws + lo.per_loss, ws + lo.per_correct, seed, step,
+                              loss_batch, row_offset, metrics, st));
   KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, p.db >= 0 ? grads + p.db : nullptr, B, p.D, p.NC, ws + lo.swg,
                                  st));
   for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
@@ -409,3 +401,5 @@ int gc_train(const kws_net* n, const float* params, float* state, const float* x
   }
   return KWS_OK;
 }
+
+}  // namespace

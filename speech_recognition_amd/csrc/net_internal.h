@@ -1,12 +1,19 @@
-// Shared between the five network programs (net.hip: conv_1d_time_sliced_with_attention; net_logmfcc.hip: the
-// residual-block family conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw;
-// net_grouped.hip: conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy; net_dwk.hip: conv_1d_gru, conv_1d_simple; net_mts.hip:
-// conv_1d_multi_time_sliced).  Not part of the public C ABI.
+// Shared between the network programs.  A model kind runs on one NetProgram: a layer table built once by kws_net_create
+// (the switch there maps a kind to its builder) plus the launch sequences over it.  Each family keeps its program class in
+// its own file and exports only its builder(s):
+//   net.hip          conv_1d_time_sliced_with_attention
+//   net_logmfcc.hip  the residual-block family: conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual,
+//                    conv_1d_mfcc_and_raw
+//   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy
+//   net_dwk.hip      conv_1d_gru, conv_1d_simple
+//   net_mts.hip      conv_1d_multi_time_sliced
+// Not part of the public C ABI.
 #pragma once
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -21,40 +28,25 @@ struct BnRef {
   int64_t mm, mv;       // state offsets
   int C;
 };
-struct Block {
-  int stride, pad_l, cin, cout, Lin, Lout;
-  int64_t dw, pw;  // param offsets
-  BnRef bn;        // BN after the pointwise conv
-};
 
-struct LmProgram;  // residual-block family layer table (net_logmfcc.hip)
-struct GcProgram;  // conv_1d_fast / conv_1d_spec / conv_1d_time_stacked / conv_1d_heavy layer table (net_grouped.hip)
-struct DkProgram;  // conv_1d_gru / conv_1d_simple layer table (net_dwk.hip)
-struct MtProgram;  // conv_1d_multi_time_sliced layer table (net_mts.hip)
+// One model's layer table and its launch sequences on one HIP stream.  The public entry points of net.hip check their
+// arguments and make one of these calls; `ws` is the caller's workspace of `ws_bytes` bytes.
+struct NetProgram {
+  virtual ~NetProgram() {}
+  virtual int64_t workspace_bytes(int B, int training) const = 0;
+  virtual int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const = 0;
+  virtual int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                      hipStream_t st) const = 0;
+  virtual int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                    float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                    hipStream_t st) const = 0;
+};
 
 struct kws_net {
   kws_net_config_t cfg;
   std::vector<kws_tensor_info_t> tensors;
   int64_t n_params = 0, n_state = 0;
-  // TS_ATTENTION
-  int L_in = 0;        // samples per clip
-  int L1 = 0, C1 = 0;  // conv1 output
-  int64_t conv1 = 0;
-  BnRef bn1;
-  std::vector<Block> blocks;
-  int T = 0, C = 0, NC = 0;
-  int64_t d1k = 0, d1b = 0, d2k = 0;
-  kws_gather_t gather1;   // the reference's view: 3 taps of 40 samples, taps 20 samples apart (K = 120)
-  kws_gather_t gather1f;  // folded view used by the GEMMs: ONE tap of 80 contiguous samples (see net.hip fold_taps_kernel)
-  int K1f = 0;            // folded K
-  // LOG_MFCC / STEFFE / RESIDUAL / MFCC_AND_RAW
-  LmProgram* lm = nullptr;
-  // CONV_1D_FAST / CONV_1D_SPEC / CONV_1D_TIME_STACKED / CONV_1D_HEAVY
-  GcProgram* gc = nullptr;
-  // CONV_1D_GRU / CONV_1D_SIMPLE
-  DkProgram* dk = nullptr;
-  // CONV_1D_MULTI_TIME_SLICED
-  MtProgram* mt = nullptr;
+  std::unique_ptr<NetProgram> program;  // installed by the kind's builder (also when it fails half way: freed with the net)
   // arithmetic of the pointwise GEMMs (kws_net_set_gemm_mode): 0 = f32 MFMA, 2 = fp16 x 2 split products (A/B arm)
   std::atomic<int> gemm_mode{0};
 };
@@ -74,7 +66,7 @@ struct KerasNames {
   int64_t conv(int k, int cin, int cout, float l2);  // conv1d_<n>/kernel [k, cin, cout]
   BnRef bn(int C, int* idx = nullptr);               // batch_normalization_<n>/...; *idx = n
   int64_t dw(int C);                                 // depthwise_conv2d_<n>/depthwise_kernel [1, 3, C, 1], l2
-  int64_t dwk(int k, int C);                         // depthwise_conv2d_<n>/depthwise_kernel [1, k, C, 1], l2 (net_dwk.hip)
+  int64_t dwk(int k, int C);                         // depthwise_conv2d_<n>/depthwise_kernel [1, k, C, 1], l2
 };
 
 struct Bump {
@@ -86,52 +78,52 @@ struct Bump {
   }
 };
 
-// ---- residual-block programs (net_logmfcc.hip) --------------------------------------------------------
-int lm_build(kws_net* n);
+// ---- the builders: each installs its program on the net and appends the net's tensors (net.hip keeps its own local) ------
+int lm_build(kws_net* n);        // net_logmfcc.hip
 int steffe_build(kws_net* n);
 int residual_build(kws_net* n);
 int mfcc_raw_build(kws_net* n);
-void lm_free(kws_net* n);
-int64_t lm_workspace_bytes(const kws_net* n, int B, int training);
-int lm_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
-int lm_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs,
-               float* ws, int64_t ws_bytes, hipStream_t st);
-int lm_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B,
-             float* grads, float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset,
-             int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st);
+int gc_build(kws_net* n);        // net_grouped.hip
+int dk_build(kws_net* n);        // net_dwk.hip
+int mt_build(kws_net* n);        // net_mts.hip
 
-// ---- grouped-Conv1D programs (net_grouped.hip) ------------------------------------------------------------------------
-int gc_build(kws_net* n);
-void gc_free(kws_net* n);
-int64_t gc_workspace_bytes(const kws_net* n, int B, int training);
-int gc_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
-int gc_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st);
-int gc_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st);
+// ---- pieces the programs share (net.hip) -------------------------------------------------------------------------------
+// KWS_E_WORKSPACE with its message when the caller's workspace is too small; who = "net_predict" / "net_train_fwd_bwd"
+int kws_workspace_check(const char* who, int64_t need_bytes, int64_t ws_bytes, int B);
+// The training step of a flat tail: t comes filled for inference; adds the training fields, launches the tail with
+// training = 1 (probs, loss, fd, dl, dA) and then the batch metrics
+int kws_flat_tail_train(kws_flat_tail_args* t, const float* labels, float* fd, float* dl, float* dA, float* per_loss,
+                        float* per_correct, uint64_t seed, uint32_t step, int loss_batch, int64_t row_offset, float* metrics,
+                        hipStream_t st);
 
-// ---- general depthwise ladder (net_dwk.hip) ------------------------------------------------------------------------------
-int dk_build(kws_net* n);
-void dk_free(kws_net* n);
-int64_t dk_workspace_bytes(const kws_net* n, int B, int training);
-int dk_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
-int dk_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st);
-int dk_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st);
-
-// ---- three-branch raw-waveform net (net_mts.hip) -------------------------------------------------------------------------
-int mt_build(kws_net* n);
-void mt_free(kws_net* n);
-int64_t mt_workspace_bytes(const kws_net* n, int B, int training);
-int mt_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count);
-int mt_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st);
-int mt_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st);
+// ---- the k-wide depthwise-separable block of net_dwk.hip and net_mts.hip (net_sepblock.hip) ------------------------------
+// DepthwiseConv2D((1, k), strides) -> Conv1D(cout, 1) -> BatchNormalization -> relu6
+struct SepBlock {
+  int Lin = 0, Lout = 0, k = 0, stride = 1, pad_l = 0, cin = 0, cout = 0;
+  int64_t dw = 0, pw = 0;  // param offsets
+  BnRef bn;                // BN behind the pointwise convolution
+};
+// scratch of one backward pass: transposed pointwise kernel, gradient wrt the depthwise output, weight-gradient GEMM
+// workspace, depthwise-backward partial rows, the producer's BatchNorm backward coefficients
+struct SepBwdScratch {
+  float *WT, *DZ, *tn, *part, *coef;
+};
+// z = dwk(in) - in read through the table bn_in (BN + ReLU6 on load) or, bn_in NULL, as it is - then y = z W with the BN
+// partial sums in stats (NULL: none).  Returns the number of statistics rows, or a negative KWS_E_* code.
+int kws_sep_fwd(const SepBlock& b, const float* params, const float* in, const float* bn_in, float* z, float* y, float* stats, int B,
+                hipStream_t st);
+// the block's table bn [4][cout]: from `rows` statistics rows over M rows (training: moving averages updated) or from the
+// moving statistics
+int kws_sep_bn_table(const SepBlock& b, const float* params, float* state, const float* stats, int rows, int64_t M, bool training,
+                     float* bn, float* red, hipStream_t st);
+// dz (s.DZ) -> the depthwise kernel's gradient and out = the gradient wrt the block's input.  prod != NULL: the input is
+// the producer's raw output read through bn_in; the producer's BatchNorm backward rides along (its dgamma / dbeta, out
+// becomes its dy).  prod NULL: out stays the gradient wrt the input as read.
+int kws_sep_dw_bwd(const SepBlock& b, const float* params, float* grads, const float* in, const float* bn_in, const BnRef* prod,
+                   float* out, const SepBwdScratch& s, int B, hipStream_t st);
+// dy [B * Lout, cout] -> the pointwise kernel's gradient (z: the block's depthwise output), dz, then kws_sep_dw_bwd
+int kws_sep_bwd(const SepBlock& b, const float* params, float* grads, const float* dy, const float* z, const float* in,
+                const float* bn_in, const BnRef* prod, float* out, const SepBwdScratch& s, int B, hipStream_t st);
 
 // ---- residual-block / log-mfcc tail launchers (resblock.hip) ------------------------------------------
 // o = maxpool_P(relu6(bn(y))) + (res_bn ? res_bn.scale*res + res_bn.shift : res)

@@ -36,8 +36,6 @@ struct LmBlock {
   int bn1_idx, bn2_idx;
 };
 
-}  // namespace
-
 // a depthwise block without a residual (conv_1d_residual's _reduce_block: strided SAME, then VALID)
 struct LmPlain {
   int64_t dw, pw;
@@ -48,7 +46,8 @@ struct LmPlain {
 // which model the table was built for; forward / backward ask it only for structure no field below describes
 enum LmStyle { LM_ATTENTION, LM_STEFFE, LM_RESIDUAL, LM_MFCC_AND_RAW };
 
-struct LmProgram {
+struct LmProgram : NetProgram {
+  const kws_net* net = nullptr;
   LmStyle style = LM_ATTENTION;
   int T0, F, C0, L0;
   int Fp;  // F rounded up to the 16-byte vectors of the gathered GEMM (spectrogram input: 257 -> 260)
@@ -85,9 +84,14 @@ struct LmProgram {
   int64_t ctx_dw = 0, ctx_pw = 0;
   BnRef ctx_bn;
   int ctx_bn_idx = 0;
-};
 
-namespace {
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
+};
 
 struct LmLayout {
   int64_t total = 0;
@@ -107,8 +111,7 @@ struct LmLayout {
   int64_t wt_ctx = 0;
 };
 
-void lm_layout(const kws_net* n, int B, LmLayout* lo) {
-  const LmProgram& p = *n->lm;
+void lm_layout(const LmProgram& p, int B, LmLayout* lo) {
   Bump bp;
   const int nb = (int)p.blocks.size();
   lo->ys.assign(nb, 0); lo->z1.assign(nb, 0); lo->y1.assign(nb, 0); lo->z2.assign(nb, 0); lo->y2.assign(nb, 0);
@@ -227,7 +230,6 @@ void lm_layout(const kws_net* n, int B, LmLayout* lo) {
 }
 
 struct Ctx {
-  const kws_net* n;
   const LmProgram* p;
   const float* params;
   float* state;        // may be written (training)
@@ -340,7 +342,7 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
   KWS_TRY(bn_table(c, p.bn0, 1, (int64_t)B * p.L0, kws_gemm_gather_stats_rows((int64_t)B * p.L0)));
   // the first convolution's activation - and, where the first block starts with a k 3 / stride 1 / 'same' depthwise convolution over it
   // (conv_1d_log_mfcc), that convolution's output in the same pass (round 6, kws_block_out_dw_fwd without a residual: bit-identical)
-  if (p.style == LM_ATTENTION && !p.blocks.empty() && kws_net_get_gemm_mode(c.n) != 1) {
+  if (p.style == LM_ATTENTION && !p.blocks.empty() && kws_net_get_gemm_mode(c.p->net) != 1) {
     const LmBlock& b0 = p.blocks[0];
     if (b0.s1 == 1 && b0.pad1 == 1 && b0.Lmid == b0.Lin && b0.Lin == p.L0 && b0.cin == p.C0) {
       KWS_TRY(kws_block_out_dw_fwd(ws + lo.y0, c.bn_at(1), nullptr, nullptr, c.params + b0.dw1, ws + lo.a0, ws + lo.z1[0], B, p.L0, p.C0, 1, c.st));
@@ -359,7 +361,7 @@ int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
     xin = ws + lo.ac;
   }
   bool z1_ready = z1_first;
-  const bool fuse_join_dw = kws_net_get_gemm_mode(c.n) != 1;
+  const bool fuse_join_dw = kws_net_get_gemm_mode(c.p->net) != 1;
   for (size_t i = 0; i < p.blocks.size(); ++i) {
     const LmBlock& b = p.blocks[i];
     const int64_t M = (int64_t)B * b.Lmid;
@@ -443,7 +445,8 @@ enum LmStridePlace {
 
 LmProgram* lm_new(kws_net* n, LmStyle style, float drop_keep) {
   LmProgram* p = new LmProgram();
-  n->lm = p;   // kws_net_create frees it when the builder fails
+  n->program.reset(p);   // freed with the net when the builder fails
+  p->net = n;
   p->style = style;
   p->drop_keep = drop_keep;
   return p;
@@ -688,23 +691,20 @@ int mfcc_raw_build(kws_net* n) {
   return KWS_OK;
 }
 
-void lm_free(kws_net* n) {
-  delete n->lm;
-  n->lm = nullptr;
-}
+namespace {
 
-int64_t lm_workspace_bytes(const kws_net* n, int B, int training) {
+int64_t LmProgram::workspace_bytes(int B, int training) const {
   (void)training;
   LmLayout lo;
-  lm_layout(n, B, &lo);
+  lm_layout(*this, B, &lo);
   return lo.total;
 }
 
-int lm_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) {
+int LmProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   (void)training;
   LmLayout lo;
-  lm_layout(n, B, &lo);
-  const LmProgram& p = *n->lm;
+  lm_layout(*this, B, &lo);
+  const LmProgram& p = *this;
   const int nb = (int)p.blocks.size();
   // what: 0 = pre-BN tensor of BN `index` (1-based Keras numbering), 2 = BN table of BN `index`,
   //       3 = attention weights, 4 = attention logits u
@@ -738,17 +738,13 @@ int lm_debug_view(const kws_net* n, int B, int training, int what, int index, in
   return KWS_E_INVALID;
 }
 
-int lm_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs,
-               float* ws, int64_t ws_bytes, hipStream_t st) {
+int LmProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
   Ctx c;
-  c.n = n; c.p = n->lm; c.params = params; c.state = const_cast<float*>(state); c.ws = ws; c.B = B;
+  c.p = this; c.params = params; c.state = const_cast<float*>(state); c.ws = ws; c.B = B;
   c.training = false; c.st = st;
-  lm_layout(n, B, &c.lo);
-  if (c.lo.total > ws_bytes) {
-    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes,
-                  (long long)c.lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
+  lm_layout(*this, B, &c.lo);
+  KWS_TRY(kws_workspace_check("net_predict", c.lo.total, ws_bytes, B));
   kws_lm_tail_args t;
   KWS_TRY(forward(c, x, &t));
   if (c.p->style != LM_ATTENTION) {
@@ -759,20 +755,16 @@ int lm_predict(const kws_net* n, const float* params, const float* state, const 
   return kws_lm_tail_fwd(&t, 0, st);
 }
 
-int lm_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B,
-             float* grads, float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset,
-             int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) {
+int LmProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                     hipStream_t st) const {
   Ctx c;
-  c.n = n; c.p = n->lm; c.params = params; c.state = state; c.ws = ws; c.B = B; c.training = true; c.st = st;
-  lm_layout(n, B, &c.lo);
-  if (c.lo.total > ws_bytes) {
-    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes,
-                  (long long)c.lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
+  c.p = this; c.params = params; c.state = state; c.ws = ws; c.B = B; c.training = true; c.st = st;
+  lm_layout(*this, B, &c.lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", c.lo.total, ws_bytes, B));
   const LmProgram& p = *c.p;
   const LmLayout& lo = c.lo;
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)n->n_params * 4, st));
+  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
   kws_lm_tail_args t;
   KWS_TRY(forward(c, x, &t));
   {  // every pointwise kernel transposed for its dgrad GEMM, KWS_TRANSPOSE_BATCH matrices per launch
@@ -804,7 +796,7 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
   float* dX = ws + lo.dOb;
   KwsSlabQueue sq;
   sq.base = ws + lo.tnq; sq.cap = lo.tnq_floats;
-  sq.allow_pair = kws_net_get_gemm_mode(n) != 1;    // mode 1: the A/B reference schedule (separate input- / weight-gradient launches)
+  sq.allow_pair = kws_net_get_gemm_mode(net) != 1;    // mode 1: the A/B reference schedule (separate input- / weight-gradient launches)
   DwFinQueue dq;
   dq.base = ws + lo.dwq; dq.cap = lo.dwq_floats; dq.st = st;
   // join backward + BatchNorm backward in two passes (round 4): reductions, fold (dgamma, dbeta, c1 | c2), then the masked /
@@ -964,3 +956,5 @@ int lm_train(const kws_net* n, const float* params, float* state, const float* x
   }
   return KWS_OK;
 }
+
+}  // namespace

@@ -12,7 +12,7 @@
 //                          head  32 context (128, 1) over the 320 concatenated features
 // Data flow (training):
 //   stem (blocks 1, 13, 25)   y = kws_stem_fwd_f32(x): depthwise + pointwise in one kernel, 4 / 5 / 25 input channels
-//   other blocks              z = kws_dwconvk_fwd_f32(input), y = z W (f32 MFMA GEMM with the BN statistics in its epilogue)
+//   other blocks              net_sepblock.hip's: z = dwk(input), y = z W (f32 MFMA GEMM with the BN statistics in its epilogue)
 //   reduce block              a = kws_pool3s2_same_fwd_f32(y, table): the pooled tensor is materialised ACTIVATED, its consumer
 //                             reads it without a table
 //   fork (blocks 8, 20)       a = relu6(bn(y)) materialised once (at most [B, 28, 160]); both consumers read it without a table
@@ -24,30 +24,31 @@
 // activation are added before the fork's single BatchNorm backward.  The three ladders reuse the same gradient buffers.
 #include "net_internal.h"
 
-struct MtBlock {
+namespace {
+
+struct MtBlock : SepBlock {   // all VALID at stride 1
   int src = -1;          // producing block, -1 = the raw input (stem)
-  int Lin = 0, Lout = 0, Lp = 0, k = 0, cin = 0, cout = 0;
+  int Lp = 0;            // rows per clip that leave the block (behind the pool, if any)
   bool pool = false;     // _reduce_conv: SAME pool behind the block
   bool fork = false;     // the activated output is materialised for two consumers
   bool onload = false;   // reads its producer's raw output through the producer's table
   int end_col = -1;      // branch end: first column in the feature buffer
-  int64_t dw = 0, pw = 0;
-  BnRef bn;
 };
 
-struct MtProgram {
+struct MtProgram : NetProgram {
+  const kws_net* net = nullptr;
   std::vector<MtBlock> blocks;   // blocks.back() is the head's context block
   int NC = 0, D = 0, H = 0;      // concatenated features, head width
   int64_t ok = 0, ob = 0;        // classifier kernel and bias
   float keep = 0.9f;
+
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
-
-void mt_free(kws_net* n) {
-  delete n->mt;
-  n->mt = nullptr;
-}
-
-namespace {
 
 constexpr float MT_DROP_KEEP = 0.9f;   // Dropout(0.1), model.py:1144, 1146
 constexpr int MT_END_WIDTH = 64, MT_HEAD_WIDTH = 128;
@@ -78,8 +79,7 @@ struct MtLayout {
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
 };
 
-void mt_layout(const kws_net* n, int B, bool training, MtLayout* lo) {
-  const MtProgram& p = *n->mt;
+void mt_layout(const MtProgram& p, int B, bool training, MtLayout* lo) {
   Bump bp;
   const int nb = (int)p.blocks.size();
   int64_t max_g = 64, max_z = 64, max_stats = 64, max_part = 64, max_tn = 64, max_w = 64, max_fork = 64, max_stem = 64;
@@ -147,19 +147,9 @@ void mt_input(const MtProgram& p, const MtLayout& lo, int i, float* ws, const fl
   }
 }
 
-int mt_bn_table(const MtBlock& b, const MtLayout& lo, const float* params, float* state, float* ws, int i, int rows, int64_t M,
-                bool training, hipStream_t st) {
-  if (training)
-    return kws_bn_stats_finalize(ws + lo.stats, rows, M, b.cout, params + b.bn.gamma, params + b.bn.beta, KWS_BN_EPS, KWS_BN_MOMENTUM,
-                                 state + b.bn.mm, state + b.bn.mv, ws + lo.bn[i], ws + lo.red, st);
-  return kws_bn_infer_prepare(params + b.bn.gamma, params + b.bn.beta, state + b.bn.mm, state + b.bn.mv, KWS_BN_EPS, b.cout,
-                              ws + lo.bn[i], st);
-}
-
 // forward through the 31 branch blocks, the concatenation and the head's block; training: batch statistics and dropout
-int mt_forward(const kws_net* n, const MtLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+int mt_forward(const MtProgram& p, const MtLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
                uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
-  const MtProgram& p = *n->mt;
   const int nb = (int)p.blocks.size();
   float* stats = training ? ws + lo.stats : nullptr;
   for (int i = 0; i + 1 < nb; ++i) {
@@ -172,11 +162,10 @@ int mt_forward(const kws_net* n, const MtLayout& lo, const float* params, float*
     } else {
       const float *in, *bn_in;
       mt_input(p, lo, i, ws, &in, &bn_in);
-      KWS_TRY(kws_dwconvk_fwd_f32(in, bn_in, params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.k, 1, 0, st));
-      KWS_TRY(kws_gemm_nn_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i], M, b.cin, b.cout, stats, st));
-      rows = kws_gemm_nn_stats_rows(M, b.cin, b.cout);
+      rows = kws_sep_fwd(b, params, in, bn_in, ws + lo.z[i], ws + lo.y[i], stats, B, st);
+      if (rows < 0) return rows;
     }
-    KWS_TRY(mt_bn_table(b, lo, params, state, ws, i, rows, M, training, st));
+    KWS_TRY(kws_sep_bn_table(b, params, state, stats, rows, M, training, ws + lo.bn[i], ws + lo.red, st));
     if (b.pool) KWS_TRY(kws_pool3s2_same_fwd_f32(ws + lo.y[i], ws + lo.bn[i], ws + lo.a[i], B, b.Lout, b.cout, st));
     if (b.fork) KWS_TRY(kws_bn_relu6_apply(ws + lo.y[i], ws + lo.bn[i], ws + lo.a[i], M, b.cout, 1, st));
     if (b.end_col >= 0) {
@@ -192,14 +181,13 @@ int mt_forward(const kws_net* n, const MtLayout& lo, const float* params, float*
     KWS_TRY(kws_dropout_fwd(ws + lo.feat, ws + lo.featd, B, p.D, p.keep, seed, step, 1, row_offset, st));
     feat = ws + lo.featd;
   }
-  KWS_TRY(kws_dwconvk_fwd_f32(feat, nullptr, params + h.dw, ws + lo.z[nb - 1], B, 1, 1, p.D, 1, 1, 0, st));
-  KWS_TRY(kws_gemm_nn_f32(ws + lo.z[nb - 1], params + h.pw, ws + lo.y[nb - 1], B, p.D, p.H, stats, st));
-  return mt_bn_table(h, lo, params, state, ws, nb - 1, kws_gemm_nn_stats_rows(B, p.D, p.H), B, training, st);
+  const int rows = kws_sep_fwd(h, params, feat, nullptr, ws + lo.z[nb - 1], ws + lo.y[nb - 1], stats, B, st);
+  if (rows < 0) return rows;
+  return kws_sep_bn_table(h, params, state, stats, rows, B, training, ws + lo.bn[nb - 1], ws + lo.red, st);
 }
 
 // relu6(bn(.)) of the head's block, Dropout (layer 2), Conv1D(num_classes, 1) + bias + softmax (+ loss and its backward)
-kws_flat_tail_args mt_tail_args(const kws_net* n, const MtLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const MtProgram& p = *n->mt;
+kws_flat_tail_args mt_tail_args(const MtProgram& p, const MtLayout& lo, const float* params, float* ws, int B, float* probs) {
   const int nb = (int)p.blocks.size();
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
@@ -219,7 +207,8 @@ int mt_build(kws_net* n) {
   KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_multi_time_sliced input_size %d (the reference reshapes exactly 16000 samples)",
               c.input_size);
   MtProgram* p = new MtProgram();
-  n->mt = p;
+  n->program.reset(p);
+  p->net = n;
   p->NC = c.num_classes;
   p->keep = MT_DROP_KEEP;
   KerasNames kn{n};
@@ -280,16 +269,18 @@ int mt_build(kws_net* n) {
   return KWS_OK;
 }
 
-int64_t mt_workspace_bytes(const kws_net* n, int B, int training) {
+namespace {
+
+int64_t MtProgram::workspace_bytes(int B, int training) const {
   MtLayout lo;
-  mt_layout(n, B, training != 0, &lo);
+  mt_layout(*this, B, training != 0, &lo);
   return lo.total;
 }
 
-int mt_debug_view(const kws_net* n, int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) {
-  const MtProgram& p = *n->mt;
+int MtProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
+  const MtProgram& p = *this;
   MtLayout lo;
-  mt_layout(n, B, training != 0, &lo);
+  mt_layout(p, B, training != 0, &lo);
   KWS_REQUIRE(index >= 0 && index < (int)p.blocks.size(), "net_debug_view: block index %d", index);
   const MtBlock& b = p.blocks[index];
   if (what == 0) {          // raw pointwise output of block `index` (creation order)
@@ -305,44 +296,35 @@ int mt_debug_view(const kws_net* n, int B, int training, int what, int index, in
   return KWS_OK;
 }
 
-int mt_predict(const kws_net* n, const float* params, const float* state, const float* x, int B, float* probs, float* ws,
-               int64_t ws_bytes, hipStream_t st) {
+int MtProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
   MtLayout lo;
-  mt_layout(n, B, false, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_predict: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
-  KWS_TRY(mt_forward(n, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = mt_tail_args(n, lo, params, ws, B, probs);
+  mt_layout(*this, B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  KWS_TRY(mt_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
+  kws_flat_tail_args t = mt_tail_args(*this, lo, params, ws, B, probs);
   return kws_flat_tail_launch(&t, 0, st);
 }
 
-int mt_train(const kws_net* n, const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads,
-             float* probs, float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws,
-             int64_t ws_bytes, hipStream_t st) {
-  const MtProgram& p = *n->mt;
+int MtProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                     hipStream_t st) const {
+  const MtProgram& p = *this;
   MtLayout lo;
-  mt_layout(n, B, true, &lo);
-  if (lo.total > ws_bytes) {
-    kws_set_error("net_train_fwd_bwd: workspace %lld B < %lld B needed for batch %d", (long long)ws_bytes, (long long)lo.total, B);
-    return KWS_E_WORKSPACE;
-  }
+  mt_layout(p, B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
   const int nb = (int)p.blocks.size();
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)n->n_params * 4, st));
-  KWS_TRY(mt_forward(n, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
+  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
+  KWS_TRY(mt_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
   float* FG = ws + lo.FG;
-  float* DZ = ws + lo.DZ;
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
+  const SepBwdScratch scratch = {ws + lo.WT, ws + lo.DZ, ws + lo.tn, part, coef};
   // ---- head ----
-  kws_flat_tail_args t = mt_tail_args(n, lo, params, ws, B, probs);
-  t.labels = y_onehot; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.dA = G[0];
-  t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct;
-  t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
-  KWS_TRY(kws_flat_tail_launch(&t, 1, st));
-  KWS_TRY(kws_metrics_launch(ws + lo.per_loss, ws + lo.per_correct, B, metrics, st));
+  kws_flat_tail_args t = mt_tail_args(p, lo, params, ws, B, probs);
+  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, G[0], ws + lo.per_loss, ws + lo.per_correct, seed, step, loss_batch,
+                              row_offset, metrics, st));
   KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.ok, grads + p.ob, B, p.H, p.NC, ws + lo.swg, st));
   float* dcat = ws + lo.featd;   // gradient wrt the concatenated features [B, 320], over the dropped features once they are spent
   {
@@ -350,12 +332,7 @@ int mt_train(const kws_net* n, const float* params, float* state, const float* x
     // G[0] = gradient wrt relu6(bn(y)) [B, 128] -> dy; the GEMM's two gradients; the one-tap depthwise layer; Dropout (layer 1)
     KWS_TRY(kws_gbn_bwd(G[0], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], B, 1, h.cout, part, coef, grads + h.bn.gamma, 0,
                         h.bn.beta - h.bn.gamma, st));
-    KWS_TRY(kws_transpose_f32(params + h.pw, ws + lo.WT, h.cin, h.cout, st));
-    KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, DZ, B, h.cout, h.cin, nullptr, st));
-    KWS_TRY(kws_gemm_tn_f32(ws + lo.z[nb - 1], G[0], grads + h.pw, B, h.cin, h.cout, ws + lo.tn, st));
-    KWS_TRY(kws_dwconvk_bwd_f32(DZ, ws + lo.featd, nullptr, params + h.dw, G[0], part, B, 1, 1, h.cin, 1, 1, 0, st));
-    KWS_TRY(kws_dwconvk_bwd_finalize(part, kws_dwconvk_bwd_part_rows(B, 1, h.cin, 1, 1), B, h.cin, 1, grads + h.dw, nullptr, nullptr,
-                                     nullptr, st));
+    KWS_TRY(kws_sep_bwd(h, params, grads, G[0], ws + lo.z[nb - 1], ws + lo.featd, nullptr, nullptr, G[0], scratch, B, st));
     KWS_TRY(kws_dropout_bwd(G[0], dcat, B, p.D, p.keep, seed, step, 1, row_offset, st));
   }
   // ---- the 31 branch blocks, descending: `grad` = what arrives at block i, wrt its output (is_dy false) or its raw y (true) ----
@@ -392,25 +369,14 @@ int mt_train(const kws_net* n, const float* params, float* state, const float* x
                                st));
       continue;
     }
-    KWS_TRY(kws_transpose_f32(params + b.pw, ws + lo.WT, b.cin, b.cout, st));
-    KWS_TRY(kws_gemm_nn_f32(dy, ws + lo.WT, DZ, M, b.cout, b.cin, nullptr, st));
-    KWS_TRY(kws_gemm_tn_f32(ws + lo.z[i], dy, grads + b.pw, M, b.cin, b.cout, ws + lo.tn, st));
     const MtBlock& pb = p.blocks[b.src];
     const bool to_fork = pb.fork;
     float* out = (to_fork && !fork_filled) ? FG : (dy == G[0] ? G[1] : G[0]);
     const float *in, *bn_in;
     mt_input(p, lo, i, ws, &in, &bn_in);
-    KWS_TRY(kws_dwconvk_bwd_f32(DZ, in, bn_in, params + b.dw, out, part, B, b.Lin, b.Lout, b.cin, b.k, 1, 0, st));
-    const int prows = kws_dwconvk_bwd_part_rows(B, b.Lin, b.cin, b.k, 1);
-    if (b.onload) {   // the producer's BatchNorm backward rides on this pass: out becomes the producer's dy
-      KWS_TRY(kws_dwconvk_bwd_finalize(part, prows, (int64_t)B * b.Lin, b.cin, b.k, grads + b.dw, grads + pb.bn.gamma, grads + pb.bn.beta,
-                                       coef, st));
-      KWS_TRY(kws_bn_bwd_apply(out, ws + lo.y[b.src], ws + lo.bn[b.src], params + pb.bn.gamma, coef, (int64_t)B * b.Lin, b.cin, st));
-      is_dy = true;
-    } else {
-      KWS_TRY(kws_dwconvk_bwd_finalize(part, prows, (int64_t)B * b.Lin, b.cin, b.k, grads + b.dw, nullptr, nullptr, nullptr, st));
-      is_dy = false;
-    }
+    // onload: the producer's BatchNorm backward rides on this pass and out becomes the producer's dy
+    KWS_TRY(kws_sep_bwd(b, params, grads, dy, ws + lo.z[i], in, bn_in, b.onload ? &pb.bn : nullptr, out, scratch, B, st));
+    is_dy = b.onload;
     if (to_fork) {
       if (fork_filled) KWS_TRY(kws_add_f32(FG, out, FG, (int64_t)B * b.Lin * b.cin, st));
       fork_filled = true;
@@ -419,3 +385,5 @@ int mt_train(const kws_net* n, const float* params, float* state, const float* x
   }
   return KWS_OK;
 }
+
+}  // namespace

@@ -34,6 +34,11 @@ CONFIGS = {
     'mfcc_and_raw': (_lib.KWS_NET_MFCC_AND_RAW, 12, 1, 98 * 40 + 16000, 98, 40),
     'conv_1d_fast': (_lib.KWS_NET_CONV_1D_FAST, 12, 1, 16000, 0, 0),
     'conv_1d_spec': (_lib.KWS_NET_CONV_1D_SPEC, 12, 1, 98 * 257, 0, 0),
+    'conv_1d_time_stacked': (_lib.KWS_NET_CONV_1D_TIME_STACKED, 12, 1, 16000, 0, 0),
+    'conv_1d_heavy': (_lib.KWS_NET_CONV_1D_HEAVY, 12, 1, 16000, 0, 0),
+    'conv_1d_gru': (_lib.KWS_NET_CONV_1D_GRU, 12, 1, 16000, 0, 0),
+    'conv_1d_simple': (_lib.KWS_NET_CONV_1D_SIMPLE, 12, 1, 16000, 0, 0),
+    'conv_1d_multi_time_sliced': (_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 12, 1, 16000, 0, 0),
 }
 
 
