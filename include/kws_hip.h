@@ -483,6 +483,33 @@ int kws_gru_bwd_f32(const float* dout, const float* x, const float* W0, const fl
                     float* dU1, float* dbias1, float* workspace, int B, int T, int I, int H, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Attention gate in front of a recurrent layer, reference model.py:973-975 (xception_with_attention):
+ *   attention = _context_conv(x, 1, k, padding='same')  (DepthwiseConv2D((1, k)) -> Conv1D(1, 1) -> BatchNormalization -> relu6),
+ *   attention = softmax(attention, axis=1) over TIME, y = x * attention.
+ *   u[b,t]   = sum_c Wa[c] sum_j wa[j,c] x[b, t + j - pl, c]     pl = (k - 1) / 2 (Keras 'same'); taps outside [0, T) read 0
+ *   table[4] = scale | shift | mean | rstd of the ONE BatchNorm channel: training != 0 from the batch statistics of all B T values
+ *              of u (fixed-order sums, biased variance, eps 1e-3; mm / mv updated at momentum 0.99), else from mm / mv
+ *   att[b,t] = softmax_t(relu6(scale u + shift));  y[b,t,c] = x[b,t,c] att[b,t]
+ * x, y, dy, dx [B, T, C]; wa [k, C] (the depthwise kernel [1, k, C, 1]); Wa [C] (the pointwise kernel [1, C, 1]); gamma, beta, mm,
+ * mv, dgamma, dbeta [1]; u, att [B, T] are kept for the backward pass.
+ *   kws_attn_gate_bwd_f32: da = sum_c dy x -> softmax backward over t -> ReLU6 mask (0 < scale u + shift <= 6) -> BatchNorm
+ *   backward (training != 0: with the two batch sums, per-clip partials folded in a fixed order; else the table is constant)
+ *   -> du [B, T];  dx = dy att + sum_j du[b, t - j + pl] Wa[c] wa[j,c];  with S_j[c] = sum_{b,t} du[b,t] x[b, t + j - pl, c]
+ *   (per-clip partial rows, fixed-order fold): dwa[j,c] = Wa[c] S_j[c], dWa[c] = sum_j wa[j,c] S_j[c].  dx and dy are distinct buffers.
+ * workspace: kws_attn_gate_fwd_floats / kws_attn_gate_bwd_floats floats (host-side planners, 0 outside the domain); the
+ * backward needs nothing the forward left in its workspace.
+ * Domain: B >= 1, 1 <= T <= 128, C % 4 == 0 with 4 <= C <= 1024, k in {3, 5}.  No atomics: bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int64_t kws_attn_gate_fwd_floats(int B, int T, int C, int k);
+int64_t kws_attn_gate_bwd_floats(int B, int T, int C, int k);
+int kws_attn_gate_fwd_f32(const float* x, const float* wa, const float* Wa, const float* gamma, const float* beta, float* mm,
+                          float* mv, float* u, float* table, float* att, float* y, float* workspace, int B, int T, int C, int k,
+                          int training, void* stream);
+int kws_attn_gate_bwd_f32(const float* dy, const float* x, const float* u, const float* att, const float* table, const float* wa,
+                          const float* Wa, const float* gamma, float* dx, float* dwa, float* dWa, float* dgamma, float* dbeta,
+                          float* workspace, int B, int T, int C, int k, int training, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a14  optimizers on one flat parameter buffer, reference model.py:834 (RMSprop(lr=1e-3)) and
  *      model.py:96,110 (SGD momentum); constants SURVEY D.5.  g_eff = grad*grad_scale + 2*l2[i]*p
  *      (l2[i] = per-element kernel_regularizer coefficient, 0 for BN/bias).
@@ -541,6 +568,14 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         [B, 10, 224] -> Bidirectional(GRU(128, dropout=.2, recurrent_dropout=.2)) (kws_gru_*) -> Dense + softmax.
  *                         Debug views: what 0 / 1 / 2 as for KWS_NET_CONV_1D_GRU (block `index` 0 .. 13), what 5 = the GRU's saved
  *                         steps [2 directions][4: z, r, c, h][B, 10, 128] (training), what 6 = the GRU output [B, 256].
+ *   KWS_NET_XCEPTION_ATTENTION: xception_with_attention_model, reference model.py:911-983 (raw input, input_size even and at least
+ *                         4000; filter_mult 1 or 2): the stem and residual blocks of KWS_NET_RESIDUAL over the block list (128, 2),
+ *                         (256, 2), 8 x (256, 1), (384, 2) -> [B, 50, 384] at 16000 samples -> the attention gate kws_attn_gate_*
+ *                         (k 5) -> Bidirectional(GRU(192, dropout=.2, recurrent_dropout=.2)) (kws_gru_*) -> Dense + softmax.
+ *                         Debug views: what 0 / 2 as for KWS_NET_RESIDUAL, what 3 = attention weights att [B, T], what 4 = attention
+ *                         logits u [B, T], what 5 = the last block's output [B, T, C], what 6 = the gate's output [B, T, C], what 7
+ *                         = the GRU's saved steps [2 directions][4: z, r, c, h][B, T, 192] (training), what 8 = the GRU output
+ *                         [B, 384], what 9 = the attention BatchNorm's table [4] = scale | shift | mean | rstd.
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -557,6 +592,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_GRU 10
 #define KWS_NET_CONV_1D_MULTI_TIME_SLICED 11
 #define KWS_NET_CONV_1D_SIMPLE 12
+#define KWS_NET_XCEPTION_ATTENTION 13
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

@@ -24,6 +24,7 @@ KWS_NET_CONV_1D_HEAVY = 9
 KWS_NET_CONV_1D_GRU = 10
 KWS_NET_CONV_1D_MULTI_TIME_SLICED = 11
 KWS_NET_CONV_1D_SIMPLE = 12
+KWS_NET_XCEPTION_ATTENTION = 13
 
 
 class KwsError(RuntimeError):
@@ -173,6 +174,10 @@ SIGNATURES = {
     "kws_gru_seq_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "kws_gru_fwd_f32": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),
     "kws_gru_bwd_f32": (_I, [_P] * 17 + [_I, _I, _I, _I, _P]),
+    "kws_attn_gate_fwd_floats": (_I64, [_I, _I, _I, _I]),
+    "kws_attn_gate_bwd_floats": (_I64, [_I, _I, _I, _I]),
+    "kws_attn_gate_fwd_f32": (_I, [_P] * 12 + [_I, _I, _I, _I, _I, _P]),
+    "kws_attn_gate_bwd_f32": (_I, [_P] * 14 + [_I, _I, _I, _I, _I, _P]),
     "kws_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
     "kws_bn_stats_finalize": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "kws_bn_infer_prepare": (_I, [_P, _P, _P, _P, _F, _I, _P, _P]),

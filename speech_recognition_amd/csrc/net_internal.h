@@ -3,7 +3,7 @@
 // its own file and exports only its builder(s):
 //   net.hip          conv_1d_time_sliced_with_attention
 //   net_logmfcc.hip  the residual-block family: conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual,
-//                    conv_1d_mfcc_and_raw
+//                    conv_1d_mfcc_and_raw, xception_with_attention
 //   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_mts.hip      conv_1d_multi_time_sliced
@@ -83,6 +83,7 @@ int lm_build(kws_net* n);        // net_logmfcc.hip
 int steffe_build(kws_net* n);
 int residual_build(kws_net* n);
 int mfcc_raw_build(kws_net* n);
+int xception_build(kws_net* n);
 int gc_build(kws_net* n);        // net_grouped.hip
 int dk_build(kws_net* n);        // net_dwk.hip
 int mt_build(kws_net* n);        // net_mts.hip

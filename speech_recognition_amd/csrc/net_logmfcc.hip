@@ -6,6 +6,8 @@
 //   LM_RESIDUAL      conv_1d_residual_model (model.py:841-908): 3-wide SAME max-pool joins, plain blocks after the
 //                    stack, global-average tail
 //   LM_MFCC_AND_RAW  conv_1d_mfcc_and_raw_model (model.py:1563-1660): two stems on packed [mfcc | raw] rows, concatenated
+//   LM_XCEPTION      xception_with_attention_model (model.py:911-983): conv_1d_residual's stem and a shorter block list, then the
+//                    attention gate (attgate.hip) feeding Bidirectional(GRU(192)) (gru.hip) and the flat tail's raw arm
 // The original description of LM_ATTENTION follows.
 // Network program of conv_1d_log_mfcc_model (reference model.py:1400-1479; SURVEY 8a row a19, layer
 // table Appendix B.2): Conv1D(64,3)+BN+ReLU6 on [98,40] features, 10 residual blocks of
@@ -44,7 +46,7 @@ struct LmPlain {
 };
 
 // which model the table was built for; forward / backward ask it only for structure no field below describes
-enum LmStyle { LM_ATTENTION, LM_STEFFE, LM_RESIDUAL, LM_MFCC_AND_RAW };
+enum LmStyle { LM_ATTENTION, LM_STEFFE, LM_RESIDUAL, LM_MFCC_AND_RAW, LM_XCEPTION };
 
 struct LmProgram : NetProgram {
   const kws_net* net = nullptr;
@@ -84,6 +86,10 @@ struct LmProgram : NetProgram {
   int64_t ctx_dw = 0, ctx_pw = 0;
   BnRef ctx_bn;
   int ctx_bn_idx = 0;
+  // xception_with_attention: the gate's kernels are att_dw [1, 5, C, 1] / att_pw / att_bn; a bidirectional GRU of gH units reads the
+  // gated sequence [T, C]; the dense layer reads its [2 gH] output
+  int gH = 0;
+  int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
 
   int64_t workspace_bytes(int B, int training) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
@@ -107,9 +113,15 @@ struct LmLayout {
   std::vector<int64_t> pz, py;             // plain blocks (conv_1d_residual)
   int64_t alast = 0;
   int64_t a0m = 0, a0r = 0;                // conv_1d_mfcc_and_raw: activated branch outputs before the concatenation
+  // xception_with_attention: gate output, gate workspaces, GRU masks / output / saved steps / workspace / output gradient
+  int64_t xgy = 0, xagf = 0, xagb = 0, gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;
   std::vector<int64_t> wt_pw1, wt_pw2, wt_ws, wt_plain;   // transposed pointwise kernels for the dgrad GEMMs
   int64_t wt_ctx = 0;
 };
+
+constexpr int XC_GATE_K = 5;          // _context_conv(x, 1, 5, padding='same'), model.py:973
+constexpr int XC_GRU_UNITS = 192;     // GRU(192, ...), model.py:976
+constexpr float XC_GRU_KEEP = 0.8f;   // dropout=0.2, recurrent_dropout=0.2
 
 void lm_layout(const LmProgram& p, int B, LmLayout* lo) {
   Bump bp;
@@ -210,14 +222,26 @@ void lm_layout(const LmProgram& p, int B, LmLayout* lo) {
   lo->G = bp.take(max_y);
   lo->DZ = bp.take(max_z);
   lo->DXS = bp.take(max_xs);
-  lo->u = bp.take((int64_t)B * 16);
+  const int tail_T = p.style == LM_XCEPTION ? p.T : 16;   // u / att: [B, T]
+  lo->u = bp.take((int64_t)B * tail_T);
   lo->fd = bp.take((int64_t)B * p.feat);
   lo->dl = bp.take((int64_t)B * p.NC);
   lo->gu = bp.take((int64_t)B * 16);
   lo->coef2 = bp.take(4);
   lo->per_loss = bp.take(B);
   lo->per_correct = bp.take(B);
-  lo->att = bp.take((int64_t)B * 16);
+  lo->att = bp.take((int64_t)B * tail_T);
+  if (p.style == LM_XCEPTION) {
+    lo->xgy = bp.take((int64_t)B * p.T * p.C);
+    lo->xagf = bp.take(kws_attn_gate_fwd_floats(B, p.T, p.C, XC_GATE_K));
+    lo->xagb = bp.take(kws_attn_gate_bwd_floats(B, p.T, p.C, XC_GATE_K));
+    lo->gmx = bp.take((int64_t)6 * B * p.C);
+    lo->gmh = bp.take((int64_t)6 * B * p.gH);
+    lo->gout = bp.take((int64_t)B * 2 * p.gH);
+    lo->gdout = bp.take((int64_t)B * 2 * p.gH);
+    lo->gsave = bp.take(kws_gru_save_floats(B, p.T, p.gH));
+    lo->gws = bp.take(kws_gru_workspace_floats(B, p.T, p.C, p.gH, 1));
+  }
   if (p.style == LM_STEFFE) {
     lo->wpad = bp.take((int64_t)p.K0p * p.C0);
     lo->gwpad = bp.take((int64_t)p.K0p * p.C0);
@@ -567,6 +591,34 @@ kws_gp_tail_args gp_tail_args(const Ctx& c, const float* x, float* probs) {
   return g;
 }
 
+// xception_with_attention: the gate over the last join's output, then the bidirectional GRU on the gated sequence as it is
+int xc_gate_gru_fwd(const Ctx& c, const float* xin, uint64_t seed, uint32_t step, int64_t row_offset) {
+  const LmProgram& p = *c.p;
+  const LmLayout& lo = c.lo;
+  float* ws = c.ws;
+  const int H = p.gH;
+  KWS_TRY(kws_attn_gate_fwd_f32(xin, c.params + p.att_dw, c.params + p.att_pw, c.params + p.att_bn.gamma, c.params + p.att_bn.beta,
+                                c.state + p.att_bn.mm, c.state + p.att_bn.mv, ws + lo.u, c.bn_at(p.att_bn_idx), ws + lo.att, ws + lo.xgy,
+                                ws + lo.xagf, c.B, p.T, p.C, XC_GATE_K, c.training ? 1 : 0, c.st));
+  if (c.training) KWS_TRY(kws_gru_masks(ws + lo.gmx, ws + lo.gmh, c.B, p.C, H, XC_GRU_KEEP, seed, step, row_offset, c.st));
+  return kws_gru_fwd_f32(ws + lo.xgy, c.params + p.gW[0], c.params + p.gU[0], c.params + p.gb[0], c.params + p.gW[1], c.params + p.gU[1],
+                         c.params + p.gb[1], c.training ? ws + lo.gmx : nullptr, c.training ? ws + lo.gmh : nullptr, ws + lo.gout,
+                         c.training ? ws + lo.gsave : nullptr, ws + lo.gws, c.B, p.T, p.C, H, c.st);
+}
+
+// Dense + softmax over the signed GRU output: the flat tail's raw arm
+kws_flat_tail_args xc_tail_args(const Ctx& c, float* probs) {
+  const LmProgram& p = *c.p;
+  kws_flat_tail_args t;
+  memset(&t, 0, sizeof(t));
+  t.y = c.ws + c.lo.gout; t.Ng = p.feat; t.raw = 1;
+  t.Wd = c.params + p.dk; t.bd = c.params + p.db;
+  t.probs = probs;
+  t.B = c.B; t.D = p.feat; t.F = p.feat; t.NC = p.NC;
+  t.keep_prob = 1.f;
+  return t;
+}
+
 }  // namespace
 
 int lm_build(kws_net* n) {
@@ -659,6 +711,47 @@ int residual_build(kws_net* n) {
   return KWS_OK;
 }
 
+// xception_with_attention_model, reference model.py:911-983: conv_1d_residual's stem, eleven of its blocks, attention gate, BiGRU
+int xception_build(kws_net* n) {
+  const kws_net_config_t& c = n->cfg;
+  KWS_REQUIRE(c.input_size >= 4000 && c.input_size % 2 == 0, "net: xception_with_attention input_size %d", c.input_size);
+  const int fm = c.filter_mult > 0 ? c.filter_mult : 1;
+  LmProgram* p = lm_new(n, LM_XCEPTION, 1.f);    // no Dropout layer: the GRU carries the model's dropout
+  KerasNames kn{n};
+  int Lf, plf;
+  kws_same_pad(c.input_size, 40, 20, &Lf, &plf);   // overlapping_time_slice_stack(x, 40, 20) fused with Conv1D(64, 3, strides=2), model.py:957-960
+  p->T0 = c.input_size; p->F = 40; p->Fp = 40; p->C0 = 64 * fm; p->L0 = (Lf - 3) / 2 + 1;
+  p->conv1 = kn.conv(3, 40, p->C0, KWS_L2_COEF);
+  p->bn0 = kn.bn(p->C0);
+  kws_gather_t g0;
+  g0.L_out = p->L0; g0.cin = 40; g0.taps = 3; g0.stride_t = 2 * 20; g0.stride_j = 20; g0.base_off = -plf;
+  g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
+  p->g0 = g0;
+  static const int spec[11][2] = {{128, 2}, {256, 2}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1},
+                                  {256, 1}, {256, 1}, {384, 2}};  // model.py:964-968
+  lm_begin_stack(p);
+  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0] * fm, s[1]));
+  KWS_REQUIRE(kws_attn_gate_fwd_floats(1, p->T, p->C, XC_GATE_K) > 0, "net: xception_with_attention tail [%d, %d] is outside the attention gate's domain",
+              p->T, p->C);
+  p->att_dw = kn.dwk(XC_GATE_K, p->C);                 // _context_conv(x, 1, 5, padding='same'), model.py:973
+  p->att_pw = kn.conv(1, p->C, 1, KWS_L2_COEF);
+  p->att_bn = kn.bn(1, &p->att_bn_idx);
+  p->gH = XC_GRU_UNITS;
+  const int H = p->gH;
+  for (int d = 0; d < 2; ++d) {   // kernel_regularizer=l2(1e-5) reaches `kernel` only; recurrent_kernel: Orthogonal, drawn by the host
+    const std::string base = std::string("bidirectional_1/") + (d ? "backward" : "forward") + "_gru_1/";
+    p->gW[d] = kws_net_add_tensor(n, base + "kernel", {p->C, 3 * H}, false, KWS_L2_COEF, p->C, 3 * H, 0.f);
+    p->gU[d] = kws_net_add_tensor(n, base + "recurrent_kernel", {H, 3 * H}, false, 0.f, 0, 0, 0.f);
+    p->gb[d] = kws_net_add_tensor(n, base + "bias", {3 * H}, false, 0.f, 0, 0, 0.f);
+  }
+  p->NC = c.num_classes;
+  p->feat = 2 * H;
+  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->feat, p->NC}, false, KWS_L2_COEF, p->feat, p->NC, 0.f);
+  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->n_bn = kn.n_bn;
+  return KWS_OK;
+}
+
 // conv_1d_mfcc_and_raw_model, reference model.py:1563-1660.  Input rows: [mfcc T*F | raw L].
 int mfcc_raw_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
@@ -701,7 +794,6 @@ int64_t LmProgram::workspace_bytes(int B, int training) const {
 }
 
 int LmProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
-  (void)training;
   LmLayout lo;
   lm_layout(*this, B, &lo);
   const LmProgram& p = *this;
@@ -717,6 +809,16 @@ int LmProgram::debug_view(int B, int training, int what, int index, int64_t* off
   if (what == 3) { *offset_floats = lo.att; *count = (int64_t)B * p.T; return KWS_OK; }
   if (what == 4) { *offset_floats = lo.u; *count = (int64_t)B * p.T; return KWS_OK; }
   if (what == 5) { *offset_floats = lo.o[nb - 1]; *count = (int64_t)B * p.T * p.C; return KWS_OK; }
+  if (p.style == LM_XCEPTION) {   // 6 = gate output, 7 = the GRU's saved steps [2][4: z, r, c, h][B, T, H], 8 = GRU output, 9 = attention BN table
+    if (what == 6) { *offset_floats = lo.xgy; *count = (int64_t)B * p.T * p.C; return KWS_OK; }
+    if (what == 7) {
+      KWS_REQUIRE(training, "lm_debug_view: view 7 exists in training only");
+      *offset_floats = lo.gsave; *count = kws_gru_save_floats(B, p.T, p.gH);
+      return KWS_OK;
+    }
+    if (what == 8) { *offset_floats = lo.gout; *count = (int64_t)B * 2 * p.gH; return KWS_OK; }
+    if (what == 9) { *offset_floats = lo.bn + lo.bn_stride * p.att_bn_idx; *count = 4; return KWS_OK; }
+  }
   if (what == 0) {
     if (p.style == LM_MFCC_AND_RAW && index <= 2) {
       *offset_floats = lo.y0 + (index == 2 ? (int64_t)B * p.L0 * p.Cm : 0);
@@ -747,6 +849,11 @@ int LmProgram::predict(const float* params, const float* state, const float* x, 
   KWS_TRY(kws_workspace_check("net_predict", c.lo.total, ws_bytes, B));
   kws_lm_tail_args t;
   KWS_TRY(forward(c, x, &t));
+  if (c.p->style == LM_XCEPTION) {
+    KWS_TRY(xc_gate_gru_fwd(c, t.x, 0, 0, 0));
+    const kws_flat_tail_args f = xc_tail_args(c, probs);
+    return kws_flat_tail_launch(&f, 0, st);
+  }
   if (c.p->style != LM_ATTENTION) {
     const kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
     return kws_gp_tail_launch(&g, 0, st);
@@ -818,7 +925,20 @@ int LmProgram::train(const float* params, float* state, const float* x, const fl
     return kws_gemm_nn_f32(dO, ws + lo.wt_ws[i], ws + lo.DXS, (int64_t)B * b.Lout, b.nf, b.cin, nullptr, st);
   };
   // ---- tail forward + backward ----
-  if (p.style != LM_ATTENTION) {
+  if (p.style == LM_XCEPTION) {   // gate -> GRU -> Dense + softmax + CE, and back: the GRU's dx is the gate's dy, the gate's dx the last block's dO
+    const int H = p.gH;
+    KWS_TRY(xc_gate_gru_fwd(c, t.x, seed, step, row_offset));
+    kws_flat_tail_args f = xc_tail_args(c, probs);
+    KWS_TRY(kws_flat_tail_train(&f, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.gdout, ws + lo.per_loss, ws + lo.per_correct, seed, step,
+                                loss_batch, row_offset, metrics, st));
+    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.feat, p.NC, ws + lo.swg, st));
+    KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.xgy, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
+                            ws + lo.gmh, ws + lo.gsave, G, grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
+                            grads + p.gU[1], grads + p.gb[1], ws + lo.gws, B, p.T, p.C, H, st));
+    KWS_TRY(kws_attn_gate_bwd_f32(G, t.x, ws + lo.u, ws + lo.att, c.bn_at(p.att_bn_idx), params + p.att_dw, params + p.att_pw,
+                                  params + p.att_bn.gamma, dO, grads + p.att_dw, grads + p.att_pw, grads + p.att_bn.gamma,
+                                  grads + p.att_bn.beta, ws + lo.xagb, B, p.T, p.C, XC_GATE_K, 1, st));
+  } else if (p.style != LM_ATTENTION) {
     kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
     g.labels = y_onehot; g.dX = dO; g.fd = ws + lo.fd; g.dl = ws + lo.dl;
     g.per_loss = ws + lo.per_loss; g.per_correct = ws + lo.per_correct;

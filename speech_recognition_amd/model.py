@@ -7,7 +7,8 @@ from .keras_api import Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
-               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple')
+               'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
+               'xception_with_attention')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -203,6 +204,15 @@ def conv_1d_simple_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, Adam(lr=1e-3), name='conv_1d_time_stacked', loss='cce')
 
 
+def xception_with_attention_model(input_size=16000, num_classes=11, filter_mult=1):
+    """reference model.py:911-983: raw waveform -> time-slice stack -> Conv1D(64, 3, strides=2) -> eleven residual blocks with 3-wide
+    max-pool joins (128, 256, 8 x 256, 384) ending at [50, 384] -> attention gate (a 5-tap depthwise block of one filter, softmax over
+    time, multiplied onto the sequence) -> Bidirectional(GRU(192, dropout=.2, recurrent_dropout=.2, l2 1e-5 on the kernels)) -> Dense;
+    RMSprop(5e-4), categorical CE."""
+    net = DeviceNet(_lib.KWS_NET_XCEPTION_ATTENTION, num_classes, filter_mult=filter_mult, input_size=input_size)
+    return Model(net, RMSprop(lr=5e-4), name='xception_with_attention', loss='cce')
+
+
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
@@ -230,6 +240,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_multi_time_sliced_model(input_size, num_classes)
     if model_type == 'conv_1d_simple':
         return conv_1d_simple_model(input_size, num_classes)
+    if model_type == 'xception_with_attention':
+        return xception_with_attention_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"
