@@ -1,5 +1,6 @@
 """Builds and loads libkws_internal_test.so: the library's own objects (csrc/build/*.o) plus tests/native/internal_shim.cpp, whose
-kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip) to ctypes.
+kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip) and the fused
+backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32) to ctypes; built once per process, whichever test module asks first.
 The public kws_* entry points come from the same library (-Wl,-Bsymbolic keeps its calls inside its own copy), so every kernel a
 test compares comes from one build.  Also: the join / shortcut shapes the residual programs launch, read from the planner of
 net_logmfcc.hip through the public net API (host-side only: no GPU needed)."""
@@ -35,6 +36,7 @@ KWST_SIGNATURES = {
     "kwst_gemm_nn_strided_f32": (_I, [_P, _I, _P, _P, _I64, _I, _I, _P, _P]),
     "kwst_gemm_tn_slabs_strided_f32": (_I, [_P, _I, _P, _I64, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "kwst_gemm_tn_slabs_f32": (_I, [_P, _P, _I64, _I, _I, _P, ctypes.POINTER(_I), _P]),
+    "kwst_gemm_dgrad_wgrad_f32": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "kwst_reduce_slabs_batch": (_I, [_P, _P, _P, _P, _I, _P]),
 }
 # the public entry points the tests compare against, taken from the same library
@@ -44,8 +46,19 @@ PUBLIC = ["kws_last_error", "kws_dwconv_fwd_f32", "kws_dwconv_bwd_f32", "kws_dwc
           "kws_net_tensor_info", "kws_net_debug_view"]
 
 
+_BUILT = None    # the library this process has already built: every test module after the first reuses it
+
+
 def build(out_dir):
-    """make the library's objects, compile the shim against the internal headers and link both; returns the .so path."""
+    """make the library's objects, compile the shim against the internal headers and link both; returns the .so path.  Built
+    once per process: a later call returns the first call's library, whatever its out_dir."""
+    global _BUILT
+    if _BUILT is None:
+        _BUILT = _build(out_dir)
+    return _BUILT
+
+
+def _build(out_dir):
     subprocess.check_call(["make", "-C", CSRC, "-j8"], stdout=subprocess.DEVNULL)
     shim_o = os.path.join(out_dir, "internal_shim.o")
     r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "--offload-arch=gfx950", "-Wall", "-Werror",

@@ -1,6 +1,7 @@
 // Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip).
-// libkws_hip.so builds them with hidden visibility; tests/test_resblock_kernels_gpu.py links this file with the library's own
-// objects into a separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them.  No kernels live here.
+// libkws_hip.so builds them with hidden visibility; tests/internal_shim.py links this file with the library's own objects into a
+// separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them (tests/test_resblock_kernels_gpu.py,
+// tests/test_gemm_pair_gpu.py).  No kernels live here.
 //
 // Every forwarder has exactly the parameter list of the declaration it forwards to: KWST_FORWARD static_asserts that the two
 // function types are the same, so a changed declaration fails this build instead of being cast into a wrong call.
@@ -67,6 +68,10 @@ KWST_FORWARD(int, gemm_tn_slabs_strided_f32,
 KWST_FORWARD(int, gemm_tn_slabs_f32,
              (const float* A, const float* G, int64_t M, int K, int N, float* workspace, int* S, hipStream_t stream),
              (A, G, M, K, N, workspace, S, stream));
+KWST_FORWARD(int, gemm_dgrad_wgrad_f32,
+             (const float* dY, const float* WT, float* dZ, const float* Z, int64_t M, int cin, int cout, float* workspace, int* S,
+              hipStream_t stream),
+             (dY, WT, dZ, Z, M, cin, cout, workspace, S, stream));
 KWST_FORWARD(int, reduce_slabs_batch,
              (const float* const* ws, float* const* out, const int64_t* n, const int* S, int count, hipStream_t stream),
              (ws, out, n, S, count, stream));

@@ -7,9 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_exact as GE
 from oracle import features as OF
 from oracle import layers as OL
 from speech_recognition_amd import _lib
+from test_resblock_kernels_gpu import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +113,77 @@ def test_gemm_gather_is_frame_plus_conv1():
     assert rel_err(dWt.cpu().numpy(), ref_dw) < 5e-6
 
 
+# ------------------------------------------------------------------------------------------------
+# The exact-integer runs (tests/gemm_exact.py): ternary operands make every partial sum an integer below 2^24, so C, the
+# BatchNorm partial rows and the weight gradients must equal float64 bit for bit whatever the tiling - a row that an epilogue
+# drops or counts twice changes an integer.  Outputs and workspaces are windows of sentinel-guarded allocations.
+def _check_stats_exact(part, rows, N, ref, what):
+    part.check(what + " statistics", written=rows * 2 * N)                 # exactly `rows` rows are written
+    folded = part.get()[:rows * 2 * N].reshape(rows, 2, N).astype(np.float64).sum(axis=0)
+    want = GE.stats_ref(ref)
+    GE.assert_exact(folded.astype(np.float32), want, what + " column sums")
+    assert np.array_equal(folded, want)
+    # controls on host data: the sums of an epilogue that lost one row, or counted it twice, are not what the device gave
+    r = GE.controls_row(ref)
+    assert not GE.same_bits(folded.astype(np.float32), GE.stats_without_row(ref, r))
+    assert not GE.same_bits(folded.astype(np.float32), GE.stats_with_row_twice(ref, r))
+
+
+@pytest.mark.parametrize("M,K,N", GE.NN_EXACT_CASES)
+def test_gemm_nn_and_stats_exact(M, K, N):
+    A, W = GE.nn_inputs(M, K, N)
+    ref = GE.f64(A) @ GE.f64(W)
+    GE.premise_columns(ref)
+    lib = _lib.load()
+    nt = lib.kws_gemm_num_row_tiles(M)
+    rows = lib.kws_gemm_nn_stats_rows(M, K, N)
+    assert 0 < rows <= nt and rows == GE.nn_plan(M, K, N)["rows"]
+    C, part = Guarded(M * N), Guarded(nt * 2 * N)
+    _lib.call("kws_gemm_nn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(W)), C.ptr(), M, K, N, part.ptr(), S())
+    C.check("gemm_nn C")
+    GE.assert_exact(C.get().reshape(M, N), ref, "C")
+    _check_stats_exact(part, rows, N, ref, "gemm_nn")
+
+
+@pytest.mark.parametrize("B", GE.GATHER_B)
+def test_gemm_gather_and_stats_exact(B):
+    """the first convolution of the headline net WITH its fused BatchNorm statistics, and its weight gradient"""
+    x, W, G = GE.gather_inputs(B)
+    ref, cols = GE.gather_ref(x, W)
+    GE.premise_columns(ref)
+    GE.premise_tn(cols, G)
+    M, N, K = B * 399, 128, 120
+    lib = _lib.load()
+    nt = lib.kws_gemm_num_row_tiles(M)
+    rows = lib.kws_gemm_gather_stats_rows(M)
+    assert rows == -(-M // 128) <= nt and M % 128 != 0
+    g = _gather_desc(**GE.GATHER_DESC)
+    dx = dev(x)
+    C, part = Guarded(M * N), Guarded(nt * 2 * N)
+    _lib.call("kws_gemm_gather_f32", _lib.ptr(dx), ctypes.byref(g), _lib.ptr(dev(W)), C.ptr(), B, N, part.ptr(), S())
+    C.check("gemm_gather C")
+    GE.assert_exact(C.get().reshape(M, N), ref, "C")
+    _check_stats_exact(part, rows, N, ref, "gemm_gather")
+    # wgrad through the same gather
+    ws = Guarded(int(lib.kws_gemm_tn_workspace_floats(M, K, N)))
+    dWt = Guarded(K * N)
+    _lib.call("kws_gemm_tn_gather_f32", _lib.ptr(dx), ctypes.byref(g), _lib.ptr(dev(G)), dWt.ptr(), B, N, ws.ptr(), S())
+    _check_tn_exact(dWt, ws, cols, G, GE.tn_plan(M, K, N, False)["S"], "gemm_tn_gather")
+
+
+def _check_tn_exact(dW, ws, A, G, S_plan, what):
+    K, N = A.shape[1], G.shape[1]
+    dW.check(what + " dW")
+    ws.check(what + " workspace", written=S_plan * K * N)                  # exactly the planned slabs, nothing past them
+    ref = GE.f64(A).T @ GE.f64(G)
+    got = dW.get().reshape(K, N)
+    GE.assert_exact(got, ref, what + " dW")
+    slabs = ws.get()[:S_plan * K * N].reshape(S_plan, K, N).astype(np.float64)
+    assert np.array_equal(slabs.sum(axis=0), ref)
+    r = GE.tn_controls_row(A, G)
+    assert not GE.same_bits(got, GE.tn_without_row(ref, A, G, r)) and not GE.same_bits(got, GE.tn_with_row_twice(ref, A, G, r))
+
+
 # wave-specialised wgrad kernel: all four tile shapes (128x128, 128x64, 64x128, 64x64), a single short split,
 # ragged last stage, M below one stage; (2000, 120, 128) and (777, 64, 100) fall back to the 4-wave kernel
 @pytest.mark.parametrize("M,K,N", [(4000, 128, 128), (999, 192, 256), (130, 320, 320), (9216, 512, 512), (100, 64, 64),
@@ -120,14 +193,26 @@ def test_gemm_tn(M, K, N):
     rng = np.random.RandomState(M)
     A = rng.randn(M, K).astype(np.float32)
     G = rng.randn(M, N).astype(np.float32)
-    ws = torch.empty(int(_lib.load().kws_gemm_tn_workspace_floats(M, K, N)), device="cuda")
-    out = torch.full((K, N), float("nan"), device="cuda")
+    gws, gout = Guarded(int(_lib.load().kws_gemm_tn_workspace_floats(M, K, N))), Guarded(K * N)
+    ws, out = gws.view, gout.view.view(K, N)
     _lib.call("kws_gemm_tn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(G)), _lib.ptr(out), M, K, N, _lib.ptr(ws), S())
+    gout.check("gemm_tn dW")
     ref = A.astype(np.float64).T @ G.astype(np.float64)
     assert rel_err(out.cpu().numpy(), ref) < 5e-6
     out2 = torch.empty_like(out)
     _lib.call("kws_gemm_tn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(G)), _lib.ptr(out2), M, K, N, _lib.ptr(ws), S())
     assert torch.equal(out, out2)            # fixed-order reduction: bit-reproducible
+    gws.check("gemm_tn workspace", written=GE.tn_plan(M, K, N, GE.tn_ws_eligible(K, N))["S"] * K * N)
+
+
+@pytest.mark.parametrize("M,K,N", GE.TN_CASES)
+def test_gemm_tn_exact(M, K, N):
+    A, G = GE.tn_inputs(M, K, N)
+    GE.premise_tn(A, G)
+    ws = Guarded(int(_lib.load().kws_gemm_tn_workspace_floats(M, K, N)))
+    dW = Guarded(K * N)
+    _lib.call("kws_gemm_tn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(G)), dW.ptr(), M, K, N, ws.ptr(), S())
+    _check_tn_exact(dW, ws, A, G, GE.tn_plan(M, K, N, GE.tn_ws_eligible(K, N))["S"], "gemm_tn")
 
 
 def test_transpose():
@@ -210,9 +295,12 @@ def test_dwconv_fwd_bwd(Lin, stride, pad, C, with_bn, B):
         assert float((dy2 - g).abs().max()) <= 1e-6 * max(1.0, float(g.abs().max()))   # vs the three-kernel path
 
 
-def test_bn_stats_finalize_and_apply():
+# one shape per NN form (64-wide / 64-deep, wide, 64 / 32, the persistent kernel), N = 64 and N = 1024, M no multiple of 64; the
+# partial rows, the bn table and the moving statistics are windows of sentinel-guarded allocations
+@pytest.mark.parametrize("M,K,N", [c[:3] for c in GE.BN_CASES])
+def test_bn_stats_finalize_and_apply(M, K, N):
+    assert GE.nn_form(M, K, N) == dict((c[:3], c[3]) for c in GE.BN_CASES)[(M, K, N)]
     rng = np.random.RandomState(2)
-    M, K, N = 3000, 128, 192
     A = rng.randn(M, K).astype(np.float32)
     W = (rng.randn(K, N) * 0.2).astype(np.float32)
     gamma = (1 + 0.1 * rng.randn(N)).astype(np.float32)
@@ -222,21 +310,26 @@ def test_bn_stats_finalize_and_apply():
     y = torch.empty((M, N), device="cuda")
     nt = _lib.load().kws_gemm_num_row_tiles(M)
     rows = _lib.load().kws_gemm_nn_stats_rows(M, K, N)
-    part = torch.full((nt, 2, N), float("nan"), device="cuda")
-    _lib.call("kws_gemm_nn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(W)), _lib.ptr(y), M, K, N, _lib.ptr(part), S())
-    bn = torch.empty(4 * N, device="cuda")
-    dmm, dmv = dev(mm), dev(mv)
-    _lib.call("kws_bn_stats_finalize", _lib.ptr(part), rows, M, N, _lib.ptr(dev(gamma)), _lib.ptr(dev(beta)), 1e-3, 0.99,
-              _lib.ptr(dmm), _lib.ptr(dmv), _lib.ptr(bn), None, S())
+    part = Guarded(nt * 2 * N)
+    _lib.call("kws_gemm_nn_f32", _lib.ptr(dev(A)), _lib.ptr(dev(W)), _lib.ptr(y), M, K, N, part.ptr(), S())
+    part.check("gemm_nn statistics", written=rows * 2 * N)
+    bn = Guarded(4 * N)
+    dmm, dmv = Guarded(N, init=mm), Guarded(N, init=mv)
+    _lib.call("kws_bn_stats_finalize", part.ptr(), rows, M, N, _lib.ptr(dev(gamma)), _lib.ptr(dev(beta)), 1e-3, 0.99,
+              dmm.ptr(), dmv.ptr(), bn.ptr(), None, S())
+    bn.check("bn_stats_finalize table")
+    dmm.check("bn_stats_finalize moving mean")
+    dmv.check("bn_stats_finalize moving variance")
+    part.check("bn_stats_finalize (partial rows)", written=rows * 2 * N)   # the rows past `rows` stay unread and unwritten
     y64 = y.cpu().numpy().astype(np.float64)[None]
     pre, (mean, var, rstd) = OL.bn_train_fwd(y64, gamma.astype(np.float64), beta.astype(np.float64))
-    b = bn.cpu().numpy()
+    b = bn.get()
     np.testing.assert_allclose(b[2 * N:3 * N], mean, atol=1e-5)
     np.testing.assert_allclose(b[3 * N:], rstd, rtol=1e-5)
-    np.testing.assert_allclose(dmm.cpu().numpy(), OL.bn_moving_update(mm.astype(np.float64), mean), atol=1e-6)
-    np.testing.assert_allclose(dmv.cpu().numpy(), OL.bn_moving_update(mv.astype(np.float64), var), rtol=1e-5)
+    np.testing.assert_allclose(dmm.get(), OL.bn_moving_update(mm.astype(np.float64), mean), atol=1e-6)
+    np.testing.assert_allclose(dmv.get(), OL.bn_moving_update(mv.astype(np.float64), var), rtol=1e-5)
     out = torch.empty_like(y)
-    _lib.call("kws_bn_relu6_apply", _lib.ptr(y), _lib.ptr(bn), _lib.ptr(out), M, N, 1, S())
+    _lib.call("kws_bn_relu6_apply", _lib.ptr(y), bn.ptr(), _lib.ptr(out), M, N, 1, S())
     assert np.abs(out.cpu().numpy() - OL.relu6(pre)[0]).max() < 2e-5
 
 
