@@ -676,6 +676,8 @@ int kws_ts_tail_launch(const kws_ts_tail_args* p, hipStream_t st) {
 int kws_small_wgrad_launch(const float* X, const float* D, float* out, float* out_bias, int B, int K, int N,
                            float* scratch, hipStream_t st) {
   const int64_t n = (int64_t)K * N;
+  // (checked before anything is launched: a refused call writes nothing)
+  KWS_REQUIRE(!out_bias || N <= 64, "small_wgrad: N=%d > 64", N);
   KwsProfScope prof("small_wgrad", 2.0 * B * K * N, 4.0 * ((double)B * K + (double)B * N + (double)K * N), st);
   int S = scratch ? KWS_SMALL_WGRAD_SLICES : 1;
   if (S > B) S = B;
@@ -698,7 +700,6 @@ int kws_small_wgrad_launch(const float* X, const float* D, float* out, float* ou
     }
   }
   if (out_bias) {
-    KWS_REQUIRE(N <= 64, "small_wgrad: N=%d > 64", N);
     // (N <= 16 keeps the 256-thread geometry: tail_post_kernel runs the same body in its 256-thread grid, bit for bit)
     if (N <= 16) hipLaunchKernelGGL((colsum_kernel<16, 256>), dim3(1), dim3(256), 0, st, D, out_bias, B, N);
     else if (N <= 32) hipLaunchKernelGGL((colsum_kernel<32, 1024>), dim3(1), dim3(1024), 0, st, D, out_bias, B, N);

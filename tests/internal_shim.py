@@ -1,6 +1,6 @@
 """Builds and loads libkws_internal_test.so: the library's own objects (csrc/build/*.o) plus tests/native/internal_shim.cpp, whose
-kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip) and the fused
-backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32) to ctypes; built once per process, whichever test module asks first.
+kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip), the fused
+backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32) and the classifier tails (tail.hip, gconv.hip kws_flat_tail_launch) to ctypes; built once per process, whichever test module asks first.
 The public kws_* entry points come from the same library (-Wl,-Bsymbolic keeps its calls inside its own copy), so every kernel a
 test compares comes from one build.  Also: the join / shortcut shapes the residual programs launch, read from the planner of
 net_logmfcc.hip through the public net API (host-side only: no GPU needed)."""
@@ -38,6 +38,13 @@ KWST_SIGNATURES = {
     "kwst_gemm_tn_slabs_f32": (_I, [_P, _P, _I64, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "kwst_gemm_dgrad_wgrad_f32": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "kwst_reduce_slabs_batch": (_I, [_P, _P, _P, _P, _I, _P]),
+    "kwst_ts_tail_launch": (_I, [_P, _P]),
+    "kwst_small_wgrad_launch": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "kwst_metrics_launch": (_I, [_P, _P, _I, _P, _P]),
+    "kwst_tail_post_launch": (_I, [_P, ctypes.POINTER(_I), _P]),
+    "kwst_flat_tail_launch": (_I, [_P, _I, _P]),
+    "kwst_reduce_slabs_f32": (_I, [_P, _P, _I64, _I, _P]),
+    "kwst_tail_struct_layout": (None, [ctypes.POINTER(_I64)]),
 }
 # the public entry points the tests compare against, taken from the same library
 PUBLIC = ["kws_last_error", "kws_dwconv_fwd_f32", "kws_dwconv_bwd_f32", "kws_dwconv_bwd_part_floats", "kws_dw_bwd_finalize",
@@ -96,6 +103,37 @@ def exported_symbols(so):
 class Gather(ctypes.Structure):
     _fields_ = [("L_out", _I), ("cin", _I), ("taps", _I), ("stride_t", _I), ("stride_j", _I), ("base_off", _I),
                 ("x_len", _I), ("x_batch_stride", _I64)]
+
+
+# ctypes mirrors of the tails' argument structs (csrc/internal.h); tail_struct_layout() below is what the library itself says
+class TsTailArgs(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("y", "bn", "W1", "b1", "W2", "labels", "probs", "g", "part", "xd", "fd", "dl1", "dl2",
+                                  "per_loss", "per_correct", "att")] + \
+               [("B", _I), ("T", _I), ("C", _I), ("NC", _I), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint32),
+                ("keep_prob", _F), ("label_smoothing", _F), ("loss_batch", _I), ("row_offset", _I64), ("train", _I)]
+
+
+class TailPostArgs(ctypes.Structure):
+    _fields_ = [("X2", _P), ("D2", _P), ("ws2", _P), ("K2", _I), ("N2", _I), ("X1", _P), ("D1", _P), ("ws1", _P), ("K1", _I),
+                ("N1", _I), ("bias1", _P), ("per_loss", _P), ("per_correct", _P), ("metrics", _P), ("B", _I)]
+
+
+class FlatTailArgs(ctypes.Structure):
+    _fields_ = [("y", _P), ("bn", _P), ("Ng", _I), ("Wd", _P), ("bd", _P), ("labels", _P), ("probs", _P), ("fd", _P), ("dl", _P),
+                ("dA", _P), ("per_loss", _P), ("per_correct", _P), ("B", _I), ("D", _I), ("F", _I), ("NC", _I),
+                ("seed", ctypes.c_uint64), ("step", ctypes.c_uint32), ("keep_prob", _F), ("loss_batch", _I), ("row_offset", _I64),
+                ("layer_id", ctypes.c_uint32), ("raw", _I)]
+
+
+# (mirror, its last member) in the order of kwst_tail_struct_layout
+TAIL_STRUCTS = [(TsTailArgs, "train"), (TailPostArgs, "B"), (FlatTailArgs, "raw")]
+
+
+def tail_struct_layout(lib):
+    """[(sizeof, offsetof last member)] of kws_ts_tail_args, kws_tail_post_args, kws_flat_tail_args as the library was compiled"""
+    out = (_I64 * 6)()
+    lib.kwst_tail_struct_layout(out)
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(3)]
 
 
 # the four residual programs of net_logmfcc.hip, configured as speech_model() builds them (model.py); C3 = conv_1d_log_mfcc at

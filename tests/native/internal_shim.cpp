@@ -1,10 +1,12 @@
-// Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip).
+// Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip) and of the
+// classifier tails (tail.hip, gconv.hip kws_flat_tail_launch).
 // libkws_hip.so builds them with hidden visibility; tests/internal_shim.py links this file with the library's own objects into a
 // separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them (tests/test_resblock_kernels_gpu.py,
-// tests/test_gemm_pair_gpu.py).  No kernels live here.
+// tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py).  No kernels live here.
 //
 // Every forwarder has exactly the parameter list of the declaration it forwards to: KWST_FORWARD static_asserts that the two
 // function types are the same, so a changed declaration fails this build instead of being cast into a wrong call.
+#include <cstddef>
 #include <type_traits>
 
 #include "net_internal.h"
@@ -75,3 +77,26 @@ KWST_FORWARD(int, gemm_dgrad_wgrad_f32,
 KWST_FORWARD(int, reduce_slabs_batch,
              (const float* const* ws, float* const* out, const int64_t* n, const int* S, int count, hipStream_t stream),
              (ws, out, n, S, count, stream));
+
+// ---- classifier tails (tail.hip, gconv.hip) and the slab sum kws_small_wgrad_launch uses (gemm.hip) ----
+KWST_FORWARD(int, ts_tail_launch, (const kws_ts_tail_args* p, hipStream_t st), (p, st));
+KWST_FORWARD(int, small_wgrad_launch,
+             (const float* X, const float* D, float* out, float* out_bias, int B, int K, int N, float* scratch, hipStream_t st),
+             (X, D, out, out_bias, B, K, N, scratch, st));
+KWST_FORWARD(int, metrics_launch, (const float* per_loss, const float* per_correct, int B, float* metrics, hipStream_t st),
+             (per_loss, per_correct, B, metrics, st));
+KWST_FORWARD(int, tail_post_launch, (const kws_tail_post_args* a, int* S_out, hipStream_t st), (a, S_out, st));
+KWST_FORWARD(int, flat_tail_launch, (const kws_flat_tail_args* a, int training, hipStream_t st), (a, training, st));
+KWST_FORWARD(int, reduce_slabs_f32, (const float* ws, float* out, int64_t n, int S, hipStream_t st), (ws, out, n, S, st));
+
+// sizeof and the offset of the last member of the three argument structs, in the order ts_tail, tail_post, flat_tail: the ctypes
+// mirrors of tests/internal_shim.py are compared with these on the build machine (tests/test_internal_shim_cpu.py), so that a
+// changed struct fails there instead of becoming a wrong call on the GPU
+KWST_API void kwst_tail_struct_layout(int64_t* out6) {
+  out6[0] = (int64_t)sizeof(kws_ts_tail_args);
+  out6[1] = (int64_t)offsetof(kws_ts_tail_args, train);
+  out6[2] = (int64_t)sizeof(kws_tail_post_args);
+  out6[3] = (int64_t)offsetof(kws_tail_post_args, B);
+  out6[4] = (int64_t)sizeof(kws_flat_tail_args);
+  out6[5] = (int64_t)offsetof(kws_flat_tail_args, raw);
+}

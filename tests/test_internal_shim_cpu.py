@@ -44,6 +44,24 @@ def test_forwarder_with_a_wrong_signature_fails_the_build(tmp_path):
     assert "does not match the declaration of kws_add_f32" in r.stderr
 
 
+def test_tail_struct_mirrors_match_the_library(shim):
+    """The ctypes mirrors of the tails' argument structs have the size and last-member offset the library was compiled with: a
+    member added, removed or retyped in csrc/internal.h fails here, on the build machine."""
+    _, lib = shim
+    mine = [(ctypes.sizeof(cls), getattr(cls, last).offset) for cls, last in internal_shim.TAIL_STRUCTS]
+    assert mine == internal_shim.tail_struct_layout(lib)
+    # the mirrors' member order, member for member, against the header's text
+    src = open(os.path.join(internal_shim.CSRC, "internal.h")).read()
+    for cls, cname in zip([c for c, _ in internal_shim.TAIL_STRUCTS], ["kws_ts_tail_args", "kws_tail_post_args", "kws_flat_tail_args"]):
+        body = src.split("struct %s {" % cname)[1].split("};")[0]
+        names = []
+        for decl in body.split(";"):
+            decl = " ".join(l.split("//")[0] for l in decl.splitlines()).strip()
+            if decl:
+                names += [part.split()[-1].lstrip("*") for part in decl.split(",")]
+        assert names == [f[0] for f in cls._fields_], cname
+
+
 def _gather(d):
     g = internal_shim.Gather()
     for k, v in d.items():
