@@ -343,6 +343,49 @@ int kws_pool3s2_same_bwd_f32(const float* dz, const float* y, const float* bn, f
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense Conv1D (stride 1, no bias) with zero padding, dilation and channel windows, on f32 MFMA: the convolutions of the
+ * reference's _inception_block / _reduce_inception_block (model.py:312-406), whose branches read one joined tensor and write
+ * the slices of the next.  X [B, L, Cx], of which the columns [x0, x0 + Cin) are read; Y and dY [B, Lout, Cy], of which the
+ * columns [y0, y0 + F) are written / read.  Kernel W [k, Cin, F] (Keras layout).  Lout = L + pad_l + pad_r - dil*(k-1) for
+ * some 0 <= pad_r <= dil*(k-1); 0 <= pad_l <= dil*(k-1) (TF SAME: pad_l = dil*(k-1) / 2, Lout = L; VALID: pad_l = 0,
+ * Lout = L - dil*(k-1)).  k 1..7, dil 1..4, any positive Cin / F.  Results are bit-identical from run to run (no atomics).
+ *   fwd    Y[b,t,y0+n] = sum_{j,c} act(X[b, t - pad_l + dil*j, x0+c]) * W[j,c,n]; a tap outside [0, L) contributes 0 (the
+ *          padding is zeros of the ACTIVATED tensor).  act = relu6(scale*x + shift) of the table bn [4][Cx]
+ *          (scale|shift|mean|rstd, indexed by x0+c), or the identity when bn is NULL.  No other column of Y is touched.
+ *          stats_part (may be NULL): [kws_conv1d_stats_rows][2][F] column sums (sum y, sum y^2) per 128-row tile.
+ *   dgrad  dX[b,tau,x0+c] = sum_j sum_n dY[b, tau + pad_l - dil*j, y0+n] * W[j,c,n]: the gradient wrt act(X) (no gate is
+ *          applied).  accumulate 0 overwrites the window, 1 adds to what is there; every element of the window is touched
+ *          exactly once by one thread, no other column of dX is touched.
+ *   wgrad  dW[j,c,n] = sum_{b,t} act(X[b, t - pad_l + dil*j, x0+c]) * dY[b,t,y0+n];
+ *          workspace >= kws_conv1d_wgrad_workspace_floats floats (fixed-order split over B*Lout).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, L, Lout;      /* clips, input rows, output rows per clip */
+  int k, dil, pad_l;   /* taps, dilation, zero rows in front of a clip */
+  int Cx, x0, Cin;     /* row pitch of X, first column read, columns read */
+  int Cy, y0, F;       /* row pitch of Y / dY, first column written, filters */
+} kws_conv1d_t;
+int kws_conv1d_stats_rows(const kws_conv1d_t* d);
+int kws_conv1d_fwd_f32(const float* X, const float* bn, const float* W, float* Y, float* stats_part, const kws_conv1d_t* d,
+                       void* stream);
+int kws_conv1d_dgrad_f32(const float* dY, const float* W, float* dX, int accumulate, const kws_conv1d_t* d, void* stream);
+int64_t kws_conv1d_wgrad_workspace_floats(const kws_conv1d_t* d);
+int kws_conv1d_wgrad_f32(const float* X, const float* bn, const float* dY, float* dW, float* workspace, const kws_conv1d_t* d,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * AveragePooling1D(pool_size=3, strides=1, padding='same') over act(x): the pool branch of the reference's _inception_block.
+ * x, z, dz, dx [B, L, C]; C % 4 == 0, L >= 1.  TensorFlow divides by the number n_t of rows that exist in window t: 3 inside
+ * a clip, 2 at its ends (1 when L = 1).
+ *   fwd  z[b,t,c] = (1 / n_t) * sum over r in {t-1, t, t+1} within [0, L) of act(x[b,r,c]); act = relu6(scale*x + shift) of the
+ *        table bn [4][C], or the identity when bn is NULL.
+ *   bwd  dx[b,u,c] = sum over t in {u-1, u, u+1} within [0, L) of dz[b,t,c] / n_t: the gradient wrt act(x) (no gate is applied).
+ *        accumulate 0 overwrites dx, 1 adds to what is there.  No atomics: results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int kws_avgpool3_same_fwd_f32(const float* x, const float* bn, float* z, int B, int L, int C, void* stream);
+int kws_avgpool3_same_bwd_f32(const float* dz, float* dx, int accumulate, int B, int L, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -576,6 +619,20 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         logits u [B, T], what 5 = the last block's output [B, T, C], what 6 = the gate's output [B, T, C], what 7
  *                         = the GRU's saved steps [2 directions][4: z, r, c, h][B, T, 192] (training), what 8 = the GRU output
  *                         [B, 384], what 9 = the attention BatchNorm's table [4] = scale | shift | mean | rstd.
+ *   KWS_NET_INCEPTION_D1: conv_inception_d1_model, reference model.py:312-406 (raw input, input_size must be 16000; Keras model
+ *                         name 'inception_d1'): the samples as [800, 20] -> Conv1D(32, 1) -> three stride-1 reduce (MaxPool1D(3, 2)
+ *                         behind) / context pairs of 64, 128, 256 filters, k 3 VALID (kws_gconv_* with one group + kws_pool3s2_*) ->
+ *                         [B, 93, 256] -> eight inception blocks (1x1(64) | 1x1(48) -> k3 dil 2 (64) | 1x1(64) -> k3 dil d (96) twice
+ *                         | AveragePooling1D(3, 1, 'same') -> 1x1(32), all SAME, concatenated: kws_conv1d_* writing the slices of the
+ *                         joined tensor, kws_avgpool3_same_*; d = 2, 2, 2, 1, 1, 1, 1, 1) with a reduce block (k3(192) + pool |
+ *                         1x1(32) -> k3(48) -> k3(48) + pool | MaxPool1D(3, 2, 'same') of the input; kws_pool3s2_same_*, 496
+ *                         channels) behind every second one: T = 93, 47, 24, 12, 6 -> Dropout(.2) -> Conv1D(num_classes, 6,
+ *                         softmax, bias) over the 6 remaining steps.  80 Conv1D in the reference's creation order; debug views: what
+ *                         0 = raw output of Conv1D `index` (0 .. 78): a column window of the tensor it was written into, from its
+ *                         first to its last element (count = (rows - 1) * pitch + filters), what 2 = table of
+ *                         batch_normalization_{index+1}: the same columns of that tensor's table, the rows scale | shift | mean |
+ *                         rstd one pitch apart (count = 3 * pitch + filters), what 3 = geometry of Conv1D `index`: offset = row
+ *                         pitch, count = filters.
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -593,6 +650,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_MULTI_TIME_SLICED 11
 #define KWS_NET_CONV_1D_SIMPLE 12
 #define KWS_NET_XCEPTION_ATTENTION 13
+#define KWS_NET_INCEPTION_D1 14
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

@@ -25,6 +25,7 @@ KWS_NET_CONV_1D_GRU = 10
 KWS_NET_CONV_1D_MULTI_TIME_SLICED = 11
 KWS_NET_CONV_1D_SIMPLE = 12
 KWS_NET_XCEPTION_ATTENTION = 13
+KWS_NET_INCEPTION_D1 = 14
 
 
 class KwsError(RuntimeError):
@@ -42,6 +43,14 @@ class GconvDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("C", ctypes.c_int), ("Lout", ctypes.c_int),
                 ("k", ctypes.c_int), ("stride", ctypes.c_int), ("g", ctypes.c_int), ("gs", ctypes.c_int),
                 ("Ng", ctypes.c_int), ("w_group_stride", ctypes.c_int64)]
+
+
+class Conv1dDesc(ctypes.Structure):
+    """kws_conv1d_t: dense Conv1D (stride 1) from the columns [x0, x0 + Cin) of [B, L, Cx] to the columns [y0, y0 + F) of
+    [B, Lout, Cy]."""
+    _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("Lout", ctypes.c_int), ("k", ctypes.c_int),
+                ("dil", ctypes.c_int), ("pad_l", ctypes.c_int), ("Cx", ctypes.c_int), ("x0", ctypes.c_int),
+                ("Cin", ctypes.c_int), ("Cy", ctypes.c_int), ("y0", ctypes.c_int), ("F", ctypes.c_int)]
 
 
 class SamplerSet(ctypes.Structure):
@@ -154,6 +163,13 @@ SIGNATURES = {
     "kws_pool3s2_same_bwd_part_rows": (_I, [_I, _I, _I]),
     "kws_pool3s2_same_bwd_part_floats": (_I64, [_I, _I, _I]),
     "kws_pool3s2_same_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kws_conv1d_stats_rows": (_I, [ctypes.POINTER(Conv1dDesc)]),
+    "kws_conv1d_fwd_f32": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(Conv1dDesc), _P]),
+    "kws_conv1d_dgrad_f32": (_I, [_P, _P, _P, _I, ctypes.POINTER(Conv1dDesc), _P]),
+    "kws_conv1d_wgrad_workspace_floats": (_I64, [ctypes.POINTER(Conv1dDesc)]),
+    "kws_conv1d_wgrad_f32": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(Conv1dDesc), _P]),
+    "kws_avgpool3_same_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "kws_avgpool3_same_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "kws_stem_stats_rows": (_I, [_I, _I]),
     "kws_stem_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "kws_stem_bwd_workspace_floats": (_I64, [_I, _I, _I, _I]),

@@ -120,6 +120,11 @@ struct kws_flat_tail_args {
   int raw;
 };
 int kws_flat_tail_launch(const kws_flat_tail_args* a, int training, hipStream_t st);
+// pool_same.hip: kws_pool3s2_same_fwd_f32 / _bwd_f32 with the pooled tensor z (its gradient dz) a column window of a wider
+// tensor: the pointer names the window's first column, zp is the row pitch in floats (a multiple of 4, >= C).  net_inception.hip
+int kws_pool3s2_same_fwd_pitch(const float* y, const float* bn, float* z, int zp, int B, int L, int C, hipStream_t st);
+int kws_pool3s2_same_bwd_pitch(const float* dz, int zp, const float* y, const float* bn, float* g, float* part, int B, int L, int C,
+                               hipStream_t st);
 #ifdef __HIPCC__
 __device__ __forceinline__ void kws_add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 __device__ __forceinline__ void kws_reduce_slabs_batch_body(const SlabBatch& b, int bid, float4 (*red)[64]) {

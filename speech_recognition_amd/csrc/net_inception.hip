@@ -1,0 +1,596 @@
+// Network program of KWS_NET_INCEPTION_D1: conv_inception_d1_model (reference model.py:312-406).
+//   raw waveform as [800, 20] -> Conv1D(32, 1) -> three pairs of a stride-1 _reduce_conv (k 3 VALID + MaxPool1D(3, 2, 'valid')) and
+//   a _context_conv (k 3 VALID), 64 / 128 / 256 filters -> [93, 256]
+//   -> _inception_block x 2 (dilation 2) -> _reduce_inception_block -> [47, 496] -> blocks (2), (1) -> reduce -> [24, 496]
+//   -> blocks (1), (1) -> reduce -> [12, 496] -> blocks (1), (1) -> reduce -> [6, 496]
+//   -> Dropout(.2) -> Conv1D(num_classes, 6, softmax, bias) = the flat tail with D = 2976.  Adam(1e-3), categorical CE.
+// Every convolution is use_bias=False, l2 1e-5, followed by its own BatchNormalization and relu6.
+//
+// The program is a list of operations over a list of tensors, run forwards and then backwards:
+//   * a tensor is [B, L, C] in the workspace.  A RAW tensor holds convolution outputs before their BatchNorm and carries one
+//     table [4][C] (scale|shift|mean|rstd) that its consumers apply on load - the project's convention; the output of an
+//     inception block is such a tensor whose four column slices were written by four convolutions (kws_conv1d_*'s y0 window),
+//     each BatchNorm filling its columns of the composite table.  An ACTIVATED tensor (the output of a pool; the output of a
+//     reduce block, whose three slices all come out of max pools) is read as it is.
+//   * the stem is the one-group kws_gconv_* ladder with kws_pool3s2_*; the blocks run kws_conv1d_* (SAME, dilation 1 or 2),
+//     kws_avgpool3_same_* and kws_pool3s2_same_* (through the pitch launchers: the pooled rows are a slice of the joined tensor).
+//   * backward: every tensor has a gradient buffer of its shape holding the gradient wrt its ACTIVATED value.  The consumers of
+//     a tensor add into it in the reverse of the forward order, which is fixed: the first overwrites, the others accumulate
+//     (one thread per element, no atomics).  The relu6 gate and the BatchNorm backward are applied once, by the convolution that
+//     produced the columns, in place on its window (inc_bn_bwd), or by the max pool behind a pooled convolution
+//     (kws_pool3s2*_bwd gates and leaves the BatchNorm sums; kws_gbn_bwd_finish ends it).  The SAME max pool that reads a block's
+//     raw input hands back an already gated gradient: it goes to a buffer of its own and is added behind the gate.
+// The three sibling 1x1 convolutions of a block stay three launches, each writing where its consumer reads.
+#include "net_internal.h"
+
+namespace {
+
+constexpr float INC_DROP_KEEP = 0.8f;   // Dropout(0.2), model.py:397
+constexpr int INC_BASE = 32;            // base_num of every block
+constexpr int INC_BWD_ROWS = 64;        // rows per partial-sum chunk of the BatchNorm backward
+constexpr int INC_FIN_CG = 16, INC_FIN_RG = 16;
+
+// ---- BatchNorm bookkeeping over a column window [y0, y0 + F) of a tensor of pitch Cy (gconv.hip's arithmetic) --------------
+struct IncWin {
+  int Cy, y0, F;
+};
+
+// part[rows][2][F] -> the window's columns of the table [4][Cy] and the moving statistics: double sums over the rows in a fixed
+// order, biased variance, AssignMovingAvg
+__global__ __launch_bounds__(256) void inc_bn_finalize_kernel(const float* __restrict__ part, int rows, double inv_count,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float* __restrict__ mm, float* __restrict__ mv, float eps, float omm,
+                                                              float* __restrict__ bn, IncWin w) {
+  __shared__ double red[2][INC_FIN_RG][INC_FIN_CG];
+  const int cg = threadIdx.x % INC_FIN_CG, rg = threadIdx.x / INC_FIN_CG;
+  const int c = blockIdx.x * INC_FIN_CG + cg;
+  double s = 0.0, ss = 0.0;
+  if (c < w.F)
+    for (int t = rg; t < rows; t += INC_FIN_RG) {
+      s += (double)part[(int64_t)t * 2 * w.F + c];
+      ss += (double)part[(int64_t)t * 2 * w.F + w.F + c];
+    }
+  red[0][rg][cg] = s;
+  red[1][rg][cg] = ss;
+  __syncthreads();
+  if (rg != 0 || c >= w.F) return;
+  s = 0.0;
+  ss = 0.0;
+  for (int q = 0; q < INC_FIN_RG; ++q) {
+    s += red[0][q][cg];
+    ss += red[1][q][cg];
+  }
+  const double mean = s * inv_count;
+  double var = ss * inv_count - mean * mean;
+  if (var < 0.0) var = 0.0;
+  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float meanf = (float)mean, varf = (float)var;
+  const float scale = gamma[c] * rstd;
+  float* t = bn + w.y0 + c;
+  t[0] = scale;
+  t[w.Cy] = beta[c] - meanf * scale;
+  t[2 * w.Cy] = meanf;
+  t[3 * w.Cy] = rstd;
+  mm[c] = mm[c] - (mm[c] - meanf) * omm;
+  mv[c] = mv[c] - (mv[c] - varf) * omm;
+}
+
+// inference table from the moving statistics
+__global__ __launch_bounds__(256) void inc_bn_infer_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ mm, const float* __restrict__ mv, float eps,
+                                                           float* __restrict__ bn, IncWin w) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= w.F) return;
+  const float rstd = 1.0f / sqrtf(mv[c] + eps);
+  const float scale = gamma[c] * rstd;
+  float* t = bn + w.y0 + c;
+  t[0] = scale;
+  t[w.Cy] = beta[c] - mm[c] * scale;
+  t[2 * w.Cy] = mm[c];
+  t[3 * w.Cy] = rstd;
+}
+
+// the table of an activated tensor for a consumer that wants one (the flat tail): relu6(1 * v + 0) = v for v in [0, 6]
+__global__ __launch_bounds__(256) void inc_identity_table_kernel(float* __restrict__ bn, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  bn[c] = 1.f;
+  bn[C + c] = 0.f;
+  bn[2 * C + c] = 0.f;
+  bn[3 * C + c] = 1.f;
+}
+
+// backward of relu6 o BN over the window, pass 1: g = dA * relu6'(bn(y)) (+ add: an already gated contribution) in place, per-chunk
+// partial sums part[chunk][2][F] of (g, g * xhat); rows of one chunk are added in ascending order
+__global__ __launch_bounds__(256) void inc_bn_bwd_part_kernel(float* __restrict__ dA, const float* __restrict__ y,
+                                                              const float* __restrict__ bn, const float* __restrict__ add, int64_t M,
+                                                              IncWin w, float* __restrict__ part) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= w.F) return;
+  const float* t = bn + w.y0 + c;
+  const float sc = t[0], sh = t[w.Cy], mean = t[2 * w.Cy], rstd = t[3 * w.Cy];
+  const int64_t m0 = (int64_t)blockIdx.x * INC_BWD_ROWS;
+  const int64_t m1 = m0 + INC_BWD_ROWS < M ? m0 + INC_BWD_ROWS : M;
+  float s = 0.f, sx = 0.f;
+  for (int64_t m = m0; m < m1; ++m) {
+    const int64_t i = m * w.Cy + w.y0 + c;
+    const float yv = y[i];
+    const float pre = fmaf(yv, sc, sh);
+    float gv = (pre > 0.f && pre <= 6.f) ? dA[i] : 0.f;
+    if (add) gv += add[i];
+    dA[i] = gv;
+    s += gv;
+    sx += gv * ((yv - mean) * rstd);
+  }
+  part[(int64_t)blockIdx.x * 2 * w.F + c] = s;
+  part[(int64_t)blockIdx.x * 2 * w.F + w.F + c] = sx;
+}
+
+// pass 2: dbeta, dgamma and coef[2][F] = (sum g / n, sum g xhat / n)
+__global__ __launch_bounds__(256) void inc_bn_bwd_fin_kernel(const float* __restrict__ part, int rows, double inv_count, int F,
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                             float* __restrict__ coef) {
+  __shared__ double red[2][INC_FIN_RG][INC_FIN_CG];
+  const int cg = threadIdx.x % INC_FIN_CG, rg = threadIdx.x / INC_FIN_CG;
+  const int c = blockIdx.x * INC_FIN_CG + cg;
+  double s = 0.0, sx = 0.0;
+  if (c < F)
+    for (int t = rg; t < rows; t += INC_FIN_RG) {
+      s += (double)part[(int64_t)t * 2 * F + c];
+      sx += (double)part[(int64_t)t * 2 * F + F + c];
+    }
+  red[0][rg][cg] = s;
+  red[1][rg][cg] = sx;
+  __syncthreads();
+  if (rg != 0 || c >= F) return;
+  s = 0.0;
+  sx = 0.0;
+  for (int q = 0; q < INC_FIN_RG; ++q) {
+    s += red[0][q][cg];
+    sx += red[1][q][cg];
+  }
+  dgamma[c] = (float)sx;
+  dbeta[c] = (float)s;
+  coef[c] = (float)(s * inv_count);
+  coef[F + c] = (float)(sx * inv_count);
+}
+
+// pass 3: dy = scale * (g - c1 - xhat * c2), in place on the window
+__global__ __launch_bounds__(256) void inc_bn_bwd_apply_kernel(float* __restrict__ g, const float* __restrict__ y,
+                                                               const float* __restrict__ bn, const float* __restrict__ coef,
+                                                               int64_t n_el, IncWin w) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_el) return;
+  const int64_t m = e / w.F;
+  const int c = (int)(e - m * w.F);
+  const int64_t i = m * w.Cy + w.y0 + c;
+  const float* t = bn + w.y0 + c;
+  g[i] = t[0] * (g[i] - coef[c] - (y[i] - t[2 * w.Cy]) * t[3 * w.Cy] * coef[w.F + c]);
+}
+
+int inc_bn_table(const float* stats, int rows, int64_t M, const float* params, float* state, const BnRef& r, bool training, float* bn,
+                 IncWin w, hipStream_t st) {
+  if (training) {
+    hipLaunchKernelGGL(inc_bn_finalize_kernel, dim3((unsigned)ceil_div(w.F, INC_FIN_CG)), dim3(256), 0, st, stats, rows, 1.0 / (double)M,
+                       params + r.gamma, params + r.beta, state + r.mm, state + r.mv, KWS_BN_EPS,
+                       (float)(1.0 - (double)KWS_BN_MOMENTUM), bn, w);
+    KWS_LAUNCH_CHECK("inc_bn_finalize_kernel");
+  } else {
+    hipLaunchKernelGGL(inc_bn_infer_kernel, dim3((unsigned)ceil_div(w.F, 256)), dim3(256), 0, st, params + r.gamma, params + r.beta,
+                       state + r.mm, state + r.mv, KWS_BN_EPS, bn, w);
+    KWS_LAUNCH_CHECK("inc_bn_infer_kernel");
+  }
+  return KWS_OK;
+}
+
+int inc_bn_bwd_rows(int64_t M) { return (int)ceil_div64(M, INC_BWD_ROWS); }
+
+// dA (gradient wrt the activated window) -> dy in place; dgamma / dbeta into the flat gradient buffer
+int inc_bn_bwd(float* dA, const float* y, const float* bn, const float* add, int64_t M, IncWin w, float* part, float* coef, float* grads,
+               const BnRef& r, hipStream_t st) {
+  const int rows = inc_bn_bwd_rows(M);
+  KwsProfScope prof("inc_bn_bwd", 0.0, 4.0 * 5.0 * (double)M * w.F, st);
+  hipLaunchKernelGGL(inc_bn_bwd_part_kernel, dim3((unsigned)rows, (unsigned)ceil_div(w.F, 256)), dim3(256), 0, st, dA, y, bn, add, M, w,
+                     part);
+  KWS_LAUNCH_CHECK("inc_bn_bwd_part_kernel");
+  hipLaunchKernelGGL(inc_bn_bwd_fin_kernel, dim3((unsigned)ceil_div(w.F, INC_FIN_CG)), dim3(256), 0, st, part, rows, 1.0 / (double)M, w.F,
+                     grads + r.gamma, grads + r.beta, coef);
+  KWS_LAUNCH_CHECK("inc_bn_bwd_fin_kernel");
+  const int64_t n_el = M * w.F;
+  hipLaunchKernelGGL(inc_bn_bwd_apply_kernel, dim3((unsigned)ceil_div64(n_el, 256)), dim3(256), 0, st, dA, y, bn, coef, n_el, w);
+  KWS_LAUNCH_CHECK("inc_bn_bwd_apply_kernel");
+  return KWS_OK;
+}
+
+// ---- the program --------------------------------------------------------------------------------------------------------------
+struct IncTensor {
+  int L, C;
+  bool raw;    // convolution outputs before their BatchNorm: read through the table [4][C]
+  bool gadd;   // a SAME max pool reads this raw tensor: its gated gradient arrives in a buffer of its own
+};
+
+enum { OP_GCONV, OP_CONV, OP_MAXV, OP_MAXS, OP_AVG };
+
+struct IncOp {
+  int kind;
+  int in, out;           // tensor ids
+  int y0, F;             // the column window of `out` this operation writes (pools: F = the input's channels)
+  int k, dil, pad_l;     // convolutions
+  int64_t w;             // kernel (params)
+  BnRef bn;
+  int prod;              // max pools: the convolution operation whose output they pool (-1: a block's input)
+  bool pooled;           // convolutions: a max pool follows and does the gate and the BatchNorm sums
+  bool acc, need_dx;     // backward: adds to the input's gradient (another consumer wrote it first) / has one to write
+};
+
+struct IncLayout {
+  int64_t total = 0;
+  std::vector<int64_t> buf, bn, grad, gadd;
+  int64_t stats = 0, part = 0, coef = 0, wws = 0, ident = 0, fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+};
+
+struct IncProgram : NetProgram {
+  std::vector<IncTensor> tensors;   // 0 = the network input [800, 20]
+  std::vector<IncOp> ops;
+  std::vector<int> convs;           // operation of Conv1D i (Keras creation order; BatchNormalization i + 1 is behind it)
+  int64_t dk = 0, db = 0;
+  int D = 0, NC = 0, top = 0;
+
+  void layout(int B, bool training, IncLayout* lo) const;
+  kws_gconv_t gdesc(const IncOp& o, int B) const;
+  kws_conv1d_t cdesc(const IncOp& o, int B) const;
+  int forward(const IncLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws, hipStream_t st) const;
+  kws_flat_tail_args tail_args(const IncLayout& lo, const float* params, float* ws, int B, float* probs) const;
+
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
+};
+
+kws_gconv_t IncProgram::gdesc(const IncOp& o, int B) const {
+  kws_gconv_t d;
+  memset(&d, 0, sizeof(d));
+  d.B = B; d.L = tensors[o.in].L; d.C = tensors[o.in].C; d.Lout = tensors[o.out].L; d.k = o.k; d.stride = 1;
+  d.g = 1; d.gs = d.C; d.Ng = o.F;
+  return d;
+}
+
+kws_conv1d_t IncProgram::cdesc(const IncOp& o, int B) const {
+  kws_conv1d_t d;
+  d.B = B; d.L = tensors[o.in].L; d.Lout = tensors[o.out].L; d.k = o.k; d.dil = o.dil; d.pad_l = o.pad_l;
+  d.Cx = tensors[o.in].C; d.x0 = 0; d.Cin = d.Cx;
+  d.Cy = tensors[o.out].C; d.y0 = o.y0; d.F = o.F;
+  return d;
+}
+
+void IncProgram::layout(int B, bool training, IncLayout* lo) const {
+  Bump bp;
+  const int nt = (int)tensors.size();
+  lo->buf.assign(nt, 0);
+  lo->bn.assign(nt, 0);
+  lo->grad.assign(nt, 0);
+  lo->gadd.assign(nt, 0);
+  for (int i = 1; i < nt; ++i) {
+    const int64_t n = (int64_t)B * tensors[i].L * tensors[i].C;
+    lo->buf[i] = bp.take(n);
+    if (tensors[i].raw) lo->bn[i] = bp.take((int64_t)4 * tensors[i].C);
+    if (training) {
+      lo->grad[i] = bp.take(n);
+      if (tensors[i].gadd) lo->gadd[i] = bp.take(n);
+    }
+  }
+  int64_t max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64;
+  for (const IncOp& o : ops) {
+    const IncTensor& ti = tensors[o.in];
+    if (o.kind == OP_GCONV || o.kind == OP_CONV) {
+      const int64_t M = (int64_t)B * tensors[o.out].L;
+      max_stats = std::max(max_stats, ceil_div64(M, 128) * 2 * o.F);
+      max_part = std::max(max_part, (int64_t)inc_bn_bwd_rows(M) * 2 * o.F);
+      max_coef = std::max(max_coef, (int64_t)2 * o.F);
+      if (o.kind == OP_GCONV) {
+        const kws_gconv_t d = gdesc(o, B);
+        max_wws = std::max(max_wws, kws_gconv_wgrad_workspace_floats(&d));
+      } else {
+        const kws_conv1d_t d = cdesc(o, B);
+        max_wws = std::max(max_wws, kws_conv1d_wgrad_workspace_floats(&d));
+      }
+    } else if (o.kind == OP_MAXV) {
+      max_part = std::max(max_part, kws_pool3s2_bwd_part_floats(B, ti.L, ti.C));
+    } else if (o.kind == OP_MAXS) {
+      max_part = std::max(max_part, kws_pool3s2_same_bwd_part_floats(B, ti.L, ti.C));
+    }
+  }
+  lo->stats = bp.take(max_stats);
+  lo->ident = bp.take((int64_t)4 * tensors[top].C);
+  if (training) {
+    lo->part = bp.take(max_part);
+    lo->coef = bp.take(max_coef);
+    lo->wws = bp.take(max_wws);
+    lo->fd = bp.take((int64_t)B * D);
+    lo->dl = bp.take((int64_t)B * NC);
+    lo->per_loss = bp.take(B);
+    lo->per_correct = bp.take(B);
+    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * D * NC);
+  }
+  lo->total = bp.cur * 4;
+}
+
+int IncProgram::forward(const IncLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+                        hipStream_t st) const {
+  for (const IncOp& o : ops) {
+    const IncTensor& ti = tensors[o.in];
+    const IncTensor& to = tensors[o.out];
+    const float* in = o.in == 0 ? x : ws + lo.buf[o.in];
+    const float* bn_in = ti.raw ? ws + lo.bn[o.in] : nullptr;
+    float* out = ws + lo.buf[o.out];
+    const int64_t M = (int64_t)B * to.L;
+    switch (o.kind) {
+      case OP_GCONV: {
+        const kws_gconv_t d = gdesc(o, B);
+        KWS_TRY(kws_gconv_fwd_f32(in, bn_in, d.C, params + o.w, out, training ? ws + lo.stats : nullptr, &d, st));
+        KWS_TRY(inc_bn_table(ws + lo.stats, kws_gconv_stats_rows(&d), M, params, state, o.bn, training, ws + lo.bn[o.out],
+                             IncWin{to.C, o.y0, o.F}, st));
+        break;
+      }
+      case OP_CONV: {
+        const kws_conv1d_t d = cdesc(o, B);
+        KWS_TRY(kws_conv1d_fwd_f32(in, bn_in, params + o.w, out, training ? ws + lo.stats : nullptr, &d, st));
+        KWS_TRY(inc_bn_table(ws + lo.stats, kws_conv1d_stats_rows(&d), M, params, state, o.bn, training, ws + lo.bn[o.out],
+                             IncWin{to.C, o.y0, o.F}, st));
+        break;
+      }
+      case OP_MAXV:
+        KWS_TRY(kws_pool3s2_fwd_f32(in, bn_in, out, B, ti.L, ti.C, st));
+        break;
+      case OP_MAXS:
+        KWS_TRY(kws_pool3s2_same_fwd_pitch(in, bn_in, out + o.y0, to.C, B, ti.L, ti.C, st));
+        break;
+      case OP_AVG:
+        KWS_TRY(kws_avgpool3_same_fwd_f32(in, bn_in, out, B, ti.L, ti.C, st));
+        break;
+    }
+  }
+  hipLaunchKernelGGL(inc_identity_table_kernel, dim3((unsigned)ceil_div(tensors[top].C, 256)), dim3(256), 0, st, ws + lo.ident,
+                     tensors[top].C);
+  KWS_LAUNCH_CHECK("inc_identity_table_kernel");
+  return KWS_OK;
+}
+
+kws_flat_tail_args IncProgram::tail_args(const IncLayout& lo, const float* params, float* ws, int B, float* probs) const {
+  kws_flat_tail_args t;
+  memset(&t, 0, sizeof(t));
+  t.y = ws + lo.buf[top]; t.bn = ws + lo.ident; t.Ng = tensors[top].C;
+  t.Wd = params + dk; t.bd = params + db;
+  t.probs = probs;
+  t.B = B; t.D = D; t.F = tensors[top].C; t.NC = NC;
+  t.keep_prob = INC_DROP_KEEP;
+  t.layer_id = 1;
+  return t;
+}
+
+// ---- the table builder ---------------------------------------------------------------------------------------------------------
+struct IncBuilder {
+  IncProgram* p;
+  KerasNames kn;
+
+  int tensor(int L, int C, bool raw) {
+    p->tensors.push_back(IncTensor{L, C, raw, false});
+    return (int)p->tensors.size() - 1;
+  }
+  // Conv1D(F, k, dilation_rate=dil, padding, use_bias=False, l2 1e-5) + BatchNormalization (+ relu6 on load) from tensor `in`
+  // into the columns [y0, y0 + F) of `out` (-1: a tensor of its own)
+  int conv(int kind, int in, int out, int y0, int F, int k, int dil, bool same, bool pooled = false) {
+    const IncTensor ti = p->tensors[in];
+    const int span = dil * (k - 1);
+    const int Lout = same ? ti.L : ti.L - span;
+    if (out < 0) out = tensor(Lout, F, true);
+    IncOp o;
+    memset(&o, 0, sizeof(o));
+    o.kind = kind; o.in = in; o.out = out; o.y0 = y0; o.F = F; o.k = k; o.dil = dil;
+    o.pad_l = same ? span / 2 : 0;   // TF SAME at stride 1: dil * (k - 1) zeros in all, the smaller half in front
+    o.w = kn.conv(k, ti.C, F, KWS_L2_COEF);
+    o.bn = kn.bn(F);
+    o.prod = -1;
+    o.pooled = pooled;
+    p->convs.push_back((int)p->ops.size());
+    p->ops.push_back(o);
+    return out;
+  }
+  // MaxPool1D(3, 2, 'valid' / 'same') of tensor `in` into the columns from y0 of `out` (-1: a tensor of its own)
+  int maxpool(int kind, int in, int out, int y0, int prod) {
+    const IncTensor ti = p->tensors[in];
+    if (out < 0) out = tensor(kind == OP_MAXV ? kws_pool3s2_out_len(ti.L) : kws_pool3s2_same_out_len(ti.L), ti.C, false);
+    IncOp o;
+    memset(&o, 0, sizeof(o));
+    o.kind = kind; o.in = in; o.out = out; o.y0 = y0; o.F = ti.C; o.prod = prod;
+    if (prod < 0) p->tensors[in].gadd = true;
+    p->ops.push_back(o);
+    return out;
+  }
+  int last_conv() const { return p->convs.back(); }
+
+  int inception_block(int x, int dil) {
+    const int L = p->tensors[x].L, b = INC_BASE;
+    const int J = tensor(L, 2 * b + 2 * b + 3 * b + b, true);
+    conv(OP_CONV, x, J, 0, 2 * b, 1, 1, true);                       // branch1x1
+    int h = conv(OP_CONV, x, -1, 0, 3 * b / 2, 1, 1, true);          // branch5x5: 1x1 -> 3 taps, dilation 2 (always)
+    conv(OP_CONV, h, J, 2 * b, 2 * b, 3, 2, true);
+    h = conv(OP_CONV, x, -1, 0, 2 * b, 1, 1, true);                  // branch3x3dbl
+    h = conv(OP_CONV, h, -1, 0, 3 * b, 3, dil, true);
+    conv(OP_CONV, h, J, 4 * b, 3 * b, 3, dil, true);
+    const int z = tensor(L, p->tensors[x].C, false);                 // branch_pool
+    IncOp o;
+    memset(&o, 0, sizeof(o));
+    o.kind = OP_AVG; o.in = x; o.out = z; o.F = p->tensors[x].C; o.prod = -1;
+    p->ops.push_back(o);
+    conv(OP_CONV, z, J, 7 * b, b, 1, 1, true);
+    return J;
+  }
+  int reduce_block(int x) {
+    const IncTensor tx = p->tensors[x];
+    const int b = INC_BASE, Lp = kws_pool3s2_same_out_len(tx.L);
+    const int J = tensor(Lp, 6 * b + 3 * b / 2 + tx.C, false);
+    int y = conv(OP_CONV, x, -1, 0, 6 * b, 3, 1, true, true);        // branch3x3
+    maxpool(OP_MAXS, y, J, 0, last_conv());
+    int h = conv(OP_CONV, x, -1, 0, b, 1, 1, true);                  // branch3x3dbl
+    h = conv(OP_CONV, h, -1, 0, 3 * b / 2, 3, 1, true);
+    y = conv(OP_CONV, h, -1, 0, 3 * b / 2, 3, 1, true, true);
+    maxpool(OP_MAXS, y, J, 6 * b, last_conv());
+    maxpool(OP_MAXS, x, J, 6 * b + 3 * b / 2, -1);                   // branch_pool
+    return J;
+  }
+};
+
+}  // namespace
+
+int inc_build(kws_net* n) {
+  const kws_net_config_t& c = n->cfg;
+  IncProgram* p = new IncProgram();
+  n->program.reset(p);
+  KWS_REQUIRE(c.input_size == 16000, "net: inception_d1 input_size %d (the reference reshapes 16000 samples)", c.input_size);
+  p->NC = c.num_classes;
+  IncBuilder b{p, KerasNames{n}};
+  int x = b.tensor(800, 20, false);   // Reshape([800, 20])
+  x = b.conv(OP_GCONV, x, -1, 0, 32, 1, 1, false);
+  const int widths[3] = {64, 128, 256};
+  for (int i = 0; i < 3; ++i) {       // _reduce_conv (stride 1; its strides argument goes to the pool only), _context_conv
+    x = b.conv(OP_GCONV, x, -1, 0, widths[i], 3, 1, false, true);
+    x = b.maxpool(OP_MAXV, x, -1, 0, b.last_conv());
+    x = b.conv(OP_GCONV, x, -1, 0, widths[i], 3, 1, false);
+  }
+  const int dils[4][2] = {{2, 2}, {2, 1}, {1, 1}, {1, 1}};
+  for (int s = 0; s < 4; ++s) {
+    x = b.inception_block(x, dils[s][0]);
+    x = b.inception_block(x, dils[s][1]);
+    KWS_REQUIRE(p->tensors[x].raw, "net: a reduce block pools a raw tensor");
+    x = b.reduce_block(x);
+  }
+  p->top = x;
+  const IncTensor& top = p->tensors[x];
+  KWS_REQUIRE(top.L == 6 && top.C == 496, "net: inception_d1 ends with [%d, %d], the head convolves [6, 496]", top.L, top.C);
+  p->D = top.L * top.C;
+  p->dk = b.kn.conv(top.L, top.C, p->NC, 0.f);   // [6, 496, NC] = the Dense kernel [2976, NC] over the t-major flatten
+  p->db = kws_net_add_tensor(n, "conv1d_" + std::to_string(b.kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  // backward plan: the consumers of a tensor write its gradient in the reverse of the forward order; the first overwrites
+  std::vector<char> written(p->tensors.size(), 0);
+  for (int i = (int)p->ops.size() - 1; i >= 0; --i) {
+    IncOp& o = p->ops[i];
+    o.need_dx = o.in != 0;
+    if (!o.need_dx || (o.kind == OP_MAXS && o.prod < 0)) continue;   // (that pool's gradient goes to the tensor's second buffer)
+    o.acc = written[o.in] != 0;
+    written[o.in] = 1;
+    KWS_REQUIRE(!o.acc || o.kind == OP_CONV || o.kind == OP_AVG, "net: operation %d cannot accumulate", i);
+  }
+  for (size_t t = 1; t < p->tensors.size(); ++t)
+    KWS_REQUIRE(written[t] || (int)t == p->top, "net: tensor %d has no consumer", (int)t);
+  return KWS_OK;
+}
+
+namespace {
+
+int64_t IncProgram::workspace_bytes(int B, int training) const {
+  IncLayout lo;
+  layout(B, training != 0, &lo);
+  return lo.total;
+}
+
+int IncProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
+  IncLayout lo;
+  layout(B, training != 0, &lo);
+  KWS_REQUIRE(what == 0 || what == 2 || what == 3, "net_debug_view: unknown view %d", what);
+  KWS_REQUIRE(index >= 0 && index < (int)convs.size(), "net_debug_view: Conv1D index %d", index);
+  const IncOp& o = ops[convs[index]];
+  const IncTensor& t = tensors[o.out];
+  if (what == 0) {          // raw output of Conv1D `index`: a column window, from its first to its last element
+    *offset_floats = lo.buf[o.out] + o.y0;
+    *count = ((int64_t)B * t.L - 1) * t.C + o.F;
+  } else if (what == 2) {   // table of batch_normalization_{index+1}: four rows one pitch apart
+    *offset_floats = lo.bn[o.out] + o.y0;
+    *count = (int64_t)3 * t.C + o.F;
+  } else {                  // geometry: row pitch, filters
+    *offset_floats = t.C;
+    *count = o.F;
+  }
+  return KWS_OK;
+}
+
+int IncProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                        hipStream_t st) const {
+  IncLayout lo;
+  layout(B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  KWS_TRY(forward(lo, params, const_cast<float*>(state), x, B, false, ws, st));
+  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
+  return kws_flat_tail_launch(&t, 0, st);
+}
+
+int IncProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                      float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                      hipStream_t st) const {
+  IncLayout lo;
+  layout(B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  KWS_TRY(forward(lo, params, state, x, B, true, ws, st));
+  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
+  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.grad[top], ws + lo.per_loss, ws + lo.per_correct, seed, step,
+                              loss_batch, row_offset, metrics, st));
+  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + dk, grads + db, B, D, NC, ws + lo.swg, st));
+  float* part = ws + lo.part;
+  float* coef = ws + lo.coef;
+  for (int i = (int)ops.size() - 1; i >= 0; --i) {
+    const IncOp& o = ops[i];
+    const IncTensor& ti = tensors[o.in];
+    const IncTensor& to = tensors[o.out];
+    const float* in = o.in == 0 ? x : ws + lo.buf[o.in];
+    const float* bn_in = ti.raw ? ws + lo.bn[o.in] : nullptr;
+    float* d_in = o.need_dx ? ws + lo.grad[o.in] : nullptr;
+    float* d_out = ws + lo.grad[o.out];
+    const int64_t M = (int64_t)B * to.L;
+    switch (o.kind) {
+      case OP_GCONV:
+      case OP_CONV: {
+        // d_out's window: the gradient wrt the activated output, or (pooled) dy already
+        if (!o.pooled)
+          KWS_TRY(inc_bn_bwd(d_out, ws + lo.buf[o.out], ws + lo.bn[o.out], to.gadd ? ws + lo.gadd[o.out] : nullptr, M,
+                             IncWin{to.C, o.y0, o.F}, part, coef, grads, o.bn, st));
+        if (o.kind == OP_GCONV) {
+          const kws_gconv_t d = gdesc(o, B);
+          KWS_TRY(kws_gconv_wgrad_f32(in, bn_in, d.C, d_out, grads + o.w, ws + lo.wws, &d, st));
+          if (o.need_dx) KWS_TRY(kws_gconv_dgrad_f32(d_out, params + o.w, d_in, &d, st));
+        } else {
+          const kws_conv1d_t d = cdesc(o, B);
+          KWS_TRY(kws_conv1d_wgrad_f32(in, bn_in, d_out, grads + o.w, ws + lo.wws, &d, st));
+          if (o.need_dx) KWS_TRY(kws_conv1d_dgrad_f32(d_out, params + o.w, d_in, o.acc ? 1 : 0, &d, st));
+        }
+        break;
+      }
+      case OP_MAXV:
+      case OP_MAXS: {
+        // route the pooled gradient to the winners and gate it; a pooled convolution's BatchNorm backward ends here
+        float* g = o.prod >= 0 ? d_in : ws + lo.gadd[o.in];
+        int rows;
+        if (o.kind == OP_MAXV) {
+          KWS_TRY(kws_pool3s2_bwd_f32(d_out, in, bn_in, g, part, B, ti.L, ti.C, st));
+          rows = kws_pool3s2_bwd_part_rows(B, ti.L, ti.C);
+        } else {
+          KWS_TRY(kws_pool3s2_same_bwd_pitch(d_out + o.y0, to.C, in, bn_in, g, part, B, ti.L, ti.C, st));
+          rows = kws_pool3s2_same_bwd_part_rows(B, ti.L, ti.C);
+        }
+        if (o.prod >= 0) {
+          const BnRef& r = ops[o.prod].bn;
+          KWS_TRY(kws_gbn_bwd_finish(g, in, bn_in, (int64_t)B * ti.L, 1, ti.C, part, rows, coef, grads + r.gamma, 0, r.beta - r.gamma, st));
+        }
+        break;
+      }
+      case OP_AVG:
+        KWS_TRY(kws_avgpool3_same_bwd_f32(d_out, d_in, o.acc ? 1 : 0, B, ti.L, ti.C, st));
+        break;
+    }
+  }
+  return KWS_OK;
+}
+
+}  // namespace

@@ -7,6 +7,7 @@
 //   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_mts.hip      conv_1d_multi_time_sliced
+//   net_inception.hip  inception_d1
 // Not part of the public C ABI.
 #pragma once
 #include <string.h>
@@ -87,6 +88,7 @@ int xception_build(kws_net* n);
 int gc_build(kws_net* n);        // net_grouped.hip
 int dk_build(kws_net* n);        // net_dwk.hip
 int mt_build(kws_net* n);        // net_mts.hip
+int inc_build(kws_net* n);       // net_inception.hip
 
 // ---- pieces the programs share (net.hip) -------------------------------------------------------------------------------
 // KWS_E_WORKSPACE with its message when the caller's workspace is too small; who = "net_predict" / "net_train_fwd_bwd"

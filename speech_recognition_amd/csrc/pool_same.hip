@@ -36,7 +36,7 @@ __device__ __forceinline__ float ps_max3(float a, float b, float c) { return fma
 
 __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_fwd_kernel(const float* __restrict__ y, const float* __restrict__ bn,
                                                                       float* __restrict__ z, int64_t n_units, int L, int Lp, int C,
-                                                                      int nchunks, int pl) {
+                                                                      int nchunks, int pl, int zp) {
   const int64_t i = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x;
   if (i >= n_units) return;
   const int C4 = C >> 2;
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_fwd_kernel(const floa
   const int t0 = (int)(unit - b * nchunks) * PS_FWD_TT;
   const float4 sc = ps_ld4(bn + c), sh = ps_ld4(bn + C + c);
   const float* yb = y + b * L * (int64_t)C + c;
-  float* zb = z + b * Lp * (int64_t)C + c;
+  float* zb = z + b * Lp * (int64_t)zp + c;   // zp: row pitch of z (C for the public entry point)
   float4 a0 = ps_act(yb, 2 * t0 - pl, L, C, sc, sh);
 #pragma unroll
   for (int k = 0; k < PS_FWD_TT; ++k) {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_fwd_kernel(const floa
     if (t >= Lp) break;
     const int r = 2 * t - pl;   // rows r, r + 1, r + 2; r + 1 <= L - 1 for every t < Lp
     const float4 a1 = ps_act(yb, r + 1, L, C, sc, sh), a2 = ps_act(yb, r + 2, L, C, sc, sh);
-    *reinterpret_cast<float4*>(zb + (int64_t)t * C) =
+    *reinterpret_cast<float4*>(zb + (int64_t)t * zp) =
         make_float4(ps_max3(a0.x, a1.x, a2.x), ps_max3(a0.y, a1.y, a2.y), ps_max3(a0.z, a1.z, a2.z), ps_max3(a0.w, a1.w, a2.w));
     a0 = a2;
   }
@@ -77,7 +77,7 @@ template <int PL>
 __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ y,
                                                                       const float* __restrict__ bn, float* __restrict__ g,
                                                                       float* __restrict__ part, int64_t units, int L, int Lp, int C,
-                                                                      int nchunks, int R) {
+                                                                      int nchunks, int R, int zp) {
   __shared__ float red[2][PS_THREADS * 4];
   const int C4 = C >> 2;
   const int tid = threadIdx.x;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_bwd_kernel(const floa
     const int u0 = (int)(unit - b * nchunks) * PS_BWD_TT;
     const float4 sc = ps_ld4(bn + c), sh = ps_ld4(bn + C + c), mean = ps_ld4(bn + 2 * C + c), rstd = ps_ld4(bn + 3 * C + c);
     const float* yb = y + b * L * (int64_t)C + c;
-    const float* dzb = dz + b * Lp * (int64_t)C + c;
+    const float* dzb = dz + b * Lp * (int64_t)zp + c;   // zp: row pitch of dz
     float4 acc[PS_BWD_TT];
 #pragma unroll
     for (int i = 0; i < PS_BWD_TT; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(PS_THREADS) void pool3s2_same_bwd_kernel(const floa
       const int r0 = 2 * t - PL;
       if (!have0) a0 = ps_act(yb, r0, L, C, sc, sh);
       const float4 a1 = ps_act(yb, r0 + 1, L, C, sc, sh), a2 = ps_act(yb, r0 + 2, L, C, sc, sh);
-      const float4 d = ps_ld4(dzb + (int64_t)t * C);
+      const float4 d = ps_ld4(dzb + (int64_t)t * zp);
 #define KWS_POOL_SAME_ROUTE(f)                                                                          \
   do {                                                                                                  \
     const int j = ps_first_max3(a0.f, a1.f, a2.f);                                                      \
@@ -168,21 +168,47 @@ PsGeom ps_geom(int B, int L, int C) {
 
 }  // namespace
 
+// ---- internal launchers (net_inception.hip): the pooled tensor z / its gradient dz is a column window of a wider tensor ----
+// zp = row pitch of z / dz in floats (a multiple of 4, >= C; the pointer names the window's first column, 16-byte aligned).
+// With zp = C these are the public entry points, bit for bit.
+int kws_pool3s2_same_fwd_pitch(const float* y, const float* bn, float* z, int zp, int B, int L, int C, hipStream_t stream) {
+  KWS_REQUIRE(y && bn && z && ps_ok(B, L, C) && zp >= C && zp % 4 == 0, "pool3s2_same_fwd: bad arguments (B=%d L=%d C=%d pitch=%d)", B,
+              L, C, zp);
+  const int Lp = kws_pool3s2_same_out_len(L);
+  const int nchunks = ceil_div(Lp, PS_FWD_TT);
+  const int64_t n_units = (int64_t)B * nchunks * (C / 4);
+  KWS_REQUIRE(ceil_div64(n_units, PS_THREADS) < (1ll << 31), "pool3s2_same_fwd: tensor too large");
+  KwsProfScope prof("pool3s2_same_fwd", 8.0 * B * L * C, 4.0 * ((double)B * L * C + (double)B * Lp * C), stream);
+  hipLaunchKernelGGL(pool3s2_same_fwd_kernel, dim3((unsigned)ceil_div64(n_units, PS_THREADS)), dim3(PS_THREADS), 0, stream, y, bn, z,
+                     n_units, L, Lp, C, nchunks, L & 1, zp);
+  KWS_LAUNCH_CHECK("pool3s2_same_fwd_kernel");
+  return KWS_OK;
+}
+
+int kws_pool3s2_same_bwd_pitch(const float* dz, int zp, const float* y, const float* bn, float* g, float* part, int B, int L, int C,
+                               hipStream_t stream) {
+  KWS_REQUIRE(dz && y && bn && g && part && ps_ok(B, L, C) && zp >= C && zp % 4 == 0,
+              "pool3s2_same_bwd: bad arguments (B=%d L=%d C=%d pitch=%d)", B, L, C, zp);
+  const PsGeom ge = ps_geom(B, L, C);
+  KWS_REQUIRE(ge.grid < (1ll << 31), "pool3s2_same_bwd: tensor too large");
+  const int Lp = kws_pool3s2_same_out_len(L);
+  KwsProfScope prof("pool3s2_same_bwd", 14.0 * B * L * C, 4.0 * (2.0 * B * L * C + (double)B * Lp * C), stream);
+  if (L & 1)
+    hipLaunchKernelGGL(pool3s2_same_bwd_kernel<1>, dim3((unsigned)ge.grid), dim3((unsigned)ge.block), 0, stream, dz, y, bn, g, part,
+                       ge.units, L, Lp, C, ge.nchunks, ge.R, zp);
+  else
+    hipLaunchKernelGGL(pool3s2_same_bwd_kernel<0>, dim3((unsigned)ge.grid), dim3((unsigned)ge.block), 0, stream, dz, y, bn, g, part,
+                       ge.units, L, Lp, C, ge.nchunks, ge.R, zp);
+  KWS_LAUNCH_CHECK("pool3s2_same_bwd_kernel");
+  return KWS_OK;
+}
+
 extern "C" {
 
 int kws_pool3s2_same_out_len(int L) { return L >= 1 ? (L + 1) / 2 : 0; }
 
 int kws_pool3s2_same_fwd_f32(const float* y, const float* bn, float* z, int B, int L, int C, void* stream) {
-  KWS_REQUIRE(y && bn && z && ps_ok(B, L, C), "pool3s2_same_fwd: bad arguments (B=%d L=%d C=%d)", B, L, C);
-  const int Lp = kws_pool3s2_same_out_len(L);
-  const int nchunks = ceil_div(Lp, PS_FWD_TT);
-  const int64_t n_units = (int64_t)B * nchunks * (C / 4);
-  KWS_REQUIRE(ceil_div64(n_units, PS_THREADS) < (1ll << 31), "pool3s2_same_fwd: tensor too large");
-  KwsProfScope prof("pool3s2_same_fwd", 8.0 * B * L * C, 4.0 * ((double)B * L * C + (double)B * Lp * C), (hipStream_t)stream);
-  hipLaunchKernelGGL(pool3s2_same_fwd_kernel, dim3((unsigned)ceil_div64(n_units, PS_THREADS)), dim3(PS_THREADS), 0,
-                     (hipStream_t)stream, y, bn, z, n_units, L, Lp, C, nchunks, L & 1);
-  KWS_LAUNCH_CHECK("pool3s2_same_fwd_kernel");
-  return KWS_OK;
+  return kws_pool3s2_same_fwd_pitch(y, bn, z, C, B, L, C, (hipStream_t)stream);
 }
 
 int kws_pool3s2_same_bwd_part_rows(int B, int L, int C) { return ps_ok(B, L, C) ? (int)ps_geom(B, L, C).grid : 0; }
@@ -191,19 +217,7 @@ int64_t kws_pool3s2_same_bwd_part_floats(int B, int L, int C) { return (int64_t)
 
 int kws_pool3s2_same_bwd_f32(const float* dz, const float* y, const float* bn, float* g, float* part, int B, int L, int C,
                              void* stream) {
-  KWS_REQUIRE(dz && y && bn && g && part && ps_ok(B, L, C), "pool3s2_same_bwd: bad arguments (B=%d L=%d C=%d)", B, L, C);
-  const PsGeom ge = ps_geom(B, L, C);
-  KWS_REQUIRE(ge.grid < (1ll << 31), "pool3s2_same_bwd: tensor too large");
-  const int Lp = kws_pool3s2_same_out_len(L);
-  KwsProfScope prof("pool3s2_same_bwd", 14.0 * B * L * C, 4.0 * (2.0 * B * L * C + (double)B * Lp * C), (hipStream_t)stream);
-  if (L & 1)
-    hipLaunchKernelGGL(pool3s2_same_bwd_kernel<1>, dim3((unsigned)ge.grid), dim3((unsigned)ge.block), 0, (hipStream_t)stream, dz, y,
-                       bn, g, part, ge.units, L, Lp, C, ge.nchunks, ge.R);
-  else
-    hipLaunchKernelGGL(pool3s2_same_bwd_kernel<0>, dim3((unsigned)ge.grid), dim3((unsigned)ge.block), 0, (hipStream_t)stream, dz, y,
-                       bn, g, part, ge.units, L, Lp, C, ge.nchunks, ge.R);
-  KWS_LAUNCH_CHECK("pool3s2_same_bwd_kernel");
-  return KWS_OK;
+  return kws_pool3s2_same_bwd_pitch(dz, C, y, bn, g, part, B, L, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

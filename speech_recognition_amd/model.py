@@ -8,7 +8,7 @@ from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
                'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
-               'xception_with_attention')
+               'xception_with_attention', 'inception_d1')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -204,6 +204,17 @@ def conv_1d_simple_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, Adam(lr=1e-3), name='conv_1d_time_stacked', loss='cce')
 
 
+def inception_d1_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:312-406 (conv_inception_d1_model): raw waveform as [800, 20] -> Conv1D(32, 1) -> three stride-1
+    reduce (MaxPool1D(3, 2) behind) / context pairs (64, 128, 256; k 3 VALID) -> eight inception blocks (1x1 | 1x1 -> k3 dil 2 |
+    1x1 -> k3 -> k3 | AveragePooling1D(3, 1, 'same') -> 1x1, concatenated to 256 channels) with a reduce block (496 channels,
+    half the steps) behind every second one -> [6, 496] -> Dropout(.2) -> Conv1D(num_classes, 6, softmax); every convolution
+    BatchNormalization + relu6, l2 1e-5; Adam(1e-3), categorical CE."""
+    _raw_16000('inception_d1', input_size)
+    net = DeviceNet(_lib.KWS_NET_INCEPTION_D1, num_classes, input_size=16000)
+    return Model(net, Adam(lr=1e-3), name='inception_d1', loss='cce')
+
+
 def xception_with_attention_model(input_size=16000, num_classes=11, filter_mult=1):
     """reference model.py:911-983: raw waveform -> time-slice stack -> Conv1D(64, 3, strides=2) -> eleven residual blocks with 3-wide
     max-pool joins (128, 256, 8 x 256, 384) ending at [50, 384] -> attention gate (a 5-tap depthwise block of one filter, softmax over
@@ -242,6 +253,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_simple_model(input_size, num_classes)
     if model_type == 'xception_with_attention':
         return xception_with_attention_model(input_size, num_classes)
+    if model_type == 'inception_d1':
+        return inception_d1_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
             "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"

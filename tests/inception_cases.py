@@ -1,0 +1,54 @@
+"""Weights and batches shared by the inception_d1 tests (CPU float32-against-float64 run and GPU parity): the same nets and
+clips on both sides, so that the figures in test_inception_models_gpu.py's docstring are those of the GPU cases."""
+import numpy as np
+
+from inception_oracle import InceptionD1Net
+
+NC = 12
+TRAIN_BATCHES = (3, 16)
+PREDICT_BATCH = 5
+SEED, STEP = 77, 2
+
+
+def perturbed(dtype=np.float64, nc=NC, seed=5):
+    """About a third of the BatchNorm scales negative, shifts that make relu6(shift) != 0, moving statistics off their
+    initial values."""
+    ora = InceptionD1Net(num_classes=nc, dtype=dtype)
+    rng = np.random.RandomState(seed)
+    for k in ora.params:
+        if k.endswith('gamma'):
+            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
+            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
+        if k.endswith('beta'):
+            ora.params[k] = (0.3 + 0.2 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+        if k.endswith('bias'):
+            ora.params[k] = (0.05 * rng.randn(nc)).astype(np.float32)
+    for k in ora.state:
+        if k.endswith('moving_mean'):
+            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
+        else:
+            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
+    return ora
+
+
+def batch(B, nc=NC, seed=None):
+    rng = np.random.RandomState(B if seed is None else seed)
+    lab = rng.randint(0, nc, B)
+    t = np.arange(16000) / 16000.0
+    x = rng.randn(B, 16000) * 0.0774 + 0.05 * np.sin(2 * np.pi * 200.0 * (1 + lab)[:, None] * t[None, :])
+    return x.astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
+
+
+def grad_errors(g, ref):
+    """max |g - ref| over a tensor, relative to the reference tensor's maximum"""
+    return {k: np.abs(np.asarray(g[k], np.float64) - np.asarray(r, np.float64).reshape(np.shape(g[k]))).max() /
+            max(np.abs(r).max(), 1e-7) for k, r in ref.items()}
+
+
+def decisions_of(ora, cache):
+    """ReLU6 gates and pool winners of a cached oracle run, in the form loss_and_grads takes them."""
+    masks = {c['idx']: (cache[c['idx']]['pre'] > 0) & (cache[c['idx']]['pre'] <= 6) for c in ora.convs}
+    inds = {c['idx']: cache[c['idx']]['ind'] for c in ora.convs if c['pool']}
+    inds.update({'mixed%d' % r['id']: cache['mixed%d' % r['id']] for r in ora.blocks if r['kind'] == 'red'})
+    return masks, inds

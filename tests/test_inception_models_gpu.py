@@ -1,0 +1,291 @@
+"""GPU parity of the inception_d1 network program (KWS_NET_INCEPTION_D1, csrc/net_inception.hip) against the float64 oracle
+tests/inception_oracle.py - the method of test_stacked_models_gpu.py / test_mts_models_gpu.py: the device's ReLU6 gates and max-pool
+winners are read back (debug views 0, 2 and 3: every Conv1D's raw output is a column window of the tensor it was written into, its
+BatchNorm table the same columns of that tensor's table) and handed to the oracle's backward pass.  About a third of the BatchNorm
+scales is negative.
+
+Bars: the siblings', unchanged - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
+statistics atol 5e-6 / rtol 1e-5; class indices and the correct-count exact.  This net is 45 convolutions deep from the input to the
+head, each behind a BatchNorm that rescales its input's rounding error, so the oracle net was first run in float32 on the CPU (NumPy,
+its column sums in float64 as the device adds them; on the float64 run's gates and winners; tests/inception_cases.py holds the
+weights and batches of both sides; test_inception_cpu.py repeats the run) against its float64 self:
+  predict, batch 5:  probabilities 1.0e-6
+  train, batch 3:    probabilities 1.0e-5, loss 2.8e-6, worst gradient 5.9e-5 of its tensor's maximum (batch_normalization_79/gamma)
+  train, batch 16:   probabilities 1.9e-5, loss 4.9e-7, worst gradient 5.2e-5 (batch_normalization_67/gamma)
+Every figure is under half its bar.  Batch 10 was the first choice for the larger case; its float32 run gave probabilities 2.9e-5,
+over half the 5e-5 bar, so the case moved to batch 16 (the figure does not fall with the batch - it is the depth, not the 6 B rows
+of the last BatchNorms, that sets it - but 16 is a draw under the half-bar line; no bar is widened)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import adam_oracle as SO
+import inception_cases as cases
+from mts_oracle import pool_same_argmax
+from speech_recognition_amd import _lib
+from speech_recognition_amd.net import DeviceNet
+from stacked_oracle import pool_argmax
+
+pytestmark = pytest.mark.gpu
+
+NC = cases.NC
+
+
+def _pair():
+    ora = cases.perturbed()
+    net = DeviceNet(_lib.KWS_NET_INCEPTION_D1, NC, input_size=16000)
+    net.set_weights(dict(ora.params, **ora.state))
+    return ora, net
+
+
+def _view(net, B, what, index, training=True):
+    off, cnt = ctypes.c_int64(), ctypes.c_int64()
+    _lib.call("kws_net_debug_view", net.handle, B, int(training), what, index, ctypes.byref(off), ctypes.byref(cnt))
+    return off.value, cnt.value
+
+
+def _window(net, B, what, index, rows):
+    """Rows of a column window: `rows` rows of F floats, one pitch apart, from the window's first to its last element."""
+    pitch, F = _view(net, B, 3, index)
+    off, cnt = _view(net, B, what, index)
+    assert cnt == (rows - 1) * pitch + F
+    flat = np.zeros(rows * pitch, np.float32)
+    flat[:cnt] = net._ws[off:off + cnt].cpu().numpy()
+    return flat.reshape(rows, pitch)[:, :F]
+
+
+def _decisions(net, ora, B):
+    """The device's ReLU6 gates and pool winners, from its raw conv outputs and BN tables (float32 fused multiply-add)."""
+    masks, inds, act = {}, {}, {}
+    for c in ora.convs:
+        idx, F = c['idx'], c['F']
+        y = _window(net, B, 0, idx - 1, B * c['Lout']).reshape(B, c['Lout'], F).astype(np.float64)
+        bn = _window(net, B, 2, idx - 1, 4).astype(np.float64)
+        pre = (y * bn[0] + bn[1]).astype(np.float32)
+        masks[idx] = (pre > 0) & (pre <= 6)
+        act[idx] = np.clip(pre, 0, 6).astype(np.float64)
+        if c['pool'] == 'valid':
+            inds[idx] = pool_argmax(act[idx])
+        elif c['pool'] == 'same':
+            inds[idx] = pool_same_argmax(act[idx], c['Lout'] & 1)
+    for prev, rec in zip(ora.blocks, ora.blocks[1:]):
+        if rec['kind'] == 'red':     # the pool branch reads the joined output of the inception block before it
+            cs = prev['convs']
+            joined = np.concatenate([act[cs[i]['idx']] for i in (0, 2, 5, 6)], axis=2)
+            inds['mixed%d' % rec['id']] = pool_same_argmax(joined, rec['L'] & 1)
+    return masks, inds
+
+
+def _device_step(ora, net, B, batch_seed=None, seed=cases.SEED, step=cases.STEP, row_offset=0):
+    x, y = cases.batch(B, seed=batch_seed)
+    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=seed, step=step, row_offset=row_offset)
+    torch.cuda.synchronize()
+    masks, inds = _decisions(net, ora, B)
+    return dict(x=x, y=y, probs=probs.cpu().numpy(), metrics=net.metrics.cpu().numpy(), grads=net.grads_dict(), masks=masks, inds=inds,
+                weights=net.get_weights())
+
+
+@pytest.fixture(scope="module")
+def step3():
+    ora, net = _pair()
+    d = _device_step(ora, net, 3)
+    d['ora'] = ora
+    d['oracle'] = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
+                                     relu_masks=d['masks'], pool_ind=d['inds'])
+    return d
+
+
+def _check_step(B, d, ora, ref):
+    loss, p, grads, cache = ref
+    got, m = d['probs'], d['metrics']
+    errs = cases.grad_errors(d['grads'], grads)
+    worst = max(errs, key=errs.get)
+    print("train inception_d1 B=%d: probs %.3g (bar 5e-5), loss %.3g (bar 1e-4), worst gradient %s %.3g (bar 2e-4)" %
+          (B, np.abs(got - p).max(), abs(m[0] / B - loss), worst, errs[worst]))
+    assert np.abs(got - p).max() < 5e-5
+    assert np.array_equal(got.argmax(1), p.argmax(1))
+    assert abs(m[0] / B - loss) < 1e-4
+    assert m[1] == (p.argmax(1) == d['y'].argmax(1)).sum()
+    for k, err in errs.items():
+        assert err < 2e-4, (k, err)
+    w = d['weights']
+    for idx, (mean, var) in cache['batch_stats'].items():
+        for nm, batch in (('moving_mean', mean), ('moving_variance', var)):
+            old = ora.state['batch_normalization_%d/%s' % (idx, nm)].astype(np.float64)
+            np.testing.assert_allclose(w['batch_normalization_%d/%s' % (idx, nm)], old - (old - batch) * 0.01, atol=5e-6, rtol=1e-5)
+
+
+def test_tensor_table_matches_oracle():
+    ora, net = _pair()
+    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
+    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
+    assert net.count_params() == ora.count_params() == 2133900
+
+
+def test_predict_matches_oracle_and_rows_do_not_see_each_other():
+    ora, net = _pair()
+    x, _ = cases.batch(cases.PREDICT_BATCH, seed=1)
+    p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
+    ref = ora.forward(x.astype(np.float64), training=False)
+    print("predict inception_d1: max |p - oracle| = %.3g (bar 2e-5)" % np.abs(p - ref).max())
+    assert np.abs(p - ref).max() < 2e-5
+    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    for r in range(cases.PREDICT_BATCH):     # a predict at batch 1 agrees with the same row of the batch of 5
+        p1 = net.predict(torch.from_numpy(x[r:r + 1]).cuda()).cpu().numpy()
+        assert np.abs(p1[0] - p[r]).max() < 1e-6, r
+
+
+def test_train_fwd_bwd_matches_oracle_batch_3(step3):
+    _check_step(3, step3, step3['ora'], step3['oracle'])
+
+
+def test_train_fwd_bwd_matches_oracle_batch_16():
+    B = cases.TRAIN_BATCHES[1]
+    ora, net = _pair()
+    d = _device_step(ora, net, B)
+    ref = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
+                             relu_masks=d['masks'], pool_ind=d['inds'])
+    _check_step(B, d, ora, ref)
+
+
+@pytest.mark.parametrize("mutate", ['ignore_dilation', 'avg_count_include_pad'])
+def test_wrong_oracles_miss_the_gradient_bar(step3, mutate):
+    """Negative controls: against an oracle without the dilation, or one whose average pool counts the padding, the device's
+    gradients miss the 2e-4 bar (that they meet it against the right one is test_train_fwd_bwd_matches_oracle_batch_3)."""
+    ora = step3['ora']
+    bad = ora.loss_and_grads(step3['x'].astype(np.float64), step3['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
+                             relu_masks=step3['masks'], pool_ind=step3['inds'], mutate=mutate)[2]
+    worst = max(cases.grad_errors(step3['grads'], bad).values())
+    print("against the %s oracle: worst gradient %.3g" % (mutate, worst))
+    assert worst > 2e-4
+
+
+def test_train_step_is_bit_reproducible():
+    ora, net = _pair()
+    x, y = cases.batch(24, seed=3)
+    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    state0 = net.state.clone()
+    p1 = net.train_fwd_bwd(xd, yd, seed=1, step=0).clone()
+    g1, s1 = net.grads.clone(), net.state.clone()
+    net.state.copy_(state0)
+    p2 = net.train_fwd_bwd(xd, yd, seed=1, step=0)
+    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state) and torch.equal(p1, p2)
+
+
+def test_data_parallel_shard_uses_the_global_dropout_rows_and_loss_batch():
+    """row_offset indexes the dropout mask by the global row (the oracle's drop_offset); loss_batch divides the loss gradient by
+    the global batch (a shard of half the batch: every gradient halves - a power of two, exact but for underflow)."""
+    ora, net = _pair()
+    B, off = 4, 37
+    d = _device_step(ora, net, B, batch_seed=21, seed=5, step=3, row_offset=off)
+    _, p, grads, _ = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=5, step=3, drop_offset=off,
+                                        relu_masks=d['masks'], pool_ind=d['inds'])
+    assert np.abs(d['probs'] - p).max() < 5e-5
+    assert max(cases.grad_errors(d['grads'], grads).values()) < 2e-4
+    g1 = net.grads.clone()
+    net.set_weights(dict(ora.params, **ora.state))
+    net.train_fwd_bwd(torch.from_numpy(d['x']).cuda(), torch.from_numpy(d['y']).cuda(), seed=5, step=3, row_offset=off, loss_batch=2 * B)
+    np.testing.assert_allclose(2.0 * net.grads.cpu().numpy(), g1.cpu().numpy(), rtol=1e-6, atol=1e-12)
+
+
+def test_adam_steps_lower_the_loss_and_move_the_weights_as_the_oracle_says():
+    """Model.train_on_batch on a fixed batch: after each of the first two steps the weights are the float64 Keras-2.1.2 Adam rule
+    applied to the device's own gradient (plus the l2 term 2 c w the optimizer folds in) to the siblings' update bar, 1e-6 (a step
+    moves a weight by about lr = 1e-3); over twelve steps the loss falls."""
+    from speech_recognition_amd.keras_api import Adam
+    from speech_recognition_amd.model import ACCELERATED, speech_model
+    assert 'inception_d1' in ACCELERATED
+    model = speech_model('inception_d1', 16000, num_classes=NC)
+    assert model.name == 'inception_d1' and model.loss == 'cce'
+    assert isinstance(model.optimizer, Adam) and abs(float(model.optimizer.lr) - 1e-3) < 1e-9
+    net = model.net
+    l2 = net.l2.cpu().numpy().astype(np.float64)
+    m, v = np.zeros(net.n_params), np.zeros(net.n_params)
+    x, y = cases.batch(32, seed=100)
+    losses = []
+    for t in range(1, 13):
+        p0 = net.params.cpu().numpy().astype(np.float64)
+        losses.append(float(model.train_on_batch(x, y)[0]))
+        if t <= 2:
+            g = net.grads.cpu().numpy().astype(np.float64) + 2.0 * l2 * p0
+            ref, m, v = SO.adam_step(p0, g, m, v, float(np.float32(1e-3)), t)
+            got = net.params.cpu().numpy()
+            moved = np.abs(got - p0).max()
+            print("adam step %d: max |w - oracle| = %.3g, largest move %.3g" % (t, np.abs(got - ref).max(), moved))
+            assert np.abs(got - ref).max() < 1e-6
+            assert 1e-4 < moved < 2e-3
+    print("inception_d1 losses on a fixed batch: %s" % ' '.join('%.4f' % q for q in losses))
+    assert np.all(np.isfinite(losses)) and np.mean(losses[-3:]) < np.mean(losses[:3])
+    with pytest.raises(ValueError):
+        speech_model('inception_d1', 8000, num_classes=NC)
+
+
+def test_checkpoint_round_trip(tmp_path):
+    """save -> load -> one more step equals the uninterrupted run bit for bit (weights, moving statistics, both Adam moments,
+    `iterations`)."""
+    from speech_recognition_amd.model import speech_model
+    a = speech_model('inception_d1', 16000, num_classes=NC)
+    batches = [cases.batch(8, seed=200 + i) for i in range(3)]
+    for xb, yb in batches[:2]:
+        a.train_on_batch(xb, yb)
+    path = str(tmp_path / "inception.npz")
+    a.save(path)
+    b = speech_model('inception_d1', 16000, num_classes=NC)
+    b.load_weights(path)
+    assert b.optimizer.iterations == 2
+    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state)
+    assert torch.equal(a.net.slots, b.net.slots) and torch.equal(a.net.slots2, b.net.slots2)
+    la, lb = a.train_on_batch(*batches[2]), b.train_on_batch(*batches[2])
+    assert la == lb
+    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state)
+    assert torch.equal(a.net.slots, b.net.slots) and torch.equal(a.net.slots2, b.net.slots2)
+
+
+def test_fit_generator_runs():
+    """Checkpoints aside, the Keras surface the training script uses: fit_generator over a generator of fixed batches."""
+    from speech_recognition_amd.model import speech_model
+    model = speech_model('inception_d1', 16000, num_classes=NC)
+
+    def gen():
+        i = 0
+        while True:
+            yield cases.batch(16, seed=400 + i % 4)
+            i += 1
+
+    hist = model.fit_generator(gen(), steps_per_epoch=3, epochs=1, verbose=0)
+    assert np.isfinite(hist.history['loss'][-1])
+
+
+@pytest.mark.parametrize("training", [0, 1])
+def test_workspace_bytes_is_honoured_and_one_byte_less_is_refused(training):
+    """A step in a workspace of exactly workspace_bytes leaves the guard bands around it alone; one byte less is KWS_E_WORKSPACE
+    with a message, and nothing runs."""
+    ora, net = _pair()
+    lib, B, guard = net.lib, 3, 4096
+    need = int(lib.kws_net_workspace_bytes(net.handle, B, training))
+    assert need > 0 and need % 4 == 0
+    buf = torch.full((need // 4 + 2 * guard,), float('nan'), dtype=torch.float32, device="cuda")
+    ws = buf[guard:guard + need // 4]
+    x, y = cases.batch(B)
+    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    probs = torch.full((B, NC), float('nan'), dtype=torch.float32, device="cuda")
+
+    def run(nbytes):
+        if training:
+            return lib.kws_net_train_fwd_bwd(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), _lib.ptr(yd), B,
+                                             _lib.ptr(net.grads), _lib.ptr(probs), _lib.ptr(net.metrics), ctypes.c_uint64(1),
+                                             ctypes.c_uint32(0), 0, B, _lib.ptr(ws), nbytes, _lib.stream_ptr())
+        return lib.kws_net_predict(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), B, _lib.ptr(probs), _lib.ptr(ws),
+                                   nbytes, _lib.stream_ptr())
+
+    assert run(need - 1) == -3                                   # KWS_E_WORKSPACE
+    assert b'workspace' in lib.kws_last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(probs).all()) and bool(torch.isnan(buf).all())
+    assert run(need) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[-guard:]).all())
+    p = probs.cpu().numpy()
+    assert np.isfinite(p).all() and np.abs(p.sum(1) - 1).max() < 1e-5
