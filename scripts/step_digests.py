@@ -1,0 +1,93 @@
+"""SHA-256 digests of what one library build computes for the eight models whose BatchNorm bookkeeping is csrc/bncols.hip: per
+model one predict and one train_fwd_bwd at batch 3, then a second train_fwd_bwd at batch 16, each digest over the raw bytes of
+probs, grads, state and metrics (and whether all of them are finite).  Weights come from a fixed NumPy seed, with gammas of both signs and moving statistics off 0 / 1
+(tests/net_parity.perturb's idea).  Two builds that agree on every digest compute the same bits; a digest says nothing across
+compiler versions, which is why this is a comparison tool and not a test.
+usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--out FILE]"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from speech_recognition_amd import _lib  # noqa: E402
+from speech_recognition_amd.net import DeviceNet  # noqa: E402
+
+MODELS = [  # (name, kind, input_size)
+    ('conv_1d_fast', _lib.KWS_NET_CONV_1D_FAST, 16000),
+    ('conv_1d_spec', _lib.KWS_NET_CONV_1D_SPEC, 98 * 257),
+    ('conv_1d_time_stacked', _lib.KWS_NET_CONV_1D_TIME_STACKED, 16000),
+    ('conv_1d_heavy', _lib.KWS_NET_CONV_1D_HEAVY, 16000),
+    ('conv_1d_gru', _lib.KWS_NET_CONV_1D_GRU, 16000),
+    ('conv_1d_simple', _lib.KWS_NET_CONV_1D_SIMPLE, 16000),
+    ('conv_1d_multi_time_sliced', _lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 16000),
+    ('inception_d1', _lib.KWS_NET_INCEPTION_D1, 16000),
+]
+NC = 12
+
+
+def perturbed_weights(net, seed):
+    rng = np.random.RandomState(seed)
+    w = net.get_weights()
+    for k in w:
+        shp = w[k].shape
+        if k.endswith('gamma'):      # both signs, away from 0
+            w[k] = ((1.0 + 0.1 * rng.randn(*shp)) * np.where(rng.rand(*shp) < 0.3, -1.0, 1.0)).astype(np.float32)
+        elif k.endswith('beta') or k.endswith('bias'):
+            w[k] = (0.1 * rng.randn(*shp)).astype(np.float32)
+        elif k.endswith('moving_mean'):
+            w[k] = (0.05 * rng.randn(*shp)).astype(np.float32)
+        elif k.endswith('moving_variance'):
+            w[k] = (1.0 + 0.2 * rng.rand(*shp)).astype(np.float32)
+    return w
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
+
+
+def digests(net, probs):
+    torch.cuda.synchronize()
+    finite = all(bool(torch.isfinite(t).all()) for t in (probs, net.grads, net.state, net.metrics))
+    return {'probs': sha(probs), 'grads': sha(net.grads), 'state': sha(net.state), 'metrics': sha(net.metrics), 'finite': finite}
+
+
+def batch(B, input_size, seed):
+    rng = np.random.RandomState(seed)
+    x = (rng.randn(B, input_size) * 0.0774).astype(np.float32)
+    y = np.eye(NC, dtype=np.float32)[rng.randint(0, NC, B)]
+    return torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+
+
+def model_digests(name, kind, input_size):
+    net = DeviceNet(kind, NC, input_size=input_size, seed=1234)
+    net.set_weights(perturbed_weights(net, 99))
+    out = {}
+    x, y = batch(3, input_size, 7)
+    out['predict_b3'] = digests(net, net.predict(x))
+    out['train_b3'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=1))
+    x, y = batch(16, input_size, 8)
+    out['train_b16'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=2))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    res = dict((name, model_digests(name, kind, size)) for name, kind, size in MODELS)
+    text = json.dumps(res, indent=1, sort_keys=True)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -14,8 +14,8 @@
 // 32 x 32 accumulators each), 16-deep K slabs double-buffered through LDS with a register prefetch of the next slab.
 // Operands are loaded element-wise with bounds checks, so group widths need not be multiples of anything (gs 42, 63,
 // 75 ... and Ng 50, 75, 105 ... of the reference models).
-// Also here: the grouped BatchNorm bookkeeping of the network programs (each group's BN is its own Keras layer, its
-// gamma / beta / moving statistics at a fixed stride in the flat buffers; its table scale|shift|mean|rstd is [4][Ng]).
+// Each group's BatchNorm is its own Keras layer with its own table scale|shift|mean|rstd [4][Ng]: bncols.hip keeps them.
+// Also here: the Flatten -> Dense -> softmax tail of the programs that end in one (kws_flat_tail_launch).
 #include "common.h"
 #include "internal.h"
 
@@ -351,146 +351,6 @@ int check_bn(const float* bn, int bg, const kws_gconv_t* d) {
 
 int64_t wstride(const kws_gconv_t* d) { return d->w_group_stride ? d->w_group_stride : (int64_t)d->k * d->gs * d->Ng; }
 
-// ---- grouped BatchNorm bookkeeping (network programs) --------------------------------------------------------------------
-// part[rows][2][F] -> per-group tables bn[g][4][Ng] (scale|shift|mean|rstd) and the moving statistics; the arithmetic of
-// bn_stats_finalize_kernel (bn.hip): double sums over the rows in a fixed order, biased variance, AssignMovingAvg.
-struct GbnRefs {
-  const float* gamma;   // group 0's gamma; group q's at + q * pstride; beta at + boff
-  int64_t pstride, boff;
-  float* mm;            // group 0's moving mean; group q's at + q * sstride; moving variance at + voff
-  int64_t sstride, voff;
-  int g, Ng;
-};
-constexpr int GFIN_CG = 16, GFIN_RG = 16;
-
-__global__ __launch_bounds__(256) void gbn_finalize_kernel(const float* __restrict__ part, int rows, double inv_count, GbnRefs r,
-                                                           float eps, float omm, float* __restrict__ bn) {
-  __shared__ double red[2][GFIN_RG][GFIN_CG];
-  const int F = r.g * r.Ng;
-  const int cg = threadIdx.x % GFIN_CG, rg = threadIdx.x / GFIN_CG;
-  const int c = blockIdx.x * GFIN_CG + cg;
-  double s = 0.0, ss = 0.0;
-  if (c < F)
-    for (int t = rg; t < rows; t += GFIN_RG) {
-      s += (double)part[(int64_t)t * 2 * F + c];
-      ss += (double)part[(int64_t)t * 2 * F + F + c];
-    }
-  red[0][rg][cg] = s;
-  red[1][rg][cg] = ss;
-  __syncthreads();
-  if (rg != 0 || c >= F) return;
-  s = 0.0;
-  ss = 0.0;
-  for (int q = 0; q < GFIN_RG; ++q) {
-    s += red[0][q][cg];
-    ss += red[1][q][cg];
-  }
-  const int grp = c / r.Ng, n = c - grp * r.Ng;
-  const double mean = s * inv_count;
-  double var = ss * inv_count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float meanf = (float)mean, varf = (float)var;
-  const float* ga = r.gamma + (int64_t)grp * r.pstride;
-  const float scale = ga[n] * rstd;
-  float* t = bn + (int64_t)grp * 4 * r.Ng;
-  t[n] = scale;
-  t[r.Ng + n] = ga[r.boff + n] - meanf * scale;
-  t[2 * r.Ng + n] = meanf;
-  t[3 * r.Ng + n] = rstd;
-  if (r.mm) {
-    float* mm = r.mm + (int64_t)grp * r.sstride;
-    mm[n] = mm[n] - (mm[n] - meanf) * omm;
-    mm[r.voff + n] = mm[r.voff + n] - (mm[r.voff + n] - varf) * omm;
-  }
-}
-
-// inference tables from the moving statistics (bn_infer_prepare_kernel's arithmetic)
-__global__ __launch_bounds__(256) void gbn_infer_kernel(GbnRefs r, const float* __restrict__ mm0, float eps, float* __restrict__ bn) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= r.g * r.Ng) return;
-  const int grp = c / r.Ng, n = c - grp * r.Ng;
-  const float* ga = r.gamma + (int64_t)grp * r.pstride;
-  const float* mm = mm0 + (int64_t)grp * r.sstride;
-  const float rstd = 1.0f / sqrtf(mm[r.voff + n] + eps);
-  const float scale = ga[n] * rstd;
-  float* t = bn + (int64_t)grp * 4 * r.Ng;
-  t[n] = scale;
-  t[r.Ng + n] = ga[r.boff + n] - mm[n] * scale;
-  t[2 * r.Ng + n] = mm[n];
-  t[3 * r.Ng + n] = rstd;
-}
-
-// backward of Activation(relu6) o BatchNormalization, pass 1: g = dA * relu6'(bn(y)) in place, per-chunk partial sums
-// part[chunk][2][F] of (g, g * xhat); rows of one chunk are added in ascending order
-constexpr int GBWD_ROWS = 64;
-__global__ __launch_bounds__(256) void gbn_bwd_part_kernel(float* __restrict__ dA, const float* __restrict__ y, const float* __restrict__ bn,
-                                                           int64_t M, int g, int Ng, float* __restrict__ part) {
-  const int F = g * Ng;
-  const int c = blockIdx.y * 256 + threadIdx.x;
-  if (c >= F) return;
-  const int grp = c / Ng, n = c - grp * Ng;
-  const float* t = bn + (int64_t)grp * 4 * Ng;
-  const float sc = t[n], sh = t[Ng + n], mean = t[2 * Ng + n], rstd = t[3 * Ng + n];
-  const int64_t m0 = (int64_t)blockIdx.x * GBWD_ROWS;
-  const int64_t m1 = m0 + GBWD_ROWS < M ? m0 + GBWD_ROWS : M;
-  float s = 0.f, sx = 0.f;
-  for (int64_t m = m0; m < m1; ++m) {
-    const float yv = y[m * F + c];
-    const float pre = fmaf(yv, sc, sh);
-    const float gv = (pre > 0.f && pre <= 6.f) ? dA[m * F + c] : 0.f;
-    dA[m * F + c] = gv;
-    s += gv;
-    sx += gv * ((yv - mean) * rstd);
-  }
-  part[(int64_t)blockIdx.x * 2 * F + c] = s;
-  part[(int64_t)blockIdx.x * 2 * F + F + c] = sx;
-}
-
-// pass 2: dbeta, dgamma (into the flat gradient buffer at the groups' offsets) and coef[2][F] = (sum g / n, sum g xhat / n)
-__global__ __launch_bounds__(256) void gbn_bwd_fin_kernel(const float* __restrict__ part, int rows, double inv_count, int g, int Ng,
-                                                          float* dgamma0, int64_t pstride, int64_t boff, float* __restrict__ coef) {
-  __shared__ double red[2][GFIN_RG][GFIN_CG];
-  const int F = g * Ng;
-  const int cg = threadIdx.x % GFIN_CG, rg = threadIdx.x / GFIN_CG;
-  const int c = blockIdx.x * GFIN_CG + cg;
-  double s = 0.0, sx = 0.0;
-  if (c < F)
-    for (int t = rg; t < rows; t += GFIN_RG) {
-      s += (double)part[(int64_t)t * 2 * F + c];
-      sx += (double)part[(int64_t)t * 2 * F + F + c];
-    }
-  red[0][rg][cg] = s;
-  red[1][rg][cg] = sx;
-  __syncthreads();
-  if (rg != 0 || c >= F) return;
-  s = 0.0;
-  sx = 0.0;
-  for (int q = 0; q < GFIN_RG; ++q) {
-    s += red[0][q][cg];
-    sx += red[1][q][cg];
-  }
-  const int grp = c / Ng, n = c - grp * Ng;
-  float* dg = dgamma0 + (int64_t)grp * pstride;
-  dg[n] = (float)sx;
-  dg[boff + n] = (float)s;
-  coef[c] = (float)(s * inv_count);
-  coef[F + c] = (float)(sx * inv_count);
-}
-
-// pass 3: dy = scale * (g - c1 - xhat * c2), in place (bn_bwd_apply_kernel's arithmetic with gamma * rstd = scale)
-__global__ __launch_bounds__(256) void gbn_bwd_apply_kernel(float* __restrict__ gbuf, const float* __restrict__ y, const float* __restrict__ bn,
-                                                            const float* __restrict__ coef, int64_t n_el, int g, int Ng) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_el) return;
-  const int F = g * Ng;
-  const int c = (int)(i % F);
-  const int grp = c / Ng, n = c - grp * Ng;
-  const float* t = bn + (int64_t)grp * 4 * Ng;
-  const float mean = t[2 * Ng + n], rstd = t[3 * Ng + n];
-  gbuf[i] = t[n] * (gbuf[i] - coef[c] - (y[i] - mean) * rstd * coef[F + c]);
-}
-
 // ---- Flatten -> Dropout -> Dense(bias) -> softmax -> keras categorical_crossentropy (conv_1d_fast / conv_1d_spec) ------
 // One workgroup per clip.  Features are relu6(bn(y)) of the last grouped block in Keras Flatten order (t * F + f); the
 // dropout element index of row r is r * D + i (layer_id 1 unless the caller names another), as in the other tails.  bd may
@@ -593,52 +453,6 @@ __global__ __launch_bounds__(256) void flat_tail_kernel(FtArgs a) {
 }  // namespace
 
 // ---- internal launchers (net_grouped.hip) ----------------------------------------------------------------------------------
-int kws_gbn_finalize(const float* part, int rows, int64_t count, const kws_gbn_refs* r, float eps, float momentum, float* bn,
-                     hipStream_t st) {
-  GbnRefs g{r->gamma, r->pstride, r->boff, r->mm, r->sstride, r->voff, r->g, r->Ng};
-  KwsProfScope prof("gbn_finalize", 0.0, 8.0 * rows * r->g * r->Ng, st);
-  hipLaunchKernelGGL(gbn_finalize_kernel, dim3((unsigned)ceil_div(r->g * r->Ng, GFIN_CG)), dim3(256), 0, st, part, rows,
-                     1.0 / (double)count, g, eps, (float)(1.0 - (double)momentum), bn);
-  KWS_LAUNCH_CHECK("gbn_finalize_kernel");
-  return KWS_OK;
-}
-
-int kws_gbn_infer(const kws_gbn_refs* r, float eps, float* bn, hipStream_t st) {
-  GbnRefs g{r->gamma, r->pstride, r->boff, nullptr, r->sstride, r->voff, r->g, r->Ng};
-  hipLaunchKernelGGL(gbn_infer_kernel, dim3((unsigned)ceil_div(r->g * r->Ng, 256)), dim3(256), 0, st, g, r->mm, eps, bn);
-  KWS_LAUNCH_CHECK("gbn_infer_kernel");
-  return KWS_OK;
-}
-
-int kws_gbn_bwd_rows(int64_t M) { return (int)ceil_div64(M, GBWD_ROWS); }
-
-static int gbn_bwd_finish_launch(float* gbuf, const float* y, const float* bn, int64_t M, int g, int Ng, const float* part, int rows,
-                                 float* coef, float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st) {
-  const int F = g * Ng;
-  hipLaunchKernelGGL(gbn_bwd_fin_kernel, dim3((unsigned)ceil_div(F, GFIN_CG)), dim3(256), 0, st, part, rows, 1.0 / (double)M, g, Ng,
-                     dgamma0, pstride, boff, coef);
-  KWS_LAUNCH_CHECK("gbn_bwd_fin_kernel");
-  const int64_t n_el = M * F;
-  hipLaunchKernelGGL(gbn_bwd_apply_kernel, dim3((unsigned)ceil_div64(n_el, 256)), dim3(256), 0, st, gbuf, y, bn, coef, n_el, g, Ng);
-  KWS_LAUNCH_CHECK("gbn_bwd_apply_kernel");
-  return KWS_OK;
-}
-
-int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, int Ng, float* part, float* coef, float* dgamma0,
-                int64_t pstride, int64_t boff, hipStream_t st) {
-  const int F = g * Ng, rows = kws_gbn_bwd_rows(M);
-  KwsProfScope prof("gbn_bwd", 0.0, 4.0 * 5.0 * (double)M * F, st);
-  hipLaunchKernelGGL(gbn_bwd_part_kernel, dim3((unsigned)rows, (unsigned)ceil_div(F, 256)), dim3(256), 0, st, dA, y, bn, M, g, Ng, part);
-  KWS_LAUNCH_CHECK("gbn_bwd_part_kernel");
-  return gbn_bwd_finish_launch(dA, y, bn, M, g, Ng, part, rows, coef, dgamma0, pstride, boff, st);
-}
-
-int kws_gbn_bwd_finish(float* gbuf, const float* y, const float* bn, int64_t M, int g, int Ng, const float* part, int rows, float* coef,
-                       float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st) {
-  KwsProfScope prof("gbn_bwd_finish", 0.0, 4.0 * 3.0 * (double)M * g * Ng, st);
-  return gbn_bwd_finish_launch(gbuf, y, bn, M, g, Ng, part, rows, coef, dgamma0, pstride, boff, st);
-}
-
 int kws_flat_tail_launch(const kws_flat_tail_args* t, int training, hipStream_t st) {
   KWS_REQUIRE(t && t->y && (t->bn || t->raw) && t->Wd && t->probs && t->B > 0 && t->D > 0 && t->D <= FT_MAXD && t->F > 0 &&
                   t->D % t->F == 0 && t->Ng > 0 && t->F % t->Ng == 0 && t->NC > 0 && t->NC <= FT_MAXNC,

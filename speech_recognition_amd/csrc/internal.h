@@ -85,30 +85,42 @@ struct SlabBatch {
 };
 extern "C" int kws_slab_batch_fill(SlabBatch* b, const float* const* ws, float* const* out, const int64_t* n, const int* S, int count,
                                    int* blocks_out, double* bytes_out);
-// gconv.hip: grouped BatchNorm bookkeeping of the grouped-Conv1D programs (net_grouped.hip).  Each group's BN is its own Keras
-// layer: gamma of group q at gamma + q * pstride, beta at + boff; moving mean at mm + q * sstride, moving variance at + voff;
-// its table scale|shift|mean|rstd is bn + q * 4 * Ng.
+// bncols.hip: BatchNorm bookkeeping of the network programs over F = g * Ng columns of a [M, .] matrix of convolution outputs.
+// kws_gbn_cols says where the columns and their table are:
+//   grouped (pitch = g * Ng, c0 = 0): the matrix is dense; each group's BN is its own Keras layer with its own table
+//     scale|shift|mean|rstd at bn + q * 4 * Ng, rows Ng apart (net_grouped.hip; g = 1: every plain [M, F] user);
+//   window (g = 1): the columns [c0, c0 + Ng) of a tensor of row pitch `pitch` (data pointers name the tensor's first column);
+//     the table is that tensor's bn[4][pitch], of which only the window's columns are touched (net_inception.hip).
+// A window of several groups has no user and no table layout: the launchers refuse it (KWS_E_INVALID, nothing launched).
+struct kws_gbn_cols {
+  int g, Ng;
+  int pitch, c0;
+};
+static inline kws_gbn_cols kws_gbn_grouped(int g, int Ng) { return kws_gbn_cols{g, Ng, g * Ng, 0}; }
+static inline kws_gbn_cols kws_gbn_window(int pitch, int c0, int F) { return kws_gbn_cols{1, F, pitch, c0}; }
+// gamma of group q at gamma + q * pstride, beta at + boff; moving mean at mm + q * sstride, moving variance at + voff (one BN
+// layer: g = 1, boff = beta - gamma, voff = mv - mm)
 struct kws_gbn_refs {
   const float* gamma;
   int64_t pstride, boff;
   float* mm;
   int64_t sstride, voff;
-  int g, Ng;
 };
-// stats rows [rows][2][g*Ng] -> tables + moving statistics (r->mm NULL: no update)
-int kws_gbn_finalize(const float* part, int rows, int64_t count, const kws_gbn_refs* r, float eps, float momentum, float* bn,
-                     hipStream_t st);
-int kws_gbn_infer(const kws_gbn_refs* r, float eps, float* bn, hipStream_t st);
-// backward of relu6 o BN over [M, g*Ng], in place on dA (-> dy); part: kws_gbn_bwd_rows(M) * 2 * F floats, coef 2 * F floats;
-// dgamma / dbeta land at dgamma0 + q * pstride (+ boff)
+// stats rows [rows][2][F] -> tables + moving statistics (r->mm NULL: no update)
+int kws_gbn_finalize(const float* part, int rows, int64_t count, const kws_gbn_cols* c, const kws_gbn_refs* r, float eps, float momentum,
+                     float* bn, hipStream_t st);
+int kws_gbn_infer(const kws_gbn_cols* c, const kws_gbn_refs* r, float eps, float* bn, hipStream_t st);
+// backward of relu6 o BN over the columns, in place on dA (-> dy); add (may be NULL): an already gated gradient of dA's layout,
+// added behind the gate; part: kws_gbn_bwd_rows(M) * 2 * F floats, coef 2 * F floats; dgamma / dbeta land at
+// dgamma0 + q * pstride (+ boff)
 int kws_gbn_bwd_rows(int64_t M);
-int kws_gbn_bwd(float* dA, const float* y, const float* bn, int64_t M, int g, int Ng, float* part, float* coef, float* dgamma0,
-                int64_t pstride, int64_t boff, hipStream_t st);
+int kws_gbn_bwd(float* dA, const float* y, const float* bn, const float* add, int64_t M, const kws_gbn_cols* c, float* part, float* coef,
+                float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
 // its last two passes alone, for a producer that wrote the gated gradient g and `rows` partial rows [2][F] of (sum g, sum g xhat)
 // itself (pool.hip kws_pool3s2_bwd_f32): dgamma / dbeta / coef from the rows, then dy in place on g
-int kws_gbn_bwd_finish(float* g, const float* y, const float* bn, int64_t M, int groups, int Ng, const float* part, int rows, float* coef,
-                       float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
-// Flatten -> Dropout -> Dense(bias or none: bd NULL) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F;
+int kws_gbn_bwd_finish(float* g, const float* y, const float* bn, int64_t M, const kws_gbn_cols* c, const float* part, int rows,
+                       float* coef, float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
+// gconv.hip: Flatten -> Dropout -> Dense(bias or none: bd NULL) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F;
 // layer_id: the dropout layer's id (0 = 1).  raw != 0: the features are y itself (signed, bn unused, no dropout): Dense + softmax
 // behind conv_1d_simple's GRU
 struct kws_flat_tail_args {

@@ -421,8 +421,8 @@ int DkProgram::train(const float* params, float* state, const float* x, const fl
     KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
                             ws + lo.gmh, ws + lo.gsave, G[0], grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
                             grads + p.gU[1], grads + p.gb[1], ws + lo.gws, B, T, I, H, st));
-    KWS_TRY(kws_gbn_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], (int64_t)B * T, 1, b.cout, part, coef, grads + b.bn.gamma, 0,
-                        b.bn.beta - b.bn.gamma, st));
+    KWS_TRY(kws_gbn_layer_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, (int64_t)B * T, kws_gbn_grouped(1, b.cout), part,
+                              coef, grads, b.bn, st));
   } else {
     KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, p.H, p.NC, ws + lo.swg, st));
     // G[0] = gradient wrt relu6(h + b1) [B, H] -> wrt h; dense_1's gradients; back through Dropout(.3) onto the activated features
@@ -433,8 +433,8 @@ int DkProgram::train(const float* params, float* state, const float* x, const fl
     KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, G[1], B, p.H, p.D, nullptr, st));
     KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, seed, step, 1, row_offset, st));
     const SepBlock& b = p.blocks[nb - 1];
-    KWS_TRY(kws_gbn_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], B, 1, b.cout, part, coef, grads + b.bn.gamma, 0,
-                        b.bn.beta - b.bn.gamma, st));
+    KWS_TRY(kws_gbn_layer_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, B, kws_gbn_grouped(1, b.cout), part, coef, grads,
+                              b.bn, st));
   }
   // ---- blocks: G[cur] = dy of block i's pointwise output ----
   for (int i = nb - 1; i >= 1; --i) {

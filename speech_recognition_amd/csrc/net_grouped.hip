@@ -170,7 +170,6 @@ kws_gbn_refs refs_of(const GcBlock& b, const float* params, float* state) {
   kws_gbn_refs r;
   r.gamma = params + b.gamma0; r.pstride = b.pstride; r.boff = b.beta_off;
   r.mm = state ? state + b.mm0 : nullptr; r.sstride = b.sstride; r.voff = b.mv_off;
-  r.g = b.d.g; r.Ng = b.d.Ng;
   return r;
 }
 
@@ -205,6 +204,7 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
     const float* bn_in = gi.bn;
     const int bg = gi.bg;
     const kws_gbn_refs r = refs_of(b, params, state);
+    const kws_gbn_cols cols = kws_gbn_grouped(d.g, d.Ng);
     if (training) {
       if (p.head2 && i + 1 == p.blocks.size()) {   // Dropout(.3) over the activated ladder output, materialised for the head's GEMMs
         const GcBlock& pb = p.blocks[i - 1];
@@ -212,11 +212,11 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
         KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.Dd, p.keep, seed, step, 1, row_offset, st));
       }
       KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], ws + lo.stats, &d, st));
-      KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&d), (int64_t)B * d.Lout, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
+      KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&d), (int64_t)B * d.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
                                ws + lo.bn[i], st));
     } else {
       KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], nullptr, &d, st));
-      KWS_TRY(kws_gbn_infer(&r, KWS_BN_EPS, ws + lo.bn[i], st));
+      KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, ws + lo.bn[i], st));
     }
     if (b.pool) KWS_TRY(kws_pool3s2_fwd_f32(ws + lo.y[i], ws + lo.bn[i], ws + lo.z[i], B, d.Lout, b.F, st));
   }
@@ -375,13 +375,14 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
     kws_gconv_t d = b.d;
     d.B = B;
     const int64_t M = (int64_t)B * d.Lout;
+    const kws_gbn_cols cols = kws_gbn_grouped(d.g, d.Ng);
     if (b.pool) {   // dA[cur] = gradient wrt the pooled output: route it to the winners, gate it, BN sums in the same pass
       KWS_TRY(kws_pool3s2_bwd_f32(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], ws + lo.dA[cur ^ 1], ws + lo.part, B, d.Lout, b.F, st));
       cur ^= 1;
-      KWS_TRY(kws_gbn_bwd_finish(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part,
+      KWS_TRY(kws_gbn_bwd_finish(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], M, &cols, ws + lo.part,
                                  kws_pool3s2_bwd_part_rows(B, d.Lout, b.F), ws + lo.coef, grads + b.gamma0, b.pstride, b.beta_off, st));
     } else {
-      KWS_TRY(kws_gbn_bwd(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], M, d.g, d.Ng, ws + lo.part, ws + lo.coef, grads + b.gamma0,
+      KWS_TRY(kws_gbn_bwd(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], nullptr, M, &cols, ws + lo.part, ws + lo.coef, grads + b.gamma0,
                           b.pstride, b.beta_off, st));
     }
     float* dy = ws + lo.dA[cur];

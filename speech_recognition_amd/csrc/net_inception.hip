@@ -17,7 +17,7 @@
 //   * backward: every tensor has a gradient buffer of its shape holding the gradient wrt its ACTIVATED value.  The consumers of
 //     a tensor add into it in the reverse of the forward order, which is fixed: the first overwrites, the others accumulate
 //     (one thread per element, no atomics).  The relu6 gate and the BatchNorm backward are applied once, by the convolution that
-//     produced the columns, in place on its window (inc_bn_bwd), or by the max pool behind a pooled convolution
+//     produced the columns, in place on its window (kws_gbn_bwd), or by the max pool behind a pooled convolution
 //     (kws_pool3s2*_bwd gates and leaves the BatchNorm sums; kws_gbn_bwd_finish ends it).  The SAME max pool that reads a block's
 //     raw input hands back an already gated gradient: it goes to a buffer of its own and is added behind the gate.
 // The three sibling 1x1 convolutions of a block stay three launches, each writing where its consumer reads.
@@ -27,68 +27,6 @@ namespace {
 
 constexpr float INC_DROP_KEEP = 0.8f;   // Dropout(0.2), model.py:397
 constexpr int INC_BASE = 32;            // base_num of every block
-constexpr int INC_BWD_ROWS = 64;        // rows per partial-sum chunk of the BatchNorm backward
-constexpr int INC_FIN_CG = 16, INC_FIN_RG = 16;
-
-// ---- BatchNorm bookkeeping over a column window [y0, y0 + F) of a tensor of pitch Cy (gconv.hip's arithmetic) --------------
-struct IncWin {
-  int Cy, y0, F;
-};
-
-// part[rows][2][F] -> the window's columns of the table [4][Cy] and the moving statistics: double sums over the rows in a fixed
-// order, biased variance, AssignMovingAvg
-__global__ __launch_bounds__(256) void inc_bn_finalize_kernel(const float* __restrict__ part, int rows, double inv_count,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              float* __restrict__ mm, float* __restrict__ mv, float eps, float omm,
-                                                              float* __restrict__ bn, IncWin w) {
-  __shared__ double red[2][INC_FIN_RG][INC_FIN_CG];
-  const int cg = threadIdx.x % INC_FIN_CG, rg = threadIdx.x / INC_FIN_CG;
-  const int c = blockIdx.x * INC_FIN_CG + cg;
-  double s = 0.0, ss = 0.0;
-  if (c < w.F)
-    for (int t = rg; t < rows; t += INC_FIN_RG) {
-      s += (double)part[(int64_t)t * 2 * w.F + c];
-      ss += (double)part[(int64_t)t * 2 * w.F + w.F + c];
-    }
-  red[0][rg][cg] = s;
-  red[1][rg][cg] = ss;
-  __syncthreads();
-  if (rg != 0 || c >= w.F) return;
-  s = 0.0;
-  ss = 0.0;
-  for (int q = 0; q < INC_FIN_RG; ++q) {
-    s += red[0][q][cg];
-    ss += red[1][q][cg];
-  }
-  const double mean = s * inv_count;
-  double var = ss * inv_count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float meanf = (float)mean, varf = (float)var;
-  const float scale = gamma[c] * rstd;
-  float* t = bn + w.y0 + c;
-  t[0] = scale;
-  t[w.Cy] = beta[c] - meanf * scale;
-  t[2 * w.Cy] = meanf;
-  t[3 * w.Cy] = rstd;
-  mm[c] = mm[c] - (mm[c] - meanf) * omm;
-  mv[c] = mv[c] - (mv[c] - varf) * omm;
-}
-
-// inference table from the moving statistics
-__global__ __launch_bounds__(256) void inc_bn_infer_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           const float* __restrict__ mm, const float* __restrict__ mv, float eps,
-                                                           float* __restrict__ bn, IncWin w) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= w.F) return;
-  const float rstd = 1.0f / sqrtf(mv[c] + eps);
-  const float scale = gamma[c] * rstd;
-  float* t = bn + w.y0 + c;
-  t[0] = scale;
-  t[w.Cy] = beta[c] - mm[c] * scale;
-  t[2 * w.Cy] = mm[c];
-  t[3 * w.Cy] = rstd;
-}
 
 // the table of an activated tensor for a consumer that wants one (the flat tail): relu6(1 * v + 0) = v for v in [0, 6]
 __global__ __launch_bounds__(256) void inc_identity_table_kernel(float* __restrict__ bn, int C) {
@@ -98,108 +36,6 @@ __global__ __launch_bounds__(256) void inc_identity_table_kernel(float* __restri
   bn[C + c] = 0.f;
   bn[2 * C + c] = 0.f;
   bn[3 * C + c] = 1.f;
-}
-
-// backward of relu6 o BN over the window, pass 1: g = dA * relu6'(bn(y)) (+ add: an already gated contribution) in place, per-chunk
-// partial sums part[chunk][2][F] of (g, g * xhat); rows of one chunk are added in ascending order
-__global__ __launch_bounds__(256) void inc_bn_bwd_part_kernel(float* __restrict__ dA, const float* __restrict__ y,
-                                                              const float* __restrict__ bn, const float* __restrict__ add, int64_t M,
-                                                              IncWin w, float* __restrict__ part) {
-  const int c = blockIdx.y * 256 + threadIdx.x;
-  if (c >= w.F) return;
-  const float* t = bn + w.y0 + c;
-  const float sc = t[0], sh = t[w.Cy], mean = t[2 * w.Cy], rstd = t[3 * w.Cy];
-  const int64_t m0 = (int64_t)blockIdx.x * INC_BWD_ROWS;
-  const int64_t m1 = m0 + INC_BWD_ROWS < M ? m0 + INC_BWD_ROWS : M;
-  float s = 0.f, sx = 0.f;
-  for (int64_t m = m0; m < m1; ++m) {
-    const int64_t i = m * w.Cy + w.y0 + c;
-    const float yv = y[i];
-    const float pre = fmaf(yv, sc, sh);
-    float gv = (pre > 0.f && pre <= 6.f) ? dA[i] : 0.f;
-    if (add) gv += add[i];
-    dA[i] = gv;
-    s += gv;
-    sx += gv * ((yv - mean) * rstd);
-  }
-  part[(int64_t)blockIdx.x * 2 * w.F + c] = s;
-  part[(int64_t)blockIdx.x * 2 * w.F + w.F + c] = sx;
-}
-
-// pass 2: dbeta, dgamma and coef[2][F] = (sum g / n, sum g xhat / n)
-__global__ __launch_bounds__(256) void inc_bn_bwd_fin_kernel(const float* __restrict__ part, int rows, double inv_count, int F,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                             float* __restrict__ coef) {
-  __shared__ double red[2][INC_FIN_RG][INC_FIN_CG];
-  const int cg = threadIdx.x % INC_FIN_CG, rg = threadIdx.x / INC_FIN_CG;
-  const int c = blockIdx.x * INC_FIN_CG + cg;
-  double s = 0.0, sx = 0.0;
-  if (c < F)
-    for (int t = rg; t < rows; t += INC_FIN_RG) {
-      s += (double)part[(int64_t)t * 2 * F + c];
-      sx += (double)part[(int64_t)t * 2 * F + F + c];
-    }
-  red[0][rg][cg] = s;
-  red[1][rg][cg] = sx;
-  __syncthreads();
-  if (rg != 0 || c >= F) return;
-  s = 0.0;
-  sx = 0.0;
-  for (int q = 0; q < INC_FIN_RG; ++q) {
-    s += red[0][q][cg];
-    sx += red[1][q][cg];
-  }
-  dgamma[c] = (float)sx;
-  dbeta[c] = (float)s;
-  coef[c] = (float)(s * inv_count);
-  coef[F + c] = (float)(sx * inv_count);
-}
-
-// pass 3: dy = scale * (g - c1 - xhat * c2), in place on the window
-__global__ __launch_bounds__(256) void inc_bn_bwd_apply_kernel(float* __restrict__ g, const float* __restrict__ y,
-                                                               const float* __restrict__ bn, const float* __restrict__ coef,
-                                                               int64_t n_el, IncWin w) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_el) return;
-  const int64_t m = e / w.F;
-  const int c = (int)(e - m * w.F);
-  const int64_t i = m * w.Cy + w.y0 + c;
-  const float* t = bn + w.y0 + c;
-  g[i] = t[0] * (g[i] - coef[c] - (y[i] - t[2 * w.Cy]) * t[3 * w.Cy] * coef[w.F + c]);
-}
-
-int inc_bn_table(const float* stats, int rows, int64_t M, const float* params, float* state, const BnRef& r, bool training, float* bn,
-                 IncWin w, hipStream_t st) {
-  if (training) {
-    hipLaunchKernelGGL(inc_bn_finalize_kernel, dim3((unsigned)ceil_div(w.F, INC_FIN_CG)), dim3(256), 0, st, stats, rows, 1.0 / (double)M,
-                       params + r.gamma, params + r.beta, state + r.mm, state + r.mv, KWS_BN_EPS,
-                       (float)(1.0 - (double)KWS_BN_MOMENTUM), bn, w);
-    KWS_LAUNCH_CHECK("inc_bn_finalize_kernel");
-  } else {
-    hipLaunchKernelGGL(inc_bn_infer_kernel, dim3((unsigned)ceil_div(w.F, 256)), dim3(256), 0, st, params + r.gamma, params + r.beta,
-                       state + r.mm, state + r.mv, KWS_BN_EPS, bn, w);
-    KWS_LAUNCH_CHECK("inc_bn_infer_kernel");
-  }
-  return KWS_OK;
-}
-
-int inc_bn_bwd_rows(int64_t M) { return (int)ceil_div64(M, INC_BWD_ROWS); }
-
-// dA (gradient wrt the activated window) -> dy in place; dgamma / dbeta into the flat gradient buffer
-int inc_bn_bwd(float* dA, const float* y, const float* bn, const float* add, int64_t M, IncWin w, float* part, float* coef, float* grads,
-               const BnRef& r, hipStream_t st) {
-  const int rows = inc_bn_bwd_rows(M);
-  KwsProfScope prof("inc_bn_bwd", 0.0, 4.0 * 5.0 * (double)M * w.F, st);
-  hipLaunchKernelGGL(inc_bn_bwd_part_kernel, dim3((unsigned)rows, (unsigned)ceil_div(w.F, 256)), dim3(256), 0, st, dA, y, bn, add, M, w,
-                     part);
-  KWS_LAUNCH_CHECK("inc_bn_bwd_part_kernel");
-  hipLaunchKernelGGL(inc_bn_bwd_fin_kernel, dim3((unsigned)ceil_div(w.F, INC_FIN_CG)), dim3(256), 0, st, part, rows, 1.0 / (double)M, w.F,
-                     grads + r.gamma, grads + r.beta, coef);
-  KWS_LAUNCH_CHECK("inc_bn_bwd_fin_kernel");
-  const int64_t n_el = M * w.F;
-  hipLaunchKernelGGL(inc_bn_bwd_apply_kernel, dim3((unsigned)ceil_div64(n_el, 256)), dim3(256), 0, st, dA, y, bn, coef, n_el, w);
-  KWS_LAUNCH_CHECK("inc_bn_bwd_apply_kernel");
-  return KWS_OK;
 }
 
 // ---- the program --------------------------------------------------------------------------------------------------------------
@@ -288,7 +124,7 @@ void IncProgram::layout(int B, bool training, IncLayout* lo) const {
     if (o.kind == OP_GCONV || o.kind == OP_CONV) {
       const int64_t M = (int64_t)B * tensors[o.out].L;
       max_stats = std::max(max_stats, ceil_div64(M, 128) * 2 * o.F);
-      max_part = std::max(max_part, (int64_t)inc_bn_bwd_rows(M) * 2 * o.F);
+      max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * o.F);
       max_coef = std::max(max_coef, (int64_t)2 * o.F);
       if (o.kind == OP_GCONV) {
         const kws_gconv_t d = gdesc(o, B);
@@ -326,20 +162,24 @@ int IncProgram::forward(const IncLayout& lo, const float* params, float* state, 
     const float* in = o.in == 0 ? x : ws + lo.buf[o.in];
     const float* bn_in = ti.raw ? ws + lo.bn[o.in] : nullptr;
     float* out = ws + lo.buf[o.out];
-    const int64_t M = (int64_t)B * to.L;
+    // the BatchNorm behind a convolution fills its columns of the output tensor's table from the rows of sums in lo.stats
+    const auto bn_table = [&](int stats_rows) {
+      const kws_gbn_cols w = kws_gbn_window(to.C, o.y0, o.F);
+      const kws_gbn_refs r = kws_gbn_layer_refs(o.bn, params, state);
+      if (!training) return kws_gbn_infer(&w, &r, KWS_BN_EPS, ws + lo.bn[o.out], st);
+      return kws_gbn_finalize(ws + lo.stats, stats_rows, (int64_t)B * to.L, &w, &r, KWS_BN_EPS, KWS_BN_MOMENTUM, ws + lo.bn[o.out], st);
+    };
     switch (o.kind) {
       case OP_GCONV: {
         const kws_gconv_t d = gdesc(o, B);
         KWS_TRY(kws_gconv_fwd_f32(in, bn_in, d.C, params + o.w, out, training ? ws + lo.stats : nullptr, &d, st));
-        KWS_TRY(inc_bn_table(ws + lo.stats, kws_gconv_stats_rows(&d), M, params, state, o.bn, training, ws + lo.bn[o.out],
-                             IncWin{to.C, o.y0, o.F}, st));
+        KWS_TRY(bn_table(kws_gconv_stats_rows(&d)));
         break;
       }
       case OP_CONV: {
         const kws_conv1d_t d = cdesc(o, B);
         KWS_TRY(kws_conv1d_fwd_f32(in, bn_in, params + o.w, out, training ? ws + lo.stats : nullptr, &d, st));
-        KWS_TRY(inc_bn_table(ws + lo.stats, kws_conv1d_stats_rows(&d), M, params, state, o.bn, training, ws + lo.bn[o.out],
-                             IncWin{to.C, o.y0, o.F}, st));
+        KWS_TRY(bn_table(kws_conv1d_stats_rows(&d)));
         break;
       }
       case OP_MAXV:
@@ -554,8 +394,8 @@ int IncProgram::train(const float* params, float* state, const float* x, const f
       case OP_CONV: {
         // d_out's window: the gradient wrt the activated output, or (pooled) dy already
         if (!o.pooled)
-          KWS_TRY(inc_bn_bwd(d_out, ws + lo.buf[o.out], ws + lo.bn[o.out], to.gadd ? ws + lo.gadd[o.out] : nullptr, M,
-                             IncWin{to.C, o.y0, o.F}, part, coef, grads, o.bn, st));
+          KWS_TRY(kws_gbn_layer_bwd(d_out, ws + lo.buf[o.out], ws + lo.bn[o.out], to.gadd ? ws + lo.gadd[o.out] : nullptr, M,
+                                    kws_gbn_window(to.C, o.y0, o.F), part, coef, grads, o.bn, st));
         if (o.kind == OP_GCONV) {
           const kws_gconv_t d = gdesc(o, B);
           KWS_TRY(kws_gconv_wgrad_f32(in, bn_in, d.C, d_out, grads + o.w, ws + lo.wws, &d, st));
@@ -580,8 +420,8 @@ int IncProgram::train(const float* params, float* state, const float* x, const f
           rows = kws_pool3s2_same_bwd_part_rows(B, ti.L, ti.C);
         }
         if (o.prod >= 0) {
-          const BnRef& r = ops[o.prod].bn;
-          KWS_TRY(kws_gbn_bwd_finish(g, in, bn_in, (int64_t)B * ti.L, 1, ti.C, part, rows, coef, grads + r.gamma, 0, r.beta - r.gamma, st));
+          KWS_TRY(kws_gbn_layer_bwd_finish(g, in, bn_in, (int64_t)B * ti.L, kws_gbn_grouped(1, ti.C), part, rows, coef, grads,
+                                           ops[o.prod].bn, st));
         }
         break;
       }

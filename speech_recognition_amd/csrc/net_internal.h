@@ -8,6 +8,7 @@
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_mts.hip      conv_1d_multi_time_sliced
 //   net_inception.hip  inception_d1
+// The BatchNorm bookkeeping all but net.hip and net_logmfcc.hip share is bncols.hip (kws_gbn_*, declared in internal.h).
 // Not part of the public C ABI.
 #pragma once
 #include <string.h>
@@ -29,6 +30,18 @@ struct BnRef {
   int64_t mm, mv;       // state offsets
   int C;
 };
+// bncols.hip's launchers for ONE BatchNorm layer r (g = 1) over the columns c: its parameters / state, and its gradients in `grads`
+inline kws_gbn_refs kws_gbn_layer_refs(const BnRef& r, const float* params, float* state) {
+  return kws_gbn_refs{params + r.gamma, 0, r.beta - r.gamma, state + r.mm, 0, r.mv - r.mm};
+}
+inline int kws_gbn_layer_bwd(float* dA, const float* y, const float* bn, const float* add, int64_t M, const kws_gbn_cols& c, float* part,
+                             float* coef, float* grads, const BnRef& r, hipStream_t st) {
+  return kws_gbn_bwd(dA, y, bn, add, M, &c, part, coef, grads + r.gamma, 0, r.beta - r.gamma, st);
+}
+inline int kws_gbn_layer_bwd_finish(float* g, const float* y, const float* bn, int64_t M, const kws_gbn_cols& c, const float* part, int rows,
+                                    float* coef, float* grads, const BnRef& r, hipStream_t st) {
+  return kws_gbn_bwd_finish(g, y, bn, M, &c, part, rows, coef, grads + r.gamma, 0, r.beta - r.gamma, st);
+}
 
 // One model's layer table and its launch sequences on one HIP stream.  The public entry points of net.hip check their
 // arguments and make one of these calls; `ws` is the caller's workspace of `ws_bytes` bytes.

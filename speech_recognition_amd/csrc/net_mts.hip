@@ -330,8 +330,8 @@ int MtProgram::train(const float* params, float* state, const float* x, const fl
   {
     const MtBlock& h = p.blocks[nb - 1];
     // G[0] = gradient wrt relu6(bn(y)) [B, 128] -> dy; the GEMM's two gradients; the one-tap depthwise layer; Dropout (layer 1)
-    KWS_TRY(kws_gbn_bwd(G[0], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], B, 1, h.cout, part, coef, grads + h.bn.gamma, 0,
-                        h.bn.beta - h.bn.gamma, st));
+    KWS_TRY(kws_gbn_layer_bwd(G[0], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, B, kws_gbn_grouped(1, h.cout), part, coef, grads,
+                              h.bn, st));
     KWS_TRY(kws_sep_bwd(h, params, grads, G[0], ws + lo.z[nb - 1], ws + lo.featd, nullptr, nullptr, G[0], scratch, B, st));
     KWS_TRY(kws_dropout_bwd(G[0], dcat, B, p.D, p.keep, seed, step, 1, row_offset, st));
   }
@@ -357,11 +357,11 @@ int MtProgram::train(const float* params, float* state, const float* x, const fl
       if (b.pool) {   // route the pooled gradient to the winners, gate it, BN sums in the same pass
         dy = grad == G[0] ? G[1] : G[0];
         KWS_TRY(kws_pool3s2_same_bwd_f32(grad, ws + lo.y[i], ws + lo.bn[i], dy, part, B, b.Lout, b.cout, st));
-        KWS_TRY(kws_gbn_bwd_finish(dy, ws + lo.y[i], ws + lo.bn[i], M, 1, b.cout, part, kws_pool3s2_same_bwd_part_rows(B, b.Lout, b.cout),
-                                   coef, grads + b.bn.gamma, 0, b.bn.beta - b.bn.gamma, st));
+        KWS_TRY(kws_gbn_layer_bwd_finish(dy, ws + lo.y[i], ws + lo.bn[i], M, kws_gbn_grouped(1, b.cout), part,
+                                         kws_pool3s2_same_bwd_part_rows(B, b.Lout, b.cout), coef, grads, b.bn, st));
       } else {
-        KWS_TRY(kws_gbn_bwd(dy, ws + lo.y[i], ws + lo.bn[i], M, 1, b.cout, part, coef, grads + b.bn.gamma, 0, b.bn.beta - b.bn.gamma,
-                            st));
+        KWS_TRY(kws_gbn_layer_bwd(dy, ws + lo.y[i], ws + lo.bn[i], nullptr, M, kws_gbn_grouped(1, b.cout), part, coef, grads, b.bn,
+                                  st));
       }
     }
     if (b.src < 0) {   // stem: both kernels' gradients from dy and x; no gradient leaves the input

@@ -9,7 +9,7 @@
 //         maximum among a window's valid rows wins (TF MaxPoolGrad) and gate = relu6'(bn(y[b,u,c])) = [0 < pre <= 6].  Every
 //         element of g is written exactly once (every row is in some window here).  In the same pass the per-workgroup
 //         BatchNorm partial sums part[row][2][C] = (sum g, sum g * xhat) go out, folded afterwards in a fixed order
-//         (gconv.hip gbn_bwd_fin_kernel): no float atomics, bit-reproducible.
+//         (bncols.hip gbn_bwd_fin_kernel): no float atomics, bit-reproducible.
 // Both are HBM-bound: one thread owns a float4 of channels and a short run of time steps (16-byte loads and stores), and a
 // row shared by two windows is read from HBM once (the forward carries it in registers, the backward's re-reads hit L1/L2).
 #include <math.h>

@@ -1,6 +1,8 @@
 """Builds and loads libkws_internal_test.so: the library's own objects (csrc/build/*.o) plus tests/native/internal_shim.cpp, whose
 kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip), the fused
-backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32) and the classifier tails (tail.hip, gconv.hip kws_flat_tail_launch) to ctypes; built once per process, whichever test module asks first.
+backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32), the classifier tails (tail.hip, gconv.hip kws_flat_tail_launch) and the
+BatchNorm bookkeeping shared by the grouped, depthwise, multi-slice and inception programs (bncols.hip kws_gbn_*) to ctypes; built
+once per process, whichever test module asks first.
 The public kws_* entry points come from the same library (-Wl,-Bsymbolic keeps its calls inside its own copy), so every kernel a
 test compares comes from one build.  Also: the join / shortcut shapes the residual programs launch, read from the planner of
 net_logmfcc.hip through the public net API (host-side only: no GPU needed)."""
@@ -45,6 +47,12 @@ KWST_SIGNATURES = {
     "kwst_flat_tail_launch": (_I, [_P, _I, _P]),
     "kwst_reduce_slabs_f32": (_I, [_P, _P, _I64, _I, _P]),
     "kwst_tail_struct_layout": (None, [ctypes.POINTER(_I64)]),
+    "kwst_gbn_finalize": (_I, [_P, _I, _I64, _P, _P, _F, _F, _P, _P]),
+    "kwst_gbn_infer": (_I, [_P, _P, _F, _P, _P]),
+    "kwst_gbn_bwd_rows": (_I, [_I64]),
+    "kwst_gbn_bwd": (_I, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P]),
+    "kwst_gbn_bwd_finish": (_I, [_P, _P, _P, _I64, _P, _P, _I, _P, _P, _I64, _I64, _P]),
+    "kwst_gbn_struct_layout": (None, [ctypes.POINTER(_I64)]),
 }
 # the public entry points the tests compare against, taken from the same library
 PUBLIC = ["kws_last_error", "kws_dwconv_fwd_f32", "kws_dwconv_bwd_f32", "kws_dwconv_bwd_part_floats", "kws_dw_bwd_finalize",
@@ -134,6 +142,25 @@ def tail_struct_layout(lib):
     out = (_I64 * 6)()
     lib.kwst_tail_struct_layout(out)
     return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(3)]
+
+
+# ctypes mirrors of bncols.hip's two descriptors (csrc/internal.h)
+class GbnCols(ctypes.Structure):
+    _fields_ = [("g", _I), ("Ng", _I), ("pitch", _I), ("c0", _I)]
+
+
+class GbnRefs(ctypes.Structure):
+    _fields_ = [("gamma", _P), ("pstride", _I64), ("boff", _I64), ("mm", _P), ("sstride", _I64), ("voff", _I64)]
+
+
+GBN_STRUCTS = [(GbnCols, "c0"), (GbnRefs, "voff")]
+
+
+def gbn_struct_layout(lib):
+    """[(sizeof, offsetof last member)] of kws_gbn_cols, kws_gbn_refs as the library was compiled"""
+    out = (_I64 * 4)()
+    lib.kwst_gbn_struct_layout(out)
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(2)]
 
 
 # the four residual programs of net_logmfcc.hip, configured as speech_model() builds them (model.py); C3 = conv_1d_log_mfcc at

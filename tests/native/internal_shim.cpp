@@ -1,8 +1,8 @@
-// Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip) and of the
-// classifier tails (tail.hip, gconv.hip kws_flat_tail_launch).
+// Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip), of the
+// classifier tails (tail.hip, gconv.hip kws_flat_tail_launch) and of the shared BatchNorm bookkeeping (bncols.hip kws_gbn_*).
 // libkws_hip.so builds them with hidden visibility; tests/internal_shim.py links this file with the library's own objects into a
 // separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them (tests/test_resblock_kernels_gpu.py,
-// tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py).  No kernels live here.
+// tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py, tests/test_bn_cols_kernels_gpu.py).  No kernels live here.
 //
 // Every forwarder has exactly the parameter list of the declaration it forwards to: KWST_FORWARD static_asserts that the two
 // function types are the same, so a changed declaration fails this build instead of being cast into a wrong call.
@@ -88,6 +88,29 @@ KWST_FORWARD(int, metrics_launch, (const float* per_loss, const float* per_corre
 KWST_FORWARD(int, tail_post_launch, (const kws_tail_post_args* a, int* S_out, hipStream_t st), (a, S_out, st));
 KWST_FORWARD(int, flat_tail_launch, (const kws_flat_tail_args* a, int training, hipStream_t st), (a, training, st));
 KWST_FORWARD(int, reduce_slabs_f32, (const float* ws, float* out, int64_t n, int S, hipStream_t st), (ws, out, n, S, st));
+
+// ---- BatchNorm bookkeeping over grouped columns or a column window (bncols.hip) ----
+KWST_FORWARD(int, gbn_finalize,
+             (const float* part, int rows, int64_t count, const kws_gbn_cols* c, const kws_gbn_refs* r, float eps, float momentum,
+              float* bn, hipStream_t st),
+             (part, rows, count, c, r, eps, momentum, bn, st));
+KWST_FORWARD(int, gbn_infer, (const kws_gbn_cols* c, const kws_gbn_refs* r, float eps, float* bn, hipStream_t st), (c, r, eps, bn, st));
+KWST_FORWARD(int, gbn_bwd_rows, (int64_t M), (M));
+KWST_FORWARD(int, gbn_bwd,
+             (float* dA, const float* y, const float* bn, const float* add, int64_t M, const kws_gbn_cols* c, float* part, float* coef,
+              float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st),
+             (dA, y, bn, add, M, c, part, coef, dgamma0, pstride, boff, st));
+KWST_FORWARD(int, gbn_bwd_finish,
+             (float* g, const float* y, const float* bn, int64_t M, const kws_gbn_cols* c, const float* part, int rows, float* coef,
+              float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st),
+             (g, y, bn, M, c, part, rows, coef, dgamma0, pstride, boff, st));
+// sizeof and the offset of the last member of kws_gbn_cols and kws_gbn_refs, for their ctypes mirrors
+KWST_API void kwst_gbn_struct_layout(int64_t* out4) {
+  out4[0] = (int64_t)sizeof(kws_gbn_cols);
+  out4[1] = (int64_t)offsetof(kws_gbn_cols, c0);
+  out4[2] = (int64_t)sizeof(kws_gbn_refs);
+  out4[3] = (int64_t)offsetof(kws_gbn_refs, voff);
+}
 
 // sizeof and the offset of the last member of the three argument structs, in the order ts_tail, tail_post, flat_tail: the ctypes
 // mirrors of tests/internal_shim.py are compared with these on the build machine (tests/test_internal_shim_cpu.py), so that a

@@ -62,6 +62,22 @@ def test_tail_struct_mirrors_match_the_library(shim):
         assert names == [f[0] for f in cls._fields_], cname
 
 
+def test_gbn_struct_mirrors_match_the_library(shim):
+    """kws_gbn_cols / kws_gbn_refs (csrc/internal.h) against their ctypes mirrors: size, last-member offset, member order."""
+    _, lib = shim
+    mine = [(ctypes.sizeof(cls), getattr(cls, last).offset) for cls, last in internal_shim.GBN_STRUCTS]
+    assert mine == internal_shim.gbn_struct_layout(lib)
+    src = open(os.path.join(internal_shim.CSRC, "internal.h")).read()
+    for (cls, _), cname in zip(internal_shim.GBN_STRUCTS, ["kws_gbn_cols", "kws_gbn_refs"]):
+        body = src.split("struct %s {" % cname)[1].split("};")[0]
+        names = []
+        for decl in body.split(";"):
+            decl = " ".join(l.split("//")[0] for l in decl.splitlines()).strip()
+            if decl:
+                names += [part.split()[-1].lstrip("*") for part in decl.split(",")]
+        assert names == [f[0] for f in cls._fields_], cname
+
+
 def _gather(d):
     g = internal_shim.Gather()
     for k, v in d.items():
