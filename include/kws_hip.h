@@ -386,6 +386,63 @@ int kws_avgpool3_same_fwd_f32(const float* x, const float* bn, float* z, int B, 
 int kws_avgpool3_same_bwd_f32(const float* dz, float* dx, int accumulate, int B, int L, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense NHWC Conv2D (no bias) on f32 MFMA: the convolution of the reference's MFCC-image models conv_2d_mobile / conv_2d_fast
+ * (model.py:547-639).  X [B, H, W, Cin]; Y and dY [B, Hout, Wout, F]; kernel Wt [kh, kw, Cin, F] (Keras layout).  kh 1..20,
+ * kw 1..8; strides sh, sw 1 or 2; dilations dh, dw 1 or 2, and 2 only on an axis whose stride is 1 (as TensorFlow requires); any
+ * positive Cin / F.  Per axis the geometry is TensorFlow's SAME - out = ceil(in / s), total = max((out - 1)*s + d*(k - 1) + 1 -
+ * in, 0), pad in front (pad_t / pad_l) = total / 2, the rest behind - or VALID: pad 0, out = (in - d*(k - 1) - 1) / s + 1.  A
+ * descriptor whose Hout / Wout / pads do not follow from its other fields is refused.  Results are bit-identical from run to run
+ * (no atomics).
+ *   fwd    Y[b,p,q,n] = sum_{i,j,c} act(X[b, p*sh - pad_t + dh*i, q*sw - pad_l + dw*j, c]) * Wt[i,j,c,n]; a tap outside the
+ *          image contributes 0 (the padding is zeros of the ACTIVATED tensor).  act: the identity when bn is NULL, else of the
+ *          producer's table bn [4][Cin] (scale|shift|mean|rstd) relu6(scale*x + shift) (d->act = KWS_ACT_RELU6) or
+ *          relu(scale*x + shift) (KWS_ACT_RELU).  stats_part (may be NULL): [kws_conv2d_stats_rows][2][F] column sums (sum y,
+ *          sum y^2) per 128-row tile of M = B*Hout*Wout, for kws_bn_stats_finalize.
+ *   dgrad  dX[b,y,x,c] = sum over (i,j,p,q) with p*sh - pad_t + dh*i = y, q*sw - pad_l + dw*j = x of sum_n dY[b,p,q,n] *
+ *          Wt[i,j,c,n]: the gradient wrt act(X) (no gate is applied).  Every element of dX is written exactly once by one
+ *          thread; rows and columns no window reads (stride 2 with a 1 x 1 or a VALID 3 x 3 window) get exact zeros.
+ *   wgrad  dWt[i,j,c,n] = sum_{b,p,q} act(X[b, p*sh - pad_t + dh*i, q*sw - pad_l + dw*j, c]) * dY[b,p,q,n];
+ *          workspace >= kws_conv2d_wgrad_workspace_floats floats (fixed-order split over M, then a fixed-order sum).
+ * ---------------------------------------------------------------------------------------- */
+#define KWS_ACT_RELU6 0
+#define KWS_ACT_RELU 1
+typedef struct {
+  int B, H, W, Hout, Wout;   /* clips, input rows / columns, output rows / columns */
+  int kh, kw;                /* window */
+  int sh, sw;                /* strides */
+  int dh, dw;                /* dilations */
+  int pad_t, pad_l;          /* zero rows above / zero columns left of the image */
+  int Cin, F;                /* input channels, filters */
+  int act;                   /* KWS_ACT_*: the activation applied on load when a table is given */
+} kws_conv2d_t;
+int kws_conv2d_stats_rows(const kws_conv2d_t* d);
+int kws_conv2d_fwd_f32(const float* X, const float* bn, const float* Wt, float* Y, float* stats_part, const kws_conv2d_t* d,
+                       void* stream);
+int kws_conv2d_dgrad_f32(const float* dY, const float* Wt, float* dX, const kws_conv2d_t* d, void* stream);
+int64_t kws_conv2d_wgrad_workspace_floats(const kws_conv2d_t* d);
+int kws_conv2d_wgrad_f32(const float* X, const float* bn, const float* dY, float* dWt, float* workspace, const kws_conv2d_t* d,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MaxPool2D(pool_size=(2, 2), strides=2, padding='valid') over act(bn(y)): the pool of the reference's conv_2d_fast_model
+ * (model.py:597-639).  The contract of kws_pool3s2_* in two dimensions.  y [B, H, W, C] is the RAW convolution output, bn its
+ * table scale|shift|mean|rstd [4][C]; z and dz [B, H / 2, W / 2, C]; C % 4 == 0, C <= 1024, H >= 2, W >= 2; act is KWS_ACT_RELU6
+ * or KWS_ACT_RELU.
+ *   fwd  z[b,p,q,c] = max_{i,j<2} act(scale[c] * y[b, 2p+i, 2q+j, c] + shift[c]): the activation BEFORE the maximum (a scale may
+ *        be negative).
+ *   bwd  g[b,r,s,c] = act'(bn(y[b,r,s,c])) * dz[b, r/2, s/2, c] if (r, s) won its window, else 0; the FIRST maximum in row-major
+ *        window order wins (TF MaxPoolGrad).  Every element of g [B, H, W, C] is written once; a last row or column that is in
+ *        no window (odd H or W) gets exact 0.  part receives kws_pool2x2_bwd_part_rows() rows [2][C] of (sum g, sum g * xhat),
+ *        xhat = (y - mean) * rstd: the BatchNorm backward's reductions, to be added over the rows in a fixed order.  No atomics:
+ *        results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int kws_pool2x2_fwd_f32(const float* y, const float* bn, float* z, int B, int H, int W, int C, int act, void* stream);
+int kws_pool2x2_bwd_part_rows(int B, int H, int W, int C);
+int64_t kws_pool2x2_bwd_part_floats(int B, int H, int W, int C);
+int kws_pool2x2_bwd_f32(const float* dz, const float* y, const float* bn, float* g, float* part, int B, int H, int W, int C, int act,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -633,6 +690,24 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         batch_normalization_{index+1}: the same columns of that tensor's table, the rows scale | shift | mean |
  *                         rstd one pitch apart (count = 3 * pitch + filters), what 3 = geometry of Conv1D `index`: offset = row
  *                         pitch, count = filters.
+ *   KWS_NET_CONV_2D_MOBILE: conv_2d_mobile_model, reference model.py:547-594 (mfcc input [98 * 40], input_size must be 3920; Keras
+ *                         model name 'conv_2d_mobile'): Reshape [98, 40, 1] -> Preprocess (clip((x + 0.8) / 7, -5, 5), no gradient) ->
+ *                         eight Conv2D(F, 3 x 3, SAME, bias) -> BatchNormalization -> relu6, F = 32, 32, 64, 64, 128, 128, 256, 256,
+ *                         the odd-numbered ones at stride 2 (49 x 20, 25 x 10, 13 x 5, 7 x 3; kws_conv2d_*), Dropout(.05) behind every
+ *                         pair -> GlobalAveragePooling2D -> Dropout(.1) -> Dense + softmax, categorical CE; SGD(1e-3, momentum .95).
+ *   KWS_NET_CONV_2D_FAST: conv_2d_fast_model, reference model.py:597-639 (the same input; 'conv_2d_fast'): four Conv2D(SAME, bias) ->
+ *                         BatchNormalization -> relu -> MaxPool2D() (kws_pool2x2_*): 16 x (11, 5) dilation (2, 1), 32 x (5, 3)
+ *                         dilation (2, 1), 64 x (3, 3), 128 x (3, 3); 98 x 40 -> 49 x 20 -> 24 x 10 -> 12 x 5 -> 6 x 2 ->
+ *                         GlobalAveragePooling2D -> Dense + softmax; SGD(1e-3, momentum .9).
+ *                         Both: weights in Keras order conv2d_<n>/kernel [kh, kw, Cin, F], conv2d_<n>/bias, batch_normalization_<n>/...
+ *                         The bias stands in front of a BatchNormalization: training leaves it out of the GEMM (it cancels; its
+ *                         gradient is written as exact 0) but adds it to the batch mean that updates moving_mean; inference folds
+ *                         it into the table's shift.  Dropout counters (kws_dropout_fwd's RNG, element (row_offset + b) * H*W*F +
+ *                         i of the NHWC tensor): layer id 1 = the tail's Dropout(.1), ids 2 .. 5 = the four Dropout(.05) in model
+ *                         order.  Debug views: what 0 = raw output of conv2d_{index+1} WITHOUT the bias [B, Hout, Wout, F], what 1 =
+ *                         what that layer hands on where it is materialised (pooled / dropped / last activation [B, Ho, Wo, F];
+ *                         count 0 where the next convolution applies the table on load), what 2 = table of
+ *                         batch_normalization_{index+1} [4][F], what 3 = the preprocessed input [B, 98, 40].
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -651,6 +726,8 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_1D_SIMPLE 12
 #define KWS_NET_XCEPTION_ATTENTION 13
 #define KWS_NET_INCEPTION_D1 14
+#define KWS_NET_CONV_2D_MOBILE 15
+#define KWS_NET_CONV_2D_FAST 16
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

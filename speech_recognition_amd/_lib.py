@@ -26,6 +26,8 @@ KWS_NET_CONV_1D_MULTI_TIME_SLICED = 11
 KWS_NET_CONV_1D_SIMPLE = 12
 KWS_NET_XCEPTION_ATTENTION = 13
 KWS_NET_INCEPTION_D1 = 14
+KWS_NET_CONV_2D_MOBILE = 15
+KWS_NET_CONV_2D_FAST = 16
 
 
 class KwsError(RuntimeError):
@@ -51,6 +53,17 @@ class Conv1dDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("Lout", ctypes.c_int), ("k", ctypes.c_int),
                 ("dil", ctypes.c_int), ("pad_l", ctypes.c_int), ("Cx", ctypes.c_int), ("x0", ctypes.c_int),
                 ("Cin", ctypes.c_int), ("Cy", ctypes.c_int), ("y0", ctypes.c_int), ("F", ctypes.c_int)]
+
+
+class Conv2dDesc(ctypes.Structure):
+    """kws_conv2d_t: dense NHWC Conv2D from [B, H, W, Cin] to [B, Hout, Wout, F]; act (ACT_RELU6 / ACT_RELU) is the activation
+    applied on load when a table is given."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "H", "W", "Hout", "Wout", "kh", "kw", "sh", "sw", "dh", "dw", "pad_t",
+                                            "pad_l", "Cin", "F", "act")]
+
+
+ACT_RELU6 = 0   # include/kws_hip.h: KWS_ACT_*
+ACT_RELU = 1
 
 
 class SamplerSet(ctypes.Structure):
@@ -168,6 +181,15 @@ SIGNATURES = {
     "kws_conv1d_dgrad_f32": (_I, [_P, _P, _P, _I, ctypes.POINTER(Conv1dDesc), _P]),
     "kws_conv1d_wgrad_workspace_floats": (_I64, [ctypes.POINTER(Conv1dDesc)]),
     "kws_conv1d_wgrad_f32": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(Conv1dDesc), _P]),
+    "kws_conv2d_stats_rows": (_I, [ctypes.POINTER(Conv2dDesc)]),
+    "kws_conv2d_fwd_f32": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(Conv2dDesc), _P]),
+    "kws_conv2d_dgrad_f32": (_I, [_P, _P, _P, ctypes.POINTER(Conv2dDesc), _P]),
+    "kws_conv2d_wgrad_workspace_floats": (_I64, [ctypes.POINTER(Conv2dDesc)]),
+    "kws_conv2d_wgrad_f32": (_I, [_P, _P, _P, _P, _P, ctypes.POINTER(Conv2dDesc), _P]),
+    "kws_pool2x2_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "kws_pool2x2_bwd_part_rows": (_I, [_I, _I, _I, _I]),
+    "kws_pool2x2_bwd_part_floats": (_I64, [_I, _I, _I, _I]),
+    "kws_pool2x2_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "kws_avgpool3_same_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "kws_avgpool3_same_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "kws_stem_stats_rows": (_I, [_I, _I]),

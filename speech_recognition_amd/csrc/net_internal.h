@@ -8,6 +8,7 @@
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_mts.hip      conv_1d_multi_time_sliced
 //   net_inception.hip  inception_d1
+//   net_conv2d.hip   conv_2d_mobile, conv_2d_fast
 // The BatchNorm bookkeeping all but net.hip and net_logmfcc.hip share is bncols.hip (kws_gbn_*, declared in internal.h).
 // Not part of the public C ABI.
 #pragma once
@@ -102,6 +103,7 @@ int gc_build(kws_net* n);        // net_grouped.hip
 int dk_build(kws_net* n);        // net_dwk.hip
 int mt_build(kws_net* n);        // net_mts.hip
 int inc_build(kws_net* n);       // net_inception.hip
+int c2n_build(kws_net* n);       // net_conv2d.hip
 
 // ---- pieces the programs share (net.hip) -------------------------------------------------------------------------------
 // KWS_E_WORKSPACE with its message when the caller's workspace is too small; who = "net_predict" / "net_train_fwd_bwd"

@@ -3,12 +3,12 @@ dispatch (reference model.py:1729-1781), `prepare_model_settings` (model.py:1785
 symbols checkpoints name as custom objects (`relu6` model.py:30-31, `overlapping_time_slice_stack`
 model.py:67-76).  The layer graphs themselves are native network programs in csrc/net.hip."""
 from . import _lib
-from .keras_api import Adam, Model, RMSprop
+from .keras_api import SGD, Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
                'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
-               'xception_with_attention', 'inception_d1')
+               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -215,6 +215,29 @@ def inception_d1_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, Adam(lr=1e-3), name='inception_d1', loss='cce')
 
 
+def _mfcc_3920(model_type, input_size):
+    if int(input_size) != 3920:
+        raise ValueError("%s: input_size %s - the reference reshapes exactly 98 x 40 mfcc features (3920)" % (model_type, input_size))
+
+
+def conv_2d_mobile_model(input_size=3920, num_classes=11, *args, **kwargs):
+    """reference model.py:547-594: the generator's 'mfcc' output as an image [98, 40, 1] -> Preprocess -> eight Conv2D(F, 3 x 3,
+    SAME, bias) + BatchNormalization + relu6 (F = 32, 32, 64, 64, 128, 128, 256, 256; the odd-numbered ones at stride 2), Dropout(.05)
+    behind every pair -> GlobalAveragePooling2D -> Dropout(.1) -> Dense; SGD(1e-3, momentum .95), categorical CE."""
+    _mfcc_3920('conv_2d_mobile', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_2D_MOBILE, num_classes, input_size=3920)
+    return Model(net, SGD(lr=1e-3, momentum=0.95), name='conv_2d_mobile', loss='cce')
+
+
+def conv_2d_fast_model(input_size=3920, num_classes=11, *args, **kwargs):
+    """reference model.py:597-639: the 'mfcc' image [98, 40, 1] -> Preprocess -> four Conv2D(SAME, bias, dilation) +
+    BatchNormalization + relu + MaxPool2D() (16 x (11, 5) and 32 x (5, 3) at dilation (2, 1), 64 and 128 x (3, 3)) ->
+    GlobalAveragePooling2D -> Dense; SGD(1e-3, momentum .9), categorical CE."""
+    _mfcc_3920('conv_2d_fast', input_size)
+    net = DeviceNet(_lib.KWS_NET_CONV_2D_FAST, num_classes, input_size=3920)
+    return Model(net, SGD(lr=1e-3, momentum=0.9), name='conv_2d_fast', loss='cce')
+
+
 def xception_with_attention_model(input_size=16000, num_classes=11, filter_mult=1):
     """reference model.py:911-983: raw waveform -> time-slice stack -> Conv1D(64, 3, strides=2) -> eleven residual blocks with 3-wide
     max-pool joins (128, 256, 8 x 256, 384) ending at [50, 384] -> attention gate (a 5-tap depthwise block of one filter, softmax over
@@ -255,9 +278,13 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return xception_with_attention_model(input_size, num_classes)
     if model_type == 'inception_d1':
         return inception_d1_model(input_size, num_classes)
+    if model_type == 'conv_2d_mobile':
+        return conv_2d_mobile_model(input_size, num_classes)
+    if model_type == 'conv_2d_fast':
+        return conv_2d_fast_model(input_size, num_classes)
     if model_type in REFERENCE_MODEL_TYPES:
         raise NotImplementedError(
-            "model '%s' is outside the accelerated hot path (SURVEY.md 8: only %s are built natively)"
+            "model '%s' has no native network program yet (built natively: %s)"
             % (model_type, ', '.join(ACCELERATED)))
     raise ValueError("Invalid model: %s" % model_type)
 
