@@ -624,9 +624,12 @@ int kws_conv1_stats_rows(int64_t M) {
 
 bool kws_conv1_supported(const kws_gather_t* g, const kws_gather_t* unfolded, int N) {
   // anything else (filter_mult = 2: 256 output channels; more than three taps folded into the 80 samples: the forward
-  // kernel's fold-on-load prologue has three tap candidates) takes the generic gathered GEMMs of gemm.hip
+  // kernel's fold-on-load prologue has three tap candidates) takes the generic gathered GEMMs of gemm.hip.  The unfolded taps
+  // must span the 80 folded samples exactly: a shorter span leaves folded rows without a weight, a longer one (say taps 3,
+  // cin 40, hop 25) drops weights in the forward fold and makes conv1_unfold_sum_kernel read rows 80.. of the NEXT slab
   return g && unfolded && g->taps == 1 && g->cin == 80 && N == NOUT && g->stride_t % 2 == 0 && g->base_off % 2 == 0 &&
-         g->x_batch_stride % 2 == 0 && g->L_out > 0 && unfolded->taps >= 1 && unfolded->taps <= 3;
+         g->x_batch_stride % 2 == 0 && g->L_out > 0 && unfolded->taps >= 1 && unfolded->taps <= 3 && unfolded->cin > 0 &&
+         unfolded->stride_j >= 0 && (int64_t)unfolded->stride_j * (unfolded->taps - 1) + unfolded->cin == 80;
 }
 
 int kws_conv1_fwd(const float* x, const kws_gather_t* g, const kws_gather_t* unfolded, const float* W, float* y, int B, int N,

@@ -1,5 +1,6 @@
 // Test-only forwarders to the INTERNAL launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip), of the
-// classifier tails (tail.hip, gconv.hip kws_flat_tail_launch) and of the shared BatchNorm bookkeeping (bncols.hip kws_gbn_*).
+// classifier tails (tail.hip, gconv.hip kws_flat_tail_launch), of the shared BatchNorm bookkeeping (bncols.hip kws_gbn_*) and of
+// the raw-waveform net's first convolution (conv1.hip kws_conv1_*; tests/test_conv1_cpu.py, tests/test_conv1_kernels_gpu.py).
 // libkws_hip.so builds them with hidden visibility; tests/internal_shim.py links this file with the library's own objects into a
 // separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them (tests/test_resblock_kernels_gpu.py,
 // tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py, tests/test_bn_cols_kernels_gpu.py).  No kernels live here.
@@ -88,6 +89,25 @@ KWST_FORWARD(int, metrics_launch, (const float* per_loss, const float* per_corre
 KWST_FORWARD(int, tail_post_launch, (const kws_tail_post_args* a, int* S_out, hipStream_t st), (a, S_out, st));
 KWST_FORWARD(int, flat_tail_launch, (const kws_flat_tail_args* a, int training, hipStream_t st), (a, training, st));
 KWST_FORWARD(int, reduce_slabs_f32, (const float* ws, float* out, int64_t n, int S, hipStream_t st), (ws, out, n, S, st));
+
+// ---- the raw-waveform net's first convolution (conv1.hip) and the first stage of its two-stage slab sum (gemm.hip) ----
+KWST_FORWARD(bool, conv1_supported, (const kws_gather_t* g, const kws_gather_t* unfolded, int N), (g, unfolded, N));
+KWST_FORWARD(int, conv1_stats_rows, (int64_t M), (M));
+KWST_FORWARD(int64_t, conv1_wgrad_workspace_floats, (int64_t M), (M));
+KWST_FORWARD(int, conv1_fwd,
+             (const float* x, const kws_gather_t* g, const kws_gather_t* unfolded, const float* W, float* y, int B, int N,
+              float* stats, hipStream_t st),
+             (x, g, unfolded, W, y, B, N, stats, st));
+KWST_FORWARD(int, conv1_wgrad,
+             (const float* x, const kws_gather_t* g, const kws_gather_t* unfolded, const float* G, float* dW, int B, int N,
+              float* workspace, hipStream_t st),
+             (x, g, unfolded, G, dW, B, N, workspace, st));
+KWST_FORWARD(int, conv1_wgrad_slabs,
+             (const float* x, const kws_gather_t* g, const kws_gather_t* unfolded, const float* G, float* dW, int B, int N,
+              float* workspace, const float* const* sl_ws, float* const* sl_out, const int64_t* sl_n, const int* sl_S, int n_sl,
+              hipStream_t st),
+             (x, g, unfolded, G, dW, B, N, workspace, sl_ws, sl_out, sl_n, sl_S, n_sl, st));
+KWST_FORWARD(int, reduce_slab_groups_f32, (float* ws, int64_t n, int S, int per_group, hipStream_t st), (ws, n, S, per_group, st));
 
 // ---- BatchNorm bookkeeping over grouped columns or a column window (bncols.hip) ----
 KWST_FORWARD(int, gbn_finalize,
