@@ -1,8 +1,9 @@
 """Builds and loads libkws_internal_test.so: the library's own objects (csrc/build/*.o) plus tests/native/internal_shim.cpp, whose
 kwst_* forwarders expose the hidden launchers of the residual-network programs (resblock.hip, dwconv.hip, gemm.hip), the fused
 backward GEMM pair (gemm.hip kws_gemm_dgrad_wgrad_f32), the classifier tails (tail.hip, gconv.hip kws_flat_tail_launch), the
-BatchNorm bookkeeping shared by the grouped, depthwise, multi-slice and inception programs (bncols.hip kws_gbn_*) and the
-raw-waveform net's first convolution (conv1.hip kws_conv1_*) to ctypes; built once per process, whichever test module asks first.
+BatchNorm bookkeeping shared by the grouped, depthwise, multi-slice and inception programs (bncols.hip kws_gbn_*), the
+raw-waveform net's first convolution (conv1.hip kws_conv1_*) and the two batch launchers of bn.hip (kws_dw_grad_finalize_batch,
+kws_bn_infer_prepare_batch) to ctypes; built once per process, whichever test module asks first.
 The public kws_* entry points come from the same library (-Wl,-Bsymbolic keeps its calls inside its own copy), so every kernel a
 test compares comes from one build.  Also: the join / shortcut shapes the residual programs launch, read from the planner of
 net_logmfcc.hip through the public net API (host-side only: no GPU needed)."""
@@ -60,12 +61,15 @@ KWST_SIGNATURES = {
     "kwst_conv1_wgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "kwst_conv1_wgrad_slabs": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "kwst_reduce_slab_groups_f32": (_I, [_P, _I64, _I, _I, _P]),
+    "kwst_dw_grad_finalize_batch": (_I, [_P, _P, _P, _P, _I, _P]),
+    "kwst_bn_infer_prepare_batch": (_I, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
 }
 # the public entry points the tests compare against, taken from the same library
 PUBLIC = ["kws_last_error", "kws_dwconv_fwd_f32", "kws_dwconv_bwd_f32", "kws_dwconv_bwd_part_floats", "kws_dw_bwd_finalize",
           "kws_bn_bwd_apply", "kws_bn_relu6_apply", "kws_gemm_nn_f32", "kws_gemm_nn_stats_rows", "kws_gemm_num_row_tiles",
           "kws_gemm_tn_f32", "kws_gemm_tn_workspace_floats", "kws_gemm_gather_f32", "kws_gemm_tn_gather_f32", "kws_net_create", "kws_net_destroy", "kws_net_num_tensors",
-          "kws_net_tensor_info", "kws_net_debug_view"]
+          "kws_net_tensor_info", "kws_net_debug_view", "kws_dwconv_fwd_amax_f32", "kws_dwconv_bwd_bn_f32", "kws_dwconv_bwd_bn_amax_f32",
+          "kws_bn_bwd_apply_amax", "kws_bn_stats_finalize", "kws_bn_infer_prepare"]
 
 
 _BUILT = None    # the library this process has already built: every test module after the first reuses it

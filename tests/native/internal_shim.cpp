@@ -3,7 +3,8 @@
 // the raw-waveform net's first convolution (conv1.hip kws_conv1_*; tests/test_conv1_cpu.py, tests/test_conv1_kernels_gpu.py).
 // libkws_hip.so builds them with hidden visibility; tests/internal_shim.py links this file with the library's own objects into a
 // separate libkws_internal_test.so (-Wl,-Bsymbolic) so that Python can call them (tests/test_resblock_kernels_gpu.py,
-// tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py, tests/test_bn_cols_kernels_gpu.py).  No kernels live here.
+// tests/test_gemm_pair_gpu.py, tests/test_tail_kernels_gpu.py, tests/test_bn_cols_kernels_gpu.py) - and to the two batch launchers
+// of bn.hip that only the network programs call (tests/test_dw3_kernels_gpu.py).  No kernels live here.
 //
 // Every forwarder has exactly the parameter list of the declaration it forwards to: KWST_FORWARD static_asserts that the two
 // function types are the same, so a changed declaration fails this build instead of being cast into a wrong call.
@@ -124,6 +125,15 @@ KWST_FORWARD(int, gbn_bwd_finish,
              (float* g, const float* y, const float* bn, int64_t M, const kws_gbn_cols* c, const float* part, int rows, float* coef,
               float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st),
              (g, y, bn, M, c, part, rows, coef, dgamma0, pstride, boff, st));
+// ---- the batch launchers of bn.hip: depthwise weight gradients / inference BatchNorm tables of several layers in one launch ----
+KWST_FORWARD(int, dw_grad_finalize_batch,
+             (const float* const* part, const int* n_parts, const int* C, float* const* dw, int count, hipStream_t stream),
+             (part, n_parts, C, dw, count, stream));
+KWST_FORWARD(int, bn_infer_prepare_batch,
+             (const float* const* gamma, const float* const* beta, const float* const* mm, const float* const* mv, float eps,
+              const int* C, float* const* bn, int count, hipStream_t stream),
+             (gamma, beta, mm, mv, eps, C, bn, count, stream));
+
 // sizeof and the offset of the last member of kws_gbn_cols and kws_gbn_refs, for their ctypes mirrors
 KWST_API void kwst_gbn_struct_layout(int64_t* out4) {
   out4[0] = (int64_t)sizeof(kws_gbn_cols);

@@ -224,7 +224,9 @@ def test_transpose():
 
 # ------------------------------------------------------------------------------------------------
 # the last five: units shorter than / one past the 8-position batch of loads, channel counts whose workgroups hold 6 and
-# 32 units (C / 4 = 80, 16), and enough units (B = 300) that the capped grids of all three kernels take several strides
+# 32 units (C / 4 = 80, 16), and enough units (B = 300: 375 unit groups) that the row-writing modes, capped at 256 workgroups, take
+# a second stride - the forward kernel (750 workgroups of at most 4096) and pass 2 (375 of at most 1024) do not stride here; their
+# grid-stride loops are reached in tests/test_dw3_kernels_gpu.py
 @pytest.mark.parametrize("Lin,stride,pad,C,with_bn,B", [(399, 1, (0, 0), 128, True, 5), (397, 2, (1, 1), 128, True, 5),
                                                         (22, 2, (0, 1), 384, True, 5), (11, 1, (0, 0), 512, True, 5),
                                                         (48, 1, (1, 1), 192, False, 5), (97, 2, (1, 1), 256, True, 5),
