@@ -443,6 +443,49 @@ int kws_pool2x2_bwd_f32(const float* dz, const float* y, const float* bn, float*
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Framed first convolution at narrow widths: overlapping_time_slice_stack(x, ksize, hop, 'SAME') followed by
+ * Conv1D(N, taps, strides=stride, 'valid', use_bias=False), the front end of the reference's conv_1d_time_sliced_model
+ * (model.py:716-772: ksize 40, hop 20, taps 3, stride 2, N = 32 * filter_mult).  The frames are never materialised.
+ *   fwd    y[b,t,n]  = sum_{j<taps} sum_{c<ksize} W[j,c,n] * x[b, hop*(stride*t + j) + c - pad_l]      (0 outside [0, L))
+ *          stats_part (may be NULL): kws_frame_conv_stats_rows() rows [2][N] of (sum y, sum y^2) for kws_bn_stats_finalize
+ *   wgrad  dW[j,c,n] = sum_{b,t} x[b, hop*(stride*t + j) + c - pad_l] * G[b,t,n]; overlapping taps each get their own
+ *          gradient.  workspace >= kws_frame_conv_wgrad_workspace_floats() floats (fixed-order split over the row tiles,
+ *          then a fixed-order sum): no atomics, bit-identical from run to run.  There is no input gradient (x is the waveform).
+ * x: B clips of L samples, x_batch_stride apart (8-byte aligned); W and dW [taps, ksize, N] (Keras layout, unfolded); y and G
+ * [B, Lout, N].  Domain: N 32 or 64; ksize, hop, taps >= 1 with span = hop*(taps-1) + ksize <= 128; stride 1 or 2; hop, pad_l
+ * (>= 0) and x_batch_stride (>= L) even; hop*(stride*(Lout-1) + taps-1) + ksize - pad_l <= L + span.  Anything else returns
+ * KWS_E_INVALID with nothing written (the planners return 0).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, L, Lout;          /* clips, samples per clip, output rows per clip */
+  int ksize, hop, pad_l;   /* samples per frame, samples between frames, zeros in front of a clip */
+  int taps, stride;        /* the Conv1D over the frames */
+  int N;                   /* filters */
+  int64_t x_batch_stride;
+} kws_frame_conv_t;
+int kws_frame_conv_stats_rows(const kws_frame_conv_t* d);
+int kws_frame_conv_fwd_f32(const float* x, const float* W, float* y, float* stats_part, const kws_frame_conv_t* d, void* stream);
+int64_t kws_frame_conv_wgrad_workspace_floats(const kws_frame_conv_t* d);
+int kws_frame_conv_wgrad_f32(const float* x, const float* G, float* dW, float* workspace, const kws_frame_conv_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GlobalAveragePooling1D over relu6(bn(y)) followed by Dropout: the head of the reference's conv_1d_time_sliced_model
+ * (model.py:716-772), whose pooled features feed a hidden Dense layer.  y [B, T, C] is the RAW convolution output, bn its
+ * table scale|shift|mean|rstd [4][C]; 1 <= T <= 16, C % 4 == 0, C <= 1024.
+ *   fwd  feat[b,c] = (1/T) * sum_t relu6(scale[c] * y[b,t,c] + shift[c]);  fd[b,c] = feat[b,c] * mask(b,c) / keep_prob
+ *   bwd  g[b,t,c]  = relu6'(bn(y[b,t,c])) * dfd[b,c] * mask(b,c) / (keep_prob * T), relu6' = [0 < pre <= 6].  Every element of g
+ *        [B, T, C] is written once.  part receives kws_gap_drop_bwd_part_rows() rows [2][C] of (sum g, sum g * xhat), xhat =
+ *        (y - mean) * rstd: the BatchNorm backward's reductions, to be added over the rows in a fixed order.
+ * mask: kws_dropout_fwd's counter RNG on element (row_offset + b) * C + c, key from (seed, step, layer_id); keep_prob = 1: no
+ * mask (inference).  No atomics: results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+int kws_gap_drop_fwd_f32(const float* y, const float* bn, float* feat, float* fd, int B, int T, int C, float keep_prob, uint64_t seed,
+                         uint32_t step, uint32_t layer_id, int64_t row_offset, void* stream);
+int kws_gap_drop_bwd_part_rows(int B, int T, int C);
+int kws_gap_drop_bwd_f32(const float* dfd, const float* y, const float* bn, float* g, float* part, int B, int T, int C, float keep_prob,
+                         uint64_t seed, uint32_t step, uint32_t layer_id, int64_t row_offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a11  BatchNormalization (training: biased batch moments over (B,L); eps 1e-3; momentum .99)
  *      + Activation(relu6), reference model.py:46-51, 809-810; constants SURVEY D.2.
  * The normalise+ReLU6 is never materialised: it is applied on load by the consumer through the
@@ -708,6 +751,15 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         what that layer hands on where it is materialised (pooled / dropped / last activation [B, Ho, Wo, F];
  *                         count 0 where the next convolution applies the table on load), what 2 = table of
  *                         batch_normalization_{index+1} [4][F], what 3 = the preprocessed input [B, 98, 40].
+ *   KWS_NET_CONV_1D_TIME_SLICED: conv_1d_time_sliced_model, reference model.py:716-772 (raw input, input_size % 4 == 0 and long
+ *                         enough for every block to keep a row: 12000 and 16000 are, 8000 is not; filter_mult 1 or 2): the front end
+ *                         of KWS_NET_TS_ATTENTION at 32 * filter_mult filters (kws_frame_conv_*) -> thirteen 3-tap depthwise blocks
+ *                         (stride, filters / filter_mult) = (1, 64) (2, 128) (1, 128) (2, 192) (1, 192) (2, 256) (1, 256) (2, 320)
+ *                         (1, 320) (2, 384) (1, 384) (2, 512) (1, 512), stride 2 SAME and stride 1 VALID -> [B, 3, 512 fm] at 16000
+ *                         samples -> GlobalAveragePooling1D -> Dropout(.4) (kws_gap_drop_*) -> Dense(256 fm, no bias) -> relu6 ->
+ *                         Dropout(.3) -> Dense + softmax (no bias), categorical CE.  Dropout layer ids 1 and 2 in model order.  Debug
+ *                         views: what 0 / 1 / 2 as for KWS_NET_TS_ATTENTION (y and tables 0 .. 13, z 0 .. 12), what 4 = the hidden
+ *                         Dense layer's output before relu6 [B, 256 fm].
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -728,11 +780,12 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_INCEPTION_D1 14
 #define KWS_NET_CONV_2D_MOBILE 15
 #define KWS_NET_CONV_2D_FAST 16
+#define KWS_NET_CONV_1D_TIME_SLICED 17
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;
   int num_classes;
-  int filter_mult;        /* TS_ATTENTION only */
+  int filter_mult;        /* TS_ATTENTION, RESIDUAL, XCEPTION_ATTENTION, CONV_1D_TIME_SLICED */
   int input_size;         /* 16000 (raw) or spectrogram_length*num_features */
   int spectrogram_length; /* LOG_MFCC only */
   int num_features;       /* LOG_MFCC only */

@@ -28,6 +28,7 @@ KWS_NET_XCEPTION_ATTENTION = 13
 KWS_NET_INCEPTION_D1 = 14
 KWS_NET_CONV_2D_MOBILE = 15
 KWS_NET_CONV_2D_FAST = 16
+KWS_NET_CONV_1D_TIME_SLICED = 17
 
 
 class KwsError(RuntimeError):
@@ -60,6 +61,13 @@ class Conv2dDesc(ctypes.Structure):
     applied on load when a table is given."""
     _fields_ = [(n, ctypes.c_int) for n in ("B", "H", "W", "Hout", "Wout", "kh", "kw", "sh", "sw", "dh", "dw", "pad_t",
                                             "pad_l", "Cin", "F", "act")]
+
+
+class FrameConvDesc(ctypes.Structure):
+    """kws_frame_conv_t: overlapping_time_slice_stack(ksize, hop, SAME) + Conv1D(N, taps, strides=stride) over B clips of L
+    samples -> [B, Lout, N]."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "Lout", "ksize", "hop", "pad_l", "taps", "stride", "N")] + \
+               [("x_batch_stride", ctypes.c_int64)]
 
 
 ACT_RELU6 = 0   # include/kws_hip.h: KWS_ACT_*
@@ -190,6 +198,14 @@ SIGNATURES = {
     "kws_pool2x2_bwd_part_rows": (_I, [_I, _I, _I, _I]),
     "kws_pool2x2_bwd_part_floats": (_I64, [_I, _I, _I, _I]),
     "kws_pool2x2_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "kws_frame_conv_stats_rows": (_I, [ctypes.POINTER(FrameConvDesc)]),
+    "kws_frame_conv_fwd_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(FrameConvDesc), _P]),
+    "kws_frame_conv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(FrameConvDesc)]),
+    "kws_frame_conv_wgrad_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(FrameConvDesc), _P]),
+    "kws_gap_drop_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _I64, _P]),
+    "kws_gap_drop_bwd_part_rows": (_I, [_I, _I, _I]),
+    "kws_gap_drop_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _I64,
+                                  _P]),
     "kws_avgpool3_same_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "kws_avgpool3_same_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "kws_stem_stats_rows": (_I, [_I, _I]),

@@ -678,6 +678,7 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     case KWS_NET_INCEPTION_D1: rc = inc_build(n); break;
     case KWS_NET_CONV_2D_MOBILE:
     case KWS_NET_CONV_2D_FAST: rc = c2n_build(n); break;
+    case KWS_NET_CONV_1D_TIME_SLICED: rc = tsl_build(n); break;
     default:
       kws_set_error("net_create: kind %d not supported", cfg->kind);
       rc = KWS_E_INVALID;

@@ -39,7 +39,6 @@ struct DkProgram : NetProgram {
 
 constexpr float DK_DROP_KEEP = 0.7f;   // Dropout(0.3), model.py:502, 504
 constexpr int DK_HIDDEN = 256;         // Dense(256), model.py:503
-constexpr int DK_BIAS_SLICES = 32;
 constexpr int DK_GRU_UNITS = 128;      // GRU(128, ...), model.py:148
 constexpr float DK_GRU_KEEP = 0.8f;    // dropout=0.2, recurrent_dropout=0.2
 
@@ -81,6 +80,15 @@ __global__ __launch_bounds__(256) void dk_bias_grad_fold_kernel(const float* __r
   dbias[i] = sum;
 }
 
+}  // namespace
+
+// (declared in net_internal.h: net_time_sliced.hip's head is this one without the bias)
+int dk_bias_table(const float* bias, int n, float* tab, hipStream_t st) {
+  hipLaunchKernelGGL(dk_bias_table_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, bias, n, tab);
+  KWS_LAUNCH_CHECK("dk_bias_table_kernel");
+  return KWS_OK;
+}
+
 // the hidden layer's backward through bias + relu6: gradient wrt relu6(h + bias) -> gradient wrt h, in place; dbias may be NULL
 // (a hidden layer without bias: conv_1d_time_sliced has this head with use_bias=False)
 int dk_bias_relu6_bwd(float* d, const float* h, const float* bias, float* dbias, int B, int n, float* part, hipStream_t st) {
@@ -95,6 +103,8 @@ int dk_bias_relu6_bwd(float* d, const float* h, const float* bias, float* dbias,
   }
   return KWS_OK;
 }
+
+namespace {
 
 struct DkLayout {
   int64_t total = 0;
@@ -225,10 +235,7 @@ int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, floa
     feat = ws + lo.fd1;
   }
   KWS_TRY(kws_gemm_nn_f32(feat, params + p.d1k, ws + lo.h, B, p.D, p.H, nullptr, st));
-  hipLaunchKernelGGL(dk_bias_table_kernel, dim3((unsigned)ceil_div(p.H, 256)), dim3(256), 0, st,
-                     p.d1b >= 0 ? params + p.d1b : nullptr, p.H, ws + lo.tab);
-  KWS_LAUNCH_CHECK("dk_bias_table_kernel");
-  return KWS_OK;
+  return dk_bias_table(p.d1b >= 0 ? params + p.d1b : nullptr, p.H, ws + lo.tab, st);
 }
 
 // bias + relu6 + Dropout (layer 2) of the hidden layer, Dense + softmax (+ loss and its backward): the flat tail over (h, table)

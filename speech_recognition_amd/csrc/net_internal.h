@@ -6,6 +6,7 @@
 //                    conv_1d_mfcc_and_raw, xception_with_attention
 //   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
+//   net_time_sliced.hip  conv_1d_time_sliced
 //   net_mts.hip      conv_1d_multi_time_sliced
 //   net_inception.hip  inception_d1
 //   net_conv2d.hip   conv_2d_mobile, conv_2d_fast
@@ -104,6 +105,7 @@ int dk_build(kws_net* n);        // net_dwk.hip
 int mt_build(kws_net* n);        // net_mts.hip
 int inc_build(kws_net* n);       // net_inception.hip
 int c2n_build(kws_net* n);       // net_conv2d.hip
+int tsl_build(kws_net* n);       // net_time_sliced.hip
 
 // ---- pieces the programs share (net.hip) -------------------------------------------------------------------------------
 // KWS_E_WORKSPACE with its message when the caller's workspace is too small; who = "net_predict" / "net_train_fwd_bwd"
@@ -113,6 +115,13 @@ int kws_workspace_check(const char* who, int64_t need_bytes, int64_t ws_bytes, i
 int kws_flat_tail_train(kws_flat_tail_args* t, const float* labels, float* fd, float* dl, float* dA, float* per_loss,
                         float* per_correct, uint64_t seed, uint32_t step, int loss_batch, int64_t row_offset, float* metrics,
                         hipStream_t st);
+
+// ---- the hidden Dense layer of conv_1d_gru and conv_1d_time_sliced (net_dwk.hip) ------------------------------------------
+constexpr int DK_BIAS_SLICES = 32;
+// tab [4][n] = 1 | bias (0 without one) | 0 | 1: what the flat tail reads as a BatchNorm table over the layer's output
+int dk_bias_table(const float* bias, int n, float* tab, hipStream_t st);
+// gradient wrt relu6(h + bias) -> gradient wrt h, in place on d [B, n]; bias and dbias may be NULL; part: DK_BIAS_SLICES * n floats
+int dk_bias_relu6_bwd(float* d, const float* h, const float* bias, float* dbias, int B, int n, float* part, hipStream_t st);
 
 // ---- the k-wide depthwise-separable block of net_dwk.hip and net_mts.hip (net_sepblock.hip) ------------------------------
 // DepthwiseConv2D((1, k), strides) -> Conv1D(cout, 1) -> BatchNormalization -> relu6

@@ -1,14 +1,15 @@
 """Host-side mirror of the reference's model.py for the accelerated models: `speech_model`
 dispatch (reference model.py:1729-1781), `prepare_model_settings` (model.py:1785-1829) and the two
 symbols checkpoints name as custom objects (`relu6` model.py:30-31, `overlapping_time_slice_stack`
-model.py:67-76).  The layer graphs themselves are native network programs in csrc/net.hip."""
+model.py:67-76).  The layer graphs themselves are native network programs in csrc/net*.hip (conv_1d_time_sliced:
+csrc/net_time_sliced.hip, whose first convolution is csrc/frame_conv.hip and whose pooled head is csrc/gap.hip)."""
 from . import _lib
 from .keras_api import SGD, Adam, Model, RMSprop
 from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
                'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
-               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast')
+               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast', 'conv_1d_time_sliced')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -81,6 +82,15 @@ def conv_1d_time_sliced_with_attention_model(input_size=16000, num_classes=11, f
     head, RMSprop(1e-3), label-smoothed CE (0.1), categorical accuracy."""
     net = DeviceNet(_lib.KWS_NET_TS_ATTENTION, num_classes, filter_mult=filter_mult, input_size=input_size)
     return Model(net, RMSprop(lr=1e-3), name='conv_1d_time_sliced_with_attention')
+
+
+def conv_1d_time_sliced_model(input_size=16000, num_classes=11, filter_mult=1):
+    """reference model.py:716-772: the model the attention net grew out of - the same time-slice front end at 32 * filter_mult
+    filters (Conv1D(3, strides=2) over overlapping_time_slice_stack(x, 40, 20)), thirteen 3-tap depthwise / pointwise blocks
+    (64 ... 512 * filter_mult) -> GlobalAveragePooling1D -> Dropout(.4) -> Dense(256 * filter_mult, no bias) + relu6 -> Dropout(.3)
+    -> Dense (no bias, l2 1e-5); RMSprop(1e-3), categorical CE."""
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_TIME_SLICED, num_classes, filter_mult=filter_mult, input_size=input_size)
+    return Model(net, RMSprop(lr=1e-3), name='conv_1d_time_sliced', loss='cce')
 
 
 def conv_1d_log_mfcc_model(input_size=16000, num_classes=11, *args, **kwargs):
@@ -250,6 +260,8 @@ def xception_with_attention_model(input_size=16000, num_classes=11, filter_mult=
 def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
     if model_type == 'conv_1d_time_sliced_with_attention':
         return conv_1d_time_sliced_with_attention_model(input_size, num_classes)
+    if model_type == 'conv_1d_time_sliced':
+        return conv_1d_time_sliced_model(input_size, num_classes)
     if model_type == 'conv_1d_log_mfcc':
         return conv_1d_log_mfcc_model(input_size, num_classes, *args, **kwargs)
     if model_type == 'conv_1d_spectrogram':
