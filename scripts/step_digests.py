@@ -3,7 +3,10 @@ model one predict and one train_fwd_bwd at batch 3, then a second train_fwd_bwd 
 probs, grads, state and metrics (and whether all of them are finite).  Weights come from a fixed NumPy seed, with gammas of both signs and moving statistics off 0 / 1
 (tests/net_parity.perturb's idea).  Two builds that agree on every digest compute the same bits; a digest says nothing across
 compiler versions, which is why this is a comparison tool and not a test.
-usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--out FILE]"""
+--set ladder: the two nets on the shared 3-tap depthwise ladder (csrc/net_dw3ladder.hip) instead - the raw-waveform attention net under
+GEMM modes 0, 1 and 2 (modes 0 and 1 also as the split step at blocks 1 and 6, with the gradients that are final between the parts)
+and conv_1d_time_sliced under modes 0 and 1.
+usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -27,6 +30,14 @@ MODELS = [  # (name, kind, input_size)
     ('conv_1d_multi_time_sliced', _lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 16000),
     ('inception_d1', _lib.KWS_NET_INCEPTION_D1, 16000),
 ]
+LADDER = [  # (name, kind, filter_mult, input_size, gemm modes, split step)
+    ('ts_attention_fm1_16000', _lib.KWS_NET_TS_ATTENTION, 1, 16000, (0, 1, 2), True),
+    ('ts_attention_fm2_16000', _lib.KWS_NET_TS_ATTENTION, 2, 16000, (0, 1, 2), True),   # the first convolution's gathered-GEMM fall-back
+    ('ts_attention_fm1_12000', _lib.KWS_NET_TS_ATTENTION, 1, 12000, (0, 1, 2), True),
+    ('conv_1d_time_sliced_fm1_16000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 1, 16000, (0, 1), False),
+    ('conv_1d_time_sliced_fm2_12000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 2, 12000, (0, 1), False),
+]
+SPLITS = (1, 6)
 NC = 12
 
 
@@ -63,8 +74,8 @@ def batch(B, input_size, seed):
     return torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
 
 
-def model_digests(name, kind, input_size):
-    net = DeviceNet(kind, NC, input_size=input_size, seed=1234)
+def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=False):
+    net = DeviceNet(kind, NC, filter_mult=filter_mult, input_size=input_size, seed=1234, gemm_mode=gemm_mode)
     net.set_weights(perturbed_weights(net, 99))
     out = {}
     x, y = batch(3, input_size, 7)
@@ -72,15 +83,27 @@ def model_digests(name, kind, input_size):
     out['train_b3'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=1))
     x, y = batch(16, input_size, 8)
     out['train_b16'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=2))
+    if split:
+        x, y = batch(3, input_size, 9)
+        for k, sb in enumerate(SPLITS):
+            net.train_fwd_bwd_part(1, sb, x, y, seed=5, step=3 + k)
+            torch.cuda.synchronize()
+            ready = sha(net.grads[net.grad_ready_offset(sb):])
+            out['split%d_b3' % sb] = dict(digests(net, net.train_fwd_bwd_part(2, sb, x, y, seed=5, step=3 + k)), ready_grads=ready)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder'))
     a = ap.parse_args()
     torch.cuda.set_device(0)
-    res = dict((name, model_digests(name, kind, size)) for name, kind, size in MODELS)
+    if a.set == 'ladder':
+        res = dict(('%s_mode%d' % (name, m), model_digests(name, kind, size, fm, m, split and m != 2))
+                   for name, kind, fm, size, modes, split in LADDER for m in modes)
+    else:
+        res = dict((name, model_digests(name, kind, size)) for name, kind, size in MODELS)
     text = json.dumps(res, indent=1, sort_keys=True)
     print(text)
     if a.out:

@@ -196,6 +196,23 @@ struct KwsSlabQueue {
     used = 0;           // the pieces are free again: later GEMMs follow the sum in stream order
     return rc;
   }
+  // slabs someone else wrote, outside `base` (S_ < 0: |S_| slabs in kws_small_wgrad_launch's summation order)
+  int push(const float* slabs, float* dW, int64_t n_, int S_, hipStream_t st) {
+    if (count == KWS_SLAB_BATCH) {
+      const int rc = flush(st);
+      if (rc) return rc;
+    }
+    ws[count] = slabs; out[count] = dW; n[count] = n_; S[count] = S_;
+    ++count;
+    return 0;
+  }
+  // for a launch that sums the queued entries (ws / out / n / S) itself in place of flush(): their number; the queue is empty afterwards
+  int hand_over() {
+    const int c = count;
+    count = 0;
+    used = 0;
+    return c;
+  }
   int gemm(const float* A, const float* G, float* dW, int64_t M, int K, int N, hipStream_t st) {
     const int64_t need = (kws_gemm_tn_workspace_floats(M, K, N) + 63) / 64 * 64;
     if (count == KWS_SLAB_BATCH || used + need > cap) {

@@ -5,13 +5,12 @@
 //
 //   KWS_NET_TS_ATTENTION  conv_1d_time_sliced_with_attention_model   reference model.py:775-838
 //
-// Data flow per depthwise block l (training):
+// Data flow per depthwise block l (training; the blocks are the ladder of net_dw3ladder.hip, shared with net_time_sliced.hip):
 //   z_l = dw_l( relu6(bn_{l-1}(y_{l-1})) )      BN+ReLU6 applied on load, never materialised
 //   y_l = z_l W_l                                f32 MFMA GEMM, BN statistics in the epilogue
 // Backward keeps two scratch tensors (G: gradient wrt a BN output / pre-BN tensor, DZ: gradient wrt
 // a depthwise output) and walks the blocks in reverse.
 #include "net_internal.h"
-#include <atomic>
 #include <math.h>
 #include <stdlib.h>
 
@@ -90,9 +89,6 @@ int kws_flat_tail_train(kws_flat_tail_args* t, const float* labels, float* fd, f
 
 namespace {
 
-constexpr float BN_EPS = KWS_BN_EPS;
-constexpr float BN_MOMENTUM = KWS_BN_MOMENTUM;
-constexpr float L2_COEF = KWS_L2_COEF;
 constexpr float DROP_KEEP = 0.6f;     // Dropout(0.4), model.py:819,828
 constexpr float LABEL_SMOOTH = 0.1f;  // model.py:835-836
 
@@ -123,32 +119,21 @@ __global__ __launch_bounds__(256) void unfold_taps_kernel(const float* __restric
 // ---- workspace layout ------------------------------------------------------------------------------
 struct Layout {
   int64_t total = 0;  // bytes
-  std::vector<int64_t> y;   // y[l], l = 0..11 (float offsets)
-  std::vector<int64_t> z;   // z[i], i = 0..10
-  int64_t G = 0, G2 = 0, DZ = 0, bn = 0, part = 0, coef = 0, tn = 0, red = 0, swg = 0, swg1 = 0;
-  std::vector<int64_t> WT;  // transposed pointwise kernel of block i (dgrad GEMM operand)
-  std::vector<int64_t> tns; // weight-gradient slabs of block i: a region of its own, summed for all blocks in ONE launch
+  Dw3Offsets a;             // the ladder's activations, BatchNorm tables and transposed pointwise kernels (float offsets)
+  int64_t G = 0, G2 = 0, DZ = 0, part = 0, coef = 0, tn = 0, red = 0, swg = 0, swg1 = 0;
+  int64_t tns = 0, tns_cap = 0;   // the blocks' weight-gradient slabs: one region, summed in ONE launch (KwsSlabQueue)
   std::vector<int64_t> WPf, WPd;  // fp16 x 2 arm: fp16 planes [2][cout][cin] (forward) / [2][cin][cout] (input gradient)
-  int64_t amax;                   // fp16 x 2 arm: 3 nb slot groups of |x| maxima: W[i] | z[i] | dy[i + 1]
+  int64_t amax = 0;               // fp16 x 2 arm: 3 nb slot groups of |x| maxima: W[i] | z[i] | dy[i + 1]
   int64_t xd = 0, fd = 0, dl1 = 0, dl2 = 0, per_loss = 0, per_correct = 0, att = 0;
   int64_t w1f = 0, g1f = 0;  // folded first-convolution kernel and its gradient [K1f, C1]
-  int64_t bn_stride = 0;
-};
-
-struct Block {   // depthwise k 3 -> pointwise -> BN -> relu6
-  int stride, pad_l, cin, cout, Lin, Lout;
-  int64_t dw, pw;  // param offsets
-  BnRef bn;        // BN after the pointwise conv
 };
 
 // The layer table of the raw-waveform attention net and its launch sequences
 struct TsProgram : NetProgram {
   const kws_net* net = nullptr;   // n_params, gemm_mode
   int L_in = 0;        // samples per clip
-  int L1 = 0, C1 = 0;  // conv1 output
   int64_t conv1 = 0;
-  BnRef bn1;
-  std::vector<Block> blocks;
+  Dw3Ladder lad;       // L1, C1, bn1: the first convolution's output
   int T = 0, C = 0, NC = 0;
   int64_t d1k = 0, d1b = 0, d2k = 0;
   kws_gather_t gather1;   // the reference's view: 3 taps of 40 samples, taps 20 samples apart (K = 120)
@@ -158,6 +143,12 @@ struct TsProgram : NetProgram {
   void make_layout(int B, bool training, Layout* lo) const;
   int fold_conv1(const float* params, float* w1f, hipStream_t st) const;
   int unfold_conv1(const float* g1f, float* grads, hipStream_t st) const;
+  // fp16 x 2 arm: the slot groups of |x| maxima of W[i] / z[i] / dy of block i's output
+  unsigned* slots(const Layout& lo, float* ws, int group, int i) const {
+    return reinterpret_cast<unsigned*>(ws + lo.amax) + (int64_t)(group * lad.nb() + i) * KWS_ABSMAX_WORDS;
+  }
+  int split_kernels(const Layout& lo, const float* params, float* ws, bool training, hipStream_t st) const;
+  int blocks_fwd(const Layout& lo, const Dw3Run& r, bool h2, float* stats) const;
   int64_t workspace_bytes(int B, int training) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
   int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
@@ -183,13 +174,14 @@ int ts_build(kws_net* n) {
   // overlapping_time_slice_stack(x, 40, 20) SAME (model.py:805) fused with Conv1D(128,3,strides=2) (model.py:807)
   int Lf, plf;
   kws_same_pad(p->L_in, 40, 20, &Lf, &plf);
-  p->L1 = (Lf - 3) / 2 + 1;
-  p->C1 = 128 * fm;
+  Dw3Ladder& lad = p->lad;
+  lad.L1 = (Lf - 3) / 2 + 1;
+  lad.C1 = 128 * fm;
   KerasNames kn{n};
-  p->conv1 = kn.conv(3, 40, p->C1, L2_COEF);
-  p->bn1 = kn.bn(p->C1);
+  p->conv1 = kn.conv(3, 40, lad.C1, KWS_L2_COEF);
+  lad.bn1 = kn.bn(lad.C1);
   kws_gather_t g;
-  g.L_out = p->L1; g.cin = 40; g.taps = 3; g.stride_t = 2 * 20; g.stride_j = 20; g.base_off = -plf;
+  g.L_out = lad.L1; g.cin = 40; g.taps = 3; g.stride_t = 2 * 20; g.stride_j = 20; g.base_off = -plf;
   g.x_len = p->L_in; g.x_batch_stride = p->L_in;
   p->gather1 = g;
   // The three taps overlap (tap j covers samples 20 j .. 20 j + 39 of an 80-sample span): the convolution is a GEMM
@@ -200,99 +192,64 @@ int ts_build(kws_net* n) {
   p->gather1f = gf;
   static const int spec[11][2] = {{1, 128}, {2, 192}, {1, 192}, {2, 256}, {1, 256}, {2, 320},
                                   {1, 320}, {2, 384}, {1, 384}, {2, 512}, {1, 512}};  // model.py:812-817
-  int L = p->L1, cin = p->C1;
-  for (int i = 0; i < 11; ++i) {
-    Block b;
-    b.stride = spec[i][0];
-    b.cin = cin;
-    b.cout = spec[i][1] * fm;
-    b.Lin = L;
-    if (b.stride == 2) {
-      kws_same_pad(L, 3, 2, &b.Lout, &b.pad_l);  // _reduce_conv: padding='same'
-    } else {
-      b.Lout = L - 2;  // _context_conv: padding='valid'
-      b.pad_l = 0;
-    }
-    KWS_REQUIRE(b.Lout >= 1, "net: input too short for block %d", i);
-    b.dw = kn.dw(cin);
-    b.pw = kn.conv(1, cin, b.cout, L2_COEF);
-    b.bn = kn.bn(b.cout);
-    p->blocks.push_back(b);
-    L = b.Lout;
-    cin = b.cout;
-  }
-  p->T = L;
-  p->C = cin;
+  KWS_TRY(lad.build(kn, spec, 11, fm, c.input_size));
+  p->T = lad.blocks.back().Lout;
+  p->C = lad.blocks.back().cout;
   p->NC = c.num_classes;
   KWS_REQUIRE(p->T <= 16, "net: %d time steps at the tail (max 16)", p->T);
-  p->d1k = kws_net_add_tensor(n, "dense_1/kernel", {(int64_t)p->T * p->C, p->T}, false, L2_COEF, p->T * p->C, p->T, 0.f);
+  p->d1k = kws_net_add_tensor(n, "dense_1/kernel", {(int64_t)p->T * p->C, p->T}, false, KWS_L2_COEF, p->T * p->C, p->T, 0.f);
   p->d1b = kws_net_add_tensor(n, "dense_1/bias", {p->T}, false, 0.f, 0, 0, 0.f);
-  p->d2k = kws_net_add_tensor(n, "dense_2/kernel", {2 * p->C, p->NC}, false, L2_COEF, 2 * p->C, p->NC, 0.f);
+  p->d2k = kws_net_add_tensor(n, "dense_2/kernel", {2 * p->C, p->NC}, false, KWS_L2_COEF, 2 * p->C, p->NC, 0.f);
   return KWS_OK;
 }
 
 int TsProgram::fold_conv1(const float* params, float* w1f, hipStream_t st) const {
   const kws_gather_t& g = gather1;
-  const int n = K1f * C1;
+  const int n = K1f * lad.C1;
   hipLaunchKernelGGL(fold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, params + conv1, w1f, g.taps, g.cin,
-                     g.stride_j, K1f, C1);
+                     g.stride_j, K1f, lad.C1);
   KWS_LAUNCH_CHECK("fold_taps_kernel");
   return KWS_OK;
 }
 int TsProgram::unfold_conv1(const float* g1f, float* grads, hipStream_t st) const {
   const kws_gather_t& g = gather1;
-  const int n = g.taps * g.cin * C1;
+  const int n = g.taps * g.cin * lad.C1;
   hipLaunchKernelGGL(unfold_taps_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, g1f, grads + conv1, g.taps, g.cin,
-                     g.stride_j, C1);
+                     g.stride_j, lad.C1);
   KWS_LAUNCH_CHECK("unfold_taps_kernel");
   return KWS_OK;
 }
 
 void TsProgram::make_layout(int B, bool training, Layout* lo) const {
   Bump bp;
-  const int nb = (int)blocks.size();
-  lo->y.assign(nb + 1, 0);
-  lo->z.assign(nb, 0);
-  int64_t max_y = (int64_t)B * L1 * C1, max_z = 0, max_part = 0, max_dwpart = 0, max_tn = 0;
-  int maxC = C1;
-  max_part = std::max((int64_t)kws_gemm_num_row_tiles((int64_t)B * L1), (int64_t)kws_conv1_stats_rows((int64_t)B * L1)) *
-             2 * C1;   // statistics rows of either first-convolution kernel
-  max_tn = std::max(kws_gemm_tn_workspace_floats((int64_t)B * L1, K1f, C1),
-                    kws_conv1_wgrad_workspace_floats((int64_t)B * L1));
-  for (int i = 0; i < nb; ++i) {
-    const Block& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    if (M * b.cout > max_y) max_y = M * b.cout;
-    if (M * b.cin > max_z) max_z = M * b.cin;
-    const int64_t p = (int64_t)kws_gemm_num_row_tiles(M) * 2 * b.cout;
-    if (p > max_part) max_part = p;
-    const int64_t dp = kws_dwconv_bwd_part_floats(B, b.Lin, b.cin);
-    if (dp > max_dwpart) max_dwpart = dp;
-    const int64_t t = std::max(kws_gemm_tn_workspace_floats(M, b.cin, b.cout),
-                               kws_gemm_tn_f16x2_workspace_floats(M, b.cin, b.cout));    // either arithmetic (run-time switch)
-    if (t > max_tn) max_tn = t;
-    if (b.cout > maxC) maxC = b.cout;
+  const int nb = lad.nb(), C1 = lad.C1;
+  const std::vector<Dw3Block>& blocks = lad.blocks;
+  const int64_t M1 = (int64_t)B * lad.L1;
+  const Dw3Sizes s = lad.sizes(B);
+  // statistics rows of either first-convolution kernel
+  const int64_t max_part =
+      std::max(s.max_part, std::max((int64_t)kws_gemm_num_row_tiles(M1), (int64_t)kws_conv1_stats_rows(M1)) * 2 * C1);
+  int64_t max_tn = std::max(kws_gemm_tn_workspace_floats(M1, K1f, C1), kws_conv1_wgrad_workspace_floats(M1));
+  lo->tns_cap = 0;
+  for (const Dw3Block& b : blocks) {
+    const int64_t M = (int64_t)B * b.Lout, t = kws_gemm_tn_workspace_floats(M, b.cin, b.cout);
+    max_tn = std::max(max_tn, std::max(t, kws_gemm_tn_f16x2_workspace_floats(M, b.cin, b.cout)));   // either arithmetic (run-time switch)
+    lo->tns_cap += (t + 63) / 64 * 64;
   }
+  lad.take_acts(bp, B, training, s, &lo->a);
   if (training) {
-    lo->y[0] = bp.take((int64_t)B * L1 * C1);
-    for (int i = 0; i < nb; ++i) {
-      const Block& b = blocks[i];
-      lo->z[i] = bp.take((int64_t)B * b.Lout * b.cin);
-      lo->y[i + 1] = bp.take((int64_t)B * b.Lout * b.cout);
-    }
-    lo->G = bp.take(max_y);
-    lo->G2 = bp.take(max_y);
-    lo->DZ = bp.take(max_z);
+    lo->G = bp.take(s.max_y);
+    lo->G2 = bp.take(s.max_y);
+    lo->DZ = bp.take(s.max_z);
     const int64_t tail_part = (int64_t)B * 5 * C;
-    lo->part = bp.take(std::max(std::max(max_part, max_dwpart), tail_part));
-    lo->coef = bp.take(2 * maxC);
-    lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * maxC);
+    lo->part = bp.take(std::max(std::max(max_part, s.max_dwpart), tail_part));
+    lo->coef = bp.take(2 * s.maxC);
+    lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * s.maxC);
     lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES *
                       std::max((int64_t)T * C * T, (int64_t)2 * C * NC));
-    // round 4: the attention dense layer's slices keep a region of their own (both dense layers' slices wait for the call's slab sum)
+    // the attention dense layer's slices keep a region of their own (both dense layers' slices wait for the call's slab sum)
     lo->swg1 = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * T * C * T);
-    lo->WT.assign(nb, 0);
-    for (int i = 0; i < nb; ++i) lo->WT[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
+    lad.take_WT(bp, &lo->a);
     lo->WPf.assign(nb, 0);
     lo->WPd.assign(nb, 0);
     for (int i = 0; i < nb; ++i) {                  // 2 fp16 per weight = 1 float; taken in every mode (1.2 M weights in all)
@@ -301,9 +258,7 @@ void TsProgram::make_layout(int B, bool training, Layout* lo) const {
     }
     lo->amax = bp.take((int64_t)3 * nb * KWS_ABSMAX_WORDS);
     lo->tn = bp.take(max_tn);
-    lo->tns.assign(nb, 0);
-    for (int i = 0; i < nb; ++i)
-      lo->tns[i] = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * blocks[i].Lout, blocks[i].cin, blocks[i].cout));
+    lo->tns = bp.take(lo->tns_cap);
     lo->xd = bp.take((int64_t)B * T * C);
     lo->fd = bp.take((int64_t)B * 2 * C);
     lo->dl1 = bp.take((int64_t)B * T);
@@ -313,21 +268,13 @@ void TsProgram::make_layout(int B, bool training, Layout* lo) const {
     lo->att = bp.take((int64_t)B * 16);
     lo->g1f = bp.take((int64_t)K1f * C1);
   } else {
-    // inference ping-pong: two y buffers and one z buffer
-    const int64_t ya = bp.take(max_y), yb = bp.take(max_y), zz = bp.take(max_z);
-    lo->y[0] = ya;
-    for (int i = 0; i < nb; ++i) {
-      lo->z[i] = zz;
-      lo->y[i + 1] = (i % 2 == 0) ? yb : ya;
-    }
     lo->part = bp.take(64);
     lo->WPf.assign(nb, 0);                          // the split-GEMM arms in inference: forward planes and |x| maxima (W | z)
     for (int i = 0; i < nb; ++i) lo->WPf[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
     lo->amax = bp.take((int64_t)2 * nb * KWS_ABSMAX_WORDS);
   }
   lo->w1f = bp.take((int64_t)K1f * C1);
-  lo->bn_stride = (4 * maxC + 63) / 64 * 64;
-  lo->bn = bp.take(lo->bn_stride * (nb + 1));
+  lad.take_bn(bp, s.maxC, &lo->a);
   lo->total = bp.cur * 4;
 }
 
@@ -340,21 +287,8 @@ int64_t TsProgram::workspace_bytes(int B, int training) const {
 int TsProgram::debug_view(int batch, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   Layout lo;
   make_layout(batch, training != 0, &lo);
-  const int nb = (int)blocks.size();
-  if (what == 0) {  // pre-BN output y[index], index 0..nb
-    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: y index %d", index);
-    *offset_floats = lo.y[index];
-    *count = index == 0 ? (int64_t)batch * L1 * C1
-                        : (int64_t)batch * blocks[index - 1].Lout * blocks[index - 1].cout;
-  } else if (what == 1) {  // depthwise output z[index]
-    KWS_REQUIRE(index >= 0 && index < nb, "net_debug_view: z index %d", index);
-    *offset_floats = lo.z[index];
-    *count = (int64_t)batch * blocks[index].Lout * blocks[index].cin;
-  } else if (what == 2) {  // bn table (scale|shift|mean|rstd) of BN index
-    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: bn index %d", index);
-    *offset_floats = lo.bn + lo.bn_stride * index;
-    *count = 4 * (index == 0 ? C1 : blocks[index - 1].cout);
-  } else if (what == 3) {  // attention weights [B, T] (training only)
+  if (what >= 0 && what <= 2) return lad.debug_view(lo.a, batch, what, index, offset_floats, count);
+  if (what == 3) {  // attention weights [B, T] (training only)
     KWS_REQUIRE(training, "net_debug_view: att is a training-only view");
     *offset_floats = lo.att;
     *count = (int64_t)batch * T;
@@ -365,66 +299,69 @@ int TsProgram::debug_view(int batch, int training, int what, int index, int64_t*
   return KWS_OK;
 }
 
+// fp16 x 2 arm (kws_net_set_gemm_mode(net, 2), gemm_f16x2.hip): maxima of the pointwise kernels (this also zeroes their slot
+// groups), zero the activations' groups, then the kernels as fp16 planes: the forward form and, in training, the input-gradient form
+int TsProgram::split_kernels(const Layout& lo, const float* params, float* ws, bool training, hipStream_t st) const {
+  const int nb = lad.nb(), per = training ? 2 : 1;
+  const float *win[24], *sin_[24];
+  int64_t wn[24];
+  void* sout[24];
+  const unsigned* ssl[24];
+  int srows[24], scols[24], str[24];
+  KWS_REQUIRE(per * nb <= 24, "net: %d blocks exceed the split batch", nb);
+  for (int i = 0; i < nb; ++i) {
+    const Dw3Block& b = lad.blocks[i];
+    win[i] = params + b.pw;
+    wn[i] = (int64_t)b.cin * b.cout;
+    for (int k = 0; k < per; ++k) {
+      const int j = per * i + k;
+      sin_[j] = win[i]; srows[j] = b.cin; scols[j] = b.cout; ssl[j] = slots(lo, ws, 0, i);
+      sout[j] = ws + (k ? lo.WPd[i] : lo.WPf[i]); str[j] = k ? 0 : 1;
+    }
+  }
+  KWS_TRY(kws_absmax_batch_f32(win, wn, slots(lo, ws, 0, 0), nb, st));
+  KWS_HIP(hipMemsetAsync(slots(lo, ws, 1, 0), 0, (size_t)per * nb * KWS_ABSMAX_WORDS * sizeof(unsigned), st));
+  return kws_f16x2_split_batch(sin_, sout, srows, scols, str, ssl, per * nb, st);
+}
+
+// The blocks' forward: the ladder's f32 step, or under the fp16 x 2 arm (h2) the split-product GEMM between the ladder's depthwise
+// step and its statistics step for every layer the arm's kernels take.  stats: the statistics rows, NULL in inference
+int TsProgram::blocks_fwd(const Layout& lo, const Dw3Run& r, bool h2, float* stats) const {
+  for (int i = 0; i < lad.nb(); ++i) {
+    const Dw3Block& b = lad.blocks[i];
+    const int64_t M = (int64_t)r.B * b.Lout;
+    unsigned* zs = h2 ? slots(lo, r.ws, 1, i) : nullptr;
+    if (h2 && kws_gemm_nn_f16x2_supported(M, b.cin, b.cout)) {
+      KWS_TRY(lad.fwd_dw(i, r, zs));
+      KWS_TRY(kws_gemm_nn_f16x2_f32(r.z(i), r.ws + lo.WPf[i], r.y(i + 1), M, b.cin, b.cout, zs, slots(lo, r.ws, 0, i), stats, r.st));
+      if (stats) KWS_TRY(lad.stats_finalize(i, r, stats, kws_gemm_nn_f16x2_stats_rows(M)));
+    } else {
+      KWS_TRY(lad.fwd_block_f32(i, r, stats, zs));
+    }
+  }
+  return KWS_OK;
+}
+
 int TsProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
                        hipStream_t st) const {
   Layout lo;
   make_layout(B, false, &lo);
   KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  const int nb = (int)blocks.size();
-  auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
-  {  // the twelve inference tables in one launch (round 4: twelve 4.5 us launches per predict call before)
-    KWS_REQUIRE(nb + 1 <= KWS_BN_INFER_BATCH, "net: %d blocks exceed the BatchNorm table batch", nb);
-    const float *ga[KWS_BN_INFER_BATCH], *be[KWS_BN_INFER_BATCH], *mm[KWS_BN_INFER_BATCH], *mv[KWS_BN_INFER_BATCH];
-    float* tb[KWS_BN_INFER_BATCH];
-    int Cs[KWS_BN_INFER_BATCH];
-    auto put = [&](const BnRef& r, int l) {
-      ga[l] = params + r.gamma; be[l] = params + r.beta; mm[l] = state + r.mm; mv[l] = state + r.mv; tb[l] = bn_at(l); Cs[l] = r.C;
-    };
-    put(bn1, 0);
-    for (int i = 0; i < nb; ++i) put(blocks[i].bn, i + 1);
-    KWS_TRY(kws_bn_infer_prepare_batch(ga, be, mm, mv, BN_EPS, Cs, tb, nb + 1, st));
-  }
+  const int nb = lad.nb(), C1 = lad.C1;
+  const Dw3Run r{&lo.a, params, const_cast<float*>(state), nullptr, ws, B, nullptr, nullptr, nullptr, nullptr, st};   // state is only read
+  KWS_TRY(lad.infer_tables(r));
   if (kws_conv1_supported(&gather1f, &gather1, C1)) {
-    KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, ws + lo.y[0], B, C1, nullptr, st));
+    KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, r.y(0), B, C1, nullptr, st));
   } else {
     KWS_TRY(fold_conv1(params, ws + lo.w1f, st));
-    KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, ws + lo.y[0], B, C1, nullptr, st));
+    KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, r.y(0), B, C1, nullptr, st));
   }
-  // the fp16 x 2 arithmetic arm (kws_net_set_gemm_mode) in inference: forward planes of the pointwise kernels, one launch;
-  // a layer the arm's kernels cannot take (kws_gemm_nn_f16x2_supported) runs the f32 kernel
   const bool h2 = kws_net_get_gemm_mode(net) == 2;
-  unsigned* amax0 = reinterpret_cast<unsigned*>(ws + lo.amax);
-  auto w_slots = [&](int i) { return amax0 + (int64_t)i * KWS_ABSMAX_WORDS; };
-  auto z_slots = [&](int i) { return amax0 + (int64_t)(nb + i) * KWS_ABSMAX_WORDS; };
-  if (h2) {
-    const float* sin_[24];
-    void* sout[24];
-    const unsigned* ssl[24];
-    int64_t wn[24];
-    int srows[24], scols[24], str[24];
-    KWS_REQUIRE(nb <= 24, "net: %d blocks exceed the split batch", nb);
-    for (int i = 0; i < nb; ++i) {
-      sin_[i] = params + blocks[i].pw; sout[i] = ws + lo.WPf[i]; ssl[i] = w_slots(i);
-      srows[i] = blocks[i].cin; scols[i] = blocks[i].cout; str[i] = 1;
-      wn[i] = (int64_t)srows[i] * scols[i];
-    }
-    KWS_TRY(kws_absmax_batch_f32(sin_, wn, w_slots(0), nb, st));
-    KWS_HIP(hipMemsetAsync(z_slots(0), 0, (size_t)nb * KWS_ABSMAX_WORDS * sizeof(unsigned), st));
-    KWS_TRY(kws_f16x2_split_batch(sin_, sout, srows, scols, str, ssl, nb, st));
-  }
-  for (int i = 0; i < nb; ++i) {
-    const Block& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    KWS_TRY(kws_dwconv_fwd_amax_f32(ws + lo.y[i], bn_at(i), params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.stride,
-                                    b.pad_l, h2 ? z_slots(i) : nullptr, st));
-    if (h2 && kws_gemm_nn_f16x2_supported(M, b.cin, b.cout))
-      KWS_TRY(kws_gemm_nn_f16x2_f32(ws + lo.z[i], ws + lo.WPf[i], ws + lo.y[i + 1], M, b.cin, b.cout, z_slots(i), w_slots(i), nullptr, st));
-    else
-      KWS_TRY(kws_gemm_nn_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i + 1], M, b.cin, b.cout, nullptr, st));
-  }
+  if (h2) KWS_TRY(split_kernels(lo, params, ws, false, st));
+  KWS_TRY(blocks_fwd(lo, r, h2, nullptr));
   kws_ts_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
+  t.y = r.y(nb); t.bn = r.bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
   t.W2 = params + d2k; t.probs = probs; t.B = B; t.T = T; t.C = C; t.NC = NC;
   t.keep_prob = 1.f; t.loss_batch = 1; t.train = 0;
   return kws_ts_tail_launch(&t, st);
@@ -439,210 +376,127 @@ int TsProgram::train_part(const float* params, float* state, const float* x, con
   Layout lo;
   make_layout(B, true, &lo);
   KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  const int nb = (int)blocks.size();
-  auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
+  const int nb = lad.nb(), C1 = lad.C1;
   float* part = ws + lo.part;
   float* DZ = ws + lo.DZ;
   float* coef = ws + lo.coef;
   float* red = ws + lo.red;
-
+  const Dw3Run r{&lo.a, params, state, grads, ws, B, red, part, coef, DZ, st};
+  const bool conv1_direct = kws_conv1_supported(&gather1f, &gather1, C1);   // conv1.hip takes the shape; else the gathered GEMMs
   const bool run_head = phase != 2;                   // forward + tail + the late blocks' backward
-  // fp16 x 2 arm (kws_net_set_gemm_mode(net, 2), gemm_f16x2.hip): the pointwise forward, input-gradient and weight-gradient
-  // GEMMs run as three f16 MFMA products of scaled two-way operand splits; the first convolution stays f32, and so does any
-  // GEMM whose shape the arm's kernels cannot take (kws_gemm_*_f16x2_supported: K granule, 2 GB buffer views)
-  const bool h2 = kws_net_get_gemm_mode(net) == 2;
+  // Gemm mode 0: f32 MFMA, a layer's input- and weight-gradient GEMMs as one launch.  Mode 1: the same arithmetic with separate
+  // launches (the A/B reference).  Mode 2, the fp16 x 2 arm: the pointwise forward, input-gradient and weight-gradient GEMMs run as
+  // three f16 MFMA products of scaled two-way operand splits; the first convolution stays f32, and so does any GEMM whose shape
+  // the arm's kernels cannot take (kws_gemm_*_f16x2_supported: K granule, 2 GB buffer views)
   const int gmode = kws_net_get_gemm_mode(net);
-  const bool pair_bwd = gmode == 0;                          // mode 1: f32 MFMA with separate dgrad / wgrad launches
-  // fp16 x 2 arm: slot groups of the operands' |x| maxima (common.h): W of block i, z of block i, dy of block i's output
-  unsigned* amax0 = reinterpret_cast<unsigned*>(ws + lo.amax);
-  auto w_slots = [&](int i) { return amax0 + (int64_t)i * KWS_ABSMAX_WORDS; };
-  auto z_slots = [&](int i) { return amax0 + (int64_t)(nb + i) * KWS_ABSMAX_WORDS; };
-  auto g_slots = [&](int i) { return amax0 + (int64_t)(2 * nb + i) * KWS_ABSMAX_WORDS; };
-  auto transpose_all = [&]() -> int {   // the pointwise kernels [cin][cout] -> [cout][cin]: all of them in one launch
-    static_assert(KWS_TRANSPOSE_BATCH >= 11, "one batch holds every block");
-    const float* tin[KWS_TRANSPOSE_BATCH];
-    float* tout[KWS_TRANSPOSE_BATCH];
-    int trows[KWS_TRANSPOSE_BATCH], tcols[KWS_TRANSPOSE_BATCH];
-    KWS_REQUIRE(nb <= KWS_TRANSPOSE_BATCH, "net: %d blocks exceed the transpose batch", nb);
-    for (int i = 0; i < nb; ++i) {
-      tin[i] = params + blocks[i].pw; tout[i] = ws + lo.WT[i];
-      trows[i] = blocks[i].cin; tcols[i] = blocks[i].cout;
-    }
-    return kws_transpose_batch_f32(tin, tout, trows, tcols, nb, st);
-  };
-  kws_ts_tail_args t;
-  memset(&t, 0, sizeof(t));
-  int tail_S = 0;                                     // > 0: the tail's dense weight gradients wait as slices for this call's slab sum
-  if (run_head) {
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
-  if (h2) {                                         // maxima of the pointwise kernels (this also zeroes their groups), then
-    const float* win[24];                           // zero the activations' groups, then both operand forms as fp16 planes
-    int64_t wn[24];
-    const float* sin_[24];
-    void* sout[24];
-    const unsigned* ssl[24];
-    int srows[24], scols[24], str[24];
-    KWS_REQUIRE(2 * nb <= 24, "net: %d blocks exceed the split batch", nb);
-    for (int i = 0; i < nb; ++i) {
-      win[i] = params + blocks[i].pw;
-      wn[i] = (int64_t)blocks[i].cin * blocks[i].cout;
-      sin_[2 * i] = sin_[2 * i + 1] = params + blocks[i].pw;
-      srows[2 * i] = srows[2 * i + 1] = blocks[i].cin;
-      scols[2 * i] = scols[2 * i + 1] = blocks[i].cout;
-      ssl[2 * i] = ssl[2 * i + 1] = w_slots(i);
-      sout[2 * i] = ws + lo.WPf[i]; str[2 * i] = 1;
-      sout[2 * i + 1] = ws + lo.WPd[i]; str[2 * i + 1] = 0;
-    }
-    KWS_TRY(kws_absmax_batch_f32(win, wn, w_slots(0), nb, st));
-    KWS_HIP(hipMemsetAsync(z_slots(0), 0, (size_t)2 * nb * KWS_ABSMAX_WORDS * sizeof(unsigned), st));
-    KWS_TRY(kws_f16x2_split_batch(sin_, sout, srows, scols, str, ssl, 2 * nb, st));
-  }
-  // ---------------- forward ----------------
-  {
-    const int64_t M = (int64_t)B * L1;
-    if (kws_conv1_supported(&gather1f, &gather1, C1)) {
-      KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, ws + lo.y[0], B, C1, part, st));
-    } else {
-      KWS_TRY(fold_conv1(params, ws + lo.w1f, st));
-      KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, ws + lo.y[0], B, C1, part, st));
-    }
-    const int rows1 = kws_conv1_supported(&gather1f, &gather1, C1) ? kws_conv1_stats_rows(M) : kws_gemm_gather_stats_rows(M);
-    KWS_TRY(kws_bn_stats_finalize(part, rows1, M, C1, params + bn1.gamma,
-                                  params + bn1.beta, BN_EPS, BN_MOMENTUM, state + bn1.mm, state + bn1.mv,
-                                  bn_at(0), red, st));
-  }
-  for (int i = 0; i < nb; ++i) {
-    const Block& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    KWS_TRY(kws_dwconv_fwd_amax_f32(ws + lo.y[i], bn_at(i), params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.stride,
-                                    b.pad_l, h2 ? z_slots(i) : nullptr, st));
-    int stat_rows;
-    if (h2 && kws_gemm_nn_f16x2_supported(M, b.cin, b.cout)) {
-      KWS_TRY(kws_gemm_nn_f16x2_f32(ws + lo.z[i], ws + lo.WPf[i], ws + lo.y[i + 1], M, b.cin, b.cout, z_slots(i), w_slots(i), part, st));
-      stat_rows = kws_gemm_nn_f16x2_stats_rows(M);
-    } else {
-      KWS_TRY(kws_gemm_nn_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i + 1], M, b.cin, b.cout, part, st));
-      stat_rows = kws_gemm_nn_stats_rows(M, b.cin, b.cout);
-    }
-    KWS_TRY(kws_bn_stats_finalize(part, stat_rows, M, b.cout, params + b.bn.gamma, params + b.bn.beta,
-                                  BN_EPS, BN_MOMENTUM, state + b.bn.mm, state + b.bn.mv, bn_at(i + 1), red, st));
-  }
-  // ---------------- tail forward + backward ----------------
-  t.y = ws + lo.y[nb]; t.bn = bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
-  t.W2 = params + d2k; t.labels = y_onehot; t.probs = probs; t.g = ws + ((nb % 2) ? lo.G2 : lo.G); t.part = part; t.xd = ws + lo.xd;
-  t.fd = ws + lo.fd; t.dl1 = ws + lo.dl1; t.dl2 = ws + lo.dl2; t.per_loss = ws + lo.per_loss;
-  t.per_correct = ws + lo.per_correct; t.att = ws + lo.att; t.B = B; t.T = T; t.C = C; t.NC = NC; t.seed = seed;
-  t.step = step; t.keep_prob = DROP_KEEP; t.label_smoothing = LABEL_SMOOTH; t.loss_batch = loss_batch;
-  t.row_offset = row_offset; t.train = 1;
-  KWS_TRY(kws_ts_tail_launch(&t, st));
-  // off the dependency chain: metrics, the two dense layers' weight gradients, the attention bias gradient.  Gemm mode 0: ONE
-  // launch writes the metrics, the bias gradient and the weight gradients' SLICES (tail.hip tail_post_kernel); the slices are
-  // summed with the pointwise layers' slabs at the end of this call (in kws_small_wgrad_launch's own order: bit-identical).
-  // Mode 1 / shapes the fused kernel does not take: the six launches of rounds 1 - 3.
-  bool tail_fused = false;
-  if (pair_bwd) {
-    kws_tail_post_args tp;
-    tp.X2 = t.fd; tp.D2 = t.dl2; tp.ws2 = ws + lo.swg; tp.K2 = 2 * C; tp.N2 = NC;
-    tp.X1 = t.xd; tp.D1 = t.dl1; tp.ws1 = ws + lo.swg1; tp.K1 = T * C; tp.N1 = T;
-    tp.bias1 = grads + d1b; tp.per_loss = t.per_loss; tp.per_correct = t.per_correct; tp.metrics = metrics; tp.B = B;
-    int S_tail = 0;
-    const int rc = kws_tail_post_launch(&tp, &S_tail, st);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      tail_fused = true;
-      tail_S = S_tail;
-    }
-  }
-  if (!tail_fused) {
-  KWS_TRY(kws_metrics_launch(t.per_loss, t.per_correct, B, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(t.fd, t.dl2, grads + d2k, nullptr, B, 2 * C, NC, ws + lo.swg, st));
-  KWS_TRY(kws_small_wgrad_launch(t.xd, t.dl1, grads + d1k, grads + d1b, B, T * C, T,
-                                 ws + lo.swg, st));
-  }
-  {
-    const BnRef& r = blocks[nb - 1].bn;
-    KWS_TRY(kws_dw_bwd_finalize(part, B, (int64_t)B * T, r.C, nullptr, grads + r.gamma,
-                                grads + r.beta, coef, red, st));
-  }
-  }  // run_head
-  // ---------------- backward through the blocks ----------------
-  // One stream: the weight-gradient GEMM of a block depends only on dy and z and COULD run beside the HBM-bound depthwise /
-  // BN kernels, but the early-layer GEMMs (32 FLOP/B) draw 3.7 TB/s themselves - with the fused two-pass depthwise
-  // backward a side-stream program took the same 5.14 - 5.20 ms (measured in rounds 1 and 2, then removed).
-  // The f32 dgrad GEMMs read the pointwise kernels transposed (the fp16 arm too, for the layers it hands back)
-  if (run_head) KWS_TRY(transpose_all());
-  float* Gb[2] = {ws + lo.G, ws + lo.G2};          // gradient wrt y[l] lives in Gb[l % 2]; the tail wrote Gb[nb % 2]
-  // the f32 weight-gradient GEMMs leave their slabs in per-block regions; ONE launch sums them when this call's blocks are done
-  const float* sl_ws[KWS_SLAB_BATCH];
-  float* sl_out[KWS_SLAB_BATCH];
-  int64_t sl_n[KWS_SLAB_BATCH];
-  int sl_S[KWS_SLAB_BATCH], n_sl = 0;
+  const bool h2 = gmode == 2;
+  auto w_slots = [&](int i) { return slots(lo, ws, 0, i); };
+  auto z_slots = [&](int i) { return slots(lo, ws, 1, i); };
+  auto g_slots = [&](int i) { return slots(lo, ws, 2, i); };
+  float* Gb[2] = {ws + lo.G, ws + lo.G2};          // gradient wrt y[l] lives in Gb[l % 2]; the tail writes Gb[nb % 2]
+  // the f32 weight-gradient GEMMs leave their slabs in lo.tns; ONE launch sums them when this call's blocks are done.  The queue
+  // cannot flush before: lo.tns_cap is the sum of the blocks' needs, and the tail's two entries + nb blocks fit one batch
+  KwsSlabQueue q;
+  q.base = ws + lo.tns;
+  q.cap = lo.tns_cap;
+  q.allow_pair = gmode == 0;
   KWS_REQUIRE(nb + 2 <= KWS_SLAB_BATCH, "net: %d blocks exceed the slab batch", nb);
-  if (tail_S > 0) {   // (negative S: kws_small_wgrad_launch's summation order)
-    sl_ws[n_sl] = ws + lo.swg; sl_out[n_sl] = grads + d2k; sl_n[n_sl] = (int64_t)2 * C * NC; sl_S[n_sl] = -tail_S; ++n_sl;
-    sl_ws[n_sl] = ws + lo.swg1; sl_out[n_sl] = grads + d1k; sl_n[n_sl] = (int64_t)T * C * T; sl_S[n_sl] = -tail_S; ++n_sl;
+  if (run_head) {
+    KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
+    if (h2) KWS_TRY(split_kernels(lo, params, ws, true, st));
+    // ---------------- forward ----------------
+    {
+      const int64_t M = (int64_t)B * lad.L1;
+      const BnRef& bn1 = lad.bn1;
+      if (conv1_direct) {
+        KWS_TRY(kws_conv1_fwd(x, &gather1f, &gather1, params + conv1, r.y(0), B, C1, part, st));
+      } else {
+        KWS_TRY(fold_conv1(params, ws + lo.w1f, st));
+        KWS_TRY(kws_gemm_gather_f32(x, &gather1f, ws + lo.w1f, r.y(0), B, C1, part, st));
+      }
+      const int rows1 = conv1_direct ? kws_conv1_stats_rows(M) : kws_gemm_gather_stats_rows(M);
+      KWS_TRY(kws_bn_stats_finalize(part, rows1, M, C1, params + bn1.gamma, params + bn1.beta, KWS_BN_EPS, KWS_BN_MOMENTUM,
+                                    state + bn1.mm, state + bn1.mv, r.bn_at(0), red, st));
+    }
+    KWS_TRY(blocks_fwd(lo, r, h2, part));
+    // ---------------- tail forward + backward ----------------
+    kws_ts_tail_args t;
+    memset(&t, 0, sizeof(t));
+    t.y = r.y(nb); t.bn = r.bn_at(nb); t.W1 = params + d1k; t.b1 = params + d1b;
+    t.W2 = params + d2k; t.labels = y_onehot; t.probs = probs; t.g = Gb[nb % 2]; t.part = part; t.xd = ws + lo.xd;
+    t.fd = ws + lo.fd; t.dl1 = ws + lo.dl1; t.dl2 = ws + lo.dl2; t.per_loss = ws + lo.per_loss;
+    t.per_correct = ws + lo.per_correct; t.att = ws + lo.att; t.B = B; t.T = T; t.C = C; t.NC = NC; t.seed = seed;
+    t.step = step; t.keep_prob = DROP_KEEP; t.label_smoothing = LABEL_SMOOTH; t.loss_batch = loss_batch;
+    t.row_offset = row_offset; t.train = 1;
+    KWS_TRY(kws_ts_tail_launch(&t, st));
+    // off the dependency chain: metrics, the two dense layers' weight gradients, the attention bias gradient.  Gemm mode 0: ONE
+    // launch writes the metrics, the bias gradient and the weight gradients' SLICES (tail.hip tail_post_kernel); the slices are
+    // queued in front of the pointwise layers' slabs and summed with them (in kws_small_wgrad_launch's own order, the negative
+    // count: bit-identical).  Mode 1 / shapes the fused kernel does not take: metrics and the two small weight-gradient launches.
+    bool tail_fused = false;
+    if (gmode == 0) {
+      kws_tail_post_args tp;
+      tp.X2 = t.fd; tp.D2 = t.dl2; tp.ws2 = ws + lo.swg; tp.K2 = 2 * C; tp.N2 = NC;
+      tp.X1 = t.xd; tp.D1 = t.dl1; tp.ws1 = ws + lo.swg1; tp.K1 = T * C; tp.N1 = T;
+      tp.bias1 = grads + d1b; tp.per_loss = t.per_loss; tp.per_correct = t.per_correct; tp.metrics = metrics; tp.B = B;
+      int S_tail = 0;
+      const int rc = kws_tail_post_launch(&tp, &S_tail, st);
+      if (rc < 0) return rc;
+      tail_fused = rc == 0;
+      if (tail_fused && S_tail > 0) {
+        KWS_TRY(q.push(ws + lo.swg, grads + d2k, (int64_t)2 * C * NC, -S_tail, st));
+        KWS_TRY(q.push(ws + lo.swg1, grads + d1k, (int64_t)T * C * T, -S_tail, st));
+      }
+    }
+    if (!tail_fused) {
+      KWS_TRY(kws_metrics_launch(t.per_loss, t.per_correct, B, metrics, st));
+      KWS_TRY(kws_small_wgrad_launch(t.fd, t.dl2, grads + d2k, nullptr, B, 2 * C, NC, ws + lo.swg, st));
+      KWS_TRY(kws_small_wgrad_launch(t.xd, t.dl1, grads + d1k, grads + d1b, B, T * C, T, ws + lo.swg, st));
+    }
+    const BnRef& last = lad.blocks[nb - 1].bn;
+    KWS_TRY(kws_dw_bwd_finalize(part, B, (int64_t)B * T, last.C, nullptr, grads + last.gamma, grads + last.beta, coef, red, st));
+    // ---------------- backward through the blocks ----------------
+    // One stream: the weight-gradient GEMM of a block depends only on dy and z and COULD run beside the HBM-bound depthwise /
+    // BN kernels, but the early-layer GEMMs (32 FLOP/B) draw 3.7 TB/s themselves - with the fused two-pass depthwise
+    // backward a side-stream program took the same 5.14 - 5.20 ms (measured, then removed).
+    // The f32 dgrad GEMMs read the pointwise kernels transposed (the fp16 arm too, for the layers it hands back)
+    KWS_TRY(lad.transpose_all(r));
   }
   const int i_hi = phase == 2 ? split - 1 : nb - 1, i_lo = phase == 1 ? split : 0;
   for (int i = i_hi; i >= i_lo; --i) {
-    const Block& b = blocks[i];
+    const Dw3Block& b = lad.blocks[i];
     const int64_t M = (int64_t)B * b.Lout;
     float* Gcur = Gb[(i + 1) % 2];
-    float* Gnext = Gb[i % 2];
-    // Gcur holds dy of this block's pointwise output: written by the depthwise backward of block i+1 (pass 2
-    // below); only the tail hands over a masked gradient that still needs its BatchNorm backward
+    // Gcur holds dy of this block's pointwise output: written by the depthwise backward of block i+1 (pass 2); only the tail
+    // hands over a masked gradient that still needs its BatchNorm backward
     if (i == nb - 1)
-      KWS_TRY(kws_bn_bwd_apply_amax(Gcur, ws + lo.y[i + 1], bn_at(i + 1), params + b.bn.gamma, coef, M, b.cout,
-                                    h2 ? g_slots(i) : nullptr, st));
-    // f32 arm, gemm mode 0 (default): the input-gradient GEMM and the weight-gradient GEMM of the layer - independent of each
-    // other - go out as ONE launch whose weight-gradient workgroups start on a CU as soon as its input-gradient workgroup has
-    // ended (gemm.hip gemm_dgrad_wgrad_kernel; same code, bit-identical dZ and slabs).  Mode 1 keeps the two launches of
-    // rounds 1 - 3 (the A/B reference), and so does any shape the fused kernel does not take (rc 1).
-    bool paired = false;
-    if (pair_bwd) {
-      const int rc = kws_gemm_dgrad_wgrad_f32(Gcur, ws + lo.WT[i], DZ, ws + lo.z[i], M, b.cin, b.cout, ws + lo.tns[i], &sl_S[n_sl], st);
-      if (rc < 0) return rc;
-      if (rc == 0) {
-        sl_ws[n_sl] = ws + lo.tns[i]; sl_out[n_sl] = grads + b.pw; sl_n[n_sl] = (int64_t)b.cin * b.cout;
-        ++n_sl;
-        paired = true;
-      }
+      KWS_TRY(kws_bn_bwd_apply_amax(Gcur, r.y(i + 1), r.bn_at(i + 1), params + b.bn.gamma, coef, M, b.cout, h2 ? g_slots(i) : nullptr, st));
+    // DZ = Gcur WT and the slabs of dW = z^T Gcur.  The two are independent: in mode 0 they go out as ONE launch whose weight-
+    // gradient workgroups start on a CU as soon as its input-gradient workgroup has ended (gemm.hip gemm_dgrad_wgrad_kernel; same
+    // code, bit-identical dZ and slabs); mode 1, and any shape the fused kernel does not take, makes the two launches
+    if (!h2) {
+      KWS_TRY(q.pair(Gcur, r.WT(i), DZ, r.z(i), grads + b.pw, M, b.cin, b.cout, st));
+    } else {
+      if (kws_gemm_nn_f16x2_supported(M, b.cout, b.cin))
+        KWS_TRY(kws_gemm_nn_f16x2_f32(Gcur, ws + lo.WPd[i], DZ, M, b.cout, b.cin, g_slots(i), w_slots(i), nullptr, st));
+      else
+        KWS_TRY(kws_gemm_nn_f32(Gcur, r.WT(i), DZ, M, b.cout, b.cin, nullptr, st));
+      if (kws_gemm_tn_f16x2_supported(M, b.cin, b.cout))
+        KWS_TRY(kws_gemm_tn_f16x2_f32(r.z(i), Gcur, grads + b.pw, M, b.cin, b.cout, z_slots(i), g_slots(i), ws + lo.tn, st));
+      else
+        KWS_TRY(q.gemm(r.z(i), Gcur, grads + b.pw, M, b.cin, b.cout, st));
     }
-    if (!paired) {
-    if (h2 && kws_gemm_nn_f16x2_supported(M, b.cout, b.cin))
-      KWS_TRY(kws_gemm_nn_f16x2_f32(Gcur, ws + lo.WPd[i], DZ, M, b.cout, b.cin, g_slots(i), w_slots(i), nullptr, st));
-    else
-      KWS_TRY(kws_gemm_nn_f32(Gcur, ws + lo.WT[i], DZ, M, b.cout, b.cin, nullptr, st));
-    if (h2 && kws_gemm_tn_f16x2_supported(M, b.cin, b.cout))
-      KWS_TRY(kws_gemm_tn_f16x2_f32(ws + lo.z[i], Gcur, grads + b.pw, M, b.cin, b.cout, z_slots(i), g_slots(i), ws + lo.tn, st));
-    else {
-      sl_ws[n_sl] = ws + lo.tns[i]; sl_out[n_sl] = grads + b.pw; sl_n[n_sl] = (int64_t)b.cin * b.cout;
-      KWS_TRY(kws_gemm_tn_slabs_f32(ws + lo.z[i], Gcur, M, b.cin, b.cout, ws + lo.tns[i], &sl_S[n_sl], st));
-      ++n_sl;
-    }
-    }
-    const BnRef& prev = (i == 0) ? bn1 : blocks[i - 1].bn;
-    // depthwise backward + BatchNorm backward of this block's input without materialising the masked
-    // gradient: reduce, fold (dw, dgamma, dbeta, c1 | c2), recompute and write dy of the previous block
-    KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y[i], bn_at(i), params + b.dw, nullptr, nullptr, part, 1, B, b.Lin, b.Lout,
-                                  b.cin, b.stride, b.pad_l, st));
-    const int n_parts = (int)(kws_dwconv_bwd_part_floats(B, b.Lin, b.cin) / (5 * b.cin));
-    KWS_TRY(kws_dw_bwd_finalize(part, n_parts, (int64_t)B * b.Lin, b.cin, grads + b.dw,
-                                grads + prev.gamma, grads + prev.beta, coef, red, st));
-    KWS_TRY(kws_dwconv_bwd_bn_amax_f32(DZ, ws + lo.y[i], bn_at(i), params + b.dw, coef, Gnext, nullptr, 2, B, b.Lin, b.Lout,
-                                       b.cin, b.stride, b.pad_l, (h2 && i > 0) ? g_slots(i - 1) : nullptr, st));
+    KWS_TRY(lad.bwd_block_input(i, r, Gb[i % 2], (h2 && i > 0) ? g_slots(i - 1) : nullptr));
   }
   // the slab sums of this call's pointwise weight gradients: beside the first convolution's weight gradient in ONE launch when
-  // that kernel runs in this call (round 4: conv1_wgrad_slabsum_kernel - the two are independent, one is MFMA / memory bound, the
+  // that kernel runs in this call (conv1_wgrad_slabsum_kernel - the two are independent, one is MFMA / memory bound, the
   // other HBM bound), their own launch otherwise (a part's gradients are final when it returns)
-  const bool sum_with_conv1 = n_sl > 0 && phase != 1 && kws_conv1_supported(&gather1f, &gather1, C1) &&
-                              kws_net_get_gemm_mode(net) != 1;
-  if (n_sl > 0 && !sum_with_conv1) KWS_TRY(kws_reduce_slabs_batch(sl_ws, sl_out, sl_n, sl_S, n_sl, st));
-  if (phase != 1) {
-    const int64_t M = (int64_t)B * L1;
-    (void)M;                                        // Gb[0] already holds dy of the first convolution
-    if (kws_conv1_supported(&gather1f, &gather1, C1)) {
-      KWS_TRY(kws_conv1_wgrad_slabs(x, &gather1f, &gather1, Gb[0], grads + conv1, B, C1, ws + lo.tn,
-                                    sl_ws, sl_out, sl_n, sl_S, sum_with_conv1 ? n_sl : 0, st));
+  const bool sum_with_conv1 = q.count > 0 && phase != 1 && conv1_direct && gmode != 1;
+  if (!sum_with_conv1) KWS_TRY(q.flush(st));
+  if (phase != 1) {                                   // Gb[0] holds dy of the first convolution
+    if (conv1_direct) {
+      KWS_TRY(kws_conv1_wgrad_slabs(x, &gather1f, &gather1, Gb[0], grads + conv1, B, C1, ws + lo.tn, q.ws, q.out, q.n, q.S,
+                                    q.hand_over(), st));
     } else {
       KWS_TRY(kws_gemm_tn_gather_f32(x, &gather1f, Gb[0], ws + lo.g1f, B, C1, ws + lo.tn, st));
       KWS_TRY(unfold_conv1(ws + lo.g1f, grads, st));
@@ -752,15 +606,15 @@ static const TsProgram* ts_program(const kws_net_t* net) {
 
 int kws_net_num_blocks(const kws_net_t* net) {
   const TsProgram* ts = ts_program(net);
-  return ts ? (int)ts->blocks.size() : 0;
+  return ts ? ts->lad.nb() : 0;
 }
 
 int64_t kws_net_grad_ready_offset(const kws_net_t* net, int split_block) {
   const TsProgram* ts = ts_program(net);
-  if (!ts || split_block < 1 || split_block >= (int)ts->blocks.size()) return -1;
+  if (!ts || split_block < 1 || split_block >= ts->lad.nb()) return -1;
   // block `split_block`'s backward writes the gradients of the BatchNorm in front of it; everything from there to the end
   // of the flat buffer (Keras layer order) is final once part 1 has run
-  return ts->blocks[split_block - 1].bn.gamma;
+  return ts->lad.blocks[split_block - 1].bn.gamma;
 }
 
 int kws_net_train_fwd_bwd_part(const kws_net_t* net, const float* params, float* state, const float* x,
@@ -772,7 +626,7 @@ int kws_net_train_fwd_bwd_part(const kws_net_t* net, const float* params, float*
   KWS_REQUIRE(loss_batch >= B, "net_train_fwd_bwd_part: loss_batch %d < B %d", loss_batch, B);
   KWS_REQUIRE(net->cfg.kind == KWS_NET_TS_ATTENTION, "net_train_fwd_bwd_part: only the raw-waveform attention net is split");
   const TsProgram* ts = ts_program(net);
-  KWS_REQUIRE((part == 1 || part == 2) && split_block >= 1 && split_block < (int)ts->blocks.size(),
+  KWS_REQUIRE((part == 1 || part == 2) && split_block >= 1 && split_block < ts->lad.nb(),
               "net_train_fwd_bwd_part: part %d split_block %d", part, split_block);
   return ts->train_part(params, state, x, y_onehot, B, grads, probs, metrics, seed, step, row_offset, loss_batch, (float*)workspace,
                         workspace_bytes, (hipStream_t)stream, part, split_block);

@@ -7,6 +7,7 @@
 //   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_time_sliced.hip  conv_1d_time_sliced
+//   net_dw3ladder.hip  no builder of its own: the 3-tap depthwise ladder (Dw3Ladder) under net.hip and net_time_sliced.hip
 //   net_mts.hip      conv_1d_multi_time_sliced
 //   net_inception.hip  inception_d1
 //   net_conv2d.hip   conv_2d_mobile, conv_2d_fast
@@ -151,6 +152,66 @@ int kws_sep_dw_bwd(const SepBlock& b, const float* params, float* grads, const f
 // dy [B * Lout, cout] -> the pointwise kernel's gradient (z: the block's depthwise output), dz, then kws_sep_dw_bwd
 int kws_sep_bwd(const SepBlock& b, const float* params, float* grads, const float* dy, const float* z, const float* in,
                 const float* bn_in, const BnRef* prod, float* out, const SepBwdScratch& s, int B, hipStream_t st);
+
+// ---- the 3-tap depthwise ladder of net.hip and net_time_sliced.hip (net_dw3ladder.hip) -----------------------------------
+// A first convolution's raw output y[0] [B, L1, C1] with its BatchNorm bn1, then blocks of
+//   z[i] = dw3_i( relu6(bn_i(y[i])) )      BN + ReLU6 of the producer applied on load, never materialised
+//   y[i + 1] = z[i] W_i                    f32 MFMA GEMM, the statistics of bn_{i+1} in its epilogue
+// The programs keep their first convolution, their head, their other buffers and the order of their workspace.
+struct Dw3Block {   // depthwise k 3 -> pointwise -> BN -> relu6
+  int stride, pad_l, cin, cout, Lin, Lout;
+  int64_t dw, pw;  // param offsets
+  BnRef bn;        // BN behind the pointwise convolution
+};
+struct Dw3Sizes {   // over y[0] and the blocks at one batch size, in floats
+  int64_t max_y = 0, max_z = 0;
+  int64_t max_part = 0;    // statistics rows of the pointwise GEMMs
+  int64_t max_dwpart = 0;  // partial rows of depthwise-backward pass 1
+  int maxC = 0;
+};
+struct Dw3Offsets {   // float offsets into the workspace
+  std::vector<int64_t> y, z;  // y[0] = first convolution, y[i + 1] / z[i] = pointwise / depthwise output of block i
+  std::vector<int64_t> WT;    // transposed pointwise kernel of block i (input-gradient GEMM operand)
+  int64_t bn = 0, bn_stride = 0;  // table l (scale|shift|mean|rstd of the BN behind y[l]) at bn + l * bn_stride
+};
+struct Dw3Run {   // one call's buffers
+  const Dw3Offsets* o;
+  const float* params;
+  float* state;   // training: moving statistics are updated
+  float* grads;   // backward only
+  float* ws;
+  int B;
+  float *red, *part, *coef, *DZ;   // reduce scratch; backward: pass-1 partial rows, the producer's coefficients, gradient wrt z[i]
+  hipStream_t st;
+  float* y(int l) const { return ws + o->y[l]; }
+  float* z(int i) const { return ws + o->z[i]; }
+  float* WT(int i) const { return ws + o->WT[i]; }
+  float* bn_at(int l) const { return ws + o->bn + o->bn_stride * l; }
+};
+struct Dw3Ladder {
+  int L1 = 0, C1 = 0;   // set, with bn1, before build()
+  BnRef bn1;
+  std::vector<Dw3Block> blocks;
+  int nb() const { return (int)blocks.size(); }
+  // spec[i] = {stride, filters}: stride 2 is a SAME block (_reduce_conv), stride 1 a VALID one (_context_conv); creates the layers
+  int build(KerasNames& kn, const int (*spec)[2], int n, int fm, int input_size);
+  Dw3Sizes sizes(int B) const;
+  // workspace pieces, each taken where the program's own order has it.  Activations: one y / z per block in training, two
+  // y buffers and one z buffer (ping-pong) in inference
+  void take_acts(Bump& bp, int B, bool training, const Dw3Sizes& s, Dw3Offsets* o) const;
+  void take_bn(Bump& bp, int maxC, Dw3Offsets* o) const;   // nb + 1 tables, each wide enough for maxC channels
+  void take_WT(Bump& bp, Dw3Offsets* o) const;
+  // what = 0: y[index], 1: z[index], 2: BatchNorm table index
+  int debug_view(const Dw3Offsets& o, int B, int what, int index, int64_t* offset_floats, int64_t* count) const;
+  int infer_tables(const Dw3Run& r) const;    // the nb + 1 inference tables from the moving statistics, one launch
+  int transpose_all(const Dw3Run& r) const;   // every pointwise kernel [cin][cout] -> WT [cout][cin], one launch
+  // the steps of block i.  amax (may be NULL): a slot group that receives the |x| maximum of the tensor the step writes
+  int fwd_dw(int i, const Dw3Run& r, unsigned* amax) const;                       // y[i] -> z[i]
+  int stats_finalize(int i, const Dw3Run& r, const float* stats, int rows) const;   // statistics rows of y[i + 1] -> table i + 1
+  int fwd_block_f32(int i, const Dw3Run& r, float* stats, unsigned* amax) const;  // both around the f32 GEMM; stats NULL: no table
+  // r.DZ = gradient wrt z[i] -> the depthwise kernel's gradient, the producing BN's dgamma / dbeta, and dy = gradient wrt y[i]
+  int bwd_block_input(int i, const Dw3Run& r, float* dy, unsigned* amax) const;
+};
 
 // ---- residual-block / log-mfcc tail launchers (resblock.hip) ------------------------------------------
 // o = maxpool_P(relu6(bn(y))) + (res_bn ? res_bn.scale*res + res_bn.shift : res)

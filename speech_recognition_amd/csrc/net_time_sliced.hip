@@ -8,8 +8,7 @@
 //   GlobalAveragePooling1D -> Dropout(.4) -> Dense(256 * fm, no bias) -> relu6 -> Dropout(.3) -> Dense(softmax, no bias, l2 1e-5)
 // with keras categorical_crossentropy.
 //   first convolution   kws_frame_conv_* (frame_conv.hip: N = 32 / 64 is outside conv1.hip)
-//   blocks              net.hip's launch forms: kws_dwconv_fwd_f32 (BN + ReLU6 of the producer applied on load), kws_gemm_nn_f32 with
-//                       the BatchNorm statistics in its epilogue, the two-pass kws_dwconv_bwd_bn_f32, and the input- and weight-
+//   blocks              the 3-tap depthwise ladder it shares with net.hip (Dw3Ladder, net_dw3ladder.hip); the input- and weight-
 //                       gradient GEMMs of a layer as one launch where the fused kernel takes the shape (KwsSlabQueue::pair; K = 32
 //                       is below its granule: two launches)
 //   head                kws_gap_drop_* (gap.hip) -> the hidden Dense product as a GEMM over the dropped features -> relu6, the second
@@ -24,17 +23,9 @@ constexpr float TSL_KEEP1 = 0.6f;   // Dropout(0.4), model.py:760
 constexpr float TSL_KEEP2 = 0.7f;   // Dropout(0.3), model.py:763
 constexpr int TSL_FRAME = 40, TSL_HOP = 20, TSL_TAPS = 3, TSL_STRIDE = 2;   // model.py:745-747
 
-struct TslBlock {   // depthwise k 3 -> pointwise -> BN -> relu6
-  int stride, pad_l, cin, cout, Lin, Lout;
-  int64_t dw, pw;  // param offsets
-  BnRef bn;        // BN behind the pointwise convolution
-};
-
 struct TslLayout {
   int64_t total = 0;             // bytes
-  std::vector<int64_t> y, z;     // y[0] = first convolution, y[i + 1] / z[i] = pointwise / depthwise output of block i
-  std::vector<int64_t> WT;       // transposed pointwise kernels
-  int64_t bn = 0, bn_stride = 0;
+  Dw3Offsets a;                  // the ladder's activations, BatchNorm tables and transposed pointwise kernels
   int64_t part = 0, red = 0, feat = 0, fd1 = 0, h = 0, tab = 0;
   int64_t G[2] = {0, 0}, DZ = 0, coef = 0, tn = 0, tns = 0, tns_cap = 0, WTd = 0, fcws = 0;
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0, bpart = 0;
@@ -42,22 +33,20 @@ struct TslLayout {
 
 struct TslProgram : NetProgram {
   const kws_net* net = nullptr;
-  int L_in = 0, L1 = 0, C1 = 0, pad1 = 0;
+  int L_in = 0, pad1 = 0;
   int64_t conv1 = 0;
-  BnRef bn1;
-  std::vector<TslBlock> blocks;
+  Dw3Ladder lad;   // L1, C1, bn1: the first convolution's output
   int T = 0, C = 0, H = 0, NC = 0;
   int64_t d1k = 0, d2k = 0;
 
   kws_frame_conv_t frame(int B) const {
     kws_frame_conv_t d;
-    d.B = B; d.L = L_in; d.Lout = L1; d.ksize = TSL_FRAME; d.hop = TSL_HOP; d.pad_l = pad1; d.taps = TSL_TAPS; d.stride = TSL_STRIDE;
-    d.N = C1; d.x_batch_stride = L_in;
+    d.B = B; d.L = L_in; d.Lout = lad.L1; d.ksize = TSL_FRAME; d.hop = TSL_HOP; d.pad_l = pad1; d.taps = TSL_TAPS; d.stride = TSL_STRIDE;
+    d.N = lad.C1; d.x_batch_stride = L_in;
     return d;
   }
   void make_layout(int B, bool training, TslLayout* lo) const;
-  int forward(const TslLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws, uint64_t seed,
-              uint32_t step, int64_t row_offset, hipStream_t st) const;
+  int forward(const TslLayout& lo, const Dw3Run& r, const float* x, bool training, uint64_t seed, uint32_t step, int64_t row_offset) const;
   kws_flat_tail_args tail_args(const TslLayout& lo, const float* params, float* ws, int B, float* probs) const;
   int64_t workspace_bytes(int B, int training) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
@@ -69,58 +58,30 @@ struct TslProgram : NetProgram {
 
 void TslProgram::make_layout(int B, bool training, TslLayout* lo) const {
   Bump bp;
-  const int nb = (int)blocks.size();
   const kws_frame_conv_t fc = frame(B);
-  lo->y.assign(nb + 1, 0);
-  lo->z.assign(nb, 0);
-  int64_t max_y = (int64_t)B * L1 * C1, max_z = 64, max_dwpart = 64;
-  int64_t max_part = (int64_t)kws_frame_conv_stats_rows(&fc) * 2 * C1;
-  int maxC = std::max(C1, H);
-  for (int i = 0; i < nb; ++i) {
-    const TslBlock& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    max_y = std::max(max_y, M * b.cout);
-    max_z = std::max(max_z, M * b.cin);
-    max_part = std::max(max_part, (int64_t)kws_gemm_num_row_tiles(M) * 2 * b.cout);
-    max_dwpart = std::max(max_dwpart, kws_dwconv_bwd_part_floats(B, b.Lin, b.cin));
-    maxC = std::max(maxC, b.cout);
-  }
-  max_part = std::max(max_part, (int64_t)kws_gap_drop_bwd_part_rows(B, T, C) * 2 * C);
-  if (training) {
-    lo->y[0] = bp.take((int64_t)B * L1 * C1);
-    for (int i = 0; i < nb; ++i) {
-      lo->z[i] = bp.take((int64_t)B * blocks[i].Lout * blocks[i].cin);
-      lo->y[i + 1] = bp.take((int64_t)B * blocks[i].Lout * blocks[i].cout);
-    }
-  } else {   // inference ping-pong: two y buffers and one z buffer
-    const int64_t ya = bp.take(max_y), yb = bp.take(max_y), zz = bp.take(max_z);
-    lo->y[0] = ya;
-    for (int i = 0; i < nb; ++i) {
-      lo->z[i] = zz;
-      lo->y[i + 1] = (i % 2 == 0) ? yb : ya;
-    }
-  }
-  lo->bn_stride = (4 * maxC + 63) / 64 * 64;
-  lo->bn = bp.take(lo->bn_stride * (nb + 1));
-  lo->part = bp.take(std::max(max_part, max_dwpart));
+  const Dw3Sizes s = lad.sizes(B);
+  const int maxC = std::max(s.maxC, H);
+  const int64_t max_part = std::max(std::max(s.max_part, (int64_t)kws_frame_conv_stats_rows(&fc) * 2 * lad.C1),
+                                    (int64_t)kws_gap_drop_bwd_part_rows(B, T, C) * 2 * C);
+  lad.take_acts(bp, B, training, s, &lo->a);
+  lad.take_bn(bp, maxC, &lo->a);
+  lo->part = bp.take(std::max(max_part, s.max_dwpart));
   lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * maxC);
   lo->feat = bp.take((int64_t)B * C);
   lo->fd1 = bp.take((int64_t)B * C);
   lo->h = bp.take((int64_t)B * H);
   lo->tab = bp.take((int64_t)4 * H);
   if (training) {
-    max_y = std::max(max_y, (int64_t)B * std::max(C, H));
-    lo->G[0] = bp.take(max_y);
-    lo->G[1] = bp.take(max_y);
-    lo->DZ = bp.take(max_z);
+    const int64_t max_g = std::max(s.max_y, (int64_t)B * std::max(C, H));
+    lo->G[0] = bp.take(max_g);
+    lo->G[1] = bp.take(max_g);
+    lo->DZ = bp.take(s.max_z);
     lo->coef = bp.take((int64_t)2 * maxC);
-    lo->WT.assign(nb, 0);
-    for (int i = 0; i < nb; ++i) lo->WT[i] = bp.take((int64_t)blocks[i].cin * blocks[i].cout);
+    lad.take_WT(bp, &lo->a);
     lo->WTd = bp.take((int64_t)C * H);
     lo->tn = bp.take(kws_gemm_tn_workspace_floats(B, C, H));
     lo->tns_cap = 0;   // the blocks' weight-gradient slabs: one region, summed in batches (KwsSlabQueue)
-    for (int i = 0; i < nb; ++i)
-      lo->tns_cap += (kws_gemm_tn_workspace_floats((int64_t)B * blocks[i].Lout, blocks[i].cin, blocks[i].cout) + 63) / 64 * 64;
+    for (const Dw3Block& b : lad.blocks) lo->tns_cap += (kws_gemm_tn_workspace_floats((int64_t)B * b.Lout, b.cin, b.cout) + 63) / 64 * 64;
     lo->tns = bp.take(lo->tns_cap);
     lo->fcws = bp.take(kws_frame_conv_wgrad_workspace_floats(&fc));
     lo->fd = bp.take((int64_t)B * H);
@@ -142,20 +103,8 @@ int64_t TslProgram::workspace_bytes(int B, int training) const {
 int TslProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   TslLayout lo;
   make_layout(B, training != 0, &lo);
-  const int nb = (int)blocks.size();
-  if (what == 0) {          // pre-BN output y[index]: 0 = the first convolution, i + 1 = block i
-    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: y index %d", index);
-    *offset_floats = lo.y[index];
-    *count = index == 0 ? (int64_t)B * L1 * C1 : (int64_t)B * blocks[index - 1].Lout * blocks[index - 1].cout;
-  } else if (what == 1) {   // depthwise output z[index]
-    KWS_REQUIRE(index >= 0 && index < nb, "net_debug_view: z index %d", index);
-    *offset_floats = lo.z[index];
-    *count = (int64_t)B * blocks[index].Lout * blocks[index].cin;
-  } else if (what == 2) {   // table of batch_normalization_{index+1}
-    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: bn index %d", index);
-    *offset_floats = lo.bn + lo.bn_stride * index;
-    *count = 4 * (index == 0 ? C1 : blocks[index - 1].cout);
-  } else if (what == 4) {   // the hidden Dense layer's output before relu6 [B, H]
+  if (what >= 0 && what <= 2) return lad.debug_view(lo.a, B, what, index, offset_floats, count);
+  if (what == 4) {   // the hidden Dense layer's output before relu6 [B, H]
     *offset_floats = lo.h;
     *count = (int64_t)B * H;
   } else {
@@ -167,41 +116,24 @@ int TslProgram::debug_view(int B, int training, int what, int index, int64_t* of
 
 // first convolution, blocks, pool + Dropout(.4) and the hidden Dense product; training: batch statistics (moving averages updated)
 // and the masks
-int TslProgram::forward(const TslLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-                        uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) const {
-  const int nb = (int)blocks.size();
-  auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
-  float* part = ws + lo.part;
-  float* red = ws + lo.red;
-  if (!training) {   // the fourteen inference tables in one launch
-    KWS_REQUIRE(nb + 1 <= KWS_BN_INFER_BATCH, "net: %d blocks exceed the BatchNorm table batch", nb);
-    const float *ga[KWS_BN_INFER_BATCH], *be[KWS_BN_INFER_BATCH], *mm[KWS_BN_INFER_BATCH], *mv[KWS_BN_INFER_BATCH];
-    float* tb[KWS_BN_INFER_BATCH];
-    int Cs[KWS_BN_INFER_BATCH];
-    auto put = [&](const BnRef& r, int l) {
-      ga[l] = params + r.gamma; be[l] = params + r.beta; mm[l] = state + r.mm; mv[l] = state + r.mv; tb[l] = bn_at(l); Cs[l] = r.C;
-    };
-    put(bn1, 0);
-    for (int i = 0; i < nb; ++i) put(blocks[i].bn, i + 1);
-    KWS_TRY(kws_bn_infer_prepare_batch(ga, be, mm, mv, KWS_BN_EPS, Cs, tb, nb + 1, st));
-  }
+int TslProgram::forward(const TslLayout& lo, const Dw3Run& r, const float* x, bool training, uint64_t seed, uint32_t step,
+                        int64_t row_offset) const {
+  const int nb = lad.nb(), B = r.B;
+  const float* params = r.params;
+  float* ws = r.ws;
+  hipStream_t st = r.st;
+  float* stats = training ? r.part : nullptr;
+  if (!training) KWS_TRY(lad.infer_tables(r));
   {
     const kws_frame_conv_t fc = frame(B);
-    KWS_TRY(kws_frame_conv_fwd_f32(x, params + conv1, ws + lo.y[0], training ? part : nullptr, &fc, st));
+    const BnRef& bn1 = lad.bn1;
+    KWS_TRY(kws_frame_conv_fwd_f32(x, params + conv1, r.y(0), stats, &fc, st));
     if (training)
-      KWS_TRY(kws_bn_stats_finalize(part, kws_frame_conv_stats_rows(&fc), (int64_t)B * L1, C1, params + bn1.gamma, params + bn1.beta,
-                                    KWS_BN_EPS, KWS_BN_MOMENTUM, state + bn1.mm, state + bn1.mv, bn_at(0), red, st));
+      KWS_TRY(kws_bn_stats_finalize(stats, kws_frame_conv_stats_rows(&fc), (int64_t)B * lad.L1, lad.C1, params + bn1.gamma,
+                                    params + bn1.beta, KWS_BN_EPS, KWS_BN_MOMENTUM, r.state + bn1.mm, r.state + bn1.mv, r.bn_at(0), r.red, st));
   }
-  for (int i = 0; i < nb; ++i) {
-    const TslBlock& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    KWS_TRY(kws_dwconv_fwd_f32(ws + lo.y[i], bn_at(i), params + b.dw, ws + lo.z[i], B, b.Lin, b.Lout, b.cin, b.stride, b.pad_l, st));
-    KWS_TRY(kws_gemm_nn_f32(ws + lo.z[i], params + b.pw, ws + lo.y[i + 1], M, b.cin, b.cout, training ? part : nullptr, st));
-    if (training)
-      KWS_TRY(kws_bn_stats_finalize(part, kws_gemm_nn_stats_rows(M, b.cin, b.cout), M, b.cout, params + b.bn.gamma, params + b.bn.beta,
-                                    KWS_BN_EPS, KWS_BN_MOMENTUM, state + b.bn.mm, state + b.bn.mv, bn_at(i + 1), red, st));
-  }
-  KWS_TRY(kws_gap_drop_fwd_f32(ws + lo.y[nb], bn_at(nb), ws + lo.feat, ws + lo.fd1, B, T, C, training ? TSL_KEEP1 : 1.f, seed, step, 1,
+  for (int i = 0; i < nb; ++i) KWS_TRY(lad.fwd_block_f32(i, r, stats, nullptr));
+  KWS_TRY(kws_gap_drop_fwd_f32(r.y(nb), r.bn_at(nb), ws + lo.feat, ws + lo.fd1, B, T, C, training ? TSL_KEEP1 : 1.f, seed, step, 1,
                                row_offset, st));
   KWS_TRY(kws_gemm_nn_f32(ws + lo.fd1, params + d1k, ws + lo.h, B, C, H, nullptr, st));
   return dk_bias_table(nullptr, H, ws + lo.tab, st);
@@ -225,7 +157,8 @@ int TslProgram::predict(const float* params, const float* state, const float* x,
   TslLayout lo;
   make_layout(B, false, &lo);
   KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(forward(lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
+  const Dw3Run r{&lo.a, params, const_cast<float*>(state), nullptr, ws, B, ws + lo.red, nullptr, nullptr, nullptr, st};   // state is only read
+  KWS_TRY(forward(lo, r, x, false, 0, 0, 0));
   kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
   return kws_flat_tail_launch(&t, 0, st);
 }
@@ -236,15 +169,14 @@ int TslProgram::train(const float* params, float* state, const float* x, const f
   TslLayout lo;
   make_layout(B, true, &lo);
   KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  const int nb = (int)blocks.size();
-  auto bn_at = [&](int l) { return ws + lo.bn + lo.bn_stride * l; };
+  const int nb = lad.nb();
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
-  float* red = ws + lo.red;
   float* DZ = ws + lo.DZ;
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
+  const Dw3Run r{&lo.a, params, state, grads, ws, B, ws + lo.red, part, coef, DZ, st};
   KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
-  KWS_TRY(forward(lo, params, state, x, B, true, ws, seed, step, row_offset, st));
+  KWS_TRY(forward(lo, r, x, true, seed, step, row_offset));
   // ---- head: G[0] = gradient wrt relu6(h) [B, H] -> wrt h; the two dense kernels' gradients; back through Dropout(.4) and the pool
   kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
   KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, G[0], ws + lo.per_loss, ws + lo.per_correct, seed, step, loss_batch,
@@ -256,44 +188,22 @@ int TslProgram::train(const float* params, float* state, const float* x, const f
   KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WTd, DZ, B, H, C, nullptr, st));
   {   // DZ = gradient wrt the dropped features [B, C] (DZ holds B * T * C floats for the last block) -> G[nb % 2] = gated gradient
       // wrt relu6(bn(y)) [B, T, C] -> dy of the last block's pointwise output, in place
-    const TslBlock& b = blocks[nb - 1];
+    const Dw3Block& b = lad.blocks[nb - 1];
     float* g = G[nb % 2];
-    KWS_TRY(kws_gap_drop_bwd_f32(DZ, ws + lo.y[nb], bn_at(nb), g, part, B, T, C, TSL_KEEP1, seed, step, 1, row_offset, st));
-    KWS_TRY(kws_gbn_layer_bwd_finish(g, ws + lo.y[nb], bn_at(nb), (int64_t)B * T, kws_gbn_grouped(1, b.cout), part,
+    KWS_TRY(kws_gap_drop_bwd_f32(DZ, r.y(nb), r.bn_at(nb), g, part, B, T, C, TSL_KEEP1, seed, step, 1, row_offset, st));
+    KWS_TRY(kws_gbn_layer_bwd_finish(g, r.y(nb), r.bn_at(nb), (int64_t)B * T, kws_gbn_grouped(1, b.cout), part,
                                      kws_gap_drop_bwd_part_rows(B, T, C), coef, grads, b.bn, st));
   }
-  // ---- blocks: G[(i + 1) % 2] = dy of block i's pointwise output (net.hip's walk)
-  {
-    static_assert(KWS_TRANSPOSE_BATCH >= 13, "one batch holds every block");
-    const float* tin[KWS_TRANSPOSE_BATCH];
-    float* tout[KWS_TRANSPOSE_BATCH];
-    int trows[KWS_TRANSPOSE_BATCH], tcols[KWS_TRANSPOSE_BATCH];
-    KWS_REQUIRE(nb <= KWS_TRANSPOSE_BATCH, "net: %d blocks exceed the transpose batch", nb);
-    for (int i = 0; i < nb; ++i) {
-      tin[i] = params + blocks[i].pw; tout[i] = ws + lo.WT[i];
-      trows[i] = blocks[i].cin; tcols[i] = blocks[i].cout;
-    }
-    KWS_TRY(kws_transpose_batch_f32(tin, tout, trows, tcols, nb, st));
-  }
+  // ---- blocks: G[(i + 1) % 2] = dy of block i's pointwise output
+  KWS_TRY(lad.transpose_all(r));
   KwsSlabQueue q;
   q.base = ws + lo.tns;
   q.cap = lo.tns_cap;
   q.allow_pair = kws_net_get_gemm_mode(net) != 1;   // mode 1: separate input- / weight-gradient launches; mode 2 is ignored
   for (int i = nb - 1; i >= 0; --i) {
-    const TslBlock& b = blocks[i];
-    const int64_t M = (int64_t)B * b.Lout;
-    float* Gcur = G[(i + 1) % 2];
-    float* Gnext = G[i % 2];
-    KWS_TRY(q.pair(Gcur, ws + lo.WT[i], DZ, ws + lo.z[i], grads + b.pw, M, b.cin, b.cout, st));
-    const BnRef& prev = (i == 0) ? bn1 : blocks[i - 1].bn;
-    // depthwise backward + BatchNorm backward of this block's input without materialising the masked gradient
-    KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y[i], bn_at(i), params + b.dw, nullptr, nullptr, part, 1, B, b.Lin, b.Lout, b.cin,
-                                  b.stride, b.pad_l, st));
-    const int n_parts = (int)(kws_dwconv_bwd_part_floats(B, b.Lin, b.cin) / (5 * b.cin));
-    KWS_TRY(kws_dw_bwd_finalize(part, n_parts, (int64_t)B * b.Lin, b.cin, grads + b.dw, grads + prev.gamma, grads + prev.beta, coef, red,
-                                st));
-    KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y[i], bn_at(i), params + b.dw, coef, Gnext, nullptr, 2, B, b.Lin, b.Lout, b.cin, b.stride,
-                                  b.pad_l, st));
+    const Dw3Block& b = lad.blocks[i];
+    KWS_TRY(q.pair(G[(i + 1) % 2], r.WT(i), DZ, r.z(i), grads + b.pw, (int64_t)B * b.Lout, b.cin, b.cout, st));
+    KWS_TRY(lad.bwd_block_input(i, r, G[i % 2], nullptr));
   }
   KWS_TRY(q.flush(st));
   // G[0] = dy of the first convolution; its input is the waveform: no input gradient
@@ -316,11 +226,12 @@ int tsl_build(kws_net* n) {
   int Lf;
   kws_same_pad(p->L_in, TSL_FRAME, TSL_HOP, &Lf, &p->pad1);
   KWS_REQUIRE(Lf >= TSL_TAPS, "net: input_size %d is too short for the first convolution", c.input_size);
-  p->L1 = (Lf - TSL_TAPS) / TSL_STRIDE + 1;
-  p->C1 = 32 * fm;
+  Dw3Ladder& lad = p->lad;
+  lad.L1 = (Lf - TSL_TAPS) / TSL_STRIDE + 1;
+  lad.C1 = 32 * fm;
   KerasNames kn{n};
-  p->conv1 = kn.conv(TSL_TAPS, TSL_FRAME, p->C1, KWS_L2_COEF);
-  p->bn1 = kn.bn(p->C1);
+  p->conv1 = kn.conv(TSL_TAPS, TSL_FRAME, lad.C1, KWS_L2_COEF);
+  lad.bn1 = kn.bn(lad.C1);
   {
     const kws_frame_conv_t fc = p->frame(1);
     KWS_REQUIRE(kws_frame_conv_stats_rows(&fc) > 0, "net: input_size %d is outside the first convolution's domain", c.input_size);
@@ -328,29 +239,9 @@ int tsl_build(kws_net* n) {
   // _context_conv(64), then six _reduce_block = _reduce_conv (stride 2, SAME) + _context_conv (VALID) (model.py:752-758)
   static const int spec[13][2] = {{1, 64},  {2, 128}, {1, 128}, {2, 192}, {1, 192}, {2, 256}, {1, 256},
                                   {2, 320}, {1, 320}, {2, 384}, {1, 384}, {2, 512}, {1, 512}};
-  int L = p->L1, cin = p->C1;
-  for (int i = 0; i < 13; ++i) {
-    TslBlock b;
-    b.stride = spec[i][0];
-    b.cin = cin;
-    b.cout = spec[i][1] * fm;
-    b.Lin = L;
-    if (b.stride == 2) {
-      kws_same_pad(L, 3, 2, &b.Lout, &b.pad_l);
-    } else {
-      b.Lout = L - 2;
-      b.pad_l = 0;
-    }
-    KWS_REQUIRE(b.Lout >= 1, "net: input_size %d is too short: block %d keeps no row", c.input_size, i);
-    b.dw = kn.dw(cin);
-    b.pw = kn.conv(1, cin, b.cout, KWS_L2_COEF);
-    b.bn = kn.bn(b.cout);
-    p->blocks.push_back(b);
-    L = b.Lout;
-    cin = b.cout;
-  }
-  p->T = L;
-  p->C = cin;
+  KWS_TRY(lad.build(kn, spec, 13, fm, c.input_size));
+  p->T = lad.blocks.back().Lout;
+  p->C = lad.blocks.back().cout;
   p->H = 256 * fm;
   p->NC = c.num_classes;
   KWS_REQUIRE(p->T <= 16, "net: %d time steps at the pool (max 16)", p->T);

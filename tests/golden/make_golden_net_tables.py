@@ -39,6 +39,8 @@ CONFIGS = {
     'conv_1d_gru': (_lib.KWS_NET_CONV_1D_GRU, 12, 1, 16000, 0, 0),
     'conv_1d_simple': (_lib.KWS_NET_CONV_1D_SIMPLE, 12, 1, 16000, 0, 0),
     'conv_1d_multi_time_sliced': (_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 12, 1, 16000, 0, 0),
+    'conv_1d_time_sliced': (_lib.KWS_NET_CONV_1D_TIME_SLICED, 12, 1, 16000, 0, 0),
+    'conv_1d_time_sliced_x2': (_lib.KWS_NET_CONV_1D_TIME_SLICED, 12, 2, 12000, 0, 0),
 }
 
 

@@ -22,7 +22,8 @@ LAYOUTS = _GOLD['layouts']
 N_VIEWS = {'ts_attention': (99, 35), 'ts_attention_32_x2': (99, 35), 'log_mfcc_32': (241, 241), 'log_mfcc_65x40': (241, 241),
            'spectrogram': (241, 241), 'steffe': (256, 256), 'residual': (260, 260), 'residual_x2': (260, 260),
            'mfcc_and_raw': (245, 245), 'conv_1d_fast': (14, 14), 'conv_1d_spec': (36, 36), 'conv_1d_time_stacked': (26, 26),
-           'conv_1d_heavy': (32, 32), 'conv_1d_gru': (82, 82), 'conv_1d_simple': (170, 106), 'conv_1d_multi_time_sliced': (64, 64)}
+           'conv_1d_heavy': (32, 32), 'conv_1d_gru': (82, 82), 'conv_1d_simple': (170, 106), 'conv_1d_multi_time_sliced': (64, 64),
+           'conv_1d_time_sliced': (105, 105), 'conv_1d_time_sliced_x2': (105, 105)}
 
 
 def _mismatches(got, gold):

@@ -29,7 +29,7 @@ def test_sampler_under_asan_ubsan(tmp_path):
 
 HIPCC = "/opt/rocm/bin/hipcc"
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wno-option-ignored", "-fno-gpu-sanitize"]
-PLANNER_TUS = ["gemm.hip", "net.hip", "net_logmfcc.hip", "dwconv.hip", "error.cpp"]
+PLANNER_TUS = ["gemm.hip", "net.hip", "net_dw3ladder.hip", "net_logmfcc.hip", "dwconv.hip", "error.cpp"]
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
