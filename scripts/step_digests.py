@@ -6,7 +6,9 @@ compiler versions, which is why this is a comparison tool and not a test.
 --set ladder: the two nets on the shared 3-tap depthwise ladder (csrc/net_dw3ladder.hip) instead - the raw-waveform attention net under
 GEMM modes 0, 1 and 2 (modes 0 and 1 also as the split step at blocks 1 and 6, with the gradients that are final between the parts)
 and conv_1d_time_sliced under modes 0 and 1.
-usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder] [--out FILE]"""
+--set pools: the six models that run the pooling kernels with [2][C] partial rows (csrc/part_rows.h): pool.hip's four, conv_2d_fast
+for pool2d.hip and conv_1d_time_sliced for gap.hip.
+usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder|pools] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -36,6 +38,11 @@ LADDER = [  # (name, kind, filter_mult, input_size, gemm modes, split step)
     ('ts_attention_fm1_12000', _lib.KWS_NET_TS_ATTENTION, 1, 12000, (0, 1, 2), True),
     ('conv_1d_time_sliced_fm1_16000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 1, 16000, (0, 1), False),
     ('conv_1d_time_sliced_fm2_12000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 2, 12000, (0, 1), False),
+]
+POOL_NAMES = ('conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_multi_time_sliced', 'inception_d1')
+POOLS = [m + (1,) for m in MODELS if m[0] in POOL_NAMES] + [  # (name, kind, input_size, filter_mult)
+    ('conv_2d_fast', _lib.KWS_NET_CONV_2D_FAST, 3920, 1),
+    ('conv_1d_time_sliced', _lib.KWS_NET_CONV_1D_TIME_SLICED, 16000, 1),
 ]
 SPLITS = (1, 6)
 NC = 12
@@ -96,12 +103,14 @@ def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=Fals
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder'))
+    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder', 'pools'))
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.set == 'ladder':
         res = dict(('%s_mode%d' % (name, m), model_digests(name, kind, size, fm, m, split and m != 2))
                    for name, kind, fm, size, modes, split in LADDER for m in modes)
+    elif a.set == 'pools':
+        res = dict((name, model_digests(name, kind, size, fm)) for name, kind, size, fm in POOLS)
     else:
         res = dict((name, model_digests(name, kind, size)) for name, kind, size in MODELS)
     text = json.dumps(res, indent=1, sort_keys=True)

@@ -12,15 +12,15 @@
 // No atomics: bit-identical from run to run.
 #include "common.h"
 #include "internal.h"
+#include "part_rows.h"
 
 namespace {
 
-constexpr int GP_THREADS = 256;
-constexpr int GP_MAXC = 1024;
+constexpr int GP_THREADS = kws_part::THREADS;
 constexpr int GP_MAXT = 16;
 
-__device__ __forceinline__ float4 gp_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float gp_gate(float pre) { return (pre > 0.f && pre <= 6.f) ? 1.f : 0.f; }
+using kws_part::gate;
+using kws_part::ld4;
 
 // 0 or `inv_keep` for the four channels c .. c + 3 of global row `row` (not masked: `inv_keep` everywhere)
 __device__ __forceinline__ float4 gp_mask4(int64_t row, int C, int c, uint32_t key, uint32_t thresh, float inv_keep, int masked) {
@@ -39,11 +39,11 @@ __global__ __launch_bounds__(GP_THREADS) void gap_drop_fwd_kernel(const float* _
   const int C4 = C >> 2;
   const int64_t b = i / C4;
   const int c = (int)(i - b * C4) * 4;
-  const float4 sc = gp_ld4(bn + c), sh = gp_ld4(bn + C + c);
+  const float4 sc = ld4(bn + c), sh = ld4(bn + C + c);
   const float* yb = y + b * T * (int64_t)C + c;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int t = 0; t < T; ++t) {
-    const float4 v = gp_ld4(yb + (int64_t)t * C);
+    const float4 v = ld4(yb + (int64_t)t * C);
     s.x += relu6f(fmaf(v.x, sc.x, sh.x));
     s.y += relu6f(fmaf(v.y, sc.y, sh.y));
     s.z += relu6f(fmaf(v.z, sc.z, sh.z));
@@ -61,7 +61,6 @@ __global__ __launch_bounds__(GP_THREADS) void gap_drop_bwd_kernel(const float* _
                                                                   const float* __restrict__ bn, float* __restrict__ g,
                                                                   float* __restrict__ part, int B, int T, int C, int R, uint32_t key,
                                                                   uint32_t thresh, float inv_keep_t, int masked, int64_t row_offset) {
-  __shared__ float red[2][GP_THREADS * 4];
   const int C4 = C >> 2;
   const int tid = threadIdx.x;
   const int r = tid / C4, c4 = tid - r * C4;
@@ -69,37 +68,24 @@ __global__ __launch_bounds__(GP_THREADS) void gap_drop_bwd_kernel(const float* _
   const int64_t b = (int64_t)blockIdx.x * R + r;
   float4 sg = make_float4(0.f, 0.f, 0.f, 0.f), sgx = sg;
   if (b < B) {
-    const float4 sc = gp_ld4(bn + c), sh = gp_ld4(bn + C + c), mean = gp_ld4(bn + 2 * C + c), rstd = gp_ld4(bn + 3 * C + c);
+    const float4 sc = ld4(bn + c), sh = ld4(bn + C + c), mean = ld4(bn + 2 * C + c), rstd = ld4(bn + 3 * C + c);
     const float4 m = gp_mask4(row_offset + b, C, c, key, thresh, inv_keep_t, masked);   // 0 or 1 / (keep T)
-    const float4 d0 = gp_ld4(dfd + b * C + c);
+    const float4 d0 = ld4(dfd + b * C + c);
     const float4 d = make_float4(d0.x * m.x, d0.y * m.y, d0.z * m.z, d0.w * m.w);   // what every row of the clip receives
     const float* yb = y + b * T * (int64_t)C + c;
     float* gb = g + b * T * (int64_t)C + c;
     for (int t = 0; t < T; ++t) {
-      const float4 yu = gp_ld4(yb + (int64_t)t * C);
-      const float4 g0 = make_float4(d.x * gp_gate(fmaf(yu.x, sc.x, sh.x)), d.y * gp_gate(fmaf(yu.y, sc.y, sh.y)),
-                                    d.z * gp_gate(fmaf(yu.z, sc.z, sh.z)), d.w * gp_gate(fmaf(yu.w, sc.w, sh.w)));
+      const float4 yu = ld4(yb + (int64_t)t * C);
+      const float4 g0 = make_float4(d.x * gate(fmaf(yu.x, sc.x, sh.x)), d.y * gate(fmaf(yu.y, sc.y, sh.y)),
+                                    d.z * gate(fmaf(yu.z, sc.z, sh.z)), d.w * gate(fmaf(yu.w, sc.w, sh.w)));
       *reinterpret_cast<float4*>(gb + (int64_t)t * C) = g0;
-      sg.x += g0.x; sg.y += g0.y; sg.z += g0.z; sg.w += g0.w;
-      sgx.x = fmaf(g0.x, (yu.x - mean.x) * rstd.x, sgx.x);
-      sgx.y = fmaf(g0.y, (yu.y - mean.y) * rstd.y, sgx.y);
-      sgx.z = fmaf(g0.z, (yu.z - mean.z) * rstd.z, sgx.z);
-      sgx.w = fmaf(g0.w, (yu.w - mean.w) * rstd.w, sgx.w);
+      KWS_PART_ACCUMULATE(sg, sgx, g0, yu, mean, rstd);
     }
   }
-  *reinterpret_cast<float4*>(&red[0][tid * 4]) = sg;
-  *reinterpret_cast<float4*>(&red[1][tid * 4]) = sgx;
-  __syncthreads();
-  for (int o = tid; o < 2 * C; o += blockDim.x) {   // the R clips of this workgroup, ascending
-    const int q = o / C, ch = o - q * C;
-    float s = 0.f;
-    for (int rr = 0; rr < R; ++rr) s += red[q][rr * C + ch];
-    part[((int64_t)blockIdx.x * 2 + q) * C + ch] = s;
-  }
+  kws_part::fold_runs(sg, sgx, part, C, R);   // the R clips of this workgroup, ascending
 }
 
-bool gp_ok(int B, int T, int C) { return B > 0 && T >= 1 && T <= GP_MAXT && C > 0 && C % 4 == 0 && C <= GP_MAXC; }
-int gp_R(int C) { return GP_THREADS / (C / 4); }
+bool gp_ok(int B, int T, int C) { return B > 0 && T >= 1 && T <= GP_MAXT && kws_part::channels_ok(C); }
 
 }  // namespace
 
@@ -120,17 +106,17 @@ int kws_gap_drop_fwd_f32(const float* y, const float* bn, float* feat, float* fd
   return KWS_OK;
 }
 
-int kws_gap_drop_bwd_part_rows(int B, int T, int C) { return gp_ok(B, T, C) ? ceil_div(B, gp_R(C)) : 0; }
+int kws_gap_drop_bwd_part_rows(int B, int T, int C) { return gp_ok(B, T, C) ? (int)kws_part::geom(B, C).grid : 0; }
 
 int kws_gap_drop_bwd_f32(const float* dfd, const float* y, const float* bn, float* g, float* part, int B, int T, int C, float keep_prob,
                          uint64_t seed, uint32_t step, uint32_t layer_id, int64_t row_offset, void* stream) {
   KWS_REQUIRE(dfd && y && bn && g && part && gp_ok(B, T, C) && keep_prob > 0.f && keep_prob <= 1.f && row_offset >= 0,
               "gap_drop_bwd: bad arguments (B=%d T=%d C=%d keep_prob=%g)", B, T, C, keep_prob);
-  const int R = gp_R(C);
+  const kws_part::Geom ge = kws_part::geom(B, C);   // one unit = a clip
   const int masked = keep_prob < 1.f;
   KwsProfScope prof("gap_drop_bwd", 8.0 * B * T * C, 4.0 * (2.0 * B * T * C + (double)B * C), (hipStream_t)stream);
-  hipLaunchKernelGGL(gap_drop_bwd_kernel, dim3((unsigned)ceil_div(B, R)), dim3((unsigned)(R * (C / 4))), 0, (hipStream_t)stream, dfd, y,
-                     bn, g, part, B, T, C, R, kws_dropout_key(seed, step, layer_id), kws_dropout_threshold(keep_prob),
+  hipLaunchKernelGGL(gap_drop_bwd_kernel, dim3((unsigned)ge.grid), dim3((unsigned)ge.block), 0, (hipStream_t)stream, dfd, y,
+                     bn, g, part, B, T, C, ge.R, kws_dropout_key(seed, step, layer_id), kws_dropout_threshold(keep_prob),
                      1.0f / (keep_prob * (float)T), masked, row_offset);
   KWS_LAUNCH_CHECK("gap_drop_bwd_kernel");
   return KWS_OK;

@@ -117,7 +117,7 @@ int kws_gbn_bwd_rows(int64_t M);
 int kws_gbn_bwd(float* dA, const float* y, const float* bn, const float* add, int64_t M, const kws_gbn_cols* c, float* part, float* coef,
                 float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
 // its last two passes alone, for a producer that wrote the gated gradient g and `rows` partial rows [2][F] of (sum g, sum g xhat)
-// itself (pool.hip kws_pool3s2_bwd_f32): dgamma / dbeta / coef from the rows, then dy in place on g
+// itself (part_rows.h; pool.hip kws_pool3s2_bwd_f32): dgamma / dbeta / coef from the rows, then dy in place on g
 int kws_gbn_bwd_finish(float* g, const float* y, const float* bn, int64_t M, const kws_gbn_cols* c, const float* part, int rows,
                        float* coef, float* dgamma0, int64_t pstride, int64_t boff, hipStream_t st);
 // gconv.hip: Flatten -> Dropout -> Dense(bias or none: bd NULL) + softmax -> categorical CE over relu6(bn(y)), y [B, D] with D = Lout * F;
@@ -132,7 +132,7 @@ struct kws_flat_tail_args {
   int raw;
 };
 int kws_flat_tail_launch(const kws_flat_tail_args* a, int training, hipStream_t st);
-// pool_same.hip: kws_pool3s2_same_fwd_f32 / _bwd_f32 with the pooled tensor z (its gradient dz) a column window of a wider
+// pool.hip: kws_pool3s2_same_fwd_f32 / _bwd_f32 with the pooled tensor z (its gradient dz) a column window of a wider
 // tensor: the pointer names the window's first column, zp is the row pitch in floats (a multiple of 4, >= C).  net_inception.hip
 int kws_pool3s2_same_fwd_pitch(const float* y, const float* bn, float* z, int zp, int B, int L, int C, hipStream_t st);
 int kws_pool3s2_same_bwd_pitch(const float* dz, int zp, const float* y, const float* bn, float* g, float* part, int B, int L, int C,

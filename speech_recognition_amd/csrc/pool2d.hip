@@ -10,19 +10,18 @@
 //         exact zeros.  In the same pass the per-workgroup BatchNorm partial sums part[row][2][C] = (sum g, sum g * xhat) go out,
 //         folded afterwards in a fixed order: no float atomics, bit-reproducible.
 // Both are HBM-bound; 16-byte loads and stores.
-#include <math.h>
-
 #include "common.h"
 #include "internal.h"
+#include "part_rows.h"
 
 namespace {
 
-constexpr int P2_THREADS = 256;
-constexpr int P2_MAXC = 1024;  // C / 4 threads of one cell fit one workgroup
+constexpr int P2_THREADS = kws_part::THREADS;
 
-__device__ __forceinline__ float4 p2_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using kws_part::ld4;
+
 __device__ __forceinline__ float4 p2_pre(const float* p, const float4 sc, const float4 sh) {
-  const float4 v = p2_ld4(p);
+  const float4 v = ld4(p);
   return make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
 }
 __device__ __forceinline__ float p2_clip(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
@@ -39,7 +38,6 @@ __device__ __forceinline__ int p2_first_max4(float a0, float a1, float a2, float
   if (a3 > m) j = 3;
   return j;
 }
-__device__ __forceinline__ float p2_gate(float pre, float hi) { return (pre > 0.f && pre <= hi) ? 1.f : 0.f; }
 
 __global__ __launch_bounds__(P2_THREADS) void pool2x2_fwd_kernel(const float* __restrict__ y, const float* __restrict__ bn,
                                                                  float* __restrict__ z, int64_t n, int H, int W, int Ho, int Wo, int C,
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(P2_THREADS) void pool2x2_fwd_kernel(const float* __
   cell /= Wo;
   const int p = (int)(cell % Ho);
   const int64_t b = cell / Ho;
-  const float4 sc = p2_ld4(bn + c), sh = p2_ld4(bn + C + c);
+  const float4 sc = ld4(bn + c), sh = ld4(bn + C + c);
   const float* y0 = y + ((b * H + 2 * p) * W + 2 * q) * (int64_t)C + c;   // 2p + 1 <= H - 1 and 2q + 1 <= W - 1
   const float* y1 = y0 + (int64_t)W * C;
   const float4 a0 = p2_clip4(p2_pre(y0, sc, sh), hi), a1 = p2_clip4(p2_pre(y0 + C, sc, sh), hi);
@@ -69,7 +67,6 @@ __global__ __launch_bounds__(P2_THREADS) void pool2x2_bwd_kernel(const float* __
                                                                  const float* __restrict__ bn, float* __restrict__ g,
                                                                  float* __restrict__ part, int64_t cells, int H, int W, int Ho, int Wo,
                                                                  int Hc, int Wc, int C, int R, float hi) {
-  __shared__ float red[2][P2_THREADS * 4];
   const int C4 = C >> 2;
   const int tid = threadIdx.x;
   const int r = tid / C4, c4 = tid - r * C4;
@@ -84,24 +81,19 @@ __global__ __launch_bounds__(P2_THREADS) void pool2x2_bwd_kernel(const float* __
     const int64_t base = ((b * H + 2 * ph) * W + 2 * pw) * (int64_t)C + c;
     const int64_t off[4] = {0, (int64_t)C, (int64_t)W * C, (int64_t)W * C + C};
     if (ph < Ho && pw < Wo) {
-      const float4 sc = p2_ld4(bn + c), sh = p2_ld4(bn + C + c), mean = p2_ld4(bn + 2 * C + c), rstd = p2_ld4(bn + 3 * C + c);
+      const float4 sc = ld4(bn + c), sh = ld4(bn + C + c), mean = ld4(bn + 2 * C + c), rstd = ld4(bn + 3 * C + c);
       float4 yv[4], pre[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        yv[e] = p2_ld4(y + base + off[e]);
+        yv[e] = ld4(y + base + off[e]);
         pre[e] = make_float4(fmaf(yv[e].x, sc.x, sh.x), fmaf(yv[e].y, sc.y, sh.y), fmaf(yv[e].z, sc.z, sh.z), fmaf(yv[e].w, sc.w, sh.w));
       }
-      const float4 d = p2_ld4(dz + ((b * Ho + ph) * Wo + pw) * (int64_t)C + c);
+      const float4 d = ld4(dz + ((b * Ho + ph) * Wo + pw) * (int64_t)C + c);
       float4 out[4];
 #define KWS_POOL2_ROUTE(f)                                                                                              \
   do {                                                                                                                  \
     const int j = p2_first_max4(p2_clip(pre[0].f, hi), p2_clip(pre[1].f, hi), p2_clip(pre[2].f, hi), p2_clip(pre[3].f, hi)); \
-    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                                     \
-      const float ge = e == j ? d.f * p2_gate(pre[e].f, hi) : 0.f;                                                      \
-      out[e].f = ge;                                                                                                    \
-      sg.f += ge;                                                                                                       \
-      sgx.f = fmaf(ge, (yv[e].f - mean.f) * rstd.f, sgx.f);                                                             \
-    }                                                                                                                   \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) out[e].f = e == j ? d.f * kws_part::gate(pre[e].f, hi) : 0.f;         \
   } while (0)
       KWS_POOL2_ROUTE(x);
       KWS_POOL2_ROUTE(y);
@@ -109,7 +101,10 @@ __global__ __launch_bounds__(P2_THREADS) void pool2x2_bwd_kernel(const float* __
       KWS_POOL2_ROUTE(w);
 #undef KWS_POOL2_ROUTE
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *reinterpret_cast<float4*>(g + base + off[e]) = out[e];
+      for (int e = 0; e < 4; ++e) {   // row-major, as the window is searched
+        *reinterpret_cast<float4*>(g + base + off[e]) = out[e];
+        KWS_PART_ACCUMULATE(sg, sgx, out[e], yv[e], mean, rstd);
+      }
     } else {
       // the last odd row / column: in no window
       const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -120,34 +115,21 @@ __global__ __launch_bounds__(P2_THREADS) void pool2x2_bwd_kernel(const float* __
       }
     }
   }
-  *reinterpret_cast<float4*>(&red[0][tid * 4]) = sg;
-  *reinterpret_cast<float4*>(&red[1][tid * 4]) = sgx;
-  __syncthreads();
-  for (int o = tid; o < 2 * C; o += blockDim.x) {   // the R cells of this workgroup, ascending
-    const int q = o / C, ch = o - q * C;
-    float s = 0.f;
-    for (int rr = 0; rr < R; ++rr) s += red[q][rr * C + ch];
-    part[((int64_t)blockIdx.x * 2 + q) * C + ch] = s;
-  }
+  kws_part::fold_runs(sg, sgx, part, C, R);   // the R cells of this workgroup, ascending
 }
 
 bool p2_ok(int B, int H, int W, int C, int act) {
-  return B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0 && C <= P2_MAXC && (act == KWS_ACT_RELU6 || act == KWS_ACT_RELU) &&
+  return B > 0 && H >= 2 && W >= 2 && kws_part::channels_ok(C) && (act == KWS_ACT_RELU6 || act == KWS_ACT_RELU) &&
          (int64_t)B * H * W * C < (1ll << 40);
 }
-struct P2Geom {
-  int Hc, Wc, R, block;
-  int64_t cells, grid;
+struct P2Geom : kws_part::Geom {
+  int Hc, Wc;
+  int64_t cells;
 };
 P2Geom p2_geom(int B, int H, int W, int C) {
-  P2Geom ge;
-  ge.Hc = (H + 1) / 2;
-  ge.Wc = (W + 1) / 2;
-  ge.R = P2_THREADS / (C / 4);
-  ge.block = ge.R * (C / 4);
-  ge.cells = (int64_t)B * ge.Hc * ge.Wc;
-  ge.grid = ceil_div64(ge.cells, ge.R);
-  return ge;
+  const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
+  const int64_t cells = (int64_t)B * Hc * Wc;
+  return P2Geom{kws_part::geom(cells, C), Hc, Wc, cells};
 }
 float p2_hi(int act) { return act == KWS_ACT_RELU ? INFINITY : 6.f; }
 

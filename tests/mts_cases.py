@@ -7,7 +7,8 @@ from mts_oracle import pool_same_argmax, pool_same_geometry, pool_same_windows
 
 # (B, L, C): both parities, the smallest L, the thread-run boundaries of forward (4 outputs) and backward (8 rows), the widest and
 # narrowest C of the ladders
-POOL_CASES = [(2, 2, 4), (2, 3, 8), (3, 20, 192), (2, 37, 128), (2, 59, 160), (2, 122, 128), (1, 1997, 32), (2, 3998, 16)]
+POOL_CASES = [(2, 2, 4), (2, 3, 8), (3, 20, 192), (2, 37, 128), (2, 59, 160), (2, 122, 128), (1, 1997, 32), (2, 3998, 16),
+              (2, 5, 1024), (2, 8, 1024)]   # C = 1024: one run per workgroup (R = 1)
 # (B, L, C, N)
 STEM_CASES = [(2, 6, 3, 8), (2, 37, 4, 16), (2, 41, 5, 16), (3, 19, 25, 32), (1, 4000, 4, 16), (2, 3200, 5, 16), (2, 640, 25, 32),
               (2, 300, 32, 64), (2, 50, 1, 4)]

@@ -21,6 +21,7 @@ from collections import OrderedDict
 
 import numpy as np
 
+import pool_oracle
 from dwk_oracle import dw_bwd, dw_fwd, glorot
 from oracle.layers import (bn_infer_fwd, bn_train_bwd, bn_train_fwd, cce_fwd_bwd, dropout_key, dropout_mask, relu6, relu6_mask,
                            softmax, softmax_bwd)
@@ -39,29 +40,19 @@ def pool_same_geometry(L, odd_left=False):
 
 def pool_same_windows(a, pad_l):
     """[B, L, C] -> [B, Lp, 3, C] windows over the input padded with -inf (rows 2t - pad_l + j)."""
-    L = a.shape[1]
-    Lp = -(-L // 2)
-    ap = np.pad(a, ((0, 0), (pad_l, 2 * Lp + 1 - pad_l - L), (0, 0)), constant_values=-np.inf)
-    return ap[:, 2 * np.arange(Lp)[:, None] + np.arange(3)[None, :], :]
+    return pool_oracle.windows(a, -(-a.shape[1] // 2), pad_l)
 
 
 def pool_same_argmax(a, pad_l, last=False):
-    """Offset (0..2) of the first (last: the last) maximum of every window."""
-    w = pool_same_windows(a, pad_l)
-    return 2 - np.argmax(w[:, :, ::-1, :], axis=2) if last else np.argmax(w, axis=2)
+    return pool_oracle.argmax(a, -(-a.shape[1] // 2), pad_l, last)
 
 
 def pool_same_fwd(a, ind, pad_l):
-    return np.take_along_axis(pool_same_windows(a, pad_l), ind[:, :, None, :], axis=2)[:, :, 0, :]
+    return pool_oracle.fwd(a, ind, pad_l)
 
 
 def pool_same_bwd(dz, ind, L, pad_l):
-    """dz [B, Lp, C], ind [B, Lp, C] -> da [B, L, C]: every window's gradient goes to the row it names."""
-    B, Lp, C = dz.shape
-    dap = np.zeros((B, 2 * Lp + 1, C), dz.dtype)
-    for j in range(3):
-        dap[:, j:j + 2 * Lp:2, :] += dz * (ind == j)
-    return dap[:, pad_l:pad_l + L, :]
+    return pool_oracle.bwd(dz, ind, L, pad_l)
 
 
 # ---- the net -------------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ from collections import OrderedDict
 
 import numpy as np
 
+import pool_oracle
 from oracle.layers import (bn_infer_fwd, bn_train_bwd, bn_train_fwd, cce_fwd_bwd, dropout_key, dropout_mask, relu6, relu6_mask,
                            softmax, softmax_bwd)
 
@@ -54,27 +55,19 @@ def pool_len(L):
 
 def pool_windows(a):
     """[B, L, C] -> [B, Lp, 3, C] windows of MaxPool1D(3, strides=2, 'valid')."""
-    Lp = pool_len(a.shape[1])
-    return a[:, 2 * np.arange(Lp)[:, None] + np.arange(3)[None, :], :]
+    return pool_oracle.windows(a, pool_len(a.shape[1]), 0)
 
 
 def pool_argmax(a, last=False):
-    """Offset (0..2) of the first (last: the last) maximum of every window."""
-    w = pool_windows(a)
-    return 2 - np.argmax(w[:, :, ::-1, :], axis=2) if last else np.argmax(w, axis=2)
+    return pool_oracle.argmax(a, pool_len(a.shape[1]), 0, last)
 
 
 def pool_fwd(a, ind):
-    return np.take_along_axis(pool_windows(a), ind[:, :, None, :], axis=2)[:, :, 0, :]
+    return pool_oracle.fwd(a, ind, 0)
 
 
 def pool_bwd(dz, ind, L):
-    """dz [B, Lp, C], ind [B, Lp, C] -> da [B, L, C]: every window's gradient goes to the row it names."""
-    B, Lp, C = dz.shape
-    da = np.zeros((B, L, C), dz.dtype)
-    for j in range(3):
-        da[:, j:j + 2 * Lp:2, :] += dz * (ind == j)
-    return da
+    return pool_oracle.bwd(dz, ind, L, 0)
 
 
 def glorot(rng, shape, fan_in, fan_out):

@@ -1,4 +1,4 @@
-"""kws_pool3s2_same_* (csrc/pool_same.hip) and kws_stem_* (csrc/stem.hip) called directly, against float64 NumPy
+"""kws_pool3s2_same_* (csrc/pool.hip) and kws_stem_* (csrc/stem.hip) called directly, against float64 NumPy
 (tests/mts_oracle.py pool_same_*, tests/mts_cases.py stem_reference), on the conv_1d_multi_time_sliced geometries and on small odd
 ones.  Outputs sit in NaN-guarded buffers.
 

@@ -1,5 +1,6 @@
-"""kws_pool3s2_fwd_f32 / kws_pool3s2_bwd_f32 (csrc/pool.hip) called directly, against float64 NumPy: MaxPool1D(3, strides=2,
-'valid') over relu6(bn(y)), forward and gather-form backward with the BatchNorm partial sums.
+"""kws_pool3s2_fwd_f32 / kws_pool3s2_bwd_f32 (csrc/pool.hip, the kernel set it shares with kws_pool3s2_same_*: VALID is
+pad_left = 0 and its own window count) called directly, against float64 NumPy: MaxPool1D(3, strides=2, 'valid') over
+relu6(bn(y)), forward and gather-form backward with the BatchNorm partial sums.
 
 The float64 reference takes the device's own decisions where float32 rounding could flip them: activations are recomputed as
 the device does (one fused multiply-add per element, rounded to float32), and windows / gates are decided on those.  Inputs
@@ -21,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 4096
 SHAPES = [(1, 7, 32), (1, 8, 48), (3, 16, 96), (2, 95, 128), (5, 194, 160), (4, 41, 192), (64, 798, 48), (256, 91, 320),
-          (1, 3, 256), (2, 4, 32)]
+          (1, 3, 256), (2, 4, 32), (1, 5, 1024), (2, 8, 1024)]   # C = 1024: one run per workgroup (R = 1)
 
 
 def _guarded(n, fill=np.nan):
@@ -118,6 +119,22 @@ def test_backward_matches_float64(B, L, C):
     if L % 2 == 0:
         assert not got[:, -1].any()                      # the row no window covers: exact zeros
     assert _guards_intact(gbuf, g.numel()) and _guards_intact(pbuf, part.numel())
+
+
+@pytest.mark.parametrize("B,L,C", [(2, 4, 32), (1, 8, 48), (3, 16, 96)])
+def test_same_padding_of_an_even_length_starts_with_the_valid_windows(B, L, C):
+    """Even L: SAME has pad_left = 0, so its first (L - 3) / 2 + 1 windows are VALID's; both entry points run one kernel."""
+    y, bn, _ = _inputs(B, L, C, 17 * L + C)
+    _, zv = _run_fwd(y, bn, B, L, C)
+    lib = _lib.load()
+    Ls = lib.kws_pool3s2_same_out_len(L)
+    assert Ls == pool_len(L) + 1
+    yd, bd = torch.from_numpy(y).cuda(), torch.from_numpy(bn).cuda()
+    buf, zs = _guarded(B * Ls * C)
+    _lib.call("kws_pool3s2_same_fwd_f32", _lib.ptr(yd), _lib.ptr(bd), _lib.ptr(zs), B, L, C, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(zs.view(B, Ls, C)[:, :pool_len(L)], zv.view(B, pool_len(L), C))
+    assert _guards_intact(buf, zs.numel())
 
 
 def test_backward_negative_controls():
