@@ -469,6 +469,38 @@ int64_t kws_frame_conv_wgrad_workspace_floats(const kws_frame_conv_t* d);
 int kws_frame_conv_wgrad_f32(const float* x, const float* G, float* dW, float* workspace, const kws_frame_conv_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Banked strided first convolution: nbanks Conv1D(N, ksize[q], strides=stride, use_bias=False) layers over the raw waveform
+ * whose outputs are concatenated, the filterbank front end of the reference's conv_1d_learned_spec_model (model.py:1159-1246:
+ * six 'same' layers of 40 filters, 479 ... 161 taps, stride 160).  The banks are one banded product over one staged segment of
+ * samples: a clip is read once, the structural zeros of a dense fold are not multiplied, y is written straight into the joined
+ * tensor.
+ *   fwd    y[b, t, q*N + n] = sum_{c < ksize[q]} W_q[c, n] * x[b, stride*t + c - pad_l[q]]      (0 outside [0, L))
+ *   wgrad  dW_q[c, n]       = sum_{b, t} x[b, stride*t + c - pad_l[q]] * G[b, t, q*N + n]
+ *          workspace >= kws_fbank_conv_wgrad_workspace_floats() floats (16-byte aligned; fixed-order split over the row tiles,
+ *          then a fixed-order sum): no atomics, bit-identical from run to run.  Every element of every bank's dW_q is written,
+ *          nothing between or around the banks is touched.  There is no input gradient (x is the waveform) and no statistics
+ *          epilogue (no BatchNorm follows).
+ * x: B clips of L samples, x_batch_stride apart (8-byte aligned; the floats between L and x_batch_stride are never read); bank
+ * q's kernel W_q and gradient dW_q [ksize[q], 1, N] (Keras layout) at W + w_off[q] / dW + w_off[q]; y and G [B, Lout, nbanks*N].
+ * TF SAME: Lout = ceil(L / stride), pad_l[q] = max((Lout - 1)*stride + ksize[q] - L, 0) / 2; VALID: pad_l 0.
+ * Domain: 1 <= nbanks <= 8; N a multiple of 4, 4 <= N <= 64; stride even, 2 <= stride <= 4096; 1 <= ksize[q] <= 512,
+ * 0 <= pad_l[q] < ksize[q] (either parity), w_off[q] >= 0; span = max(ksize - pad_l) + max(pad_l) <= 512; x_batch_stride even and
+ * >= L; stride*(Lout - 1) < L + max(pad_l) (the last row's window starts inside the padded clip); B*Lout < 2^31.  Anything else
+ * returns KWS_E_INVALID before any launch, with nothing written and no pointer dereferenced (the planner returns 0).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, L, Lout;            /* clips, samples per clip, output rows per clip */
+  int stride;                /* samples between consecutive rows */
+  int nbanks, N;             /* 1..8 banks of N filters each; output pitch F = nbanks * N */
+  int ksize[8], pad_l[8];    /* per bank: taps, zeros in front of a clip (0 <= pad_l < ksize) */
+  int64_t w_off[8];          /* per bank: offset in floats of its kernel [ksize, 1, N] (Keras layout) from W / dW */
+  int64_t x_batch_stride;
+} kws_fbank_conv_t;
+int     kws_fbank_conv_fwd_f32(const float* x, const float* W, float* y, const kws_fbank_conv_t* d, void* stream);
+int64_t kws_fbank_conv_wgrad_workspace_floats(const kws_fbank_conv_t* d);
+int     kws_fbank_conv_wgrad_f32(const float* x, const float* G, float* dW, float* workspace, const kws_fbank_conv_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GlobalAveragePooling1D over relu6(bn(y)) followed by Dropout: the head of the reference's conv_1d_time_sliced_model
  * (model.py:716-772), whose pooled features feed a hidden Dense layer.  y [B, T, C] is the RAW convolution output, bn its
  * table scale|shift|mean|rstd [4][C]; 1 <= T <= 16, C % 4 == 0, C <= 1024.
@@ -760,6 +792,14 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         Dropout(.3) -> Dense + softmax (no bias), categorical CE.  Dropout layer ids 1 and 2 in model order.  Debug
  *                         views: what 0 / 1 / 2 as for KWS_NET_TS_ATTENTION (y and tables 0 .. 13, z 0 .. 12), what 4 = the hidden
  *                         Dense layer's output before relu6 [B, 256 fm].
+ *   KWS_NET_CONV_1D_LEARNED_SPEC: conv_1d_learned_spec_model, reference model.py:1159-1246 (raw input, input_size even and at least
+ *                         14402 = 91 rows of 160 samples; Keras model name 'conv_1d_learned_spec', which conv_1d_fast shares): six
+ *                         Conv1D(40, k, strides=160, SAME, no bias, l2 1e-4), k = 479, 383, 319, 255, 191, 161, concatenated to
+ *                         [ceil(input_size / 160), 240] with no BN and no activation (kws_fbank_conv_*) -> four grouped reduce (k 3,
+ *                         stride 2, 3 groups) / context (k 3, 2 groups) pairs of 300 ... 480 filters; the first context block's groups
+ *                         read 180 and 120 of 300 channels (two kws_conv1d_* column windows) -> Flatten -> Dropout(.3) -> Dense.
+ *                         Debug views: what 0, index 0 = the front output [B, rows, 240], index i >= 1 = block i's pre-BN output;
+ *                         what 2, index j = the table of batch_normalization_{j+1} (4 * Ng floats).
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -781,6 +821,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_2D_MOBILE 15
 #define KWS_NET_CONV_2D_FAST 16
 #define KWS_NET_CONV_1D_TIME_SLICED 17
+#define KWS_NET_CONV_1D_LEARNED_SPEC 18
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

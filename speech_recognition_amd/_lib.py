@@ -29,6 +29,7 @@ KWS_NET_INCEPTION_D1 = 14
 KWS_NET_CONV_2D_MOBILE = 15
 KWS_NET_CONV_2D_FAST = 16
 KWS_NET_CONV_1D_TIME_SLICED = 17
+KWS_NET_CONV_1D_LEARNED_SPEC = 18
 
 
 class KwsError(RuntimeError):
@@ -68,6 +69,14 @@ class FrameConvDesc(ctypes.Structure):
     samples -> [B, Lout, N]."""
     _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "Lout", "ksize", "hop", "pad_l", "taps", "stride", "N")] + \
                [("x_batch_stride", ctypes.c_int64)]
+
+
+class FbankConvDesc(ctypes.Structure):
+    """kws_fbank_conv_t: nbanks Conv1D(N, ksize[q], strides=stride) layers over B clips of L samples, concatenated ->
+    [B, Lout, nbanks * N]; bank q's kernel [ksize[q], 1, N] lies w_off[q] floats behind the weight pointer."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "Lout", "stride", "nbanks", "N")] + \
+               [("ksize", ctypes.c_int * 8), ("pad_l", ctypes.c_int * 8), ("w_off", ctypes.c_int64 * 8),
+                ("x_batch_stride", ctypes.c_int64)]
 
 
 ACT_RELU6 = 0   # include/kws_hip.h: KWS_ACT_*
@@ -202,6 +211,9 @@ SIGNATURES = {
     "kws_frame_conv_fwd_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(FrameConvDesc), _P]),
     "kws_frame_conv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(FrameConvDesc)]),
     "kws_frame_conv_wgrad_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(FrameConvDesc), _P]),
+    "kws_fbank_conv_fwd_f32": (_I, [_P, _P, _P, ctypes.POINTER(FbankConvDesc), _P]),
+    "kws_fbank_conv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(FbankConvDesc)]),
+    "kws_fbank_conv_wgrad_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(FbankConvDesc), _P]),
     "kws_gap_drop_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _I64, _P]),
     "kws_gap_drop_bwd_part_rows": (_I, [_I, _I, _I]),
     "kws_gap_drop_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _I64,

@@ -21,6 +21,14 @@
 //                         Conv1D(num_classes, 1, softmax, no bias).  The 1600 -> 128 product is one more block of this program
 //                         whose input is the materialised dropped features; what follows it is the flat tail with D = 128,
 //                         dropout layer 2 and no bias.
+// And the filterbank sibling of conv_1d_fast / conv_1d_spec:
+//   KWS_NET_CONV_1D_LEARNED_SPEC  conv_1d_learned_spec_model (model.py:1159-1246): raw waveform -> six Conv1D(40, k, strides=160,
+//                         SAME, no bias, l2 1e-4), k = 479 ... 161, concatenated to [ceil(L / 160), 240] with no BN and no activation
+//                         (ONE kws_fbank_conv_fwd_f32 launch) -> four reduce (g 3, stride 2) / context (g 2) pairs, k 3 ->
+//                         Flatten -> Dropout(.3) -> Dense + softmax; RMSprop(2e-3).  Its second block slices 360 channels of a
+//                         300-channel tensor in two, so its groups read 180 and 120 channels (Keras clips the slice): a RAGGED
+//                         block, run as two kws_conv1d_* column-window convolutions over the producer's table repacked from the
+//                         grouped layout [g][4][Ng] to the flat [4][C] one those kernels index.
 #include "net_internal.h"
 
 namespace {
@@ -35,6 +43,9 @@ struct GcBlock {
   int bn_idx0;              // 0-based Keras index of group 0's BatchNormalization
   bool pool;                // MaxPool1D(3, strides=2, 'valid') behind the activation: Lp rows per clip leave the block
   int Lp;
+  bool ragged;              // two groups of different input widths: rc[q] (B filled in per call), group q's kernel at rw[q]
+  kws_conv1d_t rc[2];
+  int64_t rw[2];
 };
 
 struct GcProgram : NetProgram {
@@ -43,6 +54,9 @@ struct GcProgram : NetProgram {
   int64_t conv0 = 0;
   int K0 = 0, K0p = 0, L0 = 0, C0 = 0;
   kws_gather_t g0{};
+  bool fbank = false;       // conv_1d_learned_spec: the six-bank front convolution (w_off: the kernels' offsets in params / grads)
+  kws_fbank_conv_t fb{};
+  bool has_front() const { return front || fbank; }
   std::vector<GcBlock> blocks;
   int64_t dk = 0, db = 0;
   int D = 0, NC = 0;
@@ -105,6 +119,41 @@ int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, i
   return KWS_OK;
 }
 
+// _grouped_context_conv(x, F, k, 2, num_channels) with num_channels > C: Keras clips the second slice, so group 0 reads
+// num_channels / 2 channels and group 1 the C - num_channels / 2 that are left
+int add_ragged_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int num_channels) {
+  const int gs = num_channels / 2, Ng = F / 2;
+  KWS_REQUIRE(num_channels % 2 == 0 && F % 2 == 0 && gs < C && C < num_channels && L >= k,
+              "net: ragged block F=%d num_channels=%d C=%d L=%d", F, num_channels, C, L);
+  GcBlock b;
+  memset(&b, 0, sizeof(b));
+  b.d.L = L; b.d.C = C; b.d.k = k; b.d.stride = 1; b.d.g = 2; b.d.gs = gs; b.d.Ng = Ng;
+  b.d.Lout = L - k + 1;
+  b.F = F;
+  b.Lp = b.d.Lout;
+  b.ragged = true;
+  b.bn_idx0 = kn.n_bn;
+  for (int q = 0; q < 2; ++q) {
+    const int cin = q == 0 ? gs : C - gs;
+    b.rw[q] = kn.conv(k, cin, Ng, 0.f);
+    const BnRef r = kn.bn(Ng);
+    if (q == 0) {
+      b.w0 = b.rw[0]; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
+    } else {
+      b.pstride = r.gamma - b.gamma0;
+      b.sstride = r.mm - b.mm0;
+      KWS_REQUIRE(r.beta - r.gamma == b.beta_off && r.mv - r.mm == b.mv_off, "net: ragged block layout is not uniform");
+    }
+    kws_conv1d_t& c = b.rc[q];
+    c.L = L; c.Lout = b.d.Lout; c.k = k; c.dil = 1; c.pad_l = 0;
+    c.Cx = C; c.x0 = q * gs; c.Cin = cin;
+    c.Cy = F; c.y0 = q * Ng; c.F = Ng;
+  }
+  b.d.w_group_stride = b.rw[1] - b.rw[0];
+  p->blocks.push_back(b);
+  return KWS_OK;
+}
+
 struct GcLayout {
   int64_t total = 0;
   int64_t w0p = 0, y0 = 0;
@@ -112,6 +161,8 @@ struct GcLayout {
   int64_t fa = 0, fd1 = 0;         // head2: activated / dropped features [B, Dd]
   int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, tnws = 0, dw0p = 0;
   int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+  int64_t bnflat = 0, fbws = 0;    // a ragged block's input table as [4][C]; the banked front's weight-gradient workspace
+  int64_t rstats = 0;              // distance of the two groups' statistics rows of a ragged block
 };
 
 void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
@@ -120,6 +171,10 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
   int64_t max_act = 64, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64;
   if (p.front) {
     lo->w0p = bp.take((int64_t)p.K0p * p.C0);
+    lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
+    max_act = std::max(max_act, (int64_t)B * p.L0 * p.C0);
+  }
+  if (p.fbank) {
     lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
     max_act = std::max(max_act, (int64_t)B * p.L0 * p.C0);
   }
@@ -137,9 +192,20 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
       max_part = std::max(max_part, kws_pool3s2_bwd_part_floats(B, d.Lout, p.blocks[i].F));
     }
     max_act = std::max(max_act, std::max(M * p.blocks[i].F, (int64_t)B * d.L * d.C));
-    max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&d) * 2 * p.blocks[i].F);
     max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * p.blocks[i].F);
     max_coef = std::max(max_coef, (int64_t)2 * p.blocks[i].F);
+    if (p.blocks[i].ragged) {
+      lo->bnflat = bp.take((int64_t)4 * d.C);
+      for (int q = 0; q < 2; ++q) {
+        kws_conv1d_t c = p.blocks[i].rc[q];
+        c.B = B;
+        lo->rstats = std::max(lo->rstats, ((int64_t)kws_conv1d_stats_rows(&c) * 2 * c.F + 63) / 64 * 64);
+        max_wws = std::max(max_wws, kws_conv1d_wgrad_workspace_floats(&c));
+      }
+      max_stats = std::max(max_stats, 2 * lo->rstats);
+      continue;
+    }
+    max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&d) * 2 * p.blocks[i].F);
     max_wws = std::max(max_wws, kws_gconv_wgrad_workspace_floats(&d));
   }
   lo->stats = bp.take(max_stats);
@@ -156,6 +222,11 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
     if (p.front) {
       lo->tnws = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * p.L0, p.K0p, p.C0));
       lo->dw0p = bp.take((int64_t)p.K0p * p.C0);
+    }
+    if (p.fbank) {
+      kws_fbank_conv_t fb = p.fb;
+      fb.B = B;
+      lo->fbws = bp.take(kws_fbank_conv_wgrad_workspace_floats(&fb));
     }
     lo->fd = bp.take((int64_t)B * p.D);
     lo->dl = bp.take((int64_t)B * p.NC);
@@ -181,10 +252,48 @@ struct GcInput {
   int bg;
 };
 GcInput gc_input(const GcProgram& p, const GcLayout& lo, int i, const float* x, const float* ws, bool training) {
-  if (i == 0) return {p.front ? ws + lo.y0 : x, nullptr, 0};
+  if (i == 0) return {p.has_front() ? ws + lo.y0 : x, nullptr, 0};
   if (p.head2 && training && i + 1 == (int)p.blocks.size()) return {ws + lo.fd1, nullptr, 0};
   if (p.blocks[i - 1].pool) return {ws + lo.z[i - 1], nullptr, 0};
   return {ws + lo.y[i - 1], ws + lo.bn[i - 1], p.blocks[i - 1].d.Ng};
+}
+
+// the producer's grouped table [g][4][Ng] as the flat [4][C] one of kws_conv1d_* (C = g * Ng)
+int gc_flat_table(const float* bn, int g, int Ng, float* flat, hipStream_t st) {
+  for (int q = 0; q < g; ++q)
+    KWS_HIP(hipMemcpy2DAsync(flat + (int64_t)q * Ng, sizeof(float) * g * Ng, bn + (int64_t)q * 4 * Ng, sizeof(float) * Ng,
+                             sizeof(float) * Ng, 4, hipMemcpyDeviceToDevice, st));
+  return KWS_OK;
+}
+
+kws_gbn_refs ragged_refs(const GcBlock& b, int q, const float* params, float* state) {
+  kws_gbn_refs r;
+  r.gamma = params + b.gamma0 + q * b.pstride; r.pstride = 0; r.boff = b.beta_off;
+  r.mm = state ? state + b.mm0 + q * b.sstride : nullptr; r.sstride = 0; r.voff = b.mv_off;
+  return r;
+}
+
+// a ragged block (i >= 1, behind an unpooled grouped block): two column-window convolutions, each with its own BatchNorm layer,
+// whose tables land in the grouped layout [2][4][Ng] the next block reads
+int gc_ragged_forward(const GcProgram& p, const GcLayout& lo, int i, const float* params, float* state, int B, bool training, float* ws,
+                      hipStream_t st) {
+  const GcBlock& b = p.blocks[i];
+  const GcBlock& pb = p.blocks[i - 1];
+  KWS_TRY(gc_flat_table(ws + lo.bn[i - 1], pb.d.g, pb.d.Ng, ws + lo.bnflat, st));
+  const kws_gbn_cols cols = kws_gbn_grouped(1, b.d.Ng);
+  for (int q = 0; q < 2; ++q) {
+    kws_conv1d_t c = b.rc[q];
+    c.B = B;
+    float* stats = training ? ws + lo.stats + q * lo.rstats : nullptr;
+    KWS_TRY(kws_conv1d_fwd_f32(ws + lo.y[i - 1], ws + lo.bnflat, params + b.rw[q], ws + lo.y[i], stats, &c, st));
+    const kws_gbn_refs r = ragged_refs(b, q, params, state);
+    float* bn = ws + lo.bn[i] + (int64_t)q * 4 * b.d.Ng;
+    if (training)
+      KWS_TRY(kws_gbn_finalize(stats, kws_conv1d_stats_rows(&c), (int64_t)B * c.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM, bn, st));
+    else
+      KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, bn, st));
+  }
+  return KWS_OK;
 }
 
 // forward through the blocks; training: batch statistics (moving averages updated), else the moving statistics
@@ -194,6 +303,11 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
     KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
     KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
     KWS_TRY(kws_gemm_gather_f32(x, &p.g0, ws + lo.w0p, ws + lo.y0, B, p.C0, nullptr, st));
+  }
+  if (p.fbank) {
+    kws_fbank_conv_t fb = p.fb;
+    fb.B = B;
+    KWS_TRY(kws_fbank_conv_fwd_f32(x, params, ws + lo.y0, &fb, st));
   }
   for (size_t i = 0; i < p.blocks.size(); ++i) {
     const GcBlock& b = p.blocks[i];
@@ -205,6 +319,10 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
     const int bg = gi.bg;
     const kws_gbn_refs r = refs_of(b, params, state);
     const kws_gbn_cols cols = kws_gbn_grouped(d.g, d.Ng);
+    if (b.ragged) {
+      KWS_TRY(gc_ragged_forward(p, lo, (int)i, params, state, B, training, ws, st));
+      continue;
+    }
     if (training) {
       if (p.head2 && i + 1 == p.blocks.size()) {   // Dropout(.3) over the activated ladder output, materialised for the head's GEMMs
         const GcBlock& pb = p.blocks[i - 1];
@@ -287,6 +405,36 @@ int gc_build(kws_net* n) {
       p->db = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
     }
     return KWS_OK;
+  } else if (c.kind == KWS_NET_CONV_1D_LEARNED_SPEC) {
+    const int ks[6] = {479, 383, 319, 255, 191, 161};
+    kws_fbank_conv_t& fb = p->fb;
+    fb.L = c.input_size; fb.stride = 160; fb.nbanks = 6; fb.N = 40;
+    fb.Lout = (c.input_size + 159) / 160;
+    // the ladder's lengths are 49, 47, 23, 21, 10, 8, 3, 1 at 100 rows: 91 rows are the fewest that leave one
+    KWS_REQUIRE(c.input_size > 0 && c.input_size % 2 == 0 && fb.Lout >= 91,
+                "net: conv_1d_learned_spec input_size %d (even, >= 14402: the ladder needs 91 rows of 160 samples)", c.input_size);
+    for (int q = 0; q < 6; ++q) {
+      int Lout = 0;
+      fb.ksize[q] = ks[q];
+      kws_same_pad(c.input_size, ks[q], 160, &Lout, &fb.pad_l[q]);
+      fb.w_off[q] = kn.conv(ks[q], 1, fb.N, GC_FRONT_L2);
+    }
+    fb.x_batch_stride = c.input_size;
+    fb.B = 1;
+    KWS_REQUIRE(kws_fbank_conv_wgrad_workspace_floats(&fb) > 0, "net: input_size %d is outside the front convolution's domain",
+                c.input_size);
+    p->fbank = true;
+    p->L_in = c.input_size; p->C_in = 1;
+    p->L0 = fb.Lout; p->C0 = fb.nbanks * fb.N;
+    struct { int F, g, nch, stride; } spec[8] = {{300, 3, 240, 2}, {300, 2, 360, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
+                                                 {420, 3, 240, 2}, {420, 2, 420, 1}, {480, 3, 420, 2}, {480, 2, 480, 1}};
+    int L = p->L0, C = p->C0;
+    for (int i = 0; i < 8; ++i) {
+      if (spec[i].nch > C) KWS_TRY(add_ragged_block(kn, p, L, C, spec[i].F, 3, spec[i].nch));
+      else KWS_TRY(add_block(kn, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride));
+      L = p->blocks.back().d.Lout;
+      C = p->blocks.back().F;
+    }
   } else {
     p->L_in = 98; p->C_in = 257;   // Input(shape=[98 * 257]) -> Reshape([98, 257]); input_size is not consulted
     struct { int F, g, nch, stride; } spec[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
@@ -319,7 +467,7 @@ int GcProgram::debug_view(int B, int training, int what, int index, int64_t* off
   gc_layout(p, B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
   if (what == 0) {   // pre-BN output of conv stage `index` (conv_1d_fast: 0 = the front convolution)
-    const int i = index - (p.front ? 1 : 0);
+    const int i = index - (p.has_front() ? 1 : 0);
     KWS_REQUIRE(index >= 0 && i < nb, "net_debug_view: y index %d", index);
     if (i < 0) {
       *offset_floats = lo.y0;
@@ -386,12 +534,22 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
                           b.pstride, b.beta_off, st));
     }
     float* dy = ws + lo.dA[cur];
+    if (b.ragged) {   // the windows [0, gs) and [gs, C) together cover dA[cur ^ 1]: the gradient wrt the activated input
+      for (int q = 0; q < 2; ++q) {
+        kws_conv1d_t c = b.rc[q];
+        c.B = B;
+        KWS_TRY(kws_conv1d_wgrad_f32(ws + lo.y[i - 1], ws + lo.bnflat, dy, grads + b.rw[q], ws + lo.wws, &c, st));
+        KWS_TRY(kws_conv1d_dgrad_f32(dy, params + b.rw[q], ws + lo.dA[cur ^ 1], 0, &c, st));
+      }
+      cur ^= 1;
+      continue;
+    }
     const GcInput gi = gc_input(p, lo, i, x, ws, true);
     KWS_TRY(kws_gconv_wgrad_f32(gi.in, gi.bn, gi.bg, dy, grads + b.w0, ws + lo.wws, &d, st));
     if (p.head2 && i + 1 == (int)p.blocks.size()) {   // back through Dropout(.3): the gradient wrt the activated ladder output
       KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.fa, &d, st));
       KWS_TRY(kws_dropout_bwd(ws + lo.fa, ws + lo.dA[cur], B, p.Dd, p.keep, seed, step, 1, row_offset, st));
-    } else if (i > 0 || p.front) {
+    } else if (i > 0 || p.has_front()) {
       KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.dA[cur ^ 1], &d, st));
       cur ^= 1;
     }
@@ -399,6 +557,11 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
   if (p.front) {   // dA[cur] = gradient wrt the front convolution's output (no BN, no activation in between)
     KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, ws + lo.dA[cur], ws + lo.dw0p, B, p.C0, ws + lo.tnws, st));
     KWS_HIP(hipMemcpyAsync(grads + p.conv0, ws + lo.dw0p, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
+  }
+  if (p.fbank) {   // likewise; the six kernels' gradients land at their own offsets in grads
+    kws_fbank_conv_t fb = p.fb;
+    fb.B = B;
+    KWS_TRY(kws_fbank_conv_wgrad_f32(x, ws + lo.dA[cur], grads, ws + lo.fbws, &fb, st));
   }
   return KWS_OK;
 }

@@ -9,7 +9,7 @@ from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
                'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
-               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast', 'conv_1d_time_sliced')
+               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast', 'conv_1d_time_sliced', 'conv_1d_learned_spec')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -153,6 +153,17 @@ def conv_1d_fast_model(input_size=16000, num_classes=11, *args, **kwargs):
     return Model(net, RMSprop(lr=3e-3), name='conv_1d_learned_spec', loss='cce')
 
 
+def conv_1d_learned_spec_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:1159-1246: raw waveform -> a learned filterbank of six Conv1D(40, k, strides=160, SAME, no bias, l2 1e-4)
+    layers, k = 479, 383, 319, 255, 191, 161, concatenated to [ceil(input_size / 160), 240] (no BN, no activation; one
+    kws_fbank_conv_* launch, csrc/fbank_conv.hip) -> four grouped reduce (k 3, stride 2, 3 groups) / context (k 3, 2 groups) pairs
+    of 300 ... 480 filters, each group its own Conv1D + BatchNormalization + relu6 - the first context block slices 360 channels
+    of 300, so its groups read 180 and 120 - -> Flatten -> Dropout(.3) -> Dense; RMSprop(2e-3), categorical CE.  input_size: any
+    even size of at least 14402 samples (91 rows)."""
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_LEARNED_SPEC, num_classes, input_size=input_size)
+    return Model(net, RMSprop(lr=2e-3), name='conv_1d_learned_spec', loss='cce')
+
+
 def conv_1d_spec_model(input_size=16000, num_classes=11, *args, **kwargs):
     """reference model.py:1249-1323: the generator's 'spec' output as [98, 257] (the reference fixes Input(shape=[98 * 257])
     and ignores input_size) -> four grouped reduce (k 3, stride 2, 4 groups) / context (k 3, 3 groups) pairs of 300 ... 480
@@ -276,6 +287,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_fast_model(input_size, num_classes)
     if model_type == 'conv_1d_spec':
         return conv_1d_spec_model(input_size, num_classes)
+    if model_type == 'conv_1d_learned_spec':
+        return conv_1d_learned_spec_model(input_size, num_classes)
     if model_type == 'conv_1d_time_stacked':
         return conv_1d_time_stacked_model(input_size, num_classes)
     if model_type == 'conv_1d_heavy':
