@@ -3,6 +3,7 @@ nets, clips and shapes on both sides, so that the figures in the GPU tests' docs
 import numpy as np
 
 from conv2d_oracle import Conv2dNet, axis_geom
+from net_parity import perturb
 
 NC = 12
 KINDS = ('mobile', 'fast')
@@ -15,20 +16,7 @@ def perturbed(kind, dtype=np.float64, nc=NC, seed=5):
     """About a third of the BatchNorm scales negative, shifts that make act(shift) != 0, non-zero convolution and dense biases,
     moving statistics off their initial values."""
     ora = Conv2dNet(kind, num_classes=nc, dtype=dtype)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.3 + 0.2 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('bias'):
-            ora.params[k] = (0.05 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.3, 0.2), bias=0.05)
     assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
     assert all(np.abs(v).max() > 0 for k, v in ora.params.items() if k.endswith('bias'))
     return ora
@@ -74,7 +62,7 @@ def bias_errors(g, ref, cache):
 
 def decisions_of(ora, cache):
     """Gates and pool winners of a cached oracle run, in the form loss_and_grads takes them."""
-    from conv2d_oracle import act_mask
+    from oracle_blocks import act_mask
     masks = {l['idx']: act_mask(cache[l['idx']]['pre'], ora.act) for l in ora.layers}
     inds = {l['idx']: cache[l['idx']]['ind'] for l in ora.layers if l['pool']}
     return masks, inds

@@ -14,12 +14,9 @@ flip then); `mutate` names a deliberately wrong variant for the negative control
 (Which maximum of a tied pool window wins, and relu against relu6, are kernel-level matters: behind a relu the only ties of a float64
 run are zeros, whose gates are shut, and a normalised activation does not reach 6.  tests/test_conv2d_kernels_gpu.py constructs both.)
 """
-from collections import OrderedDict
-
 import numpy as np
 
-from inception_oracle import bn_train_bwd, bn_train_fwd
-from oracle.layers import (BN_EPS, cce_fwd_bwd, dropout_key, dropout_mask, softmax, softmax_bwd)
+from oracle_blocks import OracleNet, same_geometry
 
 H0, W0 = 98, 40
 # F, (kh, kw), stride, (dh, dw), pooled, dropout behind the activation
@@ -39,13 +36,10 @@ TAIL_DROP_ID, LADDER_DROP_ID0 = 1, 2
 
 def axis_geom(n, k, s=1, d=1, padding='same', front_heavy=False):
     """-> output length, (pad in front, pad behind) of one axis: TensorFlow SAME (the smaller half in front) or VALID"""
-    span = d * (k - 1) + 1
     if padding == 'valid':
-        return (n - span) // s + 1, (0, 0)
-    out = -(-n // s)
-    total = max((out - 1) * s + span - n, 0)
-    front = total - total // 2 if front_heavy else total // 2
-    return out, (front, total - front)
+        return (n - d * (k - 1) - 1) // s + 1, (0, 0)
+    out, front, behind = same_geometry(n, k, s, d, odd_left=front_heavy)
+    return out, (front, behind)
 
 
 def conv2d_fwd(a, W, strides=(1, 1), dil=(1, 1), pads=((0, 0), (0, 0)), out_hw=None):
@@ -111,61 +105,33 @@ def pool2_bwd(dz, ind, H, W):
     return da
 
 
-def act_fwd(pre, act):
-    return np.clip(pre, 0, 6) if act == 'relu6' else np.maximum(pre, 0)
-
-
-def act_mask(pre, act):
-    return ((pre > 0) & (pre <= 6)) if act == 'relu6' else (pre > 0)
-
-
 def preprocess(x):
     """model.py:13-16"""
     t = x.dtype.type
     return np.clip((x + t(0.8)) / t(7.0), -5, 5)
 
 
-def glorot(rng, shape, fan_in, fan_out):
-    lim = np.sqrt(6.0 / (fan_in + fan_out))
-    return rng.uniform(-lim, lim, size=shape).astype(np.float32)
-
-
-class Conv2dNet(object):
+class Conv2dNet(OracleNet):
     """kind 'mobile' or 'fast'; input [B, 3920] mfcc features."""
 
     def __init__(self, kind, num_classes=12, seed=1234, dtype=np.float64):
-        rng = np.random.RandomState(seed)
-        self.kind, self.nc, self.dtype, self.act = kind, num_classes, dtype, ACT[kind]
-        P, S = OrderedDict(), OrderedDict()
+        super(Conv2dNet, self).__init__(num_classes, seed, dtype)
+        self.kind, self.act = kind, ACT[kind]
         self.layers = []
         H, W, C = H0, W0, 1
         drop_id = LADDER_DROP_ID0
-        for n, (F, (kh, kw), s, (dh, dw), pool, drop) in enumerate(LADDERS[kind], 1):
+        for F, (kh, kw), s, (dh, dw), pool, drop in LADDERS[kind]:
             Ho, ph = axis_geom(H, kh, s, dh)
             Wo, pw = axis_geom(W, kw, s, dw)
-            P['conv2d_%d/kernel' % n] = glorot(rng, (kh, kw, C, F), kh * kw * C, kh * kw * F)
-            P['conv2d_%d/bias' % n] = np.zeros(F, np.float32)
-            base = 'batch_normalization_%d/' % n
-            P[base + 'gamma'] = np.ones(F, np.float32)
-            P[base + 'beta'] = np.zeros(F, np.float32)
-            S[base + 'moving_mean'] = np.zeros(F, np.float32)
-            S[base + 'moving_variance'] = np.ones(F, np.float32)
-            lay = dict(idx=n, k=(kh, kw), strides=(s, s), dil=(dh, dw), C=C, F=F, H=H, W=W, Hout=Ho, Wout=Wo, pads=(ph, pw), pool=pool,
-                       drop_id=drop_id if drop else 0, Ho=Ho // 2 if pool else Ho, Wo=Wo // 2 if pool else Wo)
+            self.add_kernel('conv2d', (kh, kw, C, F), kh * kw * C, kh * kw * F, bias=F)
+            lay = dict(idx=self.add_bn(F), k=(kh, kw), strides=(s, s), dil=(dh, dw), C=C, F=F, H=H, W=W, Hout=Ho, Wout=Wo, pads=(ph, pw),
+                       pool=pool, drop_id=drop_id if drop else 0, Ho=Ho // 2 if pool else Ho, Wo=Wo // 2 if pool else Wo)
             drop_id += 1 if drop else 0
             self.layers.append(lay)
             H, W, C = lay['Ho'], lay['Wo'], F
         self.T, self.C = H * W, C
-        P['dense_1/kernel'] = glorot(rng, (C, num_classes), C, num_classes)
-        P['dense_1/bias'] = np.zeros(num_classes, np.float32)
+        self.add_kernel('dense', (C, num_classes), C, num_classes, bias=num_classes)
         self.keep_tail = KEEP_TAIL if kind == 'mobile' else 1.0
-        self.params, self.state = P, S
-
-    def count_params(self):
-        return sum(v.size for v in self.params.values()) + sum(v.size for v in self.state.values())
-
-    def _p(self, name):
-        return self.params[name].astype(self.dtype)
 
     def _geom(self, lay, mutate):
         if mutate != 'pad_front':
@@ -176,71 +142,41 @@ class Conv2dNet(object):
     def forward(self, x, training=False, seed=0, step=0, cache=None, drop_offset=0, mutate=None, pool_ind=None):
         t = self.dtype
         B = x.shape[0]
-        act = self.act
+        cache = {} if cache is None else cache
+        cache['batch_stats'] = {}
         h = preprocess(x.astype(t)).reshape(B, H0, W0, 1)
-        if cache is not None:
-            cache['batch_stats'] = {}
         for lay in self.layers:
             n = lay['idx']
             pads = self._geom(lay, mutate)
             y, ap = conv2d_fwd(h, self._p('conv2d_%d/kernel' % n), lay['strides'], lay['dil'], pads, (lay['Hout'], lay['Wout']))
             y = y + self._p('conv2d_%d/bias' % n)
-            ga, be = self._p('batch_normalization_%d/gamma' % n), self._p('batch_normalization_%d/beta' % n)
-            y3 = y.reshape(B, -1, lay['F'])
-            if training:
-                pre, st = bn_train_fwd(y3, ga, be)
-            else:
-                st = None
-                mm = self.state['batch_normalization_%d/moving_mean' % n].astype(t)
-                mv = self.state['batch_normalization_%d/moving_variance' % n].astype(t)
-                inv = ga / np.sqrt(mv + t(BN_EPS))
-                pre = y3 * inv + (be - mm * inv)
-            pre = pre.reshape(y.shape)
-            a = act_fwd(pre, act)
+            a = self.bn_act_fwd(n, y, training, cache, self.act)
             ind = keep = None
             if lay['pool']:
-                if pool_ind is not None and n in pool_ind:
-                    ind = pool_ind[n]
-                else:
-                    ind = pool2_argmax(a)
-                out = pool2_fwd(a, ind)
-            else:
-                out = a
+                ind = pool_ind[n] if pool_ind is not None and n in pool_ind else pool2_argmax(a)
+                a = pool2_fwd(a, ind)
             if training and lay['drop_id']:
-                per = lay['Hout'] * lay['Wout'] * lay['F']
-                keep = dropout_mask(dropout_key(seed, step, lay['drop_id']), B * per, KEEP_LADDER, offset=drop_offset * per)
-                keep = keep.reshape(a.shape).astype(t)
-                out = out * keep / t(KEEP_LADDER)
-            if cache is not None:
-                cache[n] = dict(ap=ap, y=y, st=st, pre=pre, ind=ind, keep=keep, pads=pads)
-                if training:
-                    cache['batch_stats'][n] = (st[0], st[1])
-            h = out
+                keep = self.dropout(seed, step, lay['drop_id'], B, lay['Hout'] * lay['Wout'] * lay['F'], KEEP_LADDER, drop_offset)
+                keep = keep.reshape(y.shape).astype(t)
+                a = a * keep / t(KEEP_LADDER)
+            cache[n] = dict(cache['bn%d' % n], ap=ap, ind=ind, keep=keep, pads=pads)
+            h = a
         f = h.reshape(B, self.T, self.C).mean(axis=1)
         keep = None
         if training and self.keep_tail < 1.0:
-            keep = dropout_mask(dropout_key(seed, step, TAIL_DROP_ID), B * self.C, self.keep_tail,
-                                offset=drop_offset * self.C).reshape(B, self.C).astype(t)
+            keep = self.dropout(seed, step, TAIL_DROP_ID, B, self.C, self.keep_tail, drop_offset).astype(t)
             f = f * keep / t(self.keep_tail)
-        logits = f @ self._p('dense_1/kernel') + self._p('dense_1/bias')
-        p = softmax(logits)
-        if cache is not None:
-            cache.update(f=f, keep_tail=keep, p=p)
+        p = self.head_fwd(f, 'dense_1/kernel', 'dense_1/bias')
+        cache.update(f=f, keep_tail=keep, p=p)
         return p
 
     def loss_and_grads(self, x, y_onehot, seed=0, step=0, drop_offset=0, relu_masks=None, pool_ind=None, mutate=None):
         """Data loss (batch mean) and its gradients."""
         t = self.dtype
-        cache = {}
+        cache, grads = {}, {}
         B = x.shape[0]
-        act = self.act
         p = self.forward(x, training=True, seed=seed, step=step, cache=cache, drop_offset=drop_offset, mutate=mutate, pool_ind=pool_ind)
-        loss, per, dp = cce_fwd_bwd(p, y_onehot.astype(t))
-        dl = softmax_bwd(dp, p)
-        grads = OrderedDict()
-        grads['dense_1/kernel'] = cache['f'].T @ dl
-        grads['dense_1/bias'] = dl.sum(axis=0)
-        df = dl @ self._p('dense_1/kernel').T
+        loss, df = self.head_bwd(p, y_onehot, cache['f'], 'dense_1/kernel', 'dense_1/bias', grads)
         if cache['keep_tail'] is not None:
             df = df * cache['keep_tail'] / t(self.keep_tail)
         top = self.layers[-1]
@@ -252,20 +188,16 @@ class Conv2dNet(object):
                 da = da * cc['keep'] / t(KEEP_LADDER)
             if lay['pool']:
                 da = pool2_bwd(da, cc['ind'], lay['Hout'], lay['Wout'])
-            mask = relu_masks[n] if relu_masks is not None and n in relu_masks else act_mask(cc['pre'], act)
-            ga = self._p('batch_normalization_%d/gamma' % n)
             F = lay['F']
-            dy, dga, dbe = bn_train_bwd((da * mask.astype(t)).reshape(B, -1, F), cc['y'].reshape(B, -1, F), ga, cc['st'])
-            dy = dy.reshape(cc['y'].shape)
-            grads['batch_normalization_%d/gamma' % n] = dga
-            grads['batch_normalization_%d/beta' % n] = dbe
+            dy = self.bn_act_bwd(n, da, cache, grads, relu_masks)
+            dga, dbe = grads['batch_normalization_%d/gamma' % n], grads['batch_normalization_%d/beta' % n]
             grads['conv2d_%d/bias' % n] = dy.sum(axis=(0, 1, 2))       # zero up to rounding: the BatchNorm backward removes the mean
             # what the terms of that sum are made of, per channel: dy = gamma rstd (g - dbeta / n - xhat dgamma / n), summed over the rows
-            g3, y3 = (da * mask.astype(t)).reshape(-1, F).astype(np.float64), cc['y'].reshape(-1, F).astype(np.float64)
+            g3 = (da * self.gate(n, cache, relu_masks)).reshape(-1, F).astype(np.float64)
+            y3 = cc['y'].reshape(-1, F).astype(np.float64)
             xhat = (y3 - cc['st'][0]) * cc['st'][2]
+            ga = self._p('batch_normalization_%d/gamma' % n)
             cc['bias_terms'] = np.abs(ga * cc['st'][2]) * (np.abs(g3).sum(0) + np.abs(dbe) + np.abs(xhat).sum(0) * np.abs(dga) / g3.shape[0])
-            da, dW = conv2d_bwd(dy, cc['ap'], self._p('conv2d_%d/kernel' % n), lay['strides'], lay['dil'], cc['pads'],
-                                (lay['H'], lay['W']), need_dx=n > 1)
-            grads['conv2d_%d/kernel' % n] = dW
-        ordered = OrderedDict((k, grads[k]) for k in self.params)
-        return loss, p, ordered, cache
+            da, grads['conv2d_%d/kernel' % n] = conv2d_bwd(dy, cc['ap'], self._p('conv2d_%d/kernel' % n), lay['strides'], lay['dil'],
+                                                           cc['pads'], (lay['H'], lay['W']), need_dx=n > 1)
+        return loss, p, self.ordered(grads), cache

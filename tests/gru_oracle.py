@@ -17,13 +17,11 @@ region.  `mutate` names a deliberately wrong variant for the negative controls:
 """
 import json
 import os
-from collections import OrderedDict
 
 import numpy as np
 
-from oracle.layers import (bn_infer_fwd, bn_train_bwd, bn_train_fwd, cce_fwd_bwd, dropout_key, dropout_mask, relu6, relu6_mask,
-                           softmax, softmax_bwd)
-from dwk_oracle import dw_bwd, dw_fwd, glorot
+from oracle.layers import dropout_key, dropout_mask
+from oracle_blocks import DwPwNet, glorot
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'gru_models.json')
 KEEP = 0.8
@@ -182,30 +180,21 @@ def golden():
         return json.load(f)['conv_1d_simple']
 
 
-class SimpleNet(object):
+class SimpleNet(DwPwNet):
     """conv_1d_simple from the recorded structure; input [B, 16000] raw samples."""
 
     def __init__(self, num_classes=12, seed=1234):
+        super(SimpleNet, self).__init__(num_classes, seed)
         gold = golden()
-        rng = np.random.RandomState(seed)
-        self.nc = num_classes
-        P, S = OrderedDict(), OrderedDict()
         self.blocks = []
         dws = [l for l in gold['layers'] if l['class'] == 'DepthwiseConv2D']
         convs = [l for l in gold['layers'] if l['class'] == 'Conv1D']
-        for i, (dwl, cv) in enumerate(zip(dws, convs)):
-            n = i + 1
+        for dwl, cv in zip(dws, convs):
             assert dwl['padding'] == 'valid'
             _, k, C, _ = dwl['kernel']
             F = cv['kernel'][2]
-            P['depthwise_conv2d_%d/depthwise_kernel' % n] = glorot(rng, (1, k, C, 1), k * C, k)
-            P['conv1d_%d/kernel' % n] = glorot(rng, (1, C, F), C, F)
-            base = 'batch_normalization_%d/' % n
-            P[base + 'gamma'] = np.ones(F, np.float32)
-            P[base + 'beta'] = np.zeros(F, np.float32)
-            S[base + 'moving_mean'] = np.zeros(F, np.float32)
-            S[base + 'moving_variance'] = np.ones(F, np.float32)
-            self.blocks.append({'idx': n, 'k': k, 's': dwl['strides'], 'C': C, 'F': F, 'L': dwl['input_length'], 'Lout': dwl['output'][0]})
+            self.blocks.append({'idx': self.add_block(k, C, F), 'k': k, 's': dwl['strides'], 'C': C, 'F': F, 'L': dwl['input_length'],
+                                'Lout': dwl['output'][0]})
         bi = [l for l in gold['layers'] if l['class'] == 'Bidirectional'][0]
         self.T, self.I = bi['input']
         self.H = bi['units']
@@ -215,21 +204,11 @@ class SimpleNet(object):
         self.gru_names = []
         for d in ('forward', 'backward'):
             base = '%s/%s_%s/' % (bi['name'], d, bi['layer'])
-            P[base + 'kernel'] = glorot(rng, (self.I, 3 * self.H), self.I, 3 * self.H)
-            P[base + 'recurrent_kernel'] = orthogonal(rng, (self.H, 3 * self.H))
-            P[base + 'bias'] = np.zeros(3 * self.H, np.float32)
+            self.params[base + 'kernel'] = glorot(self.rng, (self.I, 3 * self.H), self.I, 3 * self.H)
+            self.params[base + 'recurrent_kernel'] = orthogonal(self.rng, (self.H, 3 * self.H))
+            self.params[base + 'bias'] = np.zeros(3 * self.H, np.float32)
             self.gru_names.append(base)
-        P['dense_1/kernel'] = glorot(rng, (2 * self.H, num_classes), 2 * self.H, num_classes)
-        P['dense_1/bias'] = np.zeros(num_classes, np.float32)
-        self.l2_names = [k for k in P if k.endswith('depthwise_kernel') or k.startswith('conv1d_')]
-        self.params, self.state = P, S
-        self.dtype = np.float64
-
-    def count_params(self):
-        return sum(v.size for v in self.params.values()) + sum(v.size for v in self.state.values())
-
-    def _p(self, name):
-        return self.params[name].astype(self.dtype)
+        self.add_kernel('dense', (2 * self.H, num_classes), 2 * self.H, num_classes, bias=num_classes)
 
     def _gru_weights(self):
         return [tuple(self._p(b + w) for w in ('kernel', 'recurrent_kernel', 'bias')) for b in self.gru_names]
@@ -240,21 +219,7 @@ class SimpleNet(object):
         if cache is not None:
             cache['batch_stats'] = {}
         for blk in self.blocks:
-            n = blk['idx']
-            z = dw_fwd(a, self._p('depthwise_conv2d_%d/depthwise_kernel' % n)[0, :, :, 0], blk['s'], 0, blk['Lout'])
-            y = z @ self._p('conv1d_%d/kernel' % n)[0]
-            ga, be = self._p('batch_normalization_%d/gamma' % n), self._p('batch_normalization_%d/beta' % n)
-            if training:
-                pre, st = bn_train_fwd(y, ga, be)
-            else:
-                st = None
-                pre = bn_infer_fwd(y, ga, be, self.state['batch_normalization_%d/moving_mean' % n].astype(self.dtype),
-                                   self.state['batch_normalization_%d/moving_variance' % n].astype(self.dtype))
-            if cache is not None:
-                cache['a%d' % n], cache['z%d' % n], cache['y%d' % n], cache['st%d' % n] = a, z, y, st
-                if training:
-                    cache['batch_stats'][n] = (st[0], st[1])
-            a = relu6(pre)
+            a = self.block_fwd(blk['idx'], a, blk['s'], 0, blk['Lout'], training, cache)
         mx = mh = None
         if training:
             mx, mh = draw_masks(seed, step, B, self.I, self.H, self.keep, drop_offset, self.T, per_step=mutate == 'mask_per_step')
@@ -262,38 +227,19 @@ class SimpleNet(object):
                 mx = [[m.astype(self.dtype) for m in d] for d in mx]
                 mh = [[m.astype(self.dtype) for m in d] for d in mh]
         out, caches = bigru_fwd(a, self._gru_weights(), mx, mh, mutate)
-        p = softmax(out @ self._p('dense_1/kernel') + self._p('dense_1/bias'))
+        p = self.head_fwd(out, 'dense_1/kernel', 'dense_1/bias')
         if cache is not None:
             cache.update(gru_in=a, gru_out=out, gru=caches, p=p)
         return p
 
     def loss_and_grads(self, x, y_onehot, seed=0, step=0, drop_offset=0, relu_masks=None, decisions=None, mutate=None):
         """Data loss (batch mean) and its gradients (no L2 term)."""
-        cache = {}
+        cache, grads = {}, {}
         p = self.forward(x, training=True, seed=seed, step=step, cache=cache, drop_offset=drop_offset, mutate=mutate)
-        loss, per, dp = cce_fwd_bwd(p, y_onehot.astype(self.dtype))
-        dl = softmax_bwd(dp, p)
-        grads = OrderedDict()
-        grads['dense_1/kernel'] = cache['gru_out'].T @ dl
-        grads['dense_1/bias'] = dl.sum(axis=0)
-        dout = dl @ self._p('dense_1/kernel').T
+        loss, dout = self.head_bwd(p, y_onehot, cache['gru_out'], 'dense_1/kernel', 'dense_1/bias', grads)
         da, gg = bigru_bwd(dout, cache['gru_in'], self._gru_weights(), cache['gru'], decisions, mutate)
         for base, (dW, dU, db) in zip(self.gru_names, gg):
             grads[base + 'kernel'], grads[base + 'recurrent_kernel'], grads[base + 'bias'] = dW, dU, db
         for blk in reversed(self.blocks):
-            n = blk['idx']
-            y, st = cache['y%d' % n], cache['st%d' % n]
-            ga = self._p('batch_normalization_%d/gamma' % n)
-            if relu_masks is not None and n in relu_masks:
-                mask = relu_masks[n]
-            else:
-                mask = relu6_mask(y * (st[2] * ga) + (self._p('batch_normalization_%d/beta' % n) - st[0] * st[2] * ga))
-            dy, dga, dbe = bn_train_bwd(da * mask, y, ga, st)
-            grads['batch_normalization_%d/gamma' % n] = dga
-            grads['batch_normalization_%d/beta' % n] = dbe
-            W = self._p('conv1d_%d/kernel' % n)[0]
-            z = cache['z%d' % n]
-            grads['conv1d_%d/kernel' % n] = (z.reshape(-1, z.shape[2]).T @ dy.reshape(-1, dy.shape[2]))[None]
-            da, dw = dw_bwd(dy @ W.T, cache['a%d' % n], self._p('depthwise_conv2d_%d/depthwise_kernel' % n)[0, :, :, 0], blk['s'], 0)
-            grads['depthwise_conv2d_%d/depthwise_kernel' % n] = dw[None, :, :, None]
-        return loss, p, OrderedDict((k, grads[k]) for k in self.params), cache
+            da = self.block_bwd(blk['idx'], da, blk['s'], 0, cache, grads, relu_masks)
+        return loss, p, self.ordered(grads), cache

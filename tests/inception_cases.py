@@ -3,6 +3,7 @@ clips on both sides, so that the figures in test_inception_models_gpu.py's docst
 import numpy as np
 
 from inception_oracle import InceptionD1Net
+from net_parity import perturb
 
 NC = 12
 TRAIN_BATCHES = (3, 16)
@@ -14,20 +15,7 @@ def perturbed(dtype=np.float64, nc=NC, seed=5):
     """About a third of the BatchNorm scales negative, shifts that make relu6(shift) != 0, moving statistics off their
     initial values."""
     ora = InceptionD1Net(num_classes=nc, dtype=dtype)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.3 + 0.2 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('bias'):
-            ora.params[k] = (0.05 * rng.randn(nc)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.3, 0.2), bias=0.05)
     assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
     return ora
 

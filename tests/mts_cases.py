@@ -3,7 +3,7 @@ in a plain module so that tests/test_mts_cpu.py can check on the CPU what those 
 INFRASTRUCTURE ONLY."""
 import numpy as np
 
-from mts_oracle import pool_same_argmax, pool_same_geometry, pool_same_windows
+import pool_oracle
 
 # (B, L, C): both parities, the smallest L, the thread-run boundaries of forward (4 outputs) and backward (8 rows), the widest and
 # narrowest C of the ladders
@@ -22,7 +22,7 @@ def pool_inputs(B, L, C, seed=None):
     scale = (1.0 + 0.1 * rng.randn(C)) * np.where(rng.rand(C) < 0.35, -1.0, 1.0)
     scale[0] = -abs(scale[0])
     tab = np.concatenate([scale, 0.5 + 0.3 * rng.randn(C), 0.3 * rng.randn(C), 0.5 + rng.rand(C)]).astype(np.float32)
-    dz = rng.randn(B, pool_same_geometry(L)[0], C).astype(np.float32)
+    dz = rng.randn(B, pool_oracle.same_geometry(L)[0], C).astype(np.float32)
     return y, tab, dz
 
 
@@ -39,10 +39,10 @@ def pool_compared(y, tab, dz=None):
     inside (0, 6).  (A tie of saturated values needs no exclusion: whichever row wins, its gate is shut and g is 0, except at
     pre = 6 exactly, which the kink margin covers.)"""
     B, L, C = y.shape
-    Lp, pad_l = pool_same_geometry(L)
+    Lp, pad_l = pool_oracle.same_geometry(L)
     pre, _ = pool_pre(y, tab)
     far = (np.abs(pre) > KINK_EPS) & (np.abs(pre - 6) > KINK_EPS)
-    w = np.sort(pool_same_windows(np.clip(pre, 0, 6), pad_l), axis=2)          # ascending; -inf = padding
+    w = np.sort(pool_oracle.windows(np.clip(pre, 0, 6), Lp, pad_l), axis=2)          # ascending; -inf = padding
     tie = (w[:, :, 2] - w[:, :, 1] <= TIE_EPS) & (w[:, :, 2] > 0) & (w[:, :, 2] < 6)   # [B, Lp, C]
     bad = np.zeros((B, 2 * Lp + 1, C), bool)
     for j in range(3):

@@ -1,11 +1,10 @@
 """Float64 NumPy oracle of the three-branch raw-waveform net conv_1d_multi_time_sliced (reference model.py:1080-1156): forward,
-loss and every gradient, restated layer by layer for the GPU parity tests, and the stand-alone SAME max-pool
-`pool_same_*` the kernel tests compare kws_pool3s2_same_* with.
+loss and every gradient, restated layer by layer for the GPU parity tests.
 
 TEST INFRASTRUCTURE ONLY.  The structure - names, order, shapes, l2, which tensor feeds which block, the pools and their left
 padding, the concatenation - is read from tests/golden/mts_models.json (recorded from the reference by
 tests/golden/make_golden_mts.py); nothing about it is restated here.  A block is DepthwiseConv2D((1, k), VALID, no bias) ->
-Conv1D(F, 1, no bias) -> BatchNormalization -> relu6 (dwk_oracle.dw_fwd / dw_bwd); a reduce block is followed by
+Conv1D(F, 1, no bias) -> BatchNormalization -> relu6 (oracle_blocks.DwPwNet); a reduce block is followed by
 MaxPool1D(3, strides=2, 'same'): TensorFlow's SAME geometry (ceil(L / 2) windows, pad_left = pad_total // 2, the padding never
 wins), the gradient to the FIRST maximum of a window.  Dropout masks are oracle/layers.py's counter-based ones (layer ids 1 and 2).
 
@@ -17,42 +16,14 @@ wins), the gradient to the FIRST maximum of a window.  Dropout masks are oracle/
 """
 import json
 import os
-from collections import OrderedDict
 
 import numpy as np
 
 import pool_oracle
-from dwk_oracle import dw_bwd, dw_fwd, glorot
-from oracle.layers import (bn_infer_fwd, bn_train_bwd, bn_train_fwd, cce_fwd_bwd, dropout_key, dropout_mask, relu6, relu6_mask,
-                           softmax, softmax_bwd)
+from oracle_blocks import DwPwNet, glorot
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'mts_models.json')
 MODEL = 'conv_1d_multi_time_sliced'
-
-
-# ---- MaxPool1D(3, strides=2, padding='same') ---------------------------------------------------------------------------------
-def pool_same_geometry(L, odd_left=False):
-    """-> (windows, pad_left): TensorFlow SAME for pool 3, stride 2 (odd_left: the odd padding sample on the left)."""
-    Lp = -(-L // 2)
-    total = max(2 * (Lp - 1) + 3 - L, 0)
-    return Lp, (total - total // 2) if odd_left else total // 2
-
-
-def pool_same_windows(a, pad_l):
-    """[B, L, C] -> [B, Lp, 3, C] windows over the input padded with -inf (rows 2t - pad_l + j)."""
-    return pool_oracle.windows(a, -(-a.shape[1] // 2), pad_l)
-
-
-def pool_same_argmax(a, pad_l, last=False):
-    return pool_oracle.argmax(a, -(-a.shape[1] // 2), pad_l, last)
-
-
-def pool_same_fwd(a, ind, pad_l):
-    return pool_oracle.fwd(a, ind, pad_l)
-
-
-def pool_same_bwd(dz, ind, L, pad_l):
-    return pool_oracle.bwd(dz, ind, L, pad_l)
 
 
 # ---- the net -------------------------------------------------------------------------------------------------------------------
@@ -96,16 +67,14 @@ def load_structure(num_classes=None):
     return blocks, ends, gold
 
 
-class MtsNet(object):
+class MtsNet(DwPwNet):
     """conv_1d_multi_time_sliced; input [B, 16000] raw samples."""
 
     def __init__(self, num_classes=12, seed=1234):
-        rng = np.random.RandomState(seed)
-        self.nc = num_classes
+        super(MtsNet, self).__init__(num_classes, seed)
         self.blocks, self.ends, gold = load_structure()
         self.keep = [1.0 - l['rate'] for l in gold['layers'] if l['class'] == 'Dropout']
         assert len(self.keep) == 2
-        P, S = OrderedDict(), OrderedDict()
         self.l2 = {}
         for w in gold['weights']:
             shape = list(w['shape'])
@@ -113,14 +82,14 @@ class MtsNet(object):
             if name.startswith('conv1d_%d/' % (len(self.blocks) + 1)):
                 shape[-1] = num_classes          # the fixture was recorded at 12 classes
             if name.endswith('depthwise_kernel'):
-                v = glorot(rng, shape, shape[1] * shape[2], shape[1])
+                v = glorot(self.rng, shape, shape[1] * shape[2], shape[1])
             elif name.endswith('/kernel'):
-                v = glorot(rng, shape, shape[0] * shape[1], shape[0] * shape[2])
+                v = glorot(self.rng, shape, shape[0] * shape[1], shape[0] * shape[2])
             elif name.endswith('gamma') or name.endswith('moving_variance'):
                 v = np.ones(shape, np.float32)
             else:
                 v = np.zeros(shape, np.float32)
-            (S if w.get('state') else P)[name] = v
+            (self.state if w.get('state') else self.params)[name] = v
             if not w.get('state'):
                 self.l2[name] = w['l2']
         self.l2_names = [k for k, v in self.l2.items() if v > 0]
@@ -134,13 +103,6 @@ class MtsNet(object):
             if b['src'][0] == 'act':
                 self.consumers.setdefault(b['src'][1], []).append(b['idx'])
         self.forks = sorted(k for k, v in self.consumers.items() if len(v) > 1)
-        self.params, self.state = P, S
-
-    def count_params(self):
-        return sum(v.size for v in self.params.values()) + sum(v.size for v in self.state.values())
-
-    def _p(self, name):
-        return self.params[name].astype(np.float64)
 
     def _pad_l(self, blk, mutate):
         if mutate == 'pool_pad_side':
@@ -149,31 +111,19 @@ class MtsNet(object):
 
     def _block(self, blk, a, training, cache, mutate, pool_ind):
         n = blk['idx']
-        z = dw_fwd(a, self._p('depthwise_conv2d_%d/depthwise_kernel' % n)[0, :, :, 0], 1, 0, blk['Lout'])
-        y = z @ self._p('conv1d_%d/kernel' % n)[0]
-        ga, be = self._p('batch_normalization_%d/gamma' % n), self._p('batch_normalization_%d/beta' % n)
-        if training:
-            pre, st = bn_train_fwd(y, ga, be)
-        else:
-            st = None
-            pre = bn_infer_fwd(y, ga, be, self.state['batch_normalization_%d/moving_mean' % n].astype(np.float64),
-                               self.state['batch_normalization_%d/moving_variance' % n].astype(np.float64))
-        act = relu6(pre)
+        act = self.block_fwd(n, a, 1, 0, blk['Lout'], training, cache)
         ind = pooled = None
         if blk['pool'] is not None:
-            pad_l = self._pad_l(blk, mutate)
+            pad_l, Lp = self._pad_l(blk, mutate), blk['pool']['Lp']
             if mutate == 'last_max':
-                ind = pool_same_argmax(act, pad_l, last=True)
+                ind = pool_oracle.argmax(act, Lp, pad_l, last=True)
             elif pool_ind is not None and n in pool_ind and mutate != 'pool_pad_side':
                 ind = pool_ind[n]
             else:
-                ind = pool_same_argmax(act, pad_l)
-            pooled = pool_same_fwd(act, ind, pad_l)
+                ind = pool_oracle.argmax(act, Lp, pad_l)
+            pooled = pool_oracle.fwd(act, ind, pad_l)
         if cache is not None:
-            cache['a%d' % n], cache['z%d' % n], cache['y%d' % n], cache['st%d' % n], cache['ind%d' % n] = a, z, y, st, ind
-            cache['pre%d' % n] = pre
-            if training:
-                cache['batch_stats'][n] = (st[0], st[1])
+            cache['ind%d' % n] = ind
         return act, pooled
 
     def forward(self, x, training=False, seed=0, step=0, cache=None, drop_offset=0, mutate=None, pool_ind=None):
@@ -190,49 +140,28 @@ class MtsNet(object):
         assert feat.shape == (B, 1, self.D)
         keep1 = keep2 = None
         if training:
-            keep1 = dropout_mask(dropout_key(seed, step, 1), B * self.D, self.keep[0], offset=drop_offset * self.D).reshape(B, 1, self.D)
+            keep1 = self.dropout(seed, step, 1, B, self.D, self.keep[0], drop_offset).reshape(B, 1, self.D)
             feat = feat * keep1 / self.keep[0]
         h, _ = self._block(self.head, feat, training, cache, mutate, pool_ind)
         H = self.head['F']
         h = h.reshape(B, H)
         if training:
-            keep2 = dropout_mask(dropout_key(seed, step, 2), B * H, self.keep[1], offset=drop_offset * H).reshape(B, H)
+            keep2 = self.dropout(seed, step, 2, B, H, self.keep[1], drop_offset)
             h = h * keep2 / self.keep[1]
-        p = softmax(h @ self._p(self.out_kernel)[0] + self._p(self.out_bias))
+        p = self.head_fwd(h, self.out_kernel, self.out_bias)
         if cache is not None:
             cache.update(h=h, keep1=keep1, keep2=keep2, p=p)
         return p
 
-    def _block_bwd(self, blk, dact, cache, grads, relu_masks, mutate):
-        """dact: gradient wrt the block's activated (un-pooled) output -> gradient wrt the block's input."""
-        n = blk['idx']
-        y, st = cache['y%d' % n], cache['st%d' % n]
-        ga = self._p('batch_normalization_%d/gamma' % n)
-        mask = relu_masks[n] if relu_masks is not None and n in relu_masks else relu6_mask(cache['pre%d' % n])
-        dy, dga, dbe = bn_train_bwd(dact * mask, y, ga, st)
-        grads['batch_normalization_%d/gamma' % n] = dga
-        grads['batch_normalization_%d/beta' % n] = dbe
-        z = cache['z%d' % n]
-        grads['conv1d_%d/kernel' % n] = (z.reshape(-1, z.shape[2]).T @ dy.reshape(-1, dy.shape[2]))[None]
-        dz = dy @ self._p('conv1d_%d/kernel' % n)[0].T
-        da, dw = dw_bwd(dz, cache['a%d' % n], self._p('depthwise_conv2d_%d/depthwise_kernel' % n)[0, :, :, 0], 1, 0)
-        grads['depthwise_conv2d_%d/depthwise_kernel' % n] = dw[None, :, :, None]
-        return da
-
     def loss_and_grads(self, x, y_onehot, seed=0, step=0, drop_offset=0, relu_masks=None, pool_ind=None, mutate=None):
         """Data loss (batch mean) and its gradients (no L2 term)."""
-        cache = {}
+        cache, grads = {}, {}
         B = x.shape[0]
         p = self.forward(x, training=True, seed=seed, step=step, cache=cache, drop_offset=drop_offset, mutate=mutate,
                          pool_ind=pool_ind)
-        loss, per, dp = cce_fwd_bwd(p, y_onehot.astype(np.float64))
-        dl = softmax_bwd(dp, p)
-        grads = OrderedDict()
-        grads[self.out_kernel] = (cache['h'].T @ dl)[None]
-        grads[self.out_bias] = dl.sum(axis=0)
-        H = self.head['F']
-        dh = ((dl @ self._p(self.out_kernel)[0].T) * cache['keep2'] / self.keep[1]).reshape(B, 1, H)
-        dfeat = self._block_bwd(self.head, dh, cache, grads, relu_masks, mutate) * cache['keep1'] / self.keep[0]
+        loss, dh = self.head_bwd(p, y_onehot, cache['h'], self.out_kernel, self.out_bias, grads)
+        dh = (dh * cache['keep2'] / self.keep[1]).reshape(B, 1, self.head['F'])
+        dfeat = self.block_bwd(self.head['idx'], dh, 1, 0, cache, grads, relu_masks) * cache['keep1'] / self.keep[0]
         dact, dpool = {}, {}                       # gradients wrt activated / pooled outputs, by producing block
         col = 0
         for e in self.ends:
@@ -242,9 +171,9 @@ class MtsNet(object):
         for blk in reversed(self.blocks[:-1]):
             n = blk['idx']
             if blk['pool'] is not None:
-                d = pool_same_bwd(dpool[n], cache['ind%d' % n], blk['Lout'], self._pad_l(blk, mutate))
+                d = pool_oracle.bwd(dpool[n], cache['ind%d' % n], blk['Lout'], self._pad_l(blk, mutate))
                 dact[n] = dact[n] + d if n in dact else d
-            da = self._block_bwd(blk, dact[n], cache, grads, relu_masks, mutate)
+            da = self.block_bwd(n, dact[n], 1, 0, cache, grads, relu_masks)
             s = blk['src']
             if s[0] == 'pool':
                 dpool[s[1]] = da
@@ -252,5 +181,4 @@ class MtsNet(object):
                 if mutate == 'drop_fork' and s[1] in self.forks and n in self.ends:
                     continue
                 dact[s[1]] = dact[s[1]] + da if s[1] in dact else da
-        ordered = OrderedDict((k, grads[k]) for k in self.params)
-        return loss, p, ordered, cache
+        return loss, p, self.ordered(grads), cache

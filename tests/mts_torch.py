@@ -56,11 +56,11 @@ def torch_step(ora, x, y, seed, step, dtype=torch.float64):
 
 def decisions_from_pres(ora, pres):
     """ReLU6 masks and pool winners of a run, from its pre-activations (what the GPU tests read back from the device)."""
-    from mts_oracle import pool_same_argmax
+    import pool_oracle
     masks, inds = {}, {}
     for blk in ora.blocks:
         pre = pres[blk['idx']]
         masks[blk['idx']] = ((pre > 0) & (pre <= 6)).astype(np.float64)
         if blk['pool'] is not None:
-            inds[blk['idx']] = pool_same_argmax(np.clip(pre, 0, 6), blk['pool']['pad_l'])
+            inds[blk['idx']] = pool_oracle.argmax(np.clip(pre, 0, 6), blk['pool']['Lp'], blk['pool']['pad_l'])
     return masks, inds

@@ -1,19 +1,46 @@
 """What the residual-family GPU parity files (test_logmfcc_gpu, test_steffe_gpu, test_residual_gpu, test_mfcc_and_raw_gpu)
 share: the weight perturbation of their oracle / device pairs, the waveform batch, the read-back of the device's ReLU6
-decisions, and the comparison of one training step against the oracle.  A plain module like grouped_oracle.py: no
-fixtures."""
+decisions, and the comparison of one training step against the oracle; and what the CPU files of every family share: the
+perturbation again and the read-out of a net's native tensor table.  A plain module like grouped_oracle.py: no fixtures."""
+import ctypes
+
 import numpy as np
 
 
-def perturb(ora, seed):
-    """Moves BN scales / shifts, biases and moving statistics off their initial 1 / 0 so that a mix-up shows."""
+def native_table(kind, nc=12, input_size=16000, filter_mult=1, spectrogram_length=0, num_features=0):
+    """The tensor table (a list of _lib.TensorInfo) of a net created for this configuration and destroyed again"""
+    from speech_recognition_amd import _lib
+    lib = _lib.load()
+    cfg = _lib.NetConfig(kind, nc, filter_mult, input_size, spectrogram_length, num_features)
+    h = ctypes.c_void_p()
+    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
+    out = []
+    try:
+        for i in range(lib.kws_net_num_tensors(h)):
+            ti = _lib.TensorInfo()
+            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
+            out.append(ti)
+    finally:
+        lib.kws_net_destroy(h)
+    return out
+
+
+def perturb(ora, seed, negative_fraction=0.0, beta=(0.0, 0.1), bias=0.1, state=True):
+    """Moves BN scales (1 + 0.1 n, about a negative_fraction of them negative), shifts (beta[0] + beta[1] n), biases (bias n;
+    None: left alone) and, with `state`, the moving statistics off their initial 1 / 0 so that a mix-up shows."""
     rng = np.random.RandomState(seed)
     for k in ora.params:
+        shape = ora.params[k].shape
         if k.endswith('gamma'):
-            ora.params[k] = (1.0 + 0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('beta') or k.endswith('bias'):
-            ora.params[k] = (0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-    for k in ora.state:
+            g = 1.0 + 0.1 * rng.randn(*shape)
+            if negative_fraction:
+                g = g * np.where(rng.rand(*shape) < negative_fraction, -1.0, 1.0)
+            ora.params[k] = g.astype(np.float32)
+        if k.endswith('beta'):
+            ora.params[k] = (beta[0] + beta[1] * rng.randn(*shape)).astype(np.float32)
+        if k.endswith('bias') and bias is not None:
+            ora.params[k] = (bias * rng.randn(*shape)).astype(np.float32)
+    for k in ora.state if state else ():
         if k.endswith('moving_mean'):
             ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
         else:

@@ -1,9 +1,20 @@
 """Float64-capable NumPy oracle of MaxPool1D(3, strides=2) in either padding: Lp windows over the input padded with -inf, window t
 covering the rows 2t - pad_l + j, j < 3.  TEST INFRASTRUCTURE ONLY.
-  'valid'  Lp = (L - 3) // 2 + 1, pad_l = 0 (no window reaches a padded row)      stacked_oracle.pool_*
-  'same'   Lp = ceil(L / 2),      pad_l = pad_total // 2 (TensorFlow)             mts_oracle.pool_same_*
+  'valid'  Lp = (L - 3) // 2 + 1, pad_l = 0 (no window reaches a padded row)      pool_len
+  'same'   Lp = ceil(L / 2),      pad_l = pad_total // 2 (TensorFlow)             same_geometry
 The gradient of a window goes to the FIRST maximum (TF MaxPoolGrad); the padding never wins."""
 import numpy as np
+
+import oracle_blocks
+
+
+def pool_len(L):
+    return (L - 3) // 2 + 1
+
+
+def same_geometry(L, odd_left=False):
+    """-> (windows, pad_left): TensorFlow SAME for pool 3, stride 2 (odd_left: the odd padding sample on the left)."""
+    return oracle_blocks.same_geometry(L, 3, 2, odd_left=odd_left)[:2]
 
 
 def windows(a, Lp, pad_l):

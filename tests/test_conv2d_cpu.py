@@ -16,6 +16,7 @@ import torch.nn.functional as Fn
 import conv2d_cases as cases
 from conv2d_oracle import (ACT, KEEP_LADDER, LADDERS, SGD, Conv2dNet, axis_geom, conv2d_bwd, conv2d_fwd, pool2_argmax, pool2_bwd,
                            pool2_fwd, preprocess)
+from net_parity import native_table
 from oracle.layers import dropout_key, dropout_mask, sgd_momentum_step
 from speech_recognition_amd import _lib
 
@@ -28,22 +29,6 @@ IMAGES = {'mobile': [(49, 20), (49, 20), (25, 10), (25, 10), (13, 5), (13, 5), (
 def _golden(kind):
     with open(GOLDEN) as f:
         return json.load(f)['conv_2d_' + kind]
-
-
-def _native_table(kind, nc=12, input_size=3920):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(KINDS[kind], nc, 1, input_size, 0, 0)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def test_kind_constants_and_descriptor():
@@ -156,7 +141,7 @@ def test_fixture_matches_oracle_and_native_table(kind):
     assert gap['input'][0] * gap['input'][1] == ora.T and gap['output'] == [ora.C]
     assert (ora.T, ora.C) == ((21, 256) if kind == 'mobile' else (12, 128))
     # weights: names and shapes in Keras order - fixture, oracle, native table
-    table = _native_table(kind)
+    table = native_table(KINDS[kind], 12, 3920)
     names = [w['name'] for w in gold['weights']]
     assert [t.name.decode() for t in table] == names
     assert names[:6] == ['conv2d_1/kernel', 'conv2d_1/bias', 'batch_normalization_1/gamma', 'batch_normalization_1/beta',

@@ -10,9 +10,11 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+from net_parity import native_table, perturb
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
-from dwk_oracle import HIDDEN, KEEP, LADDER, SPEC, DwkNet, dw_bwd, dw_fwd, same_geometry
+from dwk_oracle import HIDDEN, KEEP, LADDER, SPEC, DwkNet
+from oracle_blocks import dw_bwd, dw_fwd, same_geometry
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dwk_models.json')
 WIDTHS = [1, 128, 256, 384, 448, 512, 512]
@@ -21,22 +23,6 @@ WIDTHS = [1, 128, 256, 384, 448, 512, 512]
 def _golden():
     with open(GOLDEN) as f:
         return json.load(f)['conv_1d_gru']
-
-
-def _native_table(nc=12, input_size=16000):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(_lib.KWS_NET_CONV_1D_GRU, nc, 1, input_size, 0, 0)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def test_kind_constant():
@@ -60,12 +46,12 @@ def test_fixture_has_the_expected_ladder():
     # the oracle's own geometry and the TF rule agree with the recording
     for (F, k, s, pad), (L, pad_l, Lout) in zip(SPEC, LADDER):
         if pad == 'same':
-            assert same_geometry(L, k, s) == (Lout, pad_l)
+            assert same_geometry(L, k, s)[:2] == (Lout, pad_l)
 
 
 def test_native_tensor_table_matches_reference_and_oracle():
     gold = _golden()
-    table = _native_table(gold['num_classes'], gold['input_size'])
+    table = native_table(_lib.KWS_NET_CONV_1D_GRU, gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']
@@ -160,15 +146,7 @@ def test_oracle_depthwise_matches_torch_autograd(i):
 
 def _perturbed(seed=5):
     ora = DwkNet(num_classes=12)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):   # a third of the scales negative
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('bias'):
-            ora.params[k] = (0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.5, 0.3), state=False)
     return ora
 
 

@@ -1,4 +1,4 @@
-"""kws_dwconvk_* (csrc/dwconvk.hip) called directly, against float64 NumPy (tests/dwk_oracle.py dw_fwd / dw_bwd): the general
+"""kws_dwconvk_* (csrc/dwconvk.hip) called directly, against float64 NumPy (tests/oracle_blocks.py dw_fwd / dw_bwd): the general
 depthwise convolution forward, backward and finalize on the six conv_1d_gru geometries and on odd ones (k = 1, k = 64 at stride
 16, stride > k, uncovered input rows, C = 1 / 4 / 20 / 448, the direct kernels' k / s > 8), with and without a BatchNorm table
 (some scales negative); and the one-channel pointwise pair kws_dwconvk_pw1_*.
@@ -15,7 +15,8 @@ import pytest
 import torch
 
 from speech_recognition_amd import _lib
-from dwk_oracle import LADDER, SPEC, dw_bwd, dw_fwd
+from dwk_oracle import LADDER, SPEC
+from oracle_blocks import dw_bwd, dw_fwd
 
 pytestmark = pytest.mark.gpu
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from grouped_oracle import gconv_bwd, gconv_fwd
+from oracle_blocks import gconv_bwd, gconv_fwd
 from speech_recognition_amd import _lib
 
 pytestmark = pytest.mark.gpu

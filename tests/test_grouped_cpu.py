@@ -1,7 +1,6 @@
 """CPU checks of the grouped-Conv1D models: the native tensor tables against the structure recorded from the reference
 (tests/golden/grouped_models.json, made by tests/golden/make_golden_grouped.py), and the float64 oracle
 (tests/grouped_oracle.py) against torch autograd with F.conv1d(groups=g) on the sliced input."""
-import ctypes
 import json
 import os
 
@@ -10,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+from net_parity import native_table
 from grouped_oracle import FAST_BLOCKS, KEEP, SPEC_BLOCKS, GroupedConvNet
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
@@ -23,26 +23,10 @@ def _golden(name):
         return json.load(f)[name]
 
 
-def _native_table(kind, nc=12, input_size=16000, filter_mult=1, spectrogram_length=0, num_features=0):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(kind, nc, filter_mult, input_size, spectrogram_length, num_features)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
-
-
 @pytest.mark.parametrize("name", sorted(KINDS))
 def test_native_tensor_table_matches_reference(name):
     gold = _golden(name)
-    table = _native_table(KINDS[name], gold['num_classes'], gold['input_size'])
+    table = native_table(KINDS[name], gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']

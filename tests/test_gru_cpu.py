@@ -11,28 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+from net_parity import native_table
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
 from gru_oracle import (KEEP, KERNEL_CASES, SimpleNet, bigru_bwd, bigru_fwd, draw_masks, golden, kernel_inputs)
 
 GRU_SYMBOLS = ['kws_gru_save_floats', 'kws_gru_workspace_floats', 'kws_gru_masks', 'kws_gru_seq_fwd_f32', 'kws_gru_seq_bwd_f32',
                'kws_gru_fwd_f32', 'kws_gru_bwd_f32']
-
-
-def _native_table(nc=12, input_size=16000):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(_lib.KWS_NET_CONV_1D_SIMPLE, nc, 1, input_size, 0, 0)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def test_kind_constant_and_symbols(repo_root):
@@ -67,7 +52,7 @@ def test_fixture_structure():
 
 def test_native_tensor_table_matches_reference_and_oracle():
     gold = golden()
-    table = _native_table(gold['num_classes'], gold['input_size'])
+    table = native_table(_lib.KWS_NET_CONV_1D_SIMPLE, gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         name = w['name']
@@ -141,7 +126,7 @@ def test_initialize_draws_orthogonal_recurrent_kernels():
     """DeviceNet.initialize on a host stand-in for the device buffers: recurrent kernels have orthonormal rows, every other tensor
     holds what the parent's rule gives it (one RandomState(seed) stream over the tensors with fan_in > 0, in table order)."""
     from speech_recognition_amd.net import DeviceNet, TensorSpec
-    table = _native_table()
+    table = native_table(_lib.KWS_NET_CONV_1D_SIMPLE)
     net = DeviceNet.__new__(DeviceNet)
     net.tensors = OrderedDict()
     for ti in table:

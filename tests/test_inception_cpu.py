@@ -14,6 +14,7 @@ import torch.nn.functional as Fn
 
 import inception_cases as cases
 from inception_oracle import (BLOCKS, KEEP, InceptionD1Net, avgpool_bwd, avgpool_fwd, same_pool_pad_l)
+from net_parity import native_table
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
 
@@ -28,22 +29,6 @@ MIXED_DIL = {1: 2, 2: 2, 4: 2, 5: 1, 7: 1, 8: 1, 10: 1, 11: 1}
 def _golden():
     with open(GOLDEN) as f:
         return json.load(f)['inception_d1']
-
-
-def _native_table(nc=12, input_size=16000):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(KIND, nc, 1, input_size, 0, 0)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def test_kind_constant():
@@ -120,7 +105,7 @@ def test_fixture_has_the_expected_structure():
 
 def test_native_tensor_table_matches_reference_and_oracle():
     gold = _golden()
-    table = _native_table(gold['num_classes'], gold['input_size'])
+    table = native_table(KIND, gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']

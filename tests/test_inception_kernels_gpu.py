@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from inception_oracle import avgpool_bwd, avgpool_fwd, conv_bwd, conv_fwd, same_pad_l
+from inception_oracle import avgpool_bwd, avgpool_fwd
+from oracle_blocks import conv_bwd, conv_fwd, same_geometry
 from speech_recognition_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ SENT = 0x7FC0DEAD
 def _case(B, L, Cin, F, k, dil, Cx=None, x0=0, Cy=None, y0=0, valid=False):
     span = dil * (k - 1)
     return dict(B=B, L=L, Cin=Cin, F=F, k=k, dil=dil, Cx=Cx or Cin, x0=x0, Cy=Cy or F, y0=y0,
-                pad_l=0 if valid else same_pad_l(k, dil), Lout=L - span if valid else L)
+                pad_l=0 if valid else same_geometry(L, k, 1, dil)[1], Lout=L - span if valid else L)
 
 
 CASES = [
@@ -129,9 +130,9 @@ def _reference(c, x, bn, W, dy):
         b = bn.astype(np.float64)
         xw = np.clip(xw * b[0, c['x0']:c['x0'] + c['Cin']] + b[1, c['x0']:c['x0'] + c['Cin']], 0, 6)
     W64 = W.astype(np.float64)
-    y, ap = conv_fwd(xw, W64, c['dil'], c['pad_l'], c['Lout'])
+    y, ap = conv_fwd(xw, W64, 1, c['dil'], c['pad_l'], c['Lout'])
     dyw = dy[:, :, c['y0']:c['y0'] + c['F']].astype(np.float64)
-    dx, dW = conv_bwd(dyw, ap, W64, c['dil'], c['pad_l'], c['L'])
+    dx, dW = conv_bwd(dyw, ap, W64, c['L'], 1, c['dil'], c['pad_l'])
     return y, dx, dW
 
 

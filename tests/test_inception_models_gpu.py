@@ -23,10 +23,9 @@ import torch
 
 import adam_oracle as SO
 import inception_cases as cases
-from mts_oracle import pool_same_argmax
+import pool_oracle
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
-from stacked_oracle import pool_argmax
 
 pytestmark = pytest.mark.gpu
 
@@ -67,14 +66,14 @@ def _decisions(net, ora, B):
         masks[idx] = (pre > 0) & (pre <= 6)
         act[idx] = np.clip(pre, 0, 6).astype(np.float64)
         if c['pool'] == 'valid':
-            inds[idx] = pool_argmax(act[idx])
+            inds[idx] = pool_oracle.argmax(act[idx], c['Lp'], 0)
         elif c['pool'] == 'same':
-            inds[idx] = pool_same_argmax(act[idx], c['Lout'] & 1)
+            inds[idx] = pool_oracle.argmax(act[idx], c['Lp'], c['Lout'] & 1)
     for prev, rec in zip(ora.blocks, ora.blocks[1:]):
         if rec['kind'] == 'red':     # the pool branch reads the joined output of the inception block before it
             cs = prev['convs']
             joined = np.concatenate([act[cs[i]['idx']] for i in (0, 2, 5, 6)], axis=2)
-            inds['mixed%d' % rec['id']] = pool_same_argmax(joined, rec['L'] & 1)
+            inds['mixed%d' % rec['id']] = pool_oracle.argmax(joined, rec['Lout'], rec['L'] & 1)
     return masks, inds
 
 

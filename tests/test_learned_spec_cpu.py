@@ -15,6 +15,7 @@ import torch.nn.functional as Fn
 
 import fbank_conv_cases as FB
 from learned_spec_oracle import BLOCKS, FRONT_K, FRONT_N, FRONT_STRIDE, KEEP, MUTATIONS, LearnedSpecNet, padded, same_pads
+from net_parity import native_table, perturb
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
 
@@ -50,20 +51,6 @@ def _create(input_size, nc=12):
     cfg = _lib.NetConfig(KIND, nc, 1, input_size, 0, 0)
     h = ctypes.c_void_p()
     return lib, lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), h
-
-
-def _native_table(nc=12, input_size=16000):
-    lib, rc, h = _create(input_size, nc)
-    _lib.check(rc, "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def _fdesc(c, w_off=None):
@@ -173,7 +160,7 @@ def test_fixture_has_the_expected_layers():
 @pytest.mark.parametrize("L", [16000, 15000])
 def test_native_tensor_table_matches_reference_and_oracle(L):
     gold = _golden(L)
-    table = _native_table(gold['num_classes'], gold['input_size'])
+    table = native_table(KIND, gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']
@@ -275,13 +262,7 @@ def test_fbank_conv_case_table_and_planner():
 # ---- the oracle against torch autograd --------------------------------------------------------------------------------------
 def _perturbed(input_size=16000, seed=5):
     ora = LearnedSpecNet(num_classes=12, input_size=input_size)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):   # a third of the scales negative
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.5, 0.3), bias=None, state=False)
     return ora
 
 

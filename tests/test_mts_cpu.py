@@ -11,7 +11,9 @@ import torch
 import torch.nn.functional as Fn
 
 from speech_recognition_amd import _lib
-from mts_oracle import (GOLDEN, MODEL, MtsNet, load_structure, pool_same_argmax, pool_same_bwd, pool_same_fwd, pool_same_geometry)
+import pool_oracle
+from net_parity import perturb
+from mts_oracle import GOLDEN, MODEL, MtsNet, load_structure
 from mts_torch import same_pool, torch_step
 
 # (length after the block's convolution, length after its pool) of every reduce block, then the context / tap lengths
@@ -138,17 +140,7 @@ def test_native_tensor_table_matches_the_fixture():
 
 def _perturbed(seed=5, negative=True):
     ora = MtsNet(num_classes=12)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            if negative:        # a third of the scales negative
-                g = g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)
-            ora.params[k] = g.astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('bias'):
-            ora.params[k] = (0.05 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33 if negative else 0.0, beta=(0.5, 0.3), bias=0.05, state=False)
     return ora
 
 
@@ -191,24 +183,24 @@ def test_oracle_gradients_match_torch_autograd_with_positive_scales():
 def test_oracle_pool_matches_torch_max_pool1d_with_same_padding(L):
     rng = np.random.RandomState(L)
     a = np.clip(rng.randn(3, L, 8) * 3.0, 0, 6)       # saturated 0 / 6 values: plenty of ties
-    Lp, pad_l = pool_same_geometry(L)
+    Lp, pad_l = pool_oracle.same_geometry(L)
     assert (Lp, pad_l) == ((L + 1) // 2, L % 2)
-    ind = pool_same_argmax(a, pad_l)
-    z = pool_same_fwd(a, ind, pad_l)
+    ind = pool_oracle.argmax(a, Lp, pad_l)
+    z = pool_oracle.fwd(a, ind, pad_l)
     ta = torch.tensor(a, requires_grad=True)
     tz = same_pool(ta.permute(0, 2, 1), pad_l).permute(0, 2, 1)
     assert tz.shape[1] == Lp
     np.testing.assert_array_equal(z, tz.detach().numpy())
     dz = rng.randn(*z.shape)
     tz.backward(torch.tensor(dz))
-    np.testing.assert_allclose(pool_same_bwd(dz, ind, L, pad_l), ta.grad.numpy(), atol=1e-15)   # torch: the first maximum too
+    np.testing.assert_allclose(pool_oracle.bwd(dz, ind, L, pad_l), ta.grad.numpy(), atol=1e-15)   # torch: the first maximum too
     # tied values: the first maximum wins, the last-maximum variant differs
     q = rng.randint(1, 4, size=(3, L, 8)).astype(np.float64)
-    first, last = pool_same_argmax(q, pad_l), pool_same_argmax(q, pad_l, last=True)
+    first, last = pool_oracle.argmax(q, Lp, pad_l), pool_oracle.argmax(q, Lp, pad_l, last=True)
     assert (first <= last).all() and (first < last).any()
     tq = torch.tensor(q, requires_grad=True)
     same_pool(tq.permute(0, 2, 1), pad_l).permute(0, 2, 1).backward(torch.tensor(dz))
-    np.testing.assert_allclose(pool_same_bwd(dz, first, L, pad_l), tq.grad.numpy(), atol=1e-15)
+    np.testing.assert_allclose(pool_oracle.bwd(dz, first, L, pad_l), tq.grad.numpy(), atol=1e-15)
 
 
 def test_pool_comparison_excludes_little():

@@ -1,5 +1,5 @@
 """kws_pool3s2_same_* (csrc/pool.hip) and kws_stem_* (csrc/stem.hip) called directly, against float64 NumPy
-(tests/mts_oracle.py pool_same_*, tests/mts_cases.py stem_reference), on the conv_1d_multi_time_sliced geometries and on small odd
+(tests/pool_oracle.py, tests/mts_cases.py stem_reference), on the conv_1d_multi_time_sliced geometries and on small odd
 ones.  Outputs sit in NaN-guarded buffers.
 
 Bars are derived from float32 arithmetic, u = 2^-24, and do not depend on the summation order: a sum of n products is bounded by
@@ -19,7 +19,7 @@ import torch
 
 from speech_recognition_amd import _lib
 from mts_cases import (POOL_CASES, STEM_CASES, pool_compared, pool_inputs, pool_pre, stem_inputs, stem_reference)
-from mts_oracle import pool_same_argmax, pool_same_bwd, pool_same_fwd, pool_same_geometry
+import pool_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,7 @@ def _pool_fwd(y, tab):
     B, L, C = y.shape
     lib = _lib.load()
     Lp = lib.kws_pool3s2_same_out_len(L)
-    assert Lp == pool_same_geometry(L)[0]
+    assert Lp == pool_oracle.same_geometry(L)[0]
     yd, td = torch.from_numpy(y).cuda(), torch.from_numpy(tab).cuda()
     buf, z = _guarded(B * Lp * C)
     _lib.call("kws_pool3s2_same_fwd_f32", _lib.ptr(yd), _lib.ptr(td), _lib.ptr(z), B, L, C, _lib.stream_ptr())
@@ -71,17 +71,17 @@ def test_pool_forward_is_exact(B, L, C):
     z = _pool_fwd(y, tab)
     _, pre32 = pool_pre(y, tab)
     act = np.clip(pre32, 0, 6).astype(np.float64)          # the float32-rounded activations
-    Lp, pad_l = pool_same_geometry(L)
-    ref = pool_same_fwd(act, pool_same_argmax(act, pad_l), pad_l)
+    Lp, pad_l = pool_oracle.same_geometry(L)
+    ref = pool_oracle.fwd(act, pool_oracle.argmax(act, Lp, pad_l), pad_l)
     got = z.cpu().numpy().reshape(B, Lp, C).astype(np.float64)
     assert np.array_equal(got, ref)
     # negative controls: pad_left off by one; the maximum taken before the activation (negative scales)
     if L > 2:     # (with two rows both paddings give the one window the same valid rows)
-        wrong = pool_same_fwd(act, pool_same_argmax(act, 1 - pad_l), 1 - pad_l)
+        wrong = pool_oracle.fwd(act, pool_oracle.argmax(act, Lp, 1 - pad_l), 1 - pad_l)
         assert not np.array_equal(got, wrong)
     if L > 3:
         raw = y.astype(np.float64)
-        before = pool_same_fwd(act, pool_same_argmax(raw, pad_l), pad_l)
+        before = pool_oracle.fwd(act, pool_oracle.argmax(raw, Lp, pad_l), pad_l)
         assert not np.array_equal(got, before)
 
 
@@ -91,13 +91,13 @@ def test_pool_backward_matches_float64(B, L, C):
     g, part, rows = _pool_bwd(y, tab, dz)
     got = g.cpu().numpy().reshape(B, L, C).astype(np.float64)
     assert not np.isnan(got).any()                                               # every element of g is written
-    Lp, pad_l = pool_same_geometry(L)
+    Lp, pad_l = pool_oracle.same_geometry(L)
     pre, pre32 = pool_pre(y, tab)
     dz64 = dz.astype(np.float64)
     # float64 decisions, compared away from kinks and ties
-    ind = pool_same_argmax(np.clip(pre, 0, 6), pad_l)
-    ref = pool_same_bwd(dz64, ind, L, pad_l) * ((pre > 0) & (pre <= 6))
-    bar = (2 + 4) * U * pool_same_bwd(np.abs(dz64), ind, L, pad_l)
+    ind = pool_oracle.argmax(np.clip(pre, 0, 6), Lp, pad_l)
+    ref = pool_oracle.bwd(dz64, ind, L, pad_l) * ((pre > 0) & (pre <= 6))
+    bar = (2 + 4) * U * pool_oracle.bwd(np.abs(dz64), ind, L, pad_l)
     cmp_ = pool_compared(y, tab)
     share = 1.0 - cmp_.mean()
     err = np.abs(got - ref)
@@ -107,12 +107,12 @@ def test_pool_backward_matches_float64(B, L, C):
     assert (err[cmp_] <= bar[cmp_]).all()
     # the device's own decisions: exact zeros where a row wins nothing or its gate is shut; the BatchNorm part rows
     act32 = np.clip(pre32, 0, 6).astype(np.float64)
-    ind_d = pool_same_argmax(act32, pad_l)
+    ind_d = pool_oracle.argmax(act32, Lp, pad_l)
     gate_d = ((pre32 > 0) & (pre32 <= 6)).astype(np.float64)
-    ref_d = pool_same_bwd(dz64, ind_d, L, pad_l) * gate_d
-    wins = pool_same_bwd(np.ones_like(dz64), ind_d, L, pad_l)
+    ref_d = pool_oracle.bwd(dz64, ind_d, L, pad_l) * gate_d
+    wins = pool_oracle.bwd(np.ones_like(dz64), ind_d, L, pad_l)
     assert (got[(wins == 0) | (gate_d == 0)] == 0).all()
-    bar_d = (2 + 4) * U * pool_same_bwd(np.abs(dz64), ind_d, L, pad_l) * gate_d
+    bar_d = (2 + 4) * U * pool_oracle.bwd(np.abs(dz64), ind_d, L, pad_l) * gate_d
     assert (np.abs(got - ref_d) <= bar_d).all()
     n = B * L
     xhat = (y.astype(np.float64) - tab[2 * C:3 * C].astype(np.float64)) * tab[3 * C:].astype(np.float64)
@@ -123,7 +123,7 @@ def test_pool_backward_matches_float64(B, L, C):
     assert (np.abs(sums[0] - sg) <= bar_sg).all() and (np.abs(sums[1] - sgx) <= bar_sgx).all()
     # negative control: an oracle with pad_left off by one misses by far
     if L > 2:     # (with two rows both paddings give the one window the same valid rows)
-        wrong = pool_same_bwd(dz64, pool_same_argmax(np.clip(pre, 0, 6), 1 - pad_l), L, 1 - pad_l) * ((pre > 0) & (pre <= 6))
+        wrong = pool_oracle.bwd(dz64, pool_oracle.argmax(np.clip(pre, 0, 6), Lp, 1 - pad_l), L, 1 - pad_l) * ((pre > 0) & (pre <= 6))
         assert (np.abs(got - wrong)[cmp_] > 100 * np.maximum(bar[cmp_], U)).mean() > 0.05
 
 
@@ -134,22 +134,22 @@ def test_pool_first_maximum_wins_on_planted_ties():
     rng = np.random.RandomState(4)
     y = rng.randint(1, 4, size=(B, L, C)).astype(np.float32)
     tab = np.concatenate([np.ones(C), np.zeros(C), np.zeros(C), np.ones(C)]).astype(np.float32)
-    Lp, pad_l = pool_same_geometry(L)
+    Lp, pad_l = pool_oracle.same_geometry(L)
     dz = rng.randn(B, Lp, C).astype(np.float32)
     g, _, _ = _pool_bwd(y, tab, dz)
     got = g.cpu().numpy().reshape(B, L, C).astype(np.float64)
     a, dz64 = y.astype(np.float64), dz.astype(np.float64)
-    first = pool_same_bwd(dz64, pool_same_argmax(a, pad_l), L, pad_l)
-    last = pool_same_bwd(dz64, pool_same_argmax(a, pad_l, last=True), L, pad_l)
-    bar = (2 + 4) * U * pool_same_bwd(np.abs(dz64), pool_same_argmax(a, pad_l), L, pad_l)
+    first = pool_oracle.bwd(dz64, pool_oracle.argmax(a, Lp, pad_l), L, pad_l)
+    last = pool_oracle.bwd(dz64, pool_oracle.argmax(a, Lp, pad_l, last=True), L, pad_l)
+    bar = (2 + 4) * U * pool_oracle.bwd(np.abs(dz64), pool_oracle.argmax(a, Lp, pad_l), L, pad_l)
     assert (np.abs(got - first) <= bar).all()
     assert np.abs(got - last).max() > 0.1
     for Lx in (2, 3, 20):       # and on both parities at the borders, where a window has a padding row
         yx = rng.randint(1, 4, size=(B, Lx, C)).astype(np.float32)
-        Lpx, plx = pool_same_geometry(Lx)
+        Lpx, plx = pool_oracle.same_geometry(Lx)
         dzx = rng.randn(B, Lpx, C).astype(np.float32)
         gx = _pool_bwd(yx, tab, dzx)[0].cpu().numpy().reshape(B, Lx, C).astype(np.float64)
-        refx = pool_same_bwd(dzx.astype(np.float64), pool_same_argmax(yx.astype(np.float64), plx), Lx, plx)
+        refx = pool_oracle.bwd(dzx.astype(np.float64), pool_oracle.argmax(yx.astype(np.float64), Lpx, plx), Lx, plx)
         assert np.abs(gx - refx).max() <= 6 * U * np.abs(dzx).max() * 2
 
 

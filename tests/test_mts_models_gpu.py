@@ -13,10 +13,11 @@ import numpy as np
 import pytest
 import torch
 
-from net_parity import waveform_batch
+import pool_oracle
+from net_parity import perturb, waveform_batch
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
-from mts_oracle import MtsNet, pool_same_argmax
+from mts_oracle import MtsNet
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +25,7 @@ NC = 12
 
 
 def _perturb(ora, seed=5):
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):   # about a third of the scales negative
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.3 + 0.2 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('bias'):
-            ora.params[k] = (0.05 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.3, 0.2), bias=0.05)
     assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
 
 
@@ -61,7 +49,7 @@ def _decisions(net, ora, B):
         pre = (y * bn[:F] + bn[F:2 * F]).astype(np.float32)
         masks[idx] = ((pre > 0) & (pre <= 6)).astype(np.float64)
         if blk['pool'] is not None:
-            inds[idx] = pool_same_argmax(np.clip(pre, 0, 6).astype(np.float64), blk['pool']['pad_l'])
+            inds[idx] = pool_oracle.argmax(np.clip(pre, 0, 6).astype(np.float64), blk['pool']['Lp'], blk['pool']['pad_l'])
     return masks, inds
 
 

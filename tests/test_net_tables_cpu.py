@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from test_grouped_cpu import _native_table
+from net_parity import native_table
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'net_tensor_tables.json')
 with open(GOLDEN) as _f:
@@ -50,7 +50,7 @@ def test_fixture_is_complete():
 def test_tensor_table_matches_recorded(name):
     gold = TABLES[name]
     kind, nc, fm, input_size, T, F = gold['config']
-    table = _native_table(kind, nc, input_size, fm, T, F)
+    table = native_table(kind, nc, input_size, fm, T, F)
     assert _mismatches(table, gold['rows']) == []
     # the buffer sizes: the end of the last tensor of each buffer, rounded up to the 16-byte granule
     for state, total in ((0, gold['num_params']), (1, gold['num_state'])):
@@ -63,7 +63,7 @@ def test_comparison_reports_a_renumbered_name_and_a_swapped_pair(name):
     """Negative control: the comparison above is not vacuous."""
     gold = TABLES[name]
     kind, nc, fm, input_size, T, F = gold['config']
-    table = _native_table(kind, nc, input_size, fm, T, F)
+    table = native_table(kind, nc, input_size, fm, T, F)
     rows = gold['rows']
     # a Keras counter off by one on one layer (what a change in creation order does)
     i = next(k for k, r in enumerate(rows) if r[0] == 'batch_normalization_3/gamma')

@@ -10,9 +10,12 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+import pool_oracle
+from net_parity import native_table, perturb
 from oracle.layers import dropout_key, dropout_mask
+from pool_oracle import pool_len
 from speech_recognition_amd import _lib
-from stacked_oracle import HEAD_WIDTH, KEEP1, KEEP2, NETS, StackedConvNet, pool_argmax, pool_bwd, pool_fwd, pool_len
+from stacked_oracle import HEAD_WIDTH, KEEP1, KEEP2, NETS, StackedConvNet
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'stacked_models.json')
 KINDS = {'conv_1d_time_stacked': 8, 'conv_1d_heavy': 9}
@@ -25,22 +28,6 @@ LADDERS = {'conv_1d_time_stacked': [800, 798, 398, 396, 394, 196, 194, 192, 95, 
 def _golden(name):
     with open(GOLDEN) as f:
         return json.load(f)[name]
-
-
-def _native_table(kind, nc=12, input_size=16000):
-    lib = _lib.load()
-    cfg = _lib.NetConfig(kind, nc, 1, input_size, 0, 0)
-    h = ctypes.c_void_p()
-    _lib.check(lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 def test_kind_constants():
@@ -72,7 +59,7 @@ def test_fixture_has_the_expected_structure(name):
 @pytest.mark.parametrize("name", sorted(KINDS))
 def test_native_tensor_table_matches_reference_and_oracle(name):
     gold = _golden(name)
-    table = _native_table(KINDS[name], gold['num_classes'], gold['input_size'])
+    table = native_table(KINDS[name], gold['num_classes'], gold['input_size'])
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']
@@ -140,17 +127,17 @@ def test_speech_model_settings(monkeypatch):
 def test_oracle_pool_matches_torch_max_pool1d(L):
     rng = np.random.RandomState(L)
     a = np.clip(rng.randn(3, L, 8) * 3.0, 0, 6)       # saturated 0 / 6 values: plenty of ties
-    ind = pool_argmax(a)
-    z = pool_fwd(a, ind)
+    ind = pool_oracle.argmax(a, pool_len(L), 0)
+    z = pool_oracle.fwd(a, ind, 0)
     ta = torch.tensor(a, requires_grad=True)
     tz = Fn.max_pool1d(ta.permute(0, 2, 1), 3, 2).permute(0, 2, 1)
     assert tz.shape[1] == pool_len(L)
     np.testing.assert_array_equal(z, tz.detach().numpy())
     dz = rng.randn(*z.shape)
     tz.backward(torch.tensor(dz))
-    np.testing.assert_allclose(pool_bwd(dz, ind, L), ta.grad.numpy(), atol=1e-15)   # torch routes to the first maximum too
+    np.testing.assert_allclose(pool_oracle.bwd(dz, ind, L, 0), ta.grad.numpy(), atol=1e-15)   # torch routes to the first maximum too
     if L % 2 == 0:
-        assert not pool_bwd(np.ones_like(dz), ind, L)[:, -1].any()
+        assert not pool_oracle.bwd(np.ones_like(dz), ind, L, 0)[:, -1].any()
 
 
 def _torch_loss(ora, x, y, seed, step):
@@ -186,13 +173,7 @@ def _torch_loss(ora, x, y, seed, step):
 
 def _perturbed(kind, seed=5):
     ora = StackedConvNet(kind, num_classes=12)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):   # a third of the scales negative
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.5, 0.3), bias=None, state=False)
     return ora
 
 
@@ -218,8 +199,8 @@ def test_last_max_routing_differs_on_ties():
     rng = np.random.RandomState(3)
     a = rng.randint(1, 5, size=(4, 33, 16)).astype(np.float64)
     dz = rng.randn(4, pool_len(33), 16)
-    good = pool_bwd(dz, pool_argmax(a), 33)
-    bad = pool_bwd(dz, pool_argmax(a, last=True), 33)
+    good = pool_oracle.bwd(dz, pool_oracle.argmax(a, pool_len(33), 0), 33, 0)
+    bad = pool_oracle.bwd(dz, pool_oracle.argmax(a, pool_len(33), 0, last=True), 33, 0)
     assert np.abs(bad - good).max() / np.abs(good).max() > 1e-2
 
 

@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+import pool_oracle
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
-from stacked_oracle import StackedConvNet, pool_argmax
+from stacked_oracle import StackedConvNet
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +60,7 @@ def _decisions(net, ora, B):
         pre = (y * bn[:F] + bn[F:2 * F]).astype(np.float32)
         masks[idx] = (pre > 0) & (pre <= 6)
         if lay['pool']:
-            inds[idx] = pool_argmax(np.clip(pre, 0, 6))
+            inds[idx] = pool_oracle.argmax(np.clip(pre, 0, 6), lay['Lp'], 0)
     return masks, inds
 
 

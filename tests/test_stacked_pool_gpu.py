@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 import torch
 
+import pool_oracle
 from speech_recognition_amd import _lib
-from stacked_oracle import pool_argmax, pool_bwd, pool_fwd, pool_len
+from pool_oracle import pool_len
 
 pytestmark = pytest.mark.gpu
 
@@ -76,8 +77,8 @@ def _run_bwd(y, bn, dz, B, L, C):
 
 def _reference_bwd(y, bn, dz, L, C, last=False, on_raw=False, gate=True):
     pre, a = _act(y, bn, C)
-    ind = pool_argmax(y.astype(np.float64) if on_raw else a, last=last)
-    da = pool_bwd(dz.astype(np.float64), ind, L)
+    ind = pool_oracle.argmax(y.astype(np.float64) if on_raw else a, pool_len(L), 0, last=last)
+    da = pool_oracle.bwd(dz.astype(np.float64), ind, L, 0)
     g = da * ((pre > 0) & (pre <= 6)) if gate else da
     xhat = (y.astype(np.float64) - bn[2 * C:3 * C].astype(np.float64)) * bn[3 * C:].astype(np.float64)
     return g, g.sum(axis=(0, 1)), (g * xhat).sum(axis=(0, 1)), (np.abs(g).sum(axis=(0, 1)), np.abs(g * xhat).sum(axis=(0, 1)))
@@ -94,12 +95,12 @@ def test_forward_matches_float64(B, L, C):
     assert (bn[:C] < 0).any()
     buf, z = _run_fwd(y, bn, B, L, C)
     _, a = _act(y, bn, C)
-    ref = pool_fwd(a, pool_argmax(a))
+    ref = pool_oracle.fwd(a, pool_oracle.argmax(a, pool_len(L), 0), 0)
     got = z.cpu().numpy().reshape(ref.shape)
     np.testing.assert_array_equal(got, ref)
     assert _guards_intact(buf, z.numel())
     # pooling the raw output and activating afterwards is a different function here (negative scales)
-    wrong = pool_fwd(a, pool_argmax(y.astype(np.float64)))
+    wrong = pool_oracle.fwd(a, pool_oracle.argmax(y.astype(np.float64), pool_len(L), 0), 0)
     assert np.abs(wrong - ref).max() > 0.1
 
 

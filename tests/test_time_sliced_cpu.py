@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as Fn
 
 import frame_conv_cases as FC
+from net_parity import native_table, perturb
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
 from time_sliced_oracle import FRAME, HOP, KEEP1, KEEP2, LENGTHS, SPEC, STRIDE, TAPS, TimeSlicedNet, block_pad
@@ -32,20 +33,6 @@ def _create(fm, input_size, nc=12):
     cfg = _lib.NetConfig(_lib.KWS_NET_CONV_1D_TIME_SLICED, nc, fm, input_size, 0, 0)
     h = ctypes.c_void_p()
     return lib, lib.kws_net_create(ctypes.byref(cfg), ctypes.byref(h)), h
-
-
-def _native_table(fm, nc=12, input_size=16000):
-    lib, rc, h = _create(fm, input_size, nc)
-    _lib.check(rc, "kws_net_create")
-    out = []
-    try:
-        for i in range(lib.kws_net_num_tensors(h)):
-            ti = _lib.TensorInfo()
-            _lib.check(lib.kws_net_tensor_info(h, i, ctypes.byref(ti)), "kws_net_tensor_info")
-            out.append(ti)
-    finally:
-        lib.kws_net_destroy(h)
-    return out
 
 
 # ---- the public surface ---------------------------------------------------------------------------------------------------
@@ -133,7 +120,7 @@ def test_fixture_has_the_expected_layers(fm):
 @pytest.mark.parametrize("fm", [1, 2])
 def test_native_tensor_table_matches_reference_and_oracle(fm):
     gold = _golden(fm)
-    table = _native_table(fm, gold['num_classes'], gold['input_size'])
+    table = native_table(_lib.KWS_NET_CONV_1D_TIME_SLICED, gold['num_classes'], gold['input_size'], fm)
     assert [t.name.decode() for t in table] == [w['name'] for w in gold['weights']]
     for t, w in zip(table, gold['weights']):
         assert [int(t.shape[k]) for k in range(t.ndim)] == w['shape'], w['name']
@@ -245,13 +232,7 @@ def test_gap_drop_planner_and_domain():
 # ---- the oracle against torch autograd --------------------------------------------------------------------------------------
 def _perturbed(fm=1, input_size=16000, seed=5):
     ora = TimeSlicedNet(num_classes=12, filter_mult=fm, input_size=input_size)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):   # a third of the scales negative
-            g = 1.0 + 0.1 * rng.randn(*ora.params[k].shape)
-            ora.params[k] = (g * np.where(rng.rand(*g.shape) < 0.33, -1.0, 1.0)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.5 + 0.3 * rng.randn(*ora.params[k].shape)).astype(np.float32)
+    perturb(ora, seed, negative_fraction=0.33, beta=(0.5, 0.3), bias=None, state=False)
     return ora
 
 
