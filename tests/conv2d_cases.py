@@ -3,6 +3,7 @@ nets, clips and shapes on both sides, so that the figures in the GPU tests' docs
 import numpy as np
 
 from conv2d_oracle import Conv2dNet, axis_geom
+import net_parity
 from net_parity import perturb
 
 NC = 12
@@ -17,7 +18,6 @@ def perturbed(kind, dtype=np.float64, nc=NC, seed=5):
     moving statistics off their initial values."""
     ora = Conv2dNet(kind, num_classes=nc, dtype=dtype)
     perturb(ora, seed, negative_fraction=0.33, beta=(0.3, 0.2), bias=0.05)
-    assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
     assert all(np.abs(v).max() > 0 for k, v in ora.params.items() if k.endswith('bias'))
     return ora
 
@@ -32,11 +32,15 @@ def batch(B, nc=NC, seed=None):
     return x.reshape(B, 3920).astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
 
 
-def grad_errors(g, ref, skip_conv_bias=True):
-    """max |g - ref| over a tensor, relative to the reference tensor's maximum (the convolution biases, whose reference is zero
-    up to rounding, are held to an absolute bar instead: bias_errors)"""
-    return {k: np.abs(np.asarray(g[k], np.float64) - np.asarray(r, np.float64).reshape(np.shape(g[k]))).max() /
-            max(np.abs(r).max(), 1e-7) for k, r in ref.items() if not (skip_conv_bias and k.startswith('conv2d_') and k.endswith('bias'))}
+def relative(ref):
+    """The reference gradients held to the relative bar: all but the convolution biases, whose reference is zero up to rounding
+    and which are held to an absolute bar instead (bias_errors)"""
+    return {k: r for k, r in ref.items() if not (k.startswith('conv2d_') and k.endswith('bias'))}
+
+
+def grad_errors(g, ref):
+    """net_parity.grad_errors over relative(ref)"""
+    return net_parity.grad_errors(g, relative(ref))
 
 
 BIAS_BAR_ROUNDINGS = 16

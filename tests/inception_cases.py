@@ -3,7 +3,7 @@ clips on both sides, so that the figures in test_inception_models_gpu.py's docst
 import numpy as np
 
 from inception_oracle import InceptionD1Net
-from net_parity import perturb
+from net_parity import perturb, waveform_batch
 
 NC = 12
 TRAIN_BATCHES = (3, 16)
@@ -16,22 +16,11 @@ def perturbed(dtype=np.float64, nc=NC, seed=5):
     initial values."""
     ora = InceptionD1Net(num_classes=nc, dtype=dtype)
     perturb(ora, seed, negative_fraction=0.33, beta=(0.3, 0.2), bias=0.05)
-    assert any((v < 0).any() for k, v in ora.params.items() if k.endswith('gamma'))
     return ora
 
 
 def batch(B, nc=NC, seed=None):
-    rng = np.random.RandomState(B if seed is None else seed)
-    lab = rng.randint(0, nc, B)
-    t = np.arange(16000) / 16000.0
-    x = rng.randn(B, 16000) * 0.0774 + 0.05 * np.sin(2 * np.pi * 200.0 * (1 + lab)[:, None] * t[None, :])
-    return x.astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
-
-
-def grad_errors(g, ref):
-    """max |g - ref| over a tensor, relative to the reference tensor's maximum"""
-    return {k: np.abs(np.asarray(g[k], np.float64) - np.asarray(r, np.float64).reshape(np.shape(g[k]))).max() /
-            max(np.abs(r).max(), 1e-7) for k, r in ref.items()}
+    return waveform_batch(B, nc, B if seed is None else seed)
 
 
 def decisions_of(ora, cache):

@@ -1,9 +1,9 @@
 """GPU parity of the two 2-D network programs (KWS_NET_CONV_2D_MOBILE / KWS_NET_CONV_2D_FAST, csrc/net_conv2d.hip) against the
-float64 oracle tests/conv2d_oracle.py - the method of test_inception_models_gpu.py: the device's activation gates and max-pool
-winners are read back (debug views 0 and 2: every Conv2D's raw output and its BatchNorm table) and handed to the oracle's backward
+float64 oracle tests/conv2d_oracle.py on the harness of tests/net_parity.py: the device's activation gates and max-pool winners
+are read back (debug views 0 and 2: every Conv2D's raw output and its BatchNorm table) and handed to the oracle's backward
 pass.  About a third of the BatchNorm scales is negative; every bias, the convolutions' included, is non-zero.
 
-Bars: the siblings', unchanged - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
+Bars: net_parity.FAMILY_BARS - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
 statistics atol 5e-6 / rtol 1e-5; class indices and the correct-count exact.  The convolution biases stand in front of a
 BatchNormalization, so the oracle's gradient for them is zero up to rounding and the device writes exact zeros: they are held to the
 absolute bar of conv2d_cases.bias_errors (16 float32 roundings of the terms that cancel).  The oracle nets were first run in float32
@@ -18,35 +18,25 @@ selves:
                   train, batch 3:   probabilities 2.2e-7, loss 2.7e-7, worst gradient 1.9e-6 (conv2d_3/kernel), bias 0.30
                   train, batch 16:  probabilities 3.3e-7, loss 2.4e-7, worst gradient 1.5e-6 (batch_normalization_1/beta), bias 0.40
 Every figure is under half its bar at the first batches chosen."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import conv2d_cases as cases
+import net_parity as NP
 from conv2d_oracle import SGD, pool2_argmax, pool2_fwd
 from oracle.layers import sgd_momentum_step
 from speech_recognition_amd import _lib
-from speech_recognition_amd.net import DeviceNet
 
 pytestmark = pytest.mark.gpu
 
+BARS = NP.FAMILY_BARS
 NC = cases.NC
 KIND = {'mobile': _lib.KWS_NET_CONV_2D_MOBILE, 'fast': _lib.KWS_NET_CONV_2D_FAST}
 
 
 def _pair(kind):
-    ora = cases.perturbed(kind)
-    net = DeviceNet(KIND[kind], NC, input_size=3920)
-    net.set_weights(dict(ora.params, **ora.state))
-    return ora, net
-
-
-def _view(net, B, what, index, training=True):
-    off, cnt = ctypes.c_int64(), ctypes.c_int64()
-    _lib.call("kws_net_debug_view", net.handle, B, int(training), what, index, ctypes.byref(off), ctypes.byref(cnt))
-    return net._ws[off.value:off.value + cnt.value].cpu().numpy()
+    return NP.device_pair(cases.perturbed(kind), KIND[kind], NC, input_size=3920)
 
 
 def _decisions(net, ora, B):
@@ -54,8 +44,8 @@ def _decisions(net, ora, B):
     masks, inds = {}, {}
     for l in ora.layers:
         n, F = l['idx'], l['F']
-        y = _view(net, B, 0, n - 1).reshape(B, l['Hout'], l['Wout'], F).astype(np.float64)
-        bn = _view(net, B, 2, n - 1).reshape(4, F).astype(np.float64)
+        y = net.debug_view(B, 0, n - 1).reshape(B, l['Hout'], l['Wout'], F).astype(np.float64)
+        bn = net.debug_view(B, 2, n - 1).reshape(4, F).astype(np.float64)
         pre = (y * bn[0] + bn[1]).astype(np.float32)
         if ora.act == 'relu6':
             masks[n] = (pre > 0) & (pre <= 6)
@@ -65,44 +55,31 @@ def _decisions(net, ora, B):
             a = np.maximum(pre, 0)
         if l['pool']:
             inds[n] = pool2_argmax(a.astype(np.float64))
-            out = _view(net, B, 1, n - 1).reshape(B, l['Ho'], l['Wo'], F)          # the pooled tensor the device kept
+            out = net.debug_view(B, 1, n - 1).reshape(B, l['Ho'], l['Wo'], F)          # the pooled tensor the device kept
             assert np.array_equal(out, pool2_fwd(a, inds[n]))
     return masks, inds
 
 
-def _device_step(ora, net, B, batch_seed=None, seed=cases.SEED, step=cases.STEP, row_offset=0):
+def _step(ora, net, B, batch_seed=None, seed=cases.SEED, step=cases.STEP, row_offset=0):
+    """One device step and what the oracle needs to repeat it on the device's gates and winners"""
     x, y = cases.batch(B, seed=batch_seed)
-    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=seed, step=step, row_offset=row_offset)
-    torch.cuda.synchronize()
+    dev = NP.device_step(net, x, y, seed, step, row_offset)
     masks, inds = _decisions(net, ora, B)
-    return dict(x=x, y=y, probs=probs.cpu().numpy(), metrics=net.metrics.cpu().numpy(), grads=net.grads_dict(), masks=masks, inds=inds,
-                weights=net.get_weights())
+    return dict(dev, ora=ora, x=x, y=y, xy=(x.astype(np.float64), y.astype(np.float64)),
+                kw=dict(seed=seed, step=step, relu_masks=masks, pool_ind=inds))
 
 
 def _check_step(kind, B, d, ora, ref):
     loss, p, grads, cache = ref
-    got, m = d['probs'], d['metrics']
-    errs = cases.grad_errors(d['grads'], grads)
-    worst = max(errs, key=errs.get)
+    NP.check_train_step(d, d['y'], (loss, p, cases.relative(grads), cache), ora, BARS, "conv_2d_%s B=%d" % (kind, B))
     berrs = cases.bias_errors(d['grads'], grads, cache)
     bworst = max(berrs, key=berrs.get)
-    print("train conv_2d_%s B=%d: probs %.3g (bar 5e-5), loss %.3g (bar 1e-4), worst gradient %s %.3g (bar 2e-4), worst bias gradient "
-          "%s %.3g of its bar" % (kind, B, np.abs(got - p).max(), abs(m[0] / B - loss), worst, errs[worst], bworst, berrs[bworst]))
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == d['y'].argmax(1)).sum()
-    for k, err in errs.items():
-        assert err < 2e-4, (k, err)
+    print("conv_2d_%s B=%d: worst bias gradient %s %.3g of its bar" % (kind, B, bworst, berrs[bworst]))
     for k, err in berrs.items():
         assert err < 1.0, (k, err)
         assert not np.asarray(d['grads'][k]).any(), k             # the device's convolution-bias gradients are exact zeros
+    # the batch mean the moving mean was held to INCLUDES the convolution bias: without it the moving mean would miss that bar
     w = d['weights']
-    for idx, (mean, var) in cache['batch_stats'].items():        # the batch mean INCLUDES the convolution bias
-        for nm, batch in (('moving_mean', mean), ('moving_variance', var)):
-            old = ora.state['batch_normalization_%d/%s' % (idx, nm)].astype(np.float64)
-            np.testing.assert_allclose(w['batch_normalization_%d/%s' % (idx, nm)], old - (old - batch) * 0.01, atol=5e-6, rtol=1e-5)
-    # ... and without it the moving mean would miss that bar
     b1 = ora.params['conv2d_1/bias'].astype(np.float64)
     old = ora.state['batch_normalization_1/moving_mean'].astype(np.float64)
     no_bias = old - (old - (cache['batch_stats'][1][0] - b1)) * 0.01
@@ -113,19 +90,15 @@ def _check_step(kind, B, d, ora, ref):
 def step3(request):
     kind = request.param
     ora, net = _pair(kind)
-    d = _device_step(ora, net, 3)
-    d['ora'], d['kind'] = ora, kind
-    d['oracle'] = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                                     relu_masks=d['masks'], pool_ind=d['inds'])
+    d = _step(ora, net, 3)
+    d['kind'] = kind
+    d['oracle'] = ora.loss_and_grads(*d['xy'], **d['kw'])
     return d
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
 def test_tensor_table_matches_oracle(kind):
-    ora, net = _pair(kind)
-    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
-    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
-    assert net.count_params() == ora.count_params()
+    NP.check_tensor_table(*_pair(kind))
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
@@ -133,10 +106,7 @@ def test_predict_matches_oracle_and_rows_do_not_see_each_other(kind):
     ora, net = _pair(kind)
     x, _ = cases.batch(cases.PREDICT_BATCH, seed=1)
     p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
-    ref = ora.forward(x.astype(np.float64), training=False)
-    print("predict conv_2d_%s: max |p - oracle| = %.3g (bar 2e-5)" % (kind, np.abs(p - ref).max()))
-    assert np.abs(p - ref).max() < 2e-5
-    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    NP.check_predict(p, ora.forward(x.astype(np.float64), training=False), BARS, 'conv_2d_' + kind)
     for r in range(cases.PREDICT_BATCH):     # a predict at batch 1 agrees with the same row of the batch of 5
         p1 = net.predict(torch.from_numpy(x[r:r + 1]).cuda()).cpu().numpy()
         assert np.abs(p1[0] - p[r]).max() < 1e-6, r
@@ -145,7 +115,7 @@ def test_predict_matches_oracle_and_rows_do_not_see_each_other(kind):
     for k in nb.params:
         if k.startswith('conv2d_') and k.endswith('bias'):
             nb.params[k] = np.zeros_like(nb.params[k])
-    assert np.abs(p - nb.forward(x.astype(np.float64), training=False)).max() > 2e-5
+    assert np.abs(p - nb.forward(x.astype(np.float64), training=False)).max() > BARS['predict']
 
 
 def test_train_fwd_bwd_matches_oracle_batch_3(step3):
@@ -156,34 +126,23 @@ def test_train_fwd_bwd_matches_oracle_batch_3(step3):
 def test_train_fwd_bwd_matches_oracle_batch_16(kind):
     B = cases.TRAIN_BATCHES[1]
     ora, net = _pair(kind)
-    d = _device_step(ora, net, B)
-    ref = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                             relu_masks=d['masks'], pool_ind=d['inds'])
-    _check_step(kind, B, d, ora, ref)
+    d = _step(ora, net, B)
+    _check_step(kind, B, d, ora, ora.loss_and_grads(*d['xy'], **d['kw']))
 
 
 def test_wrong_padding_oracle_misses_the_gradient_bar(step3):
     """Negative control: against an oracle that puts the odd SAME padding in front, conv_2d_mobile's gradients miss the 2e-4 bar
     (conv_2d_fast's windows are odd at stride 1: its padding is symmetric and the variant is the same function)."""
-    ora = step3['ora']
-    bad = ora.loss_and_grads(step3['x'].astype(np.float64), step3['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                             relu_masks=step3['masks'], pool_ind=step3['inds'], mutate='pad_front')[2]
+    bad = step3['ora'].loss_and_grads(*step3['xy'], mutate='pad_front', **step3['kw'])[2]
     worst = max(cases.grad_errors(step3['grads'], bad).values())
     print("conv_2d_%s against the pad_front oracle: worst gradient %.3g" % (step3['kind'], worst))
-    assert worst > 2e-4 if step3['kind'] == 'mobile' else worst < 2e-4
+    assert worst > BARS['grad'] if step3['kind'] == 'mobile' else worst < BARS['grad']
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
 def test_train_step_is_bit_reproducible(kind):
     ora, net = _pair(kind)
-    x, y = cases.batch(24, seed=3)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    state0 = net.state.clone()
-    p1 = net.train_fwd_bwd(xd, yd, seed=1, step=0).clone()
-    g1, s1 = net.grads.clone(), net.state.clone()
-    net.state.copy_(state0)
-    p2 = net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state) and torch.equal(p1, p2)
+    NP.assert_bit_reproducible(net, *cases.batch(24, seed=3))
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
@@ -192,15 +151,12 @@ def test_data_parallel_shard_uses_the_global_dropout_rows_and_loss_batch(kind):
     the global batch (a shard of half the batch: every gradient halves - a power of two, exact but for underflow)."""
     ora, net = _pair(kind)
     B, off = 4, 37
-    d = _device_step(ora, net, B, batch_seed=21, seed=5, step=3, row_offset=off)
-    _, p, grads, _ = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=5, step=3, drop_offset=off,
-                                        relu_masks=d['masks'], pool_ind=d['inds'])
-    assert np.abs(d['probs'] - p).max() < 5e-5
-    assert max(cases.grad_errors(d['grads'], grads).values()) < 2e-4
+    d = _step(ora, net, B, batch_seed=21, seed=5, step=3, row_offset=off)
+    loss, p, grads, cache = ora.loss_and_grads(*d['xy'], drop_offset=off, **d['kw'])
+    NP.check_shard(d, (loss, p, cases.relative(grads), cache), BARS)
     if kind == 'mobile':     # the masks of row 0 are not those of row 37: the same oracle without the offset misses the bar
-        _, p0, g0, _ = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=5, step=3, drop_offset=0,
-                                          relu_masks=d['masks'], pool_ind=d['inds'])
-        assert max(cases.grad_errors(d['grads'], g0).values()) > 2e-4
+        g0 = ora.loss_and_grads(*d['xy'], drop_offset=0, **d['kw'])[2]
+        assert max(cases.grad_errors(d['grads'], g0).values()) > BARS['grad']
     g1 = net.grads.clone()
     net.set_weights(dict(ora.params, **ora.state))
     net.train_fwd_bwd(torch.from_numpy(d['x']).cuda(), torch.from_numpy(d['y']).cuda(), seed=5, step=3, row_offset=off, loss_batch=2 * B)
@@ -249,19 +205,8 @@ def test_sgd_steps_move_the_weights_as_the_oracle_says(kind):
 def test_checkpoint_round_trip_carries_the_velocity(tmp_path):
     """save -> load -> one more step equals the uninterrupted run bit for bit (weights, moving statistics, the SGD velocity)."""
     from speech_recognition_amd.model import speech_model
-    a = speech_model('conv_2d_mobile', 3920, num_classes=NC)
-    batches = [cases.batch(8, seed=200 + i) for i in range(3)]
-    for xb, yb in batches[:2]:
-        a.train_on_batch(xb, yb)
-    assert float(a.net.slots.abs().max()) > 0
-    path = str(tmp_path / "conv2d.npz")
-    a.save(path)
-    b = speech_model('conv_2d_mobile', 3920, num_classes=NC)
-    b.load_weights(path)
-    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state) and torch.equal(a.net.slots, b.net.slots)
-    la, lb = a.train_on_batch(*batches[2]), b.train_on_batch(*batches[2])
-    assert la == lb
-    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state) and torch.equal(a.net.slots, b.net.slots)
+    NP.check_checkpoint_round_trip(lambda: speech_model('conv_2d_mobile', 3920, num_classes=NC),
+                                   [cases.batch(8, seed=200 + i) for i in range(3)], str(tmp_path / "conv2d.npz"), slots=('slots',))
 
 
 def test_conv_2d_mobile_on_the_mfcc_generator(repo_root):
@@ -274,22 +219,8 @@ def test_conv_2d_mobile_on_the_mfcc_generator(repo_root):
     fixed-batch steps of test_sgd_steps_move_the_weights_as_the_oracle_says wobble by +-0.07 on their way down.  So the second call
     repeats the first call's draw as well as its batch (the step counter that keys the masks is set back): then the two losses are
     one function at two points, and a descent step has to lower it."""
-    import sys
-    sys.path.insert(0, repo_root)
-    import bench
-    from speech_recognition_amd.input_data import AudioProcessor, prepare_words_list
-    from speech_recognition_amd.model import prepare_model_settings, speech_model
-    from speech_recognition_amd.utils import data_gen
-    dev = torch.device("cuda", 0)
-    settings = prepare_model_settings(label_count=len(prepare_words_list(bench.WANTED)), sample_rate=16000,
-                                      clip_duration_ms=1000, window_size_ms=30.0, window_stride_ms=10.0,
-                                      dct_coefficient_count=40, num_log_mel_features=40, output_representation='mfcc')
+    gen, model, settings = NP.generator_model('conv_2d_mobile', 'mfcc', repo_root, dct=40, mel=40, settings_to_model=False)
     assert settings['fingerprint_size'] == 3920 and settings['label_count'] == 12
-    proc = AudioProcessor(bench.build_synthetic(dev, 8192, seed=59185), 13.0, 60.0, bench.WANTED, 10.0, 0.0, settings,
-                          output_representation='mfcc', device=dev)
-    np.random.seed(1234)
-    gen = data_gen(proc, None, batch_size=64, mode='training')
-    model = speech_model('conv_2d_mobile', settings['fingerprint_size'], num_classes=settings['label_count'])
     X, y = next(gen)
     assert np.asarray(X).shape == (64, 3920)
     step0 = model._step
@@ -309,29 +240,4 @@ def test_workspace_bytes_is_honoured_and_one_byte_less_is_refused(kind, training
     """A step in a workspace of exactly workspace_bytes leaves the guard bands around it alone; one byte less is KWS_E_WORKSPACE
     with a message, and nothing runs."""
     ora, net = _pair(kind)
-    lib, B, guard = net.lib, 3, 4096
-    need = int(lib.kws_net_workspace_bytes(net.handle, B, training))
-    assert need > 0 and need % 4 == 0
-    buf = torch.full((need // 4 + 2 * guard,), float('nan'), dtype=torch.float32, device="cuda")
-    ws = buf[guard:guard + need // 4]
-    x, y = cases.batch(B)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    probs = torch.full((B, NC), float('nan'), dtype=torch.float32, device="cuda")
-
-    def run(nbytes):
-        if training:
-            return lib.kws_net_train_fwd_bwd(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), _lib.ptr(yd), B,
-                                             _lib.ptr(net.grads), _lib.ptr(probs), _lib.ptr(net.metrics), ctypes.c_uint64(1),
-                                             ctypes.c_uint32(0), 0, B, _lib.ptr(ws), nbytes, _lib.stream_ptr())
-        return lib.kws_net_predict(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), B, _lib.ptr(probs), _lib.ptr(ws),
-                                   nbytes, _lib.stream_ptr())
-
-    assert run(need - 1) == -3                                   # KWS_E_WORKSPACE
-    assert b'workspace' in lib.kws_last_error()
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(probs).all()) and bool(torch.isnan(buf).all())
-    assert run(need) == 0
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[-guard:]).all())
-    p = probs.cpu().numpy()
-    assert np.isfinite(p).all() and np.abs(p.sum(1) - 1).max() < 1e-5
+    NP.check_workspace_refusal(net, *cases.batch(3), training=training)

@@ -1,6 +1,6 @@
 """GPU parity of the conv_1d_fast / conv_1d_spec network programs (KWS_NET_CONV_1D_FAST / KWS_NET_CONV_1D_SPEC) against the
-float64 oracle tests/grouped_oracle.py - the method of test_steffe_gpu.py: the device's ReLU6 decisions are read back
-(debug views 0 and 2) and handed to the oracle's backward pass."""
+float64 oracle tests/grouped_oracle.py on the harness of tests/net_parity.py (bars: its FAMILY_BARS): the device's ReLU6
+decisions are read back (debug views 0 and 2) and handed to the oracle's backward pass."""
 import json
 import os
 
@@ -8,49 +8,34 @@ import numpy as np
 import pytest
 import torch
 
+import net_parity as NP
 from grouped_oracle import GroupedConvNet
 from speech_recognition_amd import _lib
-from speech_recognition_amd.net import DeviceNet
 
 pytestmark = pytest.mark.gpu
 
+BARS = NP.FAMILY_BARS
 KIND = {'fast': _lib.KWS_NET_CONV_1D_FAST, 'spec': _lib.KWS_NET_CONV_1D_SPEC}
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'grouped_models.json')
 
 
 def _pair(kind, nc=12, seed=5):
     ora = GroupedConvNet(kind, num_classes=nc)
-    rng = np.random.RandomState(seed)
-    for k in ora.params:
-        if k.endswith('gamma'):
-            ora.params[k] = (1.0 + 0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k.endswith('beta'):
-            ora.params[k] = (0.1 * rng.randn(*ora.params[k].shape)).astype(np.float32)
-        if k == 'dense_1/bias':
-            ora.params[k] = (0.05 * rng.randn(nc)).astype(np.float32)
-    for k in ora.state:
-        if k.endswith('moving_mean'):
-            ora.state[k] = (0.05 * rng.randn(*ora.state[k].shape)).astype(np.float32)
-        else:
-            ora.state[k] = (1.0 + 0.2 * rng.rand(*ora.state[k].shape)).astype(np.float32)
-    net = DeviceNet(KIND[kind], nc, input_size=16000 if kind == 'fast' else 98 * 257)
-    net.set_weights(dict(ora.params, **ora.state))
-    return ora, net
+    NP.perturb(ora, seed, bias=0.05, bias_names=('dense_1/bias',))
+    return NP.device_pair(ora, KIND[kind], nc, input_size=16000 if kind == 'fast' else 98 * 257)
 
 
 def _batch(kind, B, nc, seed):
+    if kind == 'fast':
+        return NP.waveform_batch(B, nc, seed)
     rng = np.random.RandomState(seed)
     lab = rng.randint(0, nc, B)
-    if kind == 'fast':
-        t = np.arange(16000) / 16000.0
-        x = rng.randn(B, 16000) * 0.0774 + 0.05 * np.sin(2 * np.pi * 200.0 * (1 + lab)[:, None] * t[None, :])
-    else:
-        x = np.abs(rng.randn(B, 98, 257)) * (1.0 + 0.1 * lab[:, None, None])
-        x = x.reshape(B, -1)
-    return x.astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
+    x = np.abs(rng.randn(B, 98, 257)) * (1.0 + 0.1 * lab[:, None, None])
+    return x.reshape(B, -1).astype(np.float32), np.eye(nc, dtype=np.float32)[lab]
 
 
 def _decisions(net, ora, B):
+    """Every block's BatchNorms gate their own column slice of the block's raw output."""
     masks = {}
     stage0 = 1 if ora.front else 0
     for i, blk in enumerate(ora.blocks):
@@ -66,11 +51,7 @@ def _decisions(net, ora, B):
 @pytest.mark.parametrize("kind", ['fast', 'spec'])
 def test_tensor_table_matches_oracle_and_reference(kind):
     ora, net = _pair(kind)
-    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
-    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
-    for k, v in list(ora.params.items()) + list(ora.state.items()):
-        assert net.tensors[k].shape == v.shape, k
-    assert net.count_params() == ora.count_params()
+    NP.check_tensor_table(ora, net, shapes=True)
     with open(GOLDEN) as f:
         gold = json.load(f)['conv_1d_' + kind]
     assert [s.name for s in net.tensors.values()] == [w['name'] for w in gold['weights']]
@@ -83,49 +64,22 @@ def test_predict_matches_oracle(kind):
     ora, net = _pair(kind)
     x, _ = _batch(kind, 5, 12, 1)
     p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
-    ref = ora.forward(x.astype(np.float64), training=False)
-    assert np.abs(p - ref).max() < 2e-5
-    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    NP.check_predict(p, ora.forward(x.astype(np.float64), training=False), BARS, 'conv_1d_' + kind)
 
 
 @pytest.mark.parametrize("kind,B", [('fast', 3), ('fast', 10), ('fast', 1024), ('spec', 3), ('spec', 10), ('spec', 1024)])
 def test_train_fwd_bwd_matches_oracle(kind, B):
     ora, net = _pair(kind)
     x, y = _batch(kind, B, 12, B)
-    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
-    torch.cuda.synchronize()
-    masks = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2, relu_masks=masks)
-    got = probs.cpu().numpy()
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    m = net.metrics.cpu().numpy()
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == y.argmax(1)).sum()
-    g = net.grads_dict()
-    for k, ref in grads.items():
-        ref = ref.reshape(g[k].shape)
-        err = np.abs(g[k] - ref).max() / max(np.abs(ref).max(), 1e-7)
-        assert err < 2e-4, (k, err)
-    w = net.get_weights()
-    for idx, (mean, var) in cache['batch_stats'].items():
-        for nm, batch in (('moving_mean', mean), ('moving_variance', var)):
-            old = ora.state['batch_normalization_%d/%s' % (idx, nm)].astype(np.float64)
-            np.testing.assert_allclose(w['batch_normalization_%d/%s' % (idx, nm)], old - (old - batch) * 0.01,
-                                       atol=5e-6, rtol=1e-5)
+    dev = NP.device_step(net, x, y, seed=77, step=2)
+    ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2, relu_masks=_decisions(net, ora, B))
+    NP.check_train_step(dev, y, ref, ora, BARS, "conv_1d_%s B=%d" % (kind, B))
 
 
 @pytest.mark.parametrize("kind", ['fast', 'spec'])
 def test_train_step_is_bit_reproducible(kind):
     ora, net = _pair(kind)
-    x, y = _batch(kind, 64, 12, 3)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    state0 = net.state.clone()
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    g1, s1 = net.grads.clone(), net.state.clone()
-    net.state.copy_(state0)
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state)
+    NP.assert_bit_reproducible(net, *_batch(kind, 64, 12, 3))
 
 
 @pytest.mark.parametrize("model_type,name,lr", [('conv_1d_fast', 'conv_1d_learned_spec', 3e-3),
@@ -143,21 +97,7 @@ def test_speech_model_trains(model_type, name, lr):
 def test_conv_1d_spec_on_the_spec_generator(repo_root):
     """conv_1d_spec as train.py drives it: AudioProcessor(output_representation='spec') -> data_gen -> speech_model ->
     train_on_batch, then Model.fit_generator for one short epoch."""
-    import sys
-    sys.path.insert(0, repo_root)
-    import bench
-    from speech_recognition_amd.input_data import AudioProcessor, prepare_words_list
-    from speech_recognition_amd.model import prepare_model_settings, speech_model
-    from speech_recognition_amd.utils import data_gen
-    dev = torch.device("cuda", 0)
-    settings = prepare_model_settings(label_count=len(prepare_words_list(bench.WANTED)), sample_rate=16000,
-                                      clip_duration_ms=1000, window_size_ms=30.0, window_stride_ms=10.0,
-                                      dct_coefficient_count=80, num_log_mel_features=60, output_representation='spec')
-    proc = AudioProcessor(bench.build_synthetic(dev, 8192, seed=59185), 13.0, 60.0, bench.WANTED, 10.0, 0.0, settings,
-                          output_representation='spec', device=dev)
-    np.random.seed(1234)
-    gen = data_gen(proc, None, batch_size=64, mode='training')
-    model = speech_model('conv_1d_spec', settings['fingerprint_size'], num_classes=settings['label_count'], **settings)
+    gen, model, _ = NP.generator_model('conv_1d_spec', 'spec', repo_root)
     losses = []
     for _ in range(12):
         X, y = next(gen)

@@ -14,7 +14,7 @@ import torch.nn.functional as Fn
 
 import inception_cases as cases
 from inception_oracle import (BLOCKS, KEEP, InceptionD1Net, avgpool_bwd, avgpool_fwd, same_pool_pad_l)
-from net_parity import native_table
+from net_parity import grad_errors, native_table
 from oracle.layers import dropout_key, dropout_mask
 from speech_recognition_amd import _lib
 
@@ -249,7 +249,7 @@ def test_mutated_oracle_moves_the_gradients(mutate):
     x, y = cases.batch(3)
     _, _, good, _ = ora.loss_and_grads(x, y, seed=1, step=0)
     _, _, bad, _ = ora.loss_and_grads(x, y, seed=1, step=0, mutate=mutate)
-    err = max(cases.grad_errors(bad, good).values())
+    err = max(grad_errors(bad, good).values())
     assert err > 1e-2, err
 
 
@@ -271,7 +271,7 @@ def test_float32_oracle_train_step_is_within_half_the_gpu_bars(B):
     masks, inds = cases.decisions_of(ora, cache)
     o32 = cases.perturbed(np.float32)
     loss32, p32, grads32, cache32 = o32.loss_and_grads(x, y, seed=cases.SEED, step=cases.STEP, relu_masks=masks, pool_ind=inds)
-    errs = cases.grad_errors(grads32, grads)
+    errs = grad_errors(grads32, grads)
     worst = max(errs, key=errs.get)
     stat = max(max(np.abs(cache32['batch_stats'][i][q].astype(np.float64) - cache['batch_stats'][i][q]).max() for q in (0, 1))
                for i in cache['batch_stats'])

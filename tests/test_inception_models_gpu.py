@@ -1,10 +1,9 @@
 """GPU parity of the inception_d1 network program (KWS_NET_INCEPTION_D1, csrc/net_inception.hip) against the float64 oracle
-tests/inception_oracle.py - the method of test_stacked_models_gpu.py / test_mts_models_gpu.py: the device's ReLU6 gates and max-pool
-winners are read back (debug views 0, 2 and 3: every Conv1D's raw output is a column window of the tensor it was written into, its
+tests/inception_oracle.py on the harness of tests/net_parity.py: the device's ReLU6 gates and max-pool winners are read back (debug views 0, 2 and 3: every Conv1D's raw output is a column window of the tensor it was written into, its
 BatchNorm table the same columns of that tensor's table) and handed to the oracle's backward pass.  About a third of the BatchNorm
 scales is negative.
 
-Bars: the siblings', unchanged - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
+Bars: net_parity.FAMILY_BARS - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
 statistics atol 5e-6 / rtol 1e-5; class indices and the correct-count exact.  This net is 45 convolutions deep from the input to the
 head, each behind a BatchNorm that rescales its input's rounding error, so the oracle net was first run in float32 on the CPU (NumPy,
 its column sums in float64 as the device adds them; on the float64 run's gates and winners; tests/inception_cases.py holds the
@@ -23,20 +22,18 @@ import torch
 
 import adam_oracle as SO
 import inception_cases as cases
+import net_parity as NP
 import pool_oracle
 from speech_recognition_amd import _lib
-from speech_recognition_amd.net import DeviceNet
 
 pytestmark = pytest.mark.gpu
 
+BARS = NP.FAMILY_BARS
 NC = cases.NC
 
 
 def _pair():
-    ora = cases.perturbed()
-    net = DeviceNet(_lib.KWS_NET_INCEPTION_D1, NC, input_size=16000)
-    net.set_weights(dict(ora.params, **ora.state))
-    return ora, net
+    return NP.device_pair(cases.perturbed(), _lib.KWS_NET_INCEPTION_D1, NC, input_size=16000)
 
 
 def _view(net, B, what, index, training=True):
@@ -77,100 +74,63 @@ def _decisions(net, ora, B):
     return masks, inds
 
 
-def _device_step(ora, net, B, batch_seed=None, seed=cases.SEED, step=cases.STEP, row_offset=0):
+def _step(ora, net, B, batch_seed=None, seed=cases.SEED, step=cases.STEP, row_offset=0):
+    """One device step and what the oracle needs to repeat it on the device's gates and winners"""
     x, y = cases.batch(B, seed=batch_seed)
-    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=seed, step=step, row_offset=row_offset)
-    torch.cuda.synchronize()
+    dev = NP.device_step(net, x, y, seed, step, row_offset)
     masks, inds = _decisions(net, ora, B)
-    return dict(x=x, y=y, probs=probs.cpu().numpy(), metrics=net.metrics.cpu().numpy(), grads=net.grads_dict(), masks=masks, inds=inds,
-                weights=net.get_weights())
+    return dict(dev, ora=ora, x=x, y=y, xy=(x.astype(np.float64), y.astype(np.float64)),
+                kw=dict(seed=seed, step=step, relu_masks=masks, pool_ind=inds))
 
 
 @pytest.fixture(scope="module")
 def step3():
     ora, net = _pair()
-    d = _device_step(ora, net, 3)
-    d['ora'] = ora
-    d['oracle'] = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                                     relu_masks=d['masks'], pool_ind=d['inds'])
+    d = _step(ora, net, 3)
+    d['oracle'] = ora.loss_and_grads(*d['xy'], **d['kw'])
     return d
-
-
-def _check_step(B, d, ora, ref):
-    loss, p, grads, cache = ref
-    got, m = d['probs'], d['metrics']
-    errs = cases.grad_errors(d['grads'], grads)
-    worst = max(errs, key=errs.get)
-    print("train inception_d1 B=%d: probs %.3g (bar 5e-5), loss %.3g (bar 1e-4), worst gradient %s %.3g (bar 2e-4)" %
-          (B, np.abs(got - p).max(), abs(m[0] / B - loss), worst, errs[worst]))
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == d['y'].argmax(1)).sum()
-    for k, err in errs.items():
-        assert err < 2e-4, (k, err)
-    w = d['weights']
-    for idx, (mean, var) in cache['batch_stats'].items():
-        for nm, batch in (('moving_mean', mean), ('moving_variance', var)):
-            old = ora.state['batch_normalization_%d/%s' % (idx, nm)].astype(np.float64)
-            np.testing.assert_allclose(w['batch_normalization_%d/%s' % (idx, nm)], old - (old - batch) * 0.01, atol=5e-6, rtol=1e-5)
 
 
 def test_tensor_table_matches_oracle():
     ora, net = _pair()
-    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
-    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
-    assert net.count_params() == ora.count_params() == 2133900
+    NP.check_tensor_table(ora, net)
+    assert ora.count_params() == 2133900
 
 
 def test_predict_matches_oracle_and_rows_do_not_see_each_other():
     ora, net = _pair()
     x, _ = cases.batch(cases.PREDICT_BATCH, seed=1)
     p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
-    ref = ora.forward(x.astype(np.float64), training=False)
-    print("predict inception_d1: max |p - oracle| = %.3g (bar 2e-5)" % np.abs(p - ref).max())
-    assert np.abs(p - ref).max() < 2e-5
-    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    NP.check_predict(p, ora.forward(x.astype(np.float64), training=False), BARS, 'inception_d1')
     for r in range(cases.PREDICT_BATCH):     # a predict at batch 1 agrees with the same row of the batch of 5
         p1 = net.predict(torch.from_numpy(x[r:r + 1]).cuda()).cpu().numpy()
         assert np.abs(p1[0] - p[r]).max() < 1e-6, r
 
 
 def test_train_fwd_bwd_matches_oracle_batch_3(step3):
-    _check_step(3, step3, step3['ora'], step3['oracle'])
+    NP.check_train_step(step3, step3['y'], step3['oracle'], step3['ora'], BARS, 'inception_d1 B=3')
 
 
 def test_train_fwd_bwd_matches_oracle_batch_16():
     B = cases.TRAIN_BATCHES[1]
     ora, net = _pair()
-    d = _device_step(ora, net, B)
-    ref = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                             relu_masks=d['masks'], pool_ind=d['inds'])
-    _check_step(B, d, ora, ref)
+    d = _step(ora, net, B)
+    NP.check_train_step(d, d['y'], ora.loss_and_grads(*d['xy'], **d['kw']), ora, BARS, 'inception_d1 B=%d' % B)
 
 
 @pytest.mark.parametrize("mutate", ['ignore_dilation', 'avg_count_include_pad'])
 def test_wrong_oracles_miss_the_gradient_bar(step3, mutate):
     """Negative controls: against an oracle without the dilation, or one whose average pool counts the padding, the device's
     gradients miss the 2e-4 bar (that they meet it against the right one is test_train_fwd_bwd_matches_oracle_batch_3)."""
-    ora = step3['ora']
-    bad = ora.loss_and_grads(step3['x'].astype(np.float64), step3['y'].astype(np.float64), seed=cases.SEED, step=cases.STEP,
-                             relu_masks=step3['masks'], pool_ind=step3['inds'], mutate=mutate)[2]
-    worst = max(cases.grad_errors(step3['grads'], bad).values())
+    bad = step3['ora'].loss_and_grads(*step3['xy'], mutate=mutate, **step3['kw'])[2]
+    worst = max(NP.grad_errors(step3['grads'], bad).values())
     print("against the %s oracle: worst gradient %.3g" % (mutate, worst))
-    assert worst > 2e-4
+    assert worst > BARS['grad']
 
 
 def test_train_step_is_bit_reproducible():
     ora, net = _pair()
-    x, y = cases.batch(24, seed=3)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    state0 = net.state.clone()
-    p1 = net.train_fwd_bwd(xd, yd, seed=1, step=0).clone()
-    g1, s1 = net.grads.clone(), net.state.clone()
-    net.state.copy_(state0)
-    p2 = net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state) and torch.equal(p1, p2)
+    NP.assert_bit_reproducible(net, *cases.batch(24, seed=3))
 
 
 def test_data_parallel_shard_uses_the_global_dropout_rows_and_loss_batch():
@@ -178,11 +138,8 @@ def test_data_parallel_shard_uses_the_global_dropout_rows_and_loss_batch():
     the global batch (a shard of half the batch: every gradient halves - a power of two, exact but for underflow)."""
     ora, net = _pair()
     B, off = 4, 37
-    d = _device_step(ora, net, B, batch_seed=21, seed=5, step=3, row_offset=off)
-    _, p, grads, _ = ora.loss_and_grads(d['x'].astype(np.float64), d['y'].astype(np.float64), seed=5, step=3, drop_offset=off,
-                                        relu_masks=d['masks'], pool_ind=d['inds'])
-    assert np.abs(d['probs'] - p).max() < 5e-5
-    assert max(cases.grad_errors(d['grads'], grads).values()) < 2e-4
+    d = _step(ora, net, B, batch_seed=21, seed=5, step=3, row_offset=off)
+    NP.check_shard(d, ora.loss_and_grads(*d['xy'], drop_offset=off, **d['kw']), BARS)
     g1 = net.grads.clone()
     net.set_weights(dict(ora.params, **ora.state))
     net.train_fwd_bwd(torch.from_numpy(d['x']).cuda(), torch.from_numpy(d['y']).cuda(), seed=5, step=3, row_offset=off, loss_batch=2 * B)
@@ -225,21 +182,9 @@ def test_checkpoint_round_trip(tmp_path):
     """save -> load -> one more step equals the uninterrupted run bit for bit (weights, moving statistics, both Adam moments,
     `iterations`)."""
     from speech_recognition_amd.model import speech_model
-    a = speech_model('inception_d1', 16000, num_classes=NC)
-    batches = [cases.batch(8, seed=200 + i) for i in range(3)]
-    for xb, yb in batches[:2]:
-        a.train_on_batch(xb, yb)
-    path = str(tmp_path / "inception.npz")
-    a.save(path)
-    b = speech_model('inception_d1', 16000, num_classes=NC)
-    b.load_weights(path)
-    assert b.optimizer.iterations == 2
-    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state)
-    assert torch.equal(a.net.slots, b.net.slots) and torch.equal(a.net.slots2, b.net.slots2)
-    la, lb = a.train_on_batch(*batches[2]), b.train_on_batch(*batches[2])
-    assert la == lb
-    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state)
-    assert torch.equal(a.net.slots, b.net.slots) and torch.equal(a.net.slots2, b.net.slots2)
+    NP.check_checkpoint_round_trip(lambda: speech_model('inception_d1', 16000, num_classes=NC),
+                                   [cases.batch(8, seed=200 + i) for i in range(3)], str(tmp_path / "inception.npz"),
+                                   slots=('slots', 'slots2'), iterations=True)
 
 
 def test_fit_generator_runs():
@@ -262,29 +207,4 @@ def test_workspace_bytes_is_honoured_and_one_byte_less_is_refused(training):
     """A step in a workspace of exactly workspace_bytes leaves the guard bands around it alone; one byte less is KWS_E_WORKSPACE
     with a message, and nothing runs."""
     ora, net = _pair()
-    lib, B, guard = net.lib, 3, 4096
-    need = int(lib.kws_net_workspace_bytes(net.handle, B, training))
-    assert need > 0 and need % 4 == 0
-    buf = torch.full((need // 4 + 2 * guard,), float('nan'), dtype=torch.float32, device="cuda")
-    ws = buf[guard:guard + need // 4]
-    x, y = cases.batch(B)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    probs = torch.full((B, NC), float('nan'), dtype=torch.float32, device="cuda")
-
-    def run(nbytes):
-        if training:
-            return lib.kws_net_train_fwd_bwd(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), _lib.ptr(yd), B,
-                                             _lib.ptr(net.grads), _lib.ptr(probs), _lib.ptr(net.metrics), ctypes.c_uint64(1),
-                                             ctypes.c_uint32(0), 0, B, _lib.ptr(ws), nbytes, _lib.stream_ptr())
-        return lib.kws_net_predict(net.handle, _lib.ptr(net.params), _lib.ptr(net.state), _lib.ptr(xd), B, _lib.ptr(probs), _lib.ptr(ws),
-                                   nbytes, _lib.stream_ptr())
-
-    assert run(need - 1) == -3                                   # KWS_E_WORKSPACE
-    assert b'workspace' in lib.kws_last_error()
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(probs).all()) and bool(torch.isnan(buf).all())
-    assert run(need) == 0
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[-guard:]).all())
-    p = probs.cpu().numpy()
-    assert np.isfinite(p).all() and np.abs(p.sum(1) - 1).max() < 1e-5
+    NP.check_workspace_refusal(net, *cases.batch(3), training=training)

@@ -1,7 +1,8 @@
 """GPU parity of the conv_1d_learned_spec network program (KWS_NET_CONV_1D_LEARNED_SPEC: the banked front convolution of
-csrc/fbank_conv.hip, the grouped ladder with its ragged second block) against the float64 oracle tests/learned_spec_oracle.py -
-the method and the bars of test_grouped_models_gpu.py, whose nets run the same ladder kernels at the same depths: the device's
-ReLU6 decisions are read back (debug views 0 and 2) and handed to the oracle's backward pass."""
+csrc/fbank_conv.hip, the grouped ladder with its ragged second block) against the float64 oracle tests/learned_spec_oracle.py on
+the harness and the bars (FAMILY_BARS) of tests/net_parity.py - the bars of test_grouped_models_gpu.py, whose nets run the same
+ladder kernels at the same depths: the device's ReLU6 decisions are read back (debug views 0 and 2) and handed to the oracle's
+backward pass."""
 import json
 import os
 
@@ -12,19 +13,17 @@ import torch
 import net_parity as NP
 from learned_spec_oracle import MUTATIONS, LearnedSpecNet
 from speech_recognition_amd import _lib
-from speech_recognition_amd.net import DeviceNet
 
 pytestmark = pytest.mark.gpu
 
+BARS = NP.FAMILY_BARS
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'learned_spec_model.json')
 
 
 def _pair(L=16000, nc=12, seed=5):
     ora = LearnedSpecNet(num_classes=nc, input_size=L)
     NP.perturb(ora, seed)
-    net = DeviceNet(_lib.KWS_NET_CONV_1D_LEARNED_SPEC, nc, input_size=L)
-    net.set_weights(dict(ora.params, **ora.state))
-    return ora, net
+    return NP.device_pair(ora, _lib.KWS_NET_CONV_1D_LEARNED_SPEC, nc, input_size=L)
 
 
 def _decisions(net, ora, B):
@@ -42,11 +41,7 @@ def _decisions(net, ora, B):
 
 def test_tensor_table_matches_oracle_and_reference():
     ora, net = _pair()
-    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
-    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
-    for k, v in list(ora.params.items()) + list(ora.state.items()):
-        assert net.tensors[k].shape == v.shape, k
-    assert net.count_params() == ora.count_params()
+    NP.check_tensor_table(ora, net, shapes=True)
     with open(GOLDEN) as f:
         gold = json.load(f)['conv_1d_learned_spec_16000']
     assert [s.name for s in net.tensors.values()] == [w['name'] for w in gold['weights']]
@@ -57,58 +52,29 @@ def test_predict_matches_oracle(L):
     ora, net = _pair(L)
     x, _ = NP.waveform_batch(5, 12, 1, L=L)
     p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
-    ref = ora.forward(x.astype(np.float64), training=False)
-    assert np.abs(p - ref).max() < 2e-5
-    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    NP.check_predict(p, ora.forward(x.astype(np.float64), training=False), BARS, 'conv_1d_learned_spec L=%d' % L)
 
 
 @pytest.mark.parametrize("L,B", [(16000, 3), (16000, 10), (15000, 4), (14560, 3)])
 def test_train_fwd_bwd_matches_oracle(L, B):
     ora, net = _pair(L)
     x, y = NP.waveform_batch(B, 12, B, L=L)
-    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
-    torch.cuda.synchronize()
-    masks = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2, relu_masks=masks)
+    dev = NP.device_step(net, x, y, seed=77, step=2)
+    x64, y64, kw = x.astype(np.float64), y.astype(np.float64), dict(seed=77, step=2, relu_masks=_decisions(net, ora, B))
+    ref = ora.loss_and_grads(x64, y64, **kw)
     # the front convolution's output, straight in the joined tensor
-    y0 = net.debug_view(B, 0, 0).reshape(B, ora.rows, 240)
-    assert np.abs(y0 - cache['x0']).max() < 2e-6 * max(np.abs(cache['x0']).max(), 1.0)
-    got = probs.cpu().numpy()
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    m = net.metrics.cpu().numpy()
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == y.argmax(1)).sum()
-    g = net.grads_dict()
-    worst = {}
-    for k, ref in grads.items():
-        ref = ref.reshape(g[k].shape)
-        worst[k] = np.abs(g[k] - ref).max() / max(np.abs(ref).max(), 1e-7)
-    print("\nconv_1d_learned_spec L=%d B=%d: worst gradient error %.3e (%s)" % (L, B, max(worst.values()), max(worst, key=worst.get)))
-    for k, err in worst.items():
-        assert err < 2e-4, (k, err)
-    w = net.get_weights()
-    for idx, (mean, var) in cache['batch_stats'].items():
-        for nm, batch in (('moving_mean', mean), ('moving_variance', var)):
-            old = ora.state['batch_normalization_%d/%s' % (idx, nm)].astype(np.float64)
-            np.testing.assert_allclose(w['batch_normalization_%d/%s' % (idx, nm)], old - (old - batch) * 0.01, atol=5e-6, rtol=1e-5)
+    y0, x0 = net.debug_view(B, 0, 0).reshape(B, ora.rows, 240), ref[3]['x0']
+    assert np.abs(y0 - x0).max() < 2e-6 * max(np.abs(x0).max(), 1.0)
+    NP.check_train_step(dev, y, ref, ora, BARS, "conv_1d_learned_spec L=%d B=%d" % (L, B))
     if (L, B) == (16000, 3):       # the device agrees with neither mutated oracle
         for mutate in MUTATIONS:
-            _, _, wrong, _ = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2, relu_masks=masks,
-                                                mutate=mutate)
-            assert max(np.abs(g[k] - r.reshape(g[k].shape)).max() / max(np.abs(r).max(), 1e-7) for k, r in wrong.items()) > 1e-2, mutate
+            wrong = ora.loss_and_grads(x64, y64, mutate=mutate, **kw)[2]
+            assert max(NP.grad_errors(dev['grads'], wrong).values()) > NP.MUTATED_ORACLE_BAR, mutate
 
 
 def test_train_step_is_bit_reproducible():
     ora, net = _pair()
-    x, y = NP.waveform_batch(64, 12, 3)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    state0 = net.state.clone()
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    g1, s1 = net.grads.clone(), net.state.clone()
-    net.state.copy_(state0)
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state)
+    NP.assert_bit_reproducible(net, *NP.waveform_batch(64, 12, 3))
 
 
 def test_speech_model_trains():

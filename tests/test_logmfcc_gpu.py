@@ -14,7 +14,7 @@ from oracle.net import LogMfccNet
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
 
-from net_parity import check_step, perturb, relu_masks
+from net_parity import check_residual_step, perturb, relu_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -86,7 +86,7 @@ def test_train_fwd_bwd_matches_oracle(B, nc, F):
     masks, args = _decisions(net, ora, B)
     ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
                              relu_masks=masks, pool_args=args)
-    check_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
+    check_residual_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
                moving_mean_atol=5e-6)
 
 
@@ -173,7 +173,7 @@ def test_odd_lengths_pool_in_ceil_mode(T):
     masks, args = _decisions(net, ora, B)
     ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=5, step=1,
                              relu_masks=masks, pool_args=args)
-    check_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
+    check_residual_step(ora, net, probs, y, ref, probs_atol=2e-5, loss_atol=5e-5, grad_rtol=1e-4,
                moving_mean_atol=5e-6)
 
 

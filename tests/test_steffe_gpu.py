@@ -9,7 +9,7 @@ from oracle.net import SteffeNet
 from speech_recognition_amd import _lib
 from speech_recognition_amd.net import DeviceNet
 
-from net_parity import check_step, perturb, relu_masks, waveform_batch
+from net_parity import check_residual_step, perturb, relu_masks, waveform_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +63,7 @@ def test_train_fwd_bwd_matches_oracle(B):
     masks, ind = _decisions(net, ora, B)
     ref = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2,
                              relu_masks=masks, pool_ind=ind)
-    check_step(ora, net, probs, y, ref, probs_atol=5e-5, loss_atol=1e-4, grad_rtol=2e-4,
+    check_residual_step(ora, net, probs, y, ref, probs_atol=5e-5, loss_atol=1e-4, grad_rtol=2e-4,
                moving_mean_atol=5e-6)
 
 

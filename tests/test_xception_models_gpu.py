@@ -1,10 +1,10 @@
 """GPU parity of the xception_with_attention network program (KWS_NET_XCEPTION_ATTENTION: csrc/net_logmfcc.hip + csrc/attgate.hip +
-csrc/gru.hip) against the float64 oracle tests/xception_oracle.py - the method of test_residual_gpu.py and test_gru_models_gpu.py:
-the device's discrete decisions are handed to the oracle's backward pass: the ReLU6 masks of every BatchNorm (debug views 0 / 2;
-the one-channel attention BatchNorm from views 4 / 9), the winners of the 3-wide max-pool windows, and the hard-sigmoid decisions
-of the GRU (view 7: a gate is in its linear region iff its saved value is strictly between 0 and 1).
+csrc/gru.hip) against the float64 oracle tests/xception_oracle.py on the harness of tests/net_parity.py: the device's discrete
+decisions are handed to the oracle's backward pass: the ReLU6 masks of every BatchNorm (debug views 0 / 2; the one-channel
+attention BatchNorm from views 4 / 9), the winners of the 3-wide max-pool windows, and the hard-sigmoid decisions of the GRU (view
+7: a gate is in its linear region iff its saved value is strictly between 0 and 1).
 
-Bars (the siblings', unchanged): predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
+Bars: net_parity.FAMILY_BARS - predict 2e-5, train probabilities 5e-5, loss 1e-4, gradients 2e-4 of the tensor's maximum, moving
 statistics atol 5e-6 / rtol 1e-5; class indices and the correct-count exact.  Before relying on them the oracle net was run in
 float32 against itself in float64 on the CPU (xception_oracle.net_float32_figures: same weights and batches as below, the float32
 run on the float64 run's ReLU6, pool and hard-sigmoid decisions; gru_oracle's recurrence keeps its state in float64, so from the
@@ -17,20 +17,18 @@ import numpy as np
 import pytest
 import torch
 
+import net_parity as NP
 from oracle import layers as OL
-from net_parity import relu_masks, waveform_batch
 from speech_recognition_amd import _lib
-from speech_recognition_amd.net import DeviceNet
 from xception_oracle import perturbed_net
 
 pytestmark = pytest.mark.gpu
 
+BARS = NP.FAMILY_BARS
+
 
 def _pair(nc=12, seed=5, input_size=16000):
-    ora = perturbed_net(input_size, num_classes=nc, seed=seed)
-    net = DeviceNet(_lib.KWS_NET_XCEPTION_ATTENTION, nc, input_size=input_size)
-    net.set_weights(dict(ora.params, **ora.state))
-    return ora, net
+    return NP.device_pair(perturbed_net(input_size, num_classes=nc, seed=seed), _lib.KWS_NET_XCEPTION_ATTENTION, nc, input_size=input_size)
 
 
 def _decisions(net, ora, B):
@@ -38,7 +36,7 @@ def _decisions(net, ora, B):
     for blk in ora.blocks:
         shapes[blk['bn1']] = (B, blk['Lin'], blk['nf'])
         shapes[blk['bn2']] = (B, blk['Lin'], blk['nf'])
-    masks, pre_of = relu_masks(net, B, shapes)
+    masks, pre_of = NP.relu_masks(net, B, shapes)
     args = {}
     for i, blk in enumerate(ora.blocks):
         a = np.minimum(np.maximum(pre_of[blk['bn2']], np.float32(0)), np.float32(6))
@@ -54,53 +52,45 @@ def _decisions(net, ora, B):
     return masks, args, gates, save
 
 
-def _grad_errors(g, grads):
-    return {k: np.abs(g[k] - ref.reshape(g[k].shape)).max() / max(np.abs(ref).max(), 1e-7) for k, ref in grads.items()}
+def _step(ora, net, x, y, seed=77, step=2, row_offset=0):
+    """One device step and what the oracle needs to repeat it on the device's decisions; the saved GRU gates besides"""
+    dev = NP.device_step(net, x, y, seed, step, row_offset)
+    masks, args, gates, save = _decisions(net, ora, x.shape[0])
+    kw = dict(seed=seed, step=step, relu_masks=masks, pool_args=args, decisions=gates)
+    return dev, (x.astype(np.float64), y.astype(np.float64)), kw, save
 
 
 def test_tensor_table_matches_oracle():
     ora, net = _pair()
-    assert [s.name for s in net.tensors.values() if not s.is_state] == list(ora.params.keys())
-    assert [s.name for s in net.tensors.values() if s.is_state] == list(ora.state.keys())
-    for k, v in list(ora.params.items()) + list(ora.state.items()):
-        assert net.tensors[k].shape == v.shape, k
-    assert net.count_params() == ora.count_params()
+    NP.check_tensor_table(ora, net, shapes=True)
     assert {s.name for s in net.tensors.values() if s.l2 > 0} == set(ora.l2_names)
 
 
 def test_predict_matches_oracle():
     ora, net = _pair()
-    x, _ = waveform_batch(5, 12, 1)
+    x, _ = NP.waveform_batch(5, 12, 1)
     p = net.predict(torch.from_numpy(x).cuda()).cpu().numpy()
-    ref = ora.forward(x.astype(np.float64), training=False)
-    print("predict xception_with_attention: max |p - oracle| = %.3g" % np.abs(p - ref).max())
-    assert np.abs(p - ref).max() < 2e-5
-    assert np.array_equal(p.argmax(1), ref.argmax(1))
+    NP.check_predict(p, ora.forward(x.astype(np.float64), training=False), BARS, 'xception_with_attention')
 
 
 @pytest.mark.parametrize("B,input_size", [(8, 16000), (40, 4000)])
 def test_train_fwd_bwd_matches_oracle(B, input_size):
     ora, net = _pair(input_size=input_size)
     assert ora.T == {16000: 50, 4000: 13}[input_size]
-    x, y = waveform_batch(B, 12, B, L=input_size)
-    probs = net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
-    torch.cuda.synchronize()
-    masks, args, gates, save = _decisions(net, ora, B)
-    loss, p, grads, cache = ora.loss_and_grads(x.astype(np.float64), y.astype(np.float64), seed=77, step=2, relu_masks=masks, pool_args=args,
-                                               decisions=gates)
-    got = probs.cpu().numpy()
-    m = net.metrics.cpu().numpy()
-    errs = _grad_errors(net.grads_dict(), grads)
-    worst = max(errs, key=errs.get)
+    x, y = NP.waveform_batch(B, 12, B, L=input_size)
+    dev, xy, kw, save = _step(ora, net, x, y)
+    ref = ora.loss_and_grads(*xy, **kw)
+    cache = ref[3]
     gc = cache['gate']
     u, att = net.debug_view(B, 4, 0).reshape(B, ora.T), net.debug_view(B, 3, 0).reshape(B, ora.T)
     gy = net.debug_view(B, 6, 0).reshape(B, ora.T, ora.C)
     gout = net.debug_view(B, 8, 0).reshape(B, 2 * ora.H)
     tab = net.debug_view(B, 9, 0)
-    print("train xception B=%d L=%d: u %.3g, att %.3g, gate out %.3g, gru out %.3g, probs %.3g, loss %.3g, worst gradient %s %.3g" %
-          (B, input_size, np.abs(u - gc['u']).max() / np.abs(gc['u']).max(), np.abs(att - gc['att']).max(),
-           np.abs(gy - cache['gate_out']).max(), np.abs(gout - cache['gru_out']).max(), np.abs(got - p).max(), abs(m[0] / B - loss), worst,
-           errs[worst]))
+    assert ora.att_bn in cache['batch_stats']
+    NP.check_train_step(dev, y, ref, ora, BARS, "xception B=%d L=%d" % (B, input_size),
+                        lead="u %.3g, att %.3g, gate out %.3g, gru out %.3g, " %
+                        (np.abs(u - gc['u']).max() / np.abs(gc['u']).max(), np.abs(att - gc['att']).max(),
+                         np.abs(gy - cache['gate_out']).max(), np.abs(gout - cache['gru_out']).max()))
     assert np.abs(u - gc['u']).max() < 5e-5 * np.abs(gc['u']).max()
     np.testing.assert_allclose(tab, [gc['scale'], gc['shift'], gc['mean'], gc['rstd']], rtol=5e-5, atol=5e-6)
     assert np.abs(att - gc['att']).max() < 5e-5
@@ -116,67 +106,35 @@ def test_train_fwd_bwd_matches_oracle(B, input_size):
             assert np.abs(save[d, q] - cache['gru'][d][k])[far].max() < 5e-5, (d, k)
     assert left <= 1e-3 * total
     assert np.abs(gout - cache['gru_out']).max() < 5e-5
-    assert np.abs(got - p).max() < 5e-5
-    assert np.array_equal(got.argmax(1), p.argmax(1))
-    assert abs(m[0] / B - loss) < 1e-4
-    assert m[1] == (p.argmax(1) == y.argmax(1)).sum()
-    for k, err in errs.items():
-        assert err < 2e-4, (k, err)
-    w = net.get_weights()
-    assert ora.att_bn in cache['batch_stats']
-    for name, ref in ora.moving_after(cache).items():
-        np.testing.assert_allclose(w[name], ref, atol=5e-6, rtol=1e-5, err_msg=name)
 
 
 def test_oracle_without_the_direct_term_misses_the_gradient_bar():
     """Negative control: against the gate whose dx lacks the dy att term the device's gradients miss the bar by far."""
     ora, net = _pair(input_size=4000)
-    B = 6
-    x, y = waveform_batch(B, 12, 9, L=4000)
-    net.train_fwd_bwd(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), seed=77, step=2)
-    torch.cuda.synchronize()
-    masks, args, gates, _ = _decisions(net, ora, B)
-    x64, y64 = x.astype(np.float64), y.astype(np.float64)
-    kw = dict(seed=77, step=2, relu_masks=masks, pool_args=args, decisions=gates)
-    good = ora.loss_and_grads(x64, y64, **kw)[2]
-    bad = ora.loss_and_grads(x64, y64, mutate='no_direct_term', **kw)[2]
-    g = net.grads_dict()
-    assert max(_grad_errors(g, good).values()) < 2e-4
-    assert max(_grad_errors(g, bad).values()) > 1e-2
+    dev, xy, kw, _ = _step(ora, net, *NP.waveform_batch(6, 12, 9, L=4000))
+    NP.check_mutated_oracle(dev['grads'], ora.loss_and_grads(*xy, **kw)[2], ora.loss_and_grads(*xy, mutate='no_direct_term', **kw)[2],
+                            BARS, far=NP.MUTATED_ORACLE_BAR)
 
 
 def test_train_step_is_bit_reproducible():
     ora, net = _pair()
-    x, y = waveform_batch(40, 12, 3)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    state0 = net.state.clone()
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    g1, s1 = net.grads.clone(), net.state.clone()
-    net.state.copy_(state0)
-    net.train_fwd_bwd(xd, yd, seed=1, step=0)
-    assert torch.equal(g1, net.grads) and torch.equal(s1, net.state)
+    NP.assert_bit_reproducible(net, *NP.waveform_batch(40, 12, 3))
 
 
 def test_data_parallel_shard_draws_the_global_rows_masks():
     """row_offset = 8 on rows 8 .. 15 reproduces what those rows see inside the 16-row batch, on the GRU output (view 8).  Batch
     statistics differ between the two runs, so the shard is compared with the oracle at drop_offset = 8."""
     ora, net = _pair(input_size=4000)
-    x, y = waveform_batch(16, 12, 21, L=4000)
-    xs, ys = x[8:], y[8:]
-    probs = net.train_fwd_bwd(torch.from_numpy(xs).cuda(), torch.from_numpy(ys).cuda(), seed=5, step=3, row_offset=8)
-    torch.cuda.synchronize()
+    x, y = NP.waveform_batch(16, 12, 21, L=4000)
+    dev, (xs, ys), kw, _ = _step(ora, net, x[8:], y[8:], seed=5, step=3, row_offset=8)
     gout = net.debug_view(8, 8, 0).reshape(8, 2 * ora.H)
-    masks, args, gates, _ = _decisions(net, ora, 8)
     cache = {}
-    ora.forward(xs.astype(np.float64), training=True, seed=5, step=3, cache=cache, drop_offset=8)
+    ora.forward(xs, training=True, seed=5, step=3, cache=cache, drop_offset=8)
     assert np.abs(gout - cache['gru_out']).max() < 5e-5
     wrong = {}
-    ora.forward(xs.astype(np.float64), training=True, seed=5, step=3, cache=wrong, drop_offset=0)
+    ora.forward(xs, training=True, seed=5, step=3, cache=wrong, drop_offset=0)
     assert np.abs(gout - wrong['gru_out']).max() > 1e-2
-    _, p, grads, _ = ora.loss_and_grads(xs.astype(np.float64), ys.astype(np.float64), seed=5, step=3, drop_offset=8, relu_masks=masks,
-                                        pool_args=args, decisions=gates)
-    assert np.abs(probs.cpu().numpy() - p).max() < 5e-5
-    assert max(_grad_errors(net.grads_dict(), grads).values()) < 2e-4
+    NP.check_shard(dev, ora.loss_and_grads(xs, ys, drop_offset=8, **kw), BARS)
 
 
 def test_two_rmsprop_steps_move_the_weights_as_the_oracle_says():
@@ -193,7 +151,7 @@ def test_two_rmsprop_steps_move_the_weights_as_the_oracle_says():
     l2 = net.l2.cpu().numpy().astype(np.float64)
     acc = np.zeros(net.n_params)
     for t in (1, 2):
-        x, y = waveform_batch(16, 12, 300 + t)
+        x, y = NP.waveform_batch(16, 12, 300 + t)
         p0 = net.params.cpu().numpy().astype(np.float64)
         model.train_on_batch(x, y)
         g = net.grads.cpu().numpy().astype(np.float64) + 2.0 * l2 * p0
@@ -208,28 +166,15 @@ def test_two_rmsprop_steps_move_the_weights_as_the_oracle_says():
 def test_speech_model_trains_through_fit_generator(repo_root):
     """xception_with_attention as train.py drives it: AudioProcessor(output_representation='raw') -> data_gen -> speech_model ->
     Model.fit_generator; the loss on a fixed batch falls over a few steps."""
-    import sys
-    sys.path.insert(0, repo_root)
-    import bench
-    from speech_recognition_amd.input_data import AudioProcessor, prepare_words_list
-    from speech_recognition_amd.model import prepare_model_settings, speech_model
-    from speech_recognition_amd.utils import data_gen
+    from speech_recognition_amd.model import speech_model
     model = speech_model('xception_with_attention', 16000, num_classes=12)
-    x, y = waveform_batch(32, 12, 100)
+    x, y = NP.waveform_batch(32, 12, 100)
     losses = [float(model.train_on_batch(x, y)[0]) for _ in range(12)]
     print("xception_with_attention losses on a fixed batch: %s" % ' '.join('%.4f' % v for v in losses))
     assert np.all(np.isfinite(losses)) and np.mean(losses[-3:]) < np.mean(losses[:3])
     with pytest.raises(_lib.KwsError):
         speech_model('xception_with_attention', 3999, num_classes=12)
-    dev = torch.device("cuda", 0)
-    settings = prepare_model_settings(label_count=len(prepare_words_list(bench.WANTED)), sample_rate=16000,
-                                      clip_duration_ms=1000, window_size_ms=30.0, window_stride_ms=10.0,
-                                      dct_coefficient_count=80, num_log_mel_features=60, output_representation='raw')
-    proc = AudioProcessor(bench.build_synthetic(dev, 8192, seed=59185), 13.0, 60.0, bench.WANTED, 10.0, 0.0, settings,
-                          output_representation='raw', device=dev)
-    np.random.seed(1234)
-    gen = data_gen(proc, None, batch_size=64, mode='training')
-    model = speech_model('xception_with_attention', settings['fingerprint_size'], num_classes=settings['label_count'], **settings)
+    gen, model, _ = NP.generator_model('xception_with_attention', 'raw', repo_root)
     hist = model.fit_generator(gen, steps_per_epoch=4, epochs=1, verbose=0)
     assert np.isfinite(hist.history['loss'][-1])
 
@@ -237,15 +182,5 @@ def test_speech_model_trains_through_fit_generator(repo_root):
 def test_checkpoint_round_trip(tmp_path):
     """save -> load -> one more step equals the uninterrupted run bit for bit (weights, moving statistics, the RMSprop slots)."""
     from speech_recognition_amd.model import speech_model
-    a = speech_model('xception_with_attention', 16000, num_classes=12)
-    batches = [waveform_batch(16, 12, 200 + i) for i in range(3)]
-    for xb, yb in batches[:2]:
-        a.train_on_batch(xb, yb)
-    path = str(tmp_path / "xception.npz")
-    a.save(path)
-    b = speech_model('xception_with_attention', 16000, num_classes=12)
-    b.load_weights(path)
-    la, lb = a.train_on_batch(*batches[2]), b.train_on_batch(*batches[2])
-    assert la == lb
-    assert torch.equal(a.net.params, b.net.params) and torch.equal(a.net.state, b.net.state)
-    assert torch.equal(a.net.slots, b.net.slots)
+    NP.check_checkpoint_round_trip(lambda: speech_model('xception_with_attention', 16000, num_classes=12),
+                                   [NP.waveform_batch(16, 12, 200 + i) for i in range(3)], str(tmp_path / "xception.npz"), slots=('slots',))
