@@ -307,6 +307,50 @@ int kws_gconv_wgrad_f32(const float* X, const float* bn, int bn_group, const flo
                         const kws_gconv_t* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouped depthwise Conv1D (VALID, no bias): the depthwise halves of the g _depthwise_conv_block calls inside the reference's
+ * _grouped_reduce_conv / _grouped_context_conv of conv_1d_top_down_model (model.py:1335-1373).  Input X [B, L, C]; output
+ * Z [B, Lout, g*gs], group q at columns q*gs, made for a grouped 1x1 convolution (kws_gconv_* with k = 1) behind it.  Kernel of
+ * group q: [k, gs] at w + q * w_group_stride (0 = k*gs: back to back; larger: the groups' other tensors lie in between and are
+ * never touched).  Group q reads the channel window [x0 + q*x_step, + gs) of X: x_step = gs is the sliced form (a reduce block),
+ * x_step = 0 the shared form (a context block: the reference passes x, not the slice, to every group, so every group filters
+ * the same window with its own kernel).  Channels outside every window are never read.
+ *   act    what a value of X goes through on load: KWS_GDW_ACT_NONE identity; KWS_GDW_ACT_BN_RELU6 relu6(scale*x + shift) of
+ *          the producer's tables tab [C / bn_group][4][bn_group] (the form kws_gconv_fwd_f32 takes; indexed per channel, so
+ *          bn_group need not be a multiple of 4); KWS_GDW_ACT_BIAS x + tab[ch], tab [C] a convolution's bias, no gate.
+ *   fwd    Z[b,t,q*gs+c] = sum_j w_q[j,c] * act(X[b, stride*t + j, x0 + q*x_step + c]).  Shared form: X is read once per output
+ *          tile for all groups.
+ *   bwd    dA[b,u,ch] = sum over the groups q whose window holds ch (ascending) and the taps j with stride | (u - j) of
+ *          w_q[j,c] * dZ[b,(u-j)/stride,q*gs+c]: the gradient wrt act(X), no gate applied (kws_gconv_dgrad_f32's contract; the
+ *          BatchNorm backward does the gate).  Every element of dA [B, L, C] is written exactly once: rows no window reaches
+ *          and channels no group reads are exact zeros.
+ *          dW_q[j,c] = sum_{b,t} act(X[b, stride*t+j, ...]) * dZ[b,t,q*gs+c], written at dW + q * w_group_stride through
+ *          kws_gdwconv_bwd_part_rows partial rows [k + 1][g*gs] (row k: column sums of dZ) in workspace, added in one fixed
+ *          order.  dbias (may be NULL; KWS_GDW_ACT_BIAS only) [C]: the column sums of dA, taken from the same partial rows.
+ *          workspace >= kws_gdwconv_bwd_workspace_floats floats (0 = outside the domain).
+ * Domain: 1 <= k <= 7, 1 <= stride <= 4, 1 <= g <= 8; gs, C, x0, x_step multiples of 4; x0 + (g-1)*x_step + gs <= C;
+ * stride*(Lout-1) + k <= L; X, Z, dZ, dA, workspace 16-byte aligned.  Anything else is KWS_E_INVALID before any launch.
+ * No atomics: results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+#define KWS_GDW_ACT_NONE 0
+#define KWS_GDW_ACT_BN_RELU6 1
+#define KWS_GDW_ACT_BIAS 2
+typedef struct {
+  int B, L, C;     /* input [B, L, C] */
+  int Lout;        /* output rows per clip: stride*(Lout-1) + k <= L */
+  int k, stride;   /* taps, time stride */
+  int g, gs;       /* groups, channels per group */
+  int x0, x_step;  /* group q reads the channels [x0 + q*x_step, + gs) */
+  int act;         /* KWS_GDW_ACT_* */
+  int bn_group;    /* KWS_GDW_ACT_BN_RELU6: channels per table of tab */
+  int64_t w_group_stride;
+} kws_gdwconv_t;
+int     kws_gdwconv_fwd_f32(const float* X, const float* tab, const float* w, float* Z, const kws_gdwconv_t* d, void* stream);
+int     kws_gdwconv_bwd_part_rows(const kws_gdwconv_t* d);
+int64_t kws_gdwconv_bwd_workspace_floats(const kws_gdwconv_t* d);
+int     kws_gdwconv_bwd_f32(const float* X, const float* tab, const float* dZ, const float* w, float* dA, float* dW, float* dbias,
+                            float* workspace, const kws_gdwconv_t* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MaxPool1D(pool_size=3, strides=2, padding='valid') over relu6(bn(y)): the pool of the reference's _reduce_conv in
  * conv_1d_time_stacked_model / conv_1d_heavy_model (model.py:271-277, 423-429).  y [B, L, C] is the RAW convolution output,
  * bn its table scale|shift|mean|rstd [4][C]; C % 4 == 0, C <= 1024, L >= 3.
@@ -800,6 +844,20 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
  *                         read 180 and 120 of 300 channels (two kws_conv1d_* column windows) -> Flatten -> Dropout(.3) -> Dense.
  *                         Debug views: what 0, index 0 = the front output [B, rows, 240], index i >= 1 = block i's pre-BN output;
  *                         what 2, index j = the table of batch_normalization_{j+1} (4 * Ng floats).
+ *   KWS_NET_CONV_1D_TOP_DOWN: conv_1d_top_down_model, reference model.py:1326-1397 (raw input, input_size at least 14879 = 91 rows:
+ *                         the fewest that leave the last block a row; Keras model name 'conv_1d_top_down'): Conv1D(480, 479,
+ *                         strides=160, VALID, WITH bias; no BN, no activation, no l2 - the gathered GEMM of KWS_NET_CONV_1D_FAST, its
+ *                         bias added on load by the first block) -> four grouped reduce (3 groups, stride 2) / context (2 groups) pairs
+ *                         of depthwise-separable blocks, k 3 VALID, l2 1e-5: every group a DepthwiseConv2D((1, 3)) -> Conv1D(F / g, 1)
+ *                         -> BatchNormalization -> relu6 of its own (kws_gdwconv_* for all groups' depthwise halves, kws_gconv_* with
+ *                         k = 1 for the pointwise ones).  Reduce groups read slices of (480, 300 of 420, 360, 300) / 3 channels; the
+ *                         context groups each read ALL channels (the reference hands them x, not the slice).  Filters 420, 420, 360,
+ *                         360, 300, 300, 240, 240 -> Flatten -> Dropout(.05) -> Dense + softmax, categorical CE.  The front bias stands
+ *                         in front of block 1's BatchNormalization on batch statistics (depthwise and 1x1 keep a constant a constant):
+ *                         it cancels in a training step and its gradient is written as exact 0.  Debug views: what 0,
+ *                         index 0 = the front output WITHOUT its bias [B, rows, 480], index i >= 1 = block i's pre-BN output; what 1,
+ *                         index i >= 1 = block i's depthwise output [B, Lout, g * gs]; what 2, index j = the table of
+ *                         batch_normalization_{j+1} (4 * Ng floats).
  * The net handle holds only the host-side layer table.  Parameters live in ONE flat f32 buffer
  * (trainable, Keras layer order) + one flat state buffer (BN moving mean/variance), both owned by
  * the caller; kws_net_tensor_info enumerates the Keras-named tensors inside them.
@@ -822,6 +880,7 @@ int kws_l2_loss(const float* p, const float* l2, int64_t n, float* out, void* st
 #define KWS_NET_CONV_2D_FAST 16
 #define KWS_NET_CONV_1D_TIME_SLICED 17
 #define KWS_NET_CONV_1D_LEARNED_SPEC 18
+#define KWS_NET_CONV_1D_TOP_DOWN 19
 typedef struct kws_net kws_net_t;
 typedef struct {
   int kind;

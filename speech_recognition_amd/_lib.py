@@ -30,6 +30,7 @@ KWS_NET_CONV_2D_MOBILE = 15
 KWS_NET_CONV_2D_FAST = 16
 KWS_NET_CONV_1D_TIME_SLICED = 17
 KWS_NET_CONV_1D_LEARNED_SPEC = 18
+KWS_NET_CONV_1D_TOP_DOWN = 19
 
 
 class KwsError(RuntimeError):
@@ -47,6 +48,18 @@ class GconvDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("C", ctypes.c_int), ("Lout", ctypes.c_int),
                 ("k", ctypes.c_int), ("stride", ctypes.c_int), ("g", ctypes.c_int), ("gs", ctypes.c_int),
                 ("Ng", ctypes.c_int), ("w_group_stride", ctypes.c_int64)]
+
+
+class GdwconvDesc(ctypes.Structure):
+    """kws_gdwconv_t: grouped depthwise Conv1D from the channel windows [x0 + q * x_step, + gs) of [B, L, C] to [B, Lout, g * gs];
+    act (GDW_ACT_*) is what a value goes through on load."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "C", "Lout", "k", "stride", "g", "gs", "x0", "x_step", "act", "bn_group")] + \
+               [("w_group_stride", ctypes.c_int64)]
+
+
+GDW_ACT_NONE = 0       # include/kws_hip.h: KWS_GDW_ACT_*
+GDW_ACT_BN_RELU6 = 1
+GDW_ACT_BIAS = 2
 
 
 class Conv1dDesc(ctypes.Structure):
@@ -183,6 +196,10 @@ SIGNATURES = {
     "kws_gconv_dgrad_f32": (_I, [_P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
     "kws_gconv_wgrad_workspace_floats": (_I64, [ctypes.POINTER(GconvDesc)]),
     "kws_gconv_wgrad_f32": (_I, [_P, _P, _I, _P, _P, _P, ctypes.POINTER(GconvDesc), _P]),
+    "kws_gdwconv_fwd_f32": (_I, [_P, _P, _P, _P, ctypes.POINTER(GdwconvDesc), _P]),
+    "kws_gdwconv_bwd_part_rows": (_I, [ctypes.POINTER(GdwconvDesc)]),
+    "kws_gdwconv_bwd_workspace_floats": (_I64, [ctypes.POINTER(GdwconvDesc)]),
+    "kws_gdwconv_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(GdwconvDesc), _P]),
     "kws_pool3s2_out_len": (_I, [_I]),
     "kws_pool3s2_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "kws_pool3s2_bwd_part_rows": (_I, [_I, _I, _I]),

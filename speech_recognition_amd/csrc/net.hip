@@ -525,7 +525,8 @@ int kws_net_create(const kws_net_config_t* cfg, kws_net_t** out) {
     case KWS_NET_CONV_1D_SPEC:
     case KWS_NET_CONV_1D_TIME_STACKED:
     case KWS_NET_CONV_1D_HEAVY:
-    case KWS_NET_CONV_1D_LEARNED_SPEC: rc = gc_build(n); break;
+    case KWS_NET_CONV_1D_LEARNED_SPEC:
+    case KWS_NET_CONV_1D_TOP_DOWN: rc = gc_build(n); break;
     case KWS_NET_CONV_1D_GRU:
     case KWS_NET_CONV_1D_SIMPLE: rc = dk_build(n); break;
     case KWS_NET_XCEPTION_ATTENTION: rc = xception_build(n); break;

@@ -29,7 +29,18 @@
 //                         300-channel tensor in two, so its groups read 180 and 120 channels (Keras clips the slice): a RAGGED
 //                         block, run as two kws_conv1d_* column-window convolutions over the producer's table repacked from the
 //                         grouped layout [g][4][Ng] to the flat [4][C] one those kernels index.
+//   KWS_NET_CONV_1D_TOP_DOWN  conv_1d_top_down_model (model.py:1326-1397): raw waveform -> Conv1D(480, 479, strides=160, VALID, WITH
+//                         bias; no BN, no activation) -> four reduce (g 3, stride 2) / context (g 2) pairs whose groups are
+//                         depthwise-separable blocks (DepthwiseConv2D((1, 3)) -> Conv1D(F / g, 1) -> BatchNormalization -> relu6, l2
+//                         1e-5) -> Flatten -> Dropout(.05) -> Dense + softmax; RMSprop(3e-3).  Its own program (TdProgram, below): a
+//                         block is one kws_gdwconv_fwd_f32 launch for all groups' depthwise halves (the front bias or the producer's
+//                         table applied on load; the context groups all read the whole input), one kws_gconv_fwd_f32 with k = 1 over
+//                         its output and the grouped BN finalise.  The front bias is a per-channel constant in front of block 1's
+//                         BatchNormalization on batch statistics (depthwise and 1x1 keep it one), so it cancels in a training step:
+//                         its gradient is written as exact 0, as the Conv2D program does for its biases in front of a BatchNorm.
 #include "net_internal.h"
+
+int td_build(kws_net* n);
 
 namespace {
 
@@ -358,6 +369,7 @@ kws_flat_tail_args tail_args(const GcProgram& p, const GcLayout& lo, const float
 
 int gc_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
+  if (c.kind == KWS_NET_CONV_1D_TOP_DOWN) return td_build(n);
   GcProgram* p = new GcProgram();
   n->program.reset(p);
   p->NC = c.num_classes;
@@ -567,3 +579,313 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
 }
 
 }  // namespace
+
+// ---- conv_1d_top_down ---------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr float TD_DROP_KEEP = 0.95f;   // Dropout(0.05), model.py:1389
+
+struct TdBlock {
+  kws_gdwconv_t dw;          // B, act and bn_group filled in per call
+  kws_gconv_t pw;            // the g Conv1D(Ng, 1) layers over the depthwise output [B, Lout, g * gs]; B filled in per call
+  int F;
+  int64_t dw0, pw0;          // group 0's depthwise / pointwise kernel (params); group q's at + q * pstride
+  int64_t gamma0, beta_off, mm0, mv_off, pstride, sstride;
+  int bn_idx0;
+};
+
+struct TdProgram : NetProgram {
+  int64_t conv0 = 0, bias0 = 0;
+  int K0 = 479, K0p = 480, L0 = 0, C0 = 480;
+  kws_gather_t g0{};
+  std::vector<TdBlock> blocks;
+  int64_t dk = 0, db = 0;
+  int D = 0, NC = 0;
+
+  int64_t workspace_bytes(int B, int training) const override;
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override;
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
+};
+
+// _grouped_reduce_conv (shared = false: group q reads the slice [q * nch / g, + nch / g)) or _grouped_context_conv (shared: every
+// group reads all C channels) of F filters; the layers of a group in the reference's order: depthwise, pointwise, BatchNorm
+int td_add_block(KerasNames& kn, TdProgram* p, int L, int C, int F, int g, int num_channels, int stride, bool shared) {
+  KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C && L >= 3, "net: top-down block F=%d g=%d num_channels=%d C=%d L=%d",
+              F, g, num_channels, C, L);
+  TdBlock b;
+  memset(&b, 0, sizeof(b));
+  const int gs = shared ? C : num_channels / g, Ng = F / g;
+  b.dw.L = L; b.dw.C = C; b.dw.k = 3; b.dw.stride = stride; b.dw.g = g; b.dw.gs = gs;
+  b.dw.Lout = (L - 3) / stride + 1;
+  b.dw.x0 = 0; b.dw.x_step = shared ? 0 : gs;
+  b.pw.L = b.dw.Lout; b.pw.Lout = b.dw.Lout; b.pw.C = g * gs; b.pw.k = 1; b.pw.stride = 1; b.pw.g = g; b.pw.gs = gs; b.pw.Ng = Ng;
+  b.F = F;
+  b.bn_idx0 = kn.n_bn;
+  int64_t prev_dw = 0, prev_m = 0;
+  for (int q = 0; q < g; ++q) {
+    const int64_t dw = kn.dwk(3, gs);
+    const int64_t pw = kn.conv(1, gs, Ng, KWS_L2_COEF);
+    const BnRef r = kn.bn(Ng);
+    if (q == 0) {
+      b.dw0 = dw; b.pw0 = pw; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
+    } else {
+      if (q == 1) {
+        b.pstride = dw - prev_dw;
+        b.sstride = r.mm - prev_m;
+      }
+      KWS_REQUIRE(dw - prev_dw == b.pstride && r.mm - prev_m == b.sstride && pw - dw == b.pw0 - b.dw0 && r.gamma - dw == b.gamma0 - b.dw0,
+                  "net: top-down block layout is not uniform");
+    }
+    prev_dw = dw;
+    prev_m = r.mm;
+  }
+  if (g == 1) b.pstride = 0;
+  b.dw.w_group_stride = b.pstride;
+  b.pw.w_group_stride = b.pstride;
+  p->blocks.push_back(b);
+  return KWS_OK;
+}
+
+struct TdLayout {
+  int64_t total = 0;
+  int64_t w0p = 0, y0 = 0;
+  std::vector<int64_t> z, y, bn;
+  int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, dwws = 0, tnws = 0, dw0p = 0;
+  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+};
+
+void td_layout(const TdProgram& p, int B, bool training, TdLayout* lo) {
+  Bump bp;
+  const int nb = (int)p.blocks.size();
+  int64_t max_act = (int64_t)B * p.L0 * p.C0, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64, max_dwws = 64;
+  lo->w0p = bp.take((int64_t)p.K0p * p.C0);
+  lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
+  lo->z.assign(nb, 0);
+  lo->y.assign(nb, 0);
+  lo->bn.assign(nb, 0);
+  for (int i = 0; i < nb; ++i) {
+    const TdBlock& b = p.blocks[i];
+    kws_gdwconv_t dw = b.dw;
+    kws_gconv_t pw = b.pw;
+    dw.B = pw.B = B;
+    const int64_t M = (int64_t)B * pw.Lout;
+    lo->z[i] = bp.take(M * pw.C);
+    lo->y[i] = bp.take(M * b.F);
+    lo->bn[i] = bp.take((int64_t)4 * b.F);
+    max_act = std::max(max_act, std::max(M * pw.C, std::max(M * b.F, (int64_t)B * dw.L * dw.C)));
+    max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&pw) * 2 * b.F);
+    max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * b.F);
+    max_coef = std::max(max_coef, (int64_t)2 * b.F);
+    max_wws = std::max(max_wws, kws_gconv_wgrad_workspace_floats(&pw));
+    max_dwws = std::max(max_dwws, kws_gdwconv_bwd_workspace_floats(&dw));
+  }
+  lo->stats = bp.take(max_stats);
+  if (training) {
+    lo->dA[0] = bp.take(max_act);
+    lo->dA[1] = bp.take(max_act);
+    lo->part = bp.take(max_part);
+    lo->coef = bp.take(max_coef);
+    lo->wws = bp.take(max_wws);
+    lo->dwws = bp.take(max_dwws);
+    lo->tnws = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * p.L0, p.K0p, p.C0));
+    lo->dw0p = bp.take((int64_t)p.K0p * p.C0);
+    lo->fd = bp.take((int64_t)B * p.D);
+    lo->dl = bp.take((int64_t)B * p.NC);
+    lo->per_loss = bp.take(B);
+    lo->per_correct = bp.take(B);
+    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.D * p.NC);
+  }
+  lo->total = bp.cur * 4;
+}
+
+kws_gbn_refs td_refs(const TdBlock& b, const float* params, float* state) {
+  kws_gbn_refs r;
+  r.gamma = params + b.gamma0; r.pstride = b.pstride; r.boff = b.beta_off;
+  r.mm = state ? state + b.mm0 : nullptr; r.sstride = b.sstride; r.voff = b.mv_off;
+  return r;
+}
+
+// block i's depthwise descriptor with what it reads: the front output + its bias, or the producer's raw output through its table
+struct TdInput {
+  kws_gdwconv_t d;
+  const float* in;
+  const float* tab;
+};
+TdInput td_input(const TdProgram& p, const TdLayout& lo, int i, const float* params, const float* ws, int B) {
+  TdInput r;
+  r.d = p.blocks[i].dw;
+  r.d.B = B;
+  if (i == 0) {
+    r.d.act = KWS_GDW_ACT_BIAS;
+    r.in = ws + lo.y0;
+    r.tab = params + p.bias0;
+  } else {
+    r.d.act = KWS_GDW_ACT_BN_RELU6;
+    r.d.bn_group = p.blocks[i - 1].pw.Ng;
+    r.in = ws + lo.y[i - 1];
+    r.tab = ws + lo.bn[i - 1];
+  }
+  return r;
+}
+
+int td_forward(const TdProgram& p, const TdLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
+               hipStream_t st) {
+  KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
+  KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
+  KWS_TRY(kws_gemm_gather_f32(x, &p.g0, ws + lo.w0p, ws + lo.y0, B, p.C0, nullptr, st));
+  for (size_t i = 0; i < p.blocks.size(); ++i) {
+    const TdBlock& b = p.blocks[i];
+    const TdInput in = td_input(p, lo, (int)i, params, ws, B);
+    kws_gconv_t pw = b.pw;
+    pw.B = B;
+    const kws_gbn_refs r = td_refs(b, params, state);
+    const kws_gbn_cols cols = kws_gbn_grouped(pw.g, pw.Ng);
+    KWS_TRY(kws_gdwconv_fwd_f32(in.in, in.tab, params + b.dw0, ws + lo.z[i], &in.d, st));
+    KWS_TRY(kws_gconv_fwd_f32(ws + lo.z[i], nullptr, 0, params + b.pw0, ws + lo.y[i], training ? ws + lo.stats : nullptr, &pw, st));
+    if (training)
+      KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&pw), (int64_t)B * pw.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
+                               ws + lo.bn[i], st));
+    else
+      KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, ws + lo.bn[i], st));
+  }
+  return KWS_OK;
+}
+
+kws_flat_tail_args td_tail_args(const TdProgram& p, const TdLayout& lo, const float* params, float* ws, int B, float* probs) {
+  const TdBlock& last = p.blocks.back();
+  kws_flat_tail_args t;
+  memset(&t, 0, sizeof(t));
+  t.y = ws + lo.y.back(); t.bn = ws + lo.bn.back(); t.Ng = last.pw.Ng;
+  t.Wd = params + p.dk; t.bd = params + p.db;
+  t.probs = probs;
+  t.B = B; t.D = p.D; t.F = last.F; t.NC = p.NC;
+  t.keep_prob = TD_DROP_KEEP;
+  t.layer_id = 1;
+  return t;
+}
+
+int64_t TdProgram::workspace_bytes(int B, int training) const {
+  TdLayout lo;
+  td_layout(*this, B, training != 0, &lo);
+  return lo.total;
+}
+
+int TdProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
+  TdLayout lo;
+  td_layout(*this, B, training != 0, &lo);
+  const int nb = (int)blocks.size();
+  if (what == 0) {   // index 0: the front convolution's output (its bias not added); i >= 1: block i's pre-BN output
+    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: y index %d", index);
+    if (index == 0) {
+      *offset_floats = lo.y0;
+      *count = (int64_t)B * L0 * C0;
+    } else {
+      *offset_floats = lo.y[index - 1];
+      *count = (int64_t)B * blocks[index - 1].pw.Lout * blocks[index - 1].F;
+    }
+  } else if (what == 1) {   // block i's depthwise output
+    KWS_REQUIRE(index >= 1 && index <= nb, "net_debug_view: z index %d", index);
+    *offset_floats = lo.z[index - 1];
+    *count = (int64_t)B * blocks[index - 1].pw.Lout * blocks[index - 1].pw.C;
+  } else if (what == 2) {   // table of batch_normalization_{index+1}
+    for (int i = 0; i < nb; ++i) {
+      const TdBlock& b = blocks[i];
+      if (index >= b.bn_idx0 && index < b.bn_idx0 + b.pw.g) {
+        *offset_floats = lo.bn[i] + (int64_t)(index - b.bn_idx0) * 4 * b.pw.Ng;
+        *count = 4 * b.pw.Ng;
+        return KWS_OK;
+      }
+    }
+    kws_set_error("net_debug_view: bn index %d", index);
+    return KWS_E_INVALID;
+  } else {
+    kws_set_error("net_debug_view: unknown view %d", what);
+    return KWS_E_INVALID;
+  }
+  return KWS_OK;
+}
+
+int TdProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+                       hipStream_t st) const {
+  TdLayout lo;
+  td_layout(*this, B, false, &lo);
+  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+  KWS_TRY(td_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, st));
+  kws_flat_tail_args t = td_tail_args(*this, lo, params, ws, B, probs);
+  return kws_flat_tail_launch(&t, 0, st);
+}
+
+int TdProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
+                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
+                     hipStream_t st) const {
+  const TdProgram& p = *this;
+  TdLayout lo;
+  td_layout(p, B, true, &lo);
+  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  KWS_TRY(td_forward(p, lo, params, state, x, B, true, ws, st));
+  int cur = 0;
+  kws_flat_tail_args t = td_tail_args(p, lo, params, ws, B, probs);
+  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.dA[cur], ws + lo.per_loss, ws + lo.per_correct, seed, step,
+                              loss_batch, row_offset, metrics, st));
+  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.D, p.NC, ws + lo.swg, st));
+  for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
+    const TdBlock& b = p.blocks[i];
+    kws_gconv_t pw = b.pw;
+    pw.B = B;
+    const int64_t M = (int64_t)B * pw.Lout;
+    const kws_gbn_cols cols = kws_gbn_grouped(pw.g, pw.Ng);
+    // dA[cur]: gradient wrt the block's activated output -> dy (gate + BatchNorm backward) -> the pointwise kernels' gradients and
+    // dz -> the depthwise kernels' gradients and the gradient wrt the block's activated input
+    KWS_TRY(kws_gbn_bwd(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], nullptr, M, &cols, ws + lo.part, ws + lo.coef, grads + b.gamma0,
+                        b.pstride, b.beta_off, st));
+    KWS_TRY(kws_gconv_wgrad_f32(ws + lo.z[i], nullptr, 0, ws + lo.dA[cur], grads + b.pw0, ws + lo.wws, &pw, st));
+    KWS_TRY(kws_gconv_dgrad_f32(ws + lo.dA[cur], params + b.pw0, ws + lo.dA[cur ^ 1], &pw, st));
+    cur ^= 1;
+    const TdInput in = td_input(p, lo, i, params, ws, B);
+    KWS_TRY(kws_gdwconv_bwd_f32(in.in, in.tab, ws + lo.dA[cur], params + b.dw0, ws + lo.dA[cur ^ 1], grads + b.dw0,
+                                nullptr, ws + lo.dwws, &in.d, st));
+    cur ^= 1;
+  }
+  // the front bias cancels in block 1's BatchNorm on batch statistics: its gradient is exactly 0, not the float32 residue (1e-5)
+  // that the column sum of dA[cur] would leave
+  KWS_HIP(hipMemsetAsync(grads + p.bias0, 0, sizeof(float) * p.C0, st));
+  // dA[cur] = gradient wrt the front convolution's output
+  KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, ws + lo.dA[cur], ws + lo.dw0p, B, p.C0, ws + lo.tnws, st));
+  KWS_HIP(hipMemcpyAsync(grads + p.conv0, ws + lo.dw0p, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
+  return KWS_OK;
+}
+
+}  // namespace
+
+int td_build(kws_net* n) {
+  const kws_net_config_t& c = n->cfg;
+  TdProgram* p = new TdProgram();
+  n->program.reset(p);
+  p->NC = c.num_classes;
+  // the ladder's lengths are 45, 43, 21, 19, 9, 7, 3, 1 at 91 rows, the fewest that leave one: 14879 samples.  The gathered GEMM
+  // loads pairs of samples, so clips must start on even offsets (conv_1d_fast's rule): the first size it takes is 14880
+  KWS_REQUIRE(c.input_size >= 14879 && c.input_size % 2 == 0,
+              "net: conv_1d_top_down input_size %d (even, >= 14879: the ladder needs 91 rows of 160 samples)", c.input_size);
+  KerasNames kn{n};
+  p->L0 = (c.input_size - p->K0) / 160 + 1;
+  p->conv0 = kn.conv(p->K0, 1, p->C0, 0.f);
+  p->bias0 = kws_net_add_tensor(n, "conv1d_1/bias", {p->C0}, false, 0.f, 0, 0, 0.f);
+  p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
+  p->g0.x_len = c.input_size; p->g0.x_batch_stride = c.input_size;
+  struct { int F, g, nch, stride; } spec[8] = {{420, 3, 480, 2}, {420, 2, 420, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
+                                               {300, 3, 360, 2}, {300, 2, 300, 1}, {240, 3, 300, 2}, {240, 2, 240, 1}};
+  int L = p->L0, C = p->C0;
+  for (int i = 0; i < 8; ++i) {
+    KWS_TRY(td_add_block(kn, p, L, C, spec[i].F, spec[i].g, spec[i].nch, spec[i].stride, spec[i].stride == 1));
+    L = p->blocks.back().dw.Lout;
+    C = p->blocks.back().F;
+  }
+  const TdBlock& last = p->blocks.back();
+  p->D = last.dw.Lout * last.F;
+  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->D, p->NC}, false, 0.f, p->D, p->NC, 0.f);
+  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  return KWS_OK;
+}

@@ -4,7 +4,7 @@
 //   net.hip          conv_1d_time_sliced_with_attention
 //   net_logmfcc.hip  the residual-block family: conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual,
 //                    conv_1d_mfcc_and_raw, xception_with_attention
-//   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy, conv_1d_learned_spec
+//   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy, conv_1d_learned_spec, conv_1d_top_down
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_time_sliced.hip  conv_1d_time_sliced
 //   net_dw3ladder.hip  no builder of its own: the 3-tap depthwise ladder (Dw3Ladder) under net.hip and net_time_sliced.hip

@@ -9,7 +9,7 @@ from .net import DeviceNet
 
 ACCELERATED = ('conv_1d_time_sliced_with_attention', 'conv_1d_log_mfcc', 'conv_1d_spectrogram', 'steffeNet', 'conv_1d_residual', 'conv_1d_mfcc_and_raw',
                'conv_1d_fast', 'conv_1d_spec', 'conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_gru', 'conv_1d_multi_time_sliced', 'conv_1d_simple',
-               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast', 'conv_1d_time_sliced', 'conv_1d_learned_spec')
+               'xception_with_attention', 'inception_d1', 'conv_2d_mobile', 'conv_2d_fast', 'conv_1d_time_sliced', 'conv_1d_learned_spec', 'conv_1d_top_down')
 REFERENCE_MODEL_TYPES = (
     'simple', 'snn', 'conv_1d_time_stacked', 'conv_1d_multi_time_sliced', 'conv_1d_time_sliced',
     'conv_1d_time_sliced_group', 'conv_1d_heavy', 'conv_1d_simple', 'conv_1d_gru', 'conv_2d', 'conv_2d_fast',
@@ -164,6 +164,17 @@ def conv_1d_learned_spec_model(input_size=16000, num_classes=11, *args, **kwargs
     return Model(net, RMSprop(lr=2e-3), name='conv_1d_learned_spec', loss='cce')
 
 
+def conv_1d_top_down_model(input_size=16000, num_classes=11, *args, **kwargs):
+    """reference model.py:1326-1397: raw waveform -> Conv1D(480, 479, strides=160, with bias; no BN, no activation) -> four grouped
+    reduce (stride 2, 3 groups over slices of 480, 300 of 420, 360 and 300 channels) / context (2 groups, EACH reading all channels:
+    the reference hands them x, not the slice) pairs of 420, 360, 300, 240 filters, k 3 VALID, every group its own DepthwiseConv2D
+    -> Conv1D(F / g, 1) -> BatchNormalization -> relu6 with l2 1e-5 (the depthwise halves of a block one kws_gdwconv_* launch,
+    csrc/gdwconv.hip) -> Flatten -> Dropout(.05) -> Dense; RMSprop(3e-3), categorical CE.  input_size: any even size of at least
+    14879 samples (91 rows), so 14880 is the first."""
+    net = DeviceNet(_lib.KWS_NET_CONV_1D_TOP_DOWN, num_classes, input_size=input_size)
+    return Model(net, RMSprop(lr=3e-3), name='conv_1d_top_down', loss='cce')
+
+
 def conv_1d_spec_model(input_size=16000, num_classes=11, *args, **kwargs):
     """reference model.py:1249-1323: the generator's 'spec' output as [98, 257] (the reference fixes Input(shape=[98 * 257])
     and ignores input_size) -> four grouped reduce (k 3, stride 2, 4 groups) / context (k 3, 3 groups) pairs of 300 ... 480
@@ -289,6 +300,8 @@ def speech_model(model_type, input_size, num_classes=11, *args, **kwargs):
         return conv_1d_spec_model(input_size, num_classes)
     if model_type == 'conv_1d_learned_spec':
         return conv_1d_learned_spec_model(input_size, num_classes)
+    if model_type == 'conv_1d_top_down':
+        return conv_1d_top_down_model(input_size, num_classes)
     if model_type == 'conv_1d_time_stacked':
         return conv_1d_time_stacked_model(input_size, num_classes)
     if model_type == 'conv_1d_heavy':
