@@ -8,7 +8,9 @@ GEMM modes 0, 1 and 2 (modes 0 and 1 also as the split step at blocks 1 and 6, w
 and conv_1d_time_sliced under modes 0 and 1.
 --set pools: the six models that run the pooling kernels with [2][C] partial rows (csrc/part_rows.h): pool.hip's four, conv_2d_fast
 for pool2d.hip and conv_1d_time_sliced for gap.hip.
-usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder|pools] [--out FILE]"""
+--set flat_tail: the twelve configs of the five programs on the flat-tail skeleton (FlatTailProgram, csrc/net_internal.h): the eight
+models above, conv_1d_learned_spec, conv_1d_top_down and conv_1d_time_sliced at filter_mult 1 / 16000 and filter_mult 2 / 12000.
+usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder|pools|flat_tail] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -43,6 +45,12 @@ POOL_NAMES = ('conv_1d_time_stacked', 'conv_1d_heavy', 'conv_1d_multi_time_slice
 POOLS = [m + (1,) for m in MODELS if m[0] in POOL_NAMES] + [  # (name, kind, input_size, filter_mult)
     ('conv_2d_fast', _lib.KWS_NET_CONV_2D_FAST, 3920, 1),
     ('conv_1d_time_sliced', _lib.KWS_NET_CONV_1D_TIME_SLICED, 16000, 1),
+]
+FLAT_TAIL = [m + (1,) for m in MODELS] + [  # (name, kind, input_size, filter_mult)
+    ('conv_1d_learned_spec', _lib.KWS_NET_CONV_1D_LEARNED_SPEC, 16000, 1),
+    ('conv_1d_top_down', _lib.KWS_NET_CONV_1D_TOP_DOWN, 16000, 1),
+    ('conv_1d_time_sliced_fm1_16000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 16000, 1),
+    ('conv_1d_time_sliced_fm2_12000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 12000, 2),
 ]
 SPLITS = (1, 6)
 NC = 12
@@ -103,14 +111,14 @@ def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=Fals
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder', 'pools'))
+    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder', 'pools', 'flat_tail'))
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.set == 'ladder':
         res = dict(('%s_mode%d' % (name, m), model_digests(name, kind, size, fm, m, split and m != 2))
                    for name, kind, fm, size, modes, split in LADDER for m in modes)
-    elif a.set == 'pools':
-        res = dict((name, model_digests(name, kind, size, fm)) for name, kind, size, fm in POOLS)
+    elif a.set in ('pools', 'flat_tail'):
+        res = dict((name, model_digests(name, kind, size, fm)) for name, kind, size, fm in (POOLS if a.set == 'pools' else FLAT_TAIL))
     else:
         res = dict((name, model_digests(name, kind, size)) for name, kind, size in MODELS)
     text = json.dumps(res, indent=1, sort_keys=True)

@@ -18,23 +18,32 @@
 
 namespace {
 
-struct DkProgram : NetProgram {
-  const kws_net* net = nullptr;
+struct DkLayout {
+  int64_t total = 0;
+  std::vector<int64_t> z, y, bn;
+  int64_t stats = 0, red = 0, fa = 0, fd1 = 0, h = 0, tab = 0;
+  int64_t G[2] = {0, 0}, DZ = 0, part = 0, coef = 0, tn = 0, WT = 0, pw1ws = 0;
+  FlatTailWs tail;
+  int64_t bpart = 0;
+  int64_t gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;   // KWS_NET_CONV_1D_SIMPLE
+};
+
+struct DkProgram : FlatTailProgram<DkLayout> {
   std::vector<SepBlock> blocks;
-  int NC = 0, D = 0, H = 0;          // features into the head, hidden width
-  int64_t d1k = 0, d1b = -1, d2k = 0, d2b = 0;
+  int D = 0, H = 0;                  // features into the head, hidden width
+  int64_t d1k = 0, d1b = -1;
   float keep = 0.7f;
   // KWS_NET_CONV_1D_SIMPLE: the ladder ends in gT steps of D channels, a bidirectional GRU of gH units follows (H = 0: no hidden Dense)
   bool gru = false;
   int gT = 0, gH = 0;
   int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
 
-  int64_t workspace_bytes(int B, int training) const override;
+  void layout(int B, bool training, DkLayout* lo) const override;
+  int forward(const DkLayout& lo, const NetCall& c) const override;
+  kws_flat_tail_args tail_args(const DkLayout& lo, const NetCall& c, float* probs) const override;
+  int64_t tail_grad(const DkLayout& lo) const override { return gru ? lo.gdout : lo.G[0]; }
+  int backward(const DkLayout& lo, const NetCall& c) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
 
 constexpr float DK_DROP_KEEP = 0.7f;   // Dropout(0.3), model.py:502, 504
@@ -104,18 +113,18 @@ int dk_bias_relu6_bwd(float* d, const float* h, const float* bias, float* dbias,
   return KWS_OK;
 }
 
+int dk_dense_bwd(float* d, const float* h, const float* in, const float* W, const float* bias, float* dW, float* dbias, float* out, int B,
+                 int D, int H, const DkDenseBwdScratch& s, hipStream_t st) {
+  KWS_TRY(dk_bias_relu6_bwd(d, h, bias, dbias, B, H, s.part, st));
+  KWS_TRY(kws_gemm_tn_f32(in, d, dW, B, D, H, s.tn, st));
+  KWS_TRY(kws_transpose_f32(W, s.WT, D, H, st));
+  return kws_gemm_nn_f32(d, s.WT, out, B, H, D, nullptr, st);
+}
+
 namespace {
 
-struct DkLayout {
-  int64_t total = 0;
-  std::vector<int64_t> z, y, bn;
-  int64_t stats = 0, red = 0, fa = 0, fd1 = 0, h = 0, tab = 0;
-  int64_t G[2] = {0, 0}, DZ = 0, part = 0, coef = 0, tn = 0, WT = 0, pw1ws = 0;
-  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0, bpart = 0;
-  int64_t gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;   // KWS_NET_CONV_1D_SIMPLE
-};
-
-void dk_layout(const DkProgram& p, int B, bool training, DkLayout* lo) {
+void DkProgram::layout(int B, bool training, DkLayout* lo) const {
+  const DkProgram& p = *this;
   Bump bp;
   const int nb = (int)p.blocks.size();
   int64_t max_y = 64, max_z = 64, max_stats = 64, max_part = 64, max_tn = 64, max_w = 64;
@@ -160,11 +169,7 @@ void dk_layout(const DkProgram& p, int B, bool training, DkLayout* lo) {
       lo->tn = bp.take(max_tn);
       lo->WT = bp.take(max_w);
       lo->pw1ws = bp.take(kws_dwconvk_pw1_bwd_workspace_floats((int64_t)B * p.blocks[0].Lout, p.blocks[0].cout));
-      lo->fd = bp.take((int64_t)B * 2 * H);
-      lo->dl = bp.take((int64_t)B * p.NC);
-      lo->per_loss = bp.take(B);
-      lo->per_correct = bp.take(B);
-      lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * 2 * H * p.NC);
+      lo->tail.take(bp, B, dense.D, dense.NC);
     }
     lo->total = bp.cur * 4;
     return;
@@ -188,19 +193,22 @@ void dk_layout(const DkProgram& p, int B, bool training, DkLayout* lo) {
     lo->tn = bp.take(max_tn);
     lo->WT = bp.take(max_w);
     lo->pw1ws = bp.take(kws_dwconvk_pw1_bwd_workspace_floats((int64_t)B * p.blocks[0].Lout, p.blocks[0].cout));
-    lo->fd = bp.take((int64_t)B * p.H);
-    lo->dl = bp.take((int64_t)B * p.NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.H * p.NC);
+    lo->tail.take(bp, B, dense.D, dense.NC);
     lo->bpart = bp.take((int64_t)DK_BIAS_SLICES * p.H);
   }
   lo->total = bp.cur * 4;
 }
 
 // forward through the blocks and the hidden Dense product; training: batch statistics (moving averages updated) and dropout
-int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-               uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
+int DkProgram::forward(const DkLayout& lo, const NetCall& c) const {
+  const DkProgram& p = *this;
+  const float* params = c.params;
+  float* state = c.state;
+  const float* x = c.x;
+  float* ws = c.ws;
+  const int B = c.B;
+  const bool training = c.training;
+  hipStream_t st = c.st;
   const int nb = (int)p.blocks.size();
   for (int i = 0; i < nb; ++i) {
     const SepBlock& b = p.blocks[i];
@@ -222,7 +230,7 @@ int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, floa
   if (p.gru) {   // the activated ladder output [B, T, I] is materialised for the GRU's GEMMs; masks only in training
     const int T = p.gT, I = p.D, H = p.gH;
     KWS_TRY(kws_bn_relu6_apply(ws + lo.y[nb - 1], ws + lo.bn[nb - 1], ws + lo.fa, (int64_t)B * T, I, 1, st));
-    if (training) KWS_TRY(kws_gru_masks(ws + lo.gmx, ws + lo.gmh, B, I, H, DK_GRU_KEEP, seed, step, row_offset, st));
+    if (training) KWS_TRY(kws_gru_masks(ws + lo.gmx, ws + lo.gmh, B, I, H, DK_GRU_KEEP, c.seed, c.step, c.row_offset, st));
     return kws_gru_fwd_f32(ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gb[0], params + p.gW[1], params + p.gU[1],
                            params + p.gb[1], training ? ws + lo.gmx : nullptr, training ? ws + lo.gmh : nullptr, ws + lo.gout,
                            training ? ws + lo.gsave : nullptr, ws + lo.gws, B, T, I, H, st);
@@ -231,7 +239,7 @@ int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, floa
   KWS_TRY(kws_bn_relu6_apply(ws + lo.y[nb - 1], ws + lo.bn[nb - 1], ws + lo.fa, B, p.D, 1, st));
   const float* feat = ws + lo.fa;
   if (training) {
-    KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.D, p.keep, seed, step, 1, row_offset, st));
+    KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.D, p.keep, c.seed, c.step, 1, c.row_offset, st));
     feat = ws + lo.fd1;
   }
   KWS_TRY(kws_gemm_nn_f32(feat, params + p.d1k, ws + lo.h, B, p.D, p.H, nullptr, st));
@@ -239,21 +247,20 @@ int dk_forward(const DkProgram& p, const DkLayout& lo, const float* params, floa
 }
 
 // bias + relu6 + Dropout (layer 2) of the hidden layer, Dense + softmax (+ loss and its backward): the flat tail over (h, table)
-kws_flat_tail_args dk_tail_args(const DkProgram& p, const DkLayout& lo, const float* params, float* ws, int B, float* probs) {
+kws_flat_tail_args DkProgram::tail_args(const DkLayout& lo, const NetCall& c, float* probs) const {
+  const DkProgram& p = *this;
+  float* ws = c.ws;
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
+  t.Wd = c.params + dense.kernel; t.bd = c.params + dense.bias;
+  t.probs = probs;
+  t.B = c.B; t.D = dense.D; t.F = dense.D; t.NC = dense.NC; t.Ng = dense.D;
   if (p.gru) {   // Dense + softmax over the signed GRU output: the raw arm
-    t.y = ws + lo.gout; t.Ng = 2 * p.gH; t.raw = 1;
-    t.Wd = params + p.d2k; t.bd = params + p.d2b;
-    t.probs = probs;
-    t.B = B; t.D = 2 * p.gH; t.F = 2 * p.gH; t.NC = p.NC;
+    t.y = ws + lo.gout; t.raw = 1;
     t.keep_prob = 1.f;
     return t;
   }
-  t.y = ws + lo.h; t.bn = ws + lo.tab; t.Ng = p.H;
-  t.Wd = params + p.d2k; t.bd = params + p.d2b;
-  t.probs = probs;
-  t.B = B; t.D = p.H; t.F = p.H; t.NC = p.NC;
+  t.y = ws + lo.h; t.bn = ws + lo.tab;
   t.keep_prob = p.keep;
   t.layer_id = 2;
   return t;
@@ -268,7 +275,8 @@ int dk_build_simple(kws_net* n) {
   DkProgram* p = new DkProgram();
   n->program.reset(p);
   p->net = n;
-  p->NC = c.num_classes;
+  p->dense.NC = c.num_classes;
+  p->zero_grads = true;   // the padding behind a tensor of 63 taps stays zero
   p->gru = true;
   KerasNames kn{n};
   int L = c.input_size, cin = 1;
@@ -296,8 +304,9 @@ int dk_build_simple(kws_net* n) {
     p->gU[d] = kws_net_add_tensor(n, base + "recurrent_kernel", {H, 3 * H}, false, 0.f, 0, 0, 0.f);
     p->gb[d] = kws_net_add_tensor(n, base + "bias", {3 * H}, false, 0.f, 0, 0, 0.f);
   }
-  p->d2k = kws_net_add_tensor(n, "dense_1/kernel", {2 * H, p->NC}, false, 0.f, 2 * H, p->NC, 0.f);
-  p->d2b = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->dense.D = 2 * H;
+  p->dense.kernel = kws_net_add_tensor(n, "dense_1/kernel", {2 * H, c.num_classes}, false, 0.f, 2 * H, c.num_classes, 0.f);
+  p->dense.bias = kws_net_add_tensor(n, "dense_1/bias", {c.num_classes}, false, 0.f, 0, 0, 0.f);
   return KWS_OK;
 }
 
@@ -311,7 +320,8 @@ int dk_build(kws_net* n) {
   DkProgram* p = new DkProgram();
   n->program.reset(p);
   p->net = n;
-  p->NC = c.num_classes;
+  p->dense.NC = c.num_classes;
+  p->zero_grads = true;   // the padding behind a tensor of 63 taps stays zero
   p->keep = DK_DROP_KEEP;
   KerasNames kn{n};
   // _reduce_conv(x, F, k, strides) padding='same' x 5, _context_conv(x, 512, 8) padding='valid' (model.py:495-500)
@@ -340,23 +350,18 @@ int dk_build(kws_net* n) {
   p->H = DK_HIDDEN;
   p->d1k = kws_net_add_tensor(n, "dense_1/kernel", {p->D, p->H}, false, 0.f, p->D, p->H, 0.f);
   p->d1b = kws_net_add_tensor(n, "dense_1/bias", {p->H}, false, 0.f, 0, 0, 0.f);
-  p->d2k = kws_net_add_tensor(n, "dense_2/kernel", {p->H, p->NC}, false, 0.f, p->H, p->NC, 0.f);
-  p->d2b = kws_net_add_tensor(n, "dense_2/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->dense.D = p->H;
+  p->dense.kernel = kws_net_add_tensor(n, "dense_2/kernel", {p->H, c.num_classes}, false, 0.f, p->H, c.num_classes, 0.f);
+  p->dense.bias = kws_net_add_tensor(n, "dense_2/bias", {c.num_classes}, false, 0.f, 0, 0, 0.f);
   return KWS_OK;
 }
 
 namespace {
 
-int64_t DkProgram::workspace_bytes(int B, int training) const {
-  DkLayout lo;
-  dk_layout(*this, B, training != 0, &lo);
-  return lo.total;
-}
-
 int DkProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   const DkProgram& p = *this;
   DkLayout lo;
-  dk_layout(p, B, training != 0, &lo);
+  layout(B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
   if (p.gru && what == 5) {   // the GRU's saved steps [2][4: z, r, c, h][B, T, H] (training)
     KWS_REQUIRE(training, "net_debug_view: view 5 exists in training only");
@@ -392,53 +397,34 @@ int DkProgram::debug_view(int B, int training, int what, int index, int64_t* off
   return KWS_OK;
 }
 
-int DkProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                       hipStream_t st) const {
-  DkLayout lo;
-  dk_layout(*this, B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(dk_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = dk_tail_args(*this, lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int DkProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                     hipStream_t st) const {
+// everything behind the Dense + softmax layer's weight gradient: the GRU or the hidden Dense layer, then the blocks
+int DkProgram::backward(const DkLayout& lo, const NetCall& c) const {
   const DkProgram& p = *this;
-  DkLayout lo;
-  dk_layout(p, B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  const float* params = c.params;
+  const float* x = c.x;
+  float* grads = c.grads;
+  float* ws = c.ws;
+  const int B = c.B;
+  hipStream_t st = c.st;
   const int nb = (int)p.blocks.size();
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));   // the padding behind a tensor of 63 taps stays zero
-  KWS_TRY(dk_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
   const SepBwdScratch scratch = {ws + lo.WT, ws + lo.DZ, ws + lo.tn, part, coef};
-  // ---- head ----
-  kws_flat_tail_args t = dk_tail_args(p, lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, p.gru ? ws + lo.gdout : G[0], ws + lo.per_loss, ws + lo.per_correct,
-                              seed, step, loss_batch, row_offset, metrics, st));
   int cur = 0;   // G[cur] = gradient wrt the activated output of the last block [B, T, D]
   if (p.gru) {
     const int T = p.gT, I = p.D, H = p.gH;
     const SepBlock& b = p.blocks[nb - 1];
-    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, 2 * H, p.NC, ws + lo.swg, st));
     KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.fa, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
                             ws + lo.gmh, ws + lo.gsave, G[0], grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
                             grads + p.gU[1], grads + p.gb[1], ws + lo.gws, B, T, I, H, st));
     KWS_TRY(kws_gbn_layer_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, (int64_t)B * T, kws_gbn_grouped(1, b.cout), part,
                               coef, grads, b.bn, st));
   } else {
-    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.d2k, grads + p.d2b, B, p.H, p.NC, ws + lo.swg, st));
     // G[0] = gradient wrt relu6(h + b1) [B, H] -> wrt h; dense_1's gradients; back through Dropout(.3) onto the activated features
-    KWS_TRY(dk_bias_relu6_bwd(G[0], ws + lo.h, p.d1b >= 0 ? params + p.d1b : nullptr, p.d1b >= 0 ? grads + p.d1b : nullptr, B, p.H,
-                              ws + lo.bpart, st));
-    KWS_TRY(kws_gemm_tn_f32(ws + lo.fd1, G[0], grads + p.d1k, B, p.D, p.H, ws + lo.tn, st));
-    KWS_TRY(kws_transpose_f32(params + p.d1k, ws + lo.WT, p.D, p.H, st));
-    KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WT, G[1], B, p.H, p.D, nullptr, st));
-    KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, seed, step, 1, row_offset, st));
+    KWS_TRY(dk_dense_bwd(G[0], ws + lo.h, ws + lo.fd1, params + p.d1k, p.d1b >= 0 ? params + p.d1b : nullptr, grads + p.d1k,
+                         p.d1b >= 0 ? grads + p.d1b : nullptr, G[1], B, p.D, p.H, {ws + lo.WT, ws + lo.tn, ws + lo.bpart}, st));
+    KWS_TRY(kws_dropout_bwd(G[1], G[0], B, p.D, p.keep, c.seed, c.step, 1, c.row_offset, st));
     const SepBlock& b = p.blocks[nb - 1];
     KWS_TRY(kws_gbn_layer_bwd(G[cur], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, B, kws_gbn_grouped(1, b.cout), part, coef, grads,
                               b.bn, st));

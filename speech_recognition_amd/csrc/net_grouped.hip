@@ -32,15 +32,15 @@
 //   KWS_NET_CONV_1D_TOP_DOWN  conv_1d_top_down_model (model.py:1326-1397): raw waveform -> Conv1D(480, 479, strides=160, VALID, WITH
 //                         bias; no BN, no activation) -> four reduce (g 3, stride 2) / context (g 2) pairs whose groups are
 //                         depthwise-separable blocks (DepthwiseConv2D((1, 3)) -> Conv1D(F / g, 1) -> BatchNormalization -> relu6, l2
-//                         1e-5) -> Flatten -> Dropout(.05) -> Dense + softmax; RMSprop(3e-3).  Its own program (TdProgram, below): a
+//                         1e-5) -> Flatten -> Dropout(.05) -> Dense + softmax; RMSprop(3e-3).  A SEPARABLE block of this program: a
 //                         block is one kws_gdwconv_fwd_f32 launch for all groups' depthwise halves (the front bias or the producer's
 //                         table applied on load; the context groups all read the whole input), one kws_gconv_fwd_f32 with k = 1 over
 //                         its output and the grouped BN finalise.  The front bias is a per-channel constant in front of block 1's
 //                         BatchNormalization on batch statistics (depthwise and 1x1 keep it one), so it cancels in a training step:
 //                         its gradient is written as exact 0, as the Conv2D program does for its biases in front of a BatchNorm.
+// So a block has one of four forms - plain, pooled, ragged, separable - and everything around the blocks (the two 479-tap fronts,
+// the banked front, the tables, the gradient ping-pong, the flat tail through FlatTailProgram) is written once.
 #include "net_internal.h"
-
-int td_build(kws_net* n);
 
 namespace {
 
@@ -57,77 +57,121 @@ struct GcBlock {
   bool ragged;              // two groups of different input widths: rc[q] (B filled in per call), group q's kernel at rw[q]
   kws_conv1d_t rc[2];
   int64_t rw[2];
+  bool sep;                 // a depthwise half (k 3) in front: d is the k = 1 pointwise descriptor over its output [B, Lout, g * gs]
+  bool dw_shared;           // its groups all read the whole input (_grouped_context_conv), else group q the slice [q * gs, + gs)
+  kws_gdwconv_t dw;         // B, act and bn_group filled in per call
+  int64_t dw0;              // group 0's depthwise kernel (params); group q's at + q * pstride
 };
 
-struct GcProgram : NetProgram {
-  bool front = false;       // conv_1d_fast: the 479-tap front convolution
+struct GcLayout {
+  int64_t total = 0;
+  int64_t w0p = 0, y0 = 0;
+  std::vector<int64_t> y, bn, z, dwo;   // z: the pooled activated output of a pooled block; dwo: a separable block's depthwise output
+  int64_t fa = 0, fd1 = 0;         // head2: activated / dropped features [B, Dd]
+  int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, dwws = 0, tnws = 0, dw0p = 0;
+  FlatTailWs tail;
+  int64_t bnflat = 0, fbws = 0;    // a ragged block's input table as [4][C]; the banked front's weight-gradient workspace
+  int64_t rstats = 0;              // distance of the two groups' statistics rows of a ragged block
+};
+
+struct GcProgram : FlatTailProgram<GcLayout> {
+  bool front = false;       // conv_1d_fast, conv_1d_top_down: the 479-tap front convolution
   int L_in = 0, C_in = 0;   // the input seen as [L_in, C_in]
-  int64_t conv0 = 0;
+  int64_t conv0 = 0, bias0 = -1;   // its kernel; conv_1d_top_down: its bias, applied on load by block 1
   int K0 = 0, K0p = 0, L0 = 0, C0 = 0;
   kws_gather_t g0{};
   bool fbank = false;       // conv_1d_learned_spec: the six-bank front convolution (w_off: the kernels' offsets in params / grads)
   kws_fbank_conv_t fb{};
   bool has_front() const { return front || fbank; }
   std::vector<GcBlock> blocks;
-  int64_t dk = 0, db = 0;
-  int D = 0, NC = 0;
   float keep = 0.7f;
   bool head2 = false;       // conv_1d_heavy: the last block is the Conv1D(128, 5) head over the dropped features [B, Dd]
   int Dd = 0;
   float keep2 = 1.f;        // Dropout(0.1) between that block and the softmax convolution (dropout layer 2)
 
-  int64_t workspace_bytes(int B, int training) const override;
+  void layout(int B, bool training, GcLayout* lo) const override;
+  int forward(const GcLayout& lo, const NetCall& c) const override;
+  kws_flat_tail_args tail_args(const GcLayout& lo, const NetCall& c, float* probs) const override;
+  int64_t tail_grad(const GcLayout& lo) const override { return lo.dA[0]; }
+  int backward(const GcLayout& lo, const NetCall& c) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
 
 constexpr float GC_DROP_KEEP = 0.7f;      // Dropout(0.3), model.py:710 / 1318
 constexpr float GC_FRONT_L2 = 1e-4f;      // kernel_regularizer=l2(0.0001), model.py:700
 constexpr float GC_HEAD2_KEEP = 0.9f;     // Dropout(0.1), model.py:458
+constexpr float GC_TOP_DOWN_KEEP = 0.95f; // Dropout(0.05), model.py:1389
 
+enum GcDw { GC_NO_DW, GC_DW_SLICED, GC_DW_SHARED };
+
+// A grouped block of F filters and k taps over g slices of num_channels / g channels.  dw: the groups are depthwise-separable
+// (DepthwiseConv2D((1, k)) -> Conv1D(F / g, 1)), group q reading its slice (_grouped_reduce_conv) or, shared, all C channels
+// (_grouped_context_conv); the layers of a group in the reference's order: [depthwise,] convolution, BatchNorm
 int add_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, int g, int num_channels, int stride, float l2 = 0.f,
-              bool pool = false) {
+              bool pool = false, GcDw dw = GC_NO_DW) {
   KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C, "net: grouped block F=%d g=%d num_channels=%d C=%d", F, g,
               num_channels, C);
+  KWS_REQUIRE(L >= k, "net: grouped block input length %d < %d taps", L, k);
   GcBlock b;
   memset(&b, 0, sizeof(b));
-  b.d.L = L; b.d.C = C; b.d.k = k; b.d.stride = stride; b.d.g = g; b.d.gs = num_channels / g; b.d.Ng = F / g;
-  KWS_REQUIRE(L >= k, "net: grouped block input length %d < %d taps", L, k);
-  b.d.Lout = (L - k) / stride + 1;
+  const int gs = dw == GC_DW_SHARED ? C : num_channels / g, Ng = F / g, Lout = (L - k) / stride + 1;
+  b.sep = dw != GC_NO_DW;
+  b.dw_shared = dw == GC_DW_SHARED;
+  if (b.sep) {
+    b.dw.L = L; b.dw.C = C; b.dw.k = k; b.dw.stride = stride; b.dw.g = g; b.dw.gs = gs; b.dw.Lout = Lout;
+    b.dw.x0 = 0; b.dw.x_step = b.dw_shared ? 0 : gs;
+    b.d.L = Lout; b.d.C = g * gs; b.d.k = 1; b.d.stride = 1;
+  } else {
+    b.d.L = L; b.d.C = C; b.d.k = k; b.d.stride = stride;
+  }
+  b.d.Lout = Lout; b.d.g = g; b.d.gs = gs; b.d.Ng = Ng;
   b.F = F;
   b.pool = pool;
-  KWS_REQUIRE(!pool || (g == 1 && b.d.Lout >= 3), "net: pooled block needs one group and >= 3 rows (g=%d Lout=%d)", g, b.d.Lout);
-  b.Lp = pool ? kws_pool3s2_out_len(b.d.Lout) : b.d.Lout;
+  KWS_REQUIRE(!pool || (g == 1 && !b.sep && Lout >= 3), "net: pooled block needs one group and >= 3 rows (g=%d Lout=%d)", g, Lout);
+  b.Lp = pool ? kws_pool3s2_out_len(Lout) : Lout;
   b.bn_idx0 = kn.n_bn;
-  const int gs = b.d.gs, Ng = b.d.Ng;
-  int64_t prev_w = 0, prev_m = 0;
+  int64_t prev_first = 0, prev_m = 0;
   for (int q = 0; q < g; ++q) {
-    const int64_t w = kn.conv(k, gs, Ng, l2);
+    const int64_t dwk = b.sep ? kn.dwk(k, gs) : -1;
+    const int64_t w = kn.conv(b.d.k, gs, Ng, l2);
     const BnRef r = kn.bn(Ng);
+    const int64_t first = b.sep ? dwk : w;   // the group's first tensor
     if (q == 0) {
-      b.w0 = w; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
+      b.dw0 = first; b.w0 = w; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
     } else {
       // every group has the same tensors in the same order: one stride per buffer
       if (q == 1) {
-        b.pstride = w - prev_w;
+        b.pstride = first - prev_first;
         b.sstride = r.mm - prev_m;
       }
-      KWS_REQUIRE(w - prev_w == b.pstride && r.mm - prev_m == b.sstride && r.gamma - w == b.gamma0 - b.w0,
+      KWS_REQUIRE(first - prev_first == b.pstride && r.mm - prev_m == b.sstride && w - first == b.w0 - b.dw0 &&
+                      r.gamma - w == b.gamma0 - b.w0,
                   "net: grouped block layout is not uniform");
     }
-    prev_w = w;
+    prev_first = first;
     prev_m = r.mm;
   }
   if (g == 1) {
-    b.pstride = (int64_t)k * gs * Ng;
+    b.pstride = b.sep ? 0 : (int64_t)k * gs * Ng;
     b.sstride = 0;
   }
   b.d.w_group_stride = b.pstride;
+  b.dw.w_group_stride = b.pstride;
   p->blocks.push_back(b);
   return KWS_OK;
+}
+
+// Conv1D(C0, 479, strides=160, VALID) over the raw waveform, no BN and no activation behind it, as the gathered GEMM on ONE tap
+// of 480 samples (the 480th weight is a zero row): window t starts at 160 t and ends at 160 t + 479 < input_size
+void add_front(KerasNames& kn, GcProgram* p, int input_size, int C0, float l2, bool bias) {
+  p->front = true;
+  p->K0 = 479; p->K0p = 480; p->C0 = C0;
+  p->L0 = (input_size - p->K0) / 160 + 1;
+  p->conv0 = kn.conv(p->K0, 1, C0, l2);
+  if (bias) p->bias0 = kws_net_add_tensor(kn.n, "conv1d_1/bias", {C0}, false, 0.f, 0, 0, 0.f);
+  p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
+  p->g0.x_len = input_size; p->g0.x_batch_stride = input_size;
+  p->L_in = input_size; p->C_in = 1;
 }
 
 // _grouped_context_conv(x, F, k, 2, num_channels) with num_channels > C: Keras clips the second slice, so group 0 reads
@@ -165,21 +209,11 @@ int add_ragged_block(KerasNames& kn, GcProgram* p, int L, int C, int F, int k, i
   return KWS_OK;
 }
 
-struct GcLayout {
-  int64_t total = 0;
-  int64_t w0p = 0, y0 = 0;
-  std::vector<int64_t> y, bn, z;   // z: the pooled activated output of a pooled block
-  int64_t fa = 0, fd1 = 0;         // head2: activated / dropped features [B, Dd]
-  int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, tnws = 0, dw0p = 0;
-  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
-  int64_t bnflat = 0, fbws = 0;    // a ragged block's input table as [4][C]; the banked front's weight-gradient workspace
-  int64_t rstats = 0;              // distance of the two groups' statistics rows of a ragged block
-};
-
-void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
+void GcProgram::layout(int B, bool training, GcLayout* lo) const {
+  const GcProgram& p = *this;
   Bump bp;
   const int nb = (int)p.blocks.size();
-  int64_t max_act = 64, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64;
+  int64_t max_act = 64, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64, max_dwws = 0;
   if (p.front) {
     lo->w0p = bp.take((int64_t)p.K0p * p.C0);
     lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
@@ -192,10 +226,18 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
   lo->y.assign(nb, 0);
   lo->bn.assign(nb, 0);
   lo->z.assign(nb, 0);
+  lo->dwo.assign(nb, 0);
   for (int i = 0; i < nb; ++i) {
     kws_gconv_t d = p.blocks[i].d;
     d.B = B;
     const int64_t M = (int64_t)B * d.Lout;
+    if (p.blocks[i].sep) {
+      kws_gdwconv_t dw = p.blocks[i].dw;
+      dw.B = B;
+      lo->dwo[i] = bp.take(M * d.C);
+      max_act = std::max(max_act, (int64_t)B * dw.L * dw.C);
+      max_dwws = std::max(std::max(max_dwws, (int64_t)64), kws_gdwconv_bwd_workspace_floats(&dw));
+    }
     lo->y[i] = bp.take(M * p.blocks[i].F);
     lo->bn[i] = bp.take((int64_t)4 * p.blocks[i].F);
     if (p.blocks[i].pool) {
@@ -230,6 +272,7 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
     lo->part = bp.take(max_part);
     lo->coef = bp.take(max_coef);
     lo->wws = bp.take(max_wws);
+    if (max_dwws) lo->dwws = bp.take(max_dwws);
     if (p.front) {
       lo->tnws = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * p.L0, p.K0p, p.C0));
       lo->dw0p = bp.take((int64_t)p.K0p * p.C0);
@@ -239,11 +282,7 @@ void gc_layout(const GcProgram& p, int B, bool training, GcLayout* lo) {
       fb.B = B;
       lo->fbws = bp.take(kws_fbank_conv_wgrad_workspace_floats(&fb));
     }
-    lo->fd = bp.take((int64_t)B * p.D);
-    lo->dl = bp.take((int64_t)B * p.NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.D * p.NC);
+    lo->tail.take(bp, B, dense.D, dense.NC);
   }
   lo->total = bp.cur * 4;
 }
@@ -262,11 +301,31 @@ struct GcInput {
   const float* bn;
   int bg;
 };
-GcInput gc_input(const GcProgram& p, const GcLayout& lo, int i, const float* x, const float* ws, bool training) {
-  if (i == 0) return {p.has_front() ? ws + lo.y0 : x, nullptr, 0};
-  if (p.head2 && training && i + 1 == (int)p.blocks.size()) return {ws + lo.fd1, nullptr, 0};
+GcInput gc_input(const GcProgram& p, const GcLayout& lo, int i, const NetCall& c) {
+  const float* ws = c.ws;
+  if (i == 0) return {p.has_front() ? ws + lo.y0 : c.x, nullptr, 0};
+  if (p.head2 && c.training && i + 1 == (int)p.blocks.size()) return {ws + lo.fd1, nullptr, 0};
   if (p.blocks[i - 1].pool) return {ws + lo.z[i - 1], nullptr, 0};
   return {ws + lo.y[i - 1], ws + lo.bn[i - 1], p.blocks[i - 1].d.Ng};
+}
+
+// the depthwise half of separable block i over that input: its descriptor with what it applies on load - the producer's table,
+// or (block 1 behind a front with a bias) that bias - and the table
+struct GcDwInput {
+  kws_gdwconv_t d;
+  const float* tab;
+};
+GcDwInput gc_dw_input(const GcProgram& p, int i, const GcInput& gi, const NetCall& c) {
+  GcDwInput r{p.blocks[i].dw, gi.bn};
+  r.d.B = c.B;
+  if (gi.bn) {
+    r.d.act = KWS_GDW_ACT_BN_RELU6;
+    r.d.bn_group = gi.bg;
+  } else if (i == 0 && p.bias0 >= 0) {
+    r.d.act = KWS_GDW_ACT_BIAS;
+    r.tab = c.params + p.bias0;
+  }
+  return r;
 }
 
 // the producer's grouped table [g][4][Ng] as the flat [4][C] one of kws_conv1d_* (C = g * Ng)
@@ -286,21 +345,26 @@ kws_gbn_refs ragged_refs(const GcBlock& b, int q, const float* params, float* st
 
 // a ragged block (i >= 1, behind an unpooled grouped block): two column-window convolutions, each with its own BatchNorm layer,
 // whose tables land in the grouped layout [2][4][Ng] the next block reads
-int gc_ragged_forward(const GcProgram& p, const GcLayout& lo, int i, const float* params, float* state, int B, bool training, float* ws,
-                      hipStream_t st) {
+int gc_ragged_forward(const GcProgram& p, const GcLayout& lo, int i, const NetCall& c) {
+  const float* params = c.params;
+  float* state = c.state;
+  float* ws = c.ws;
+  const int B = c.B;
+  const bool training = c.training;
+  hipStream_t st = c.st;
   const GcBlock& b = p.blocks[i];
   const GcBlock& pb = p.blocks[i - 1];
   KWS_TRY(gc_flat_table(ws + lo.bn[i - 1], pb.d.g, pb.d.Ng, ws + lo.bnflat, st));
   const kws_gbn_cols cols = kws_gbn_grouped(1, b.d.Ng);
   for (int q = 0; q < 2; ++q) {
-    kws_conv1d_t c = b.rc[q];
-    c.B = B;
+    kws_conv1d_t cv = b.rc[q];
+    cv.B = B;
     float* stats = training ? ws + lo.stats + q * lo.rstats : nullptr;
-    KWS_TRY(kws_conv1d_fwd_f32(ws + lo.y[i - 1], ws + lo.bnflat, params + b.rw[q], ws + lo.y[i], stats, &c, st));
+    KWS_TRY(kws_conv1d_fwd_f32(ws + lo.y[i - 1], ws + lo.bnflat, params + b.rw[q], ws + lo.y[i], stats, &cv, st));
     const kws_gbn_refs r = ragged_refs(b, q, params, state);
     float* bn = ws + lo.bn[i] + (int64_t)q * 4 * b.d.Ng;
     if (training)
-      KWS_TRY(kws_gbn_finalize(stats, kws_conv1d_stats_rows(&c), (int64_t)B * c.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM, bn, st));
+      KWS_TRY(kws_gbn_finalize(stats, kws_conv1d_stats_rows(&cv), (int64_t)B * cv.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM, bn, st));
     else
       KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, bn, st));
   }
@@ -308,8 +372,15 @@ int gc_ragged_forward(const GcProgram& p, const GcLayout& lo, int i, const float
 }
 
 // forward through the blocks; training: batch statistics (moving averages updated), else the moving statistics
-int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-               uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
+int GcProgram::forward(const GcLayout& lo, const NetCall& c) const {
+  const GcProgram& p = *this;
+  const float* params = c.params;
+  float* state = c.state;
+  const float* x = c.x;
+  float* ws = c.ws;
+  const int B = c.B;
+  const bool training = c.training;
+  hipStream_t st = c.st;
   if (p.front) {
     KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
     KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
@@ -324,27 +395,29 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
     const GcBlock& b = p.blocks[i];
     kws_gconv_t d = b.d;
     d.B = B;
-    const GcInput gi = gc_input(p, lo, (int)i, x, ws, training);
-    const float* in = gi.in;
-    const float* bn_in = gi.bn;
-    const int bg = gi.bg;
+    GcInput gi = gc_input(p, lo, (int)i, c);
     const kws_gbn_refs r = refs_of(b, params, state);
     const kws_gbn_cols cols = kws_gbn_grouped(d.g, d.Ng);
     if (b.ragged) {
-      KWS_TRY(gc_ragged_forward(p, lo, (int)i, params, state, B, training, ws, st));
+      KWS_TRY(gc_ragged_forward(p, lo, (int)i, c));
       continue;
+    }
+    if (b.sep) {   // all groups' depthwise halves in one launch; the k = 1 convolution reads their output as it is
+      const GcDwInput di = gc_dw_input(p, (int)i, gi, c);
+      KWS_TRY(kws_gdwconv_fwd_f32(gi.in, di.tab, params + b.dw0, ws + lo.dwo[i], &di.d, st));
+      gi = {ws + lo.dwo[i], nullptr, 0};
     }
     if (training) {
       if (p.head2 && i + 1 == p.blocks.size()) {   // Dropout(.3) over the activated ladder output, materialised for the head's GEMMs
         const GcBlock& pb = p.blocks[i - 1];
         KWS_TRY(kws_bn_relu6_apply(ws + lo.y[i - 1], ws + lo.bn[i - 1], ws + lo.fa, (int64_t)B * pb.d.Lout, pb.F, 1, st));
-        KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.Dd, p.keep, seed, step, 1, row_offset, st));
+        KWS_TRY(kws_dropout_fwd(ws + lo.fa, ws + lo.fd1, B, p.Dd, p.keep, c.seed, c.step, 1, c.row_offset, st));
       }
-      KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], ws + lo.stats, &d, st));
+      KWS_TRY(kws_gconv_fwd_f32(gi.in, gi.bn, gi.bg, params + b.w0, ws + lo.y[i], ws + lo.stats, &d, st));
       KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&d), (int64_t)B * d.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
                                ws + lo.bn[i], st));
     } else {
-      KWS_TRY(kws_gconv_fwd_f32(in, bn_in, bg, params + b.w0, ws + lo.y[i], nullptr, &d, st));
+      KWS_TRY(kws_gconv_fwd_f32(gi.in, gi.bn, gi.bg, params + b.w0, ws + lo.y[i], nullptr, &d, st));
       KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, ws + lo.bn[i], st));
     }
     if (b.pool) KWS_TRY(kws_pool3s2_fwd_f32(ws + lo.y[i], ws + lo.bn[i], ws + lo.z[i], B, d.Lout, b.F, st));
@@ -352,16 +425,16 @@ int gc_forward(const GcProgram& p, const GcLayout& lo, const float* params, floa
   return KWS_OK;
 }
 
-kws_flat_tail_args tail_args(const GcProgram& p, const GcLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const GcBlock& last = p.blocks.back();
+kws_flat_tail_args GcProgram::tail_args(const GcLayout& lo, const NetCall& c, float* probs) const {
+  const GcBlock& last = blocks.back();
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.y.back(); t.bn = ws + lo.bn.back(); t.Ng = last.d.Ng;
-  t.Wd = params + p.dk; t.bd = p.db >= 0 ? params + p.db : nullptr;
+  t.y = c.ws + lo.y.back(); t.bn = c.ws + lo.bn.back(); t.Ng = last.d.Ng;
+  t.Wd = c.params + dense.kernel; t.bd = dense.bias >= 0 ? c.params + dense.bias : nullptr;
   t.probs = probs;
-  t.B = B; t.D = p.D; t.F = last.F; t.NC = p.NC;
-  t.keep_prob = p.head2 ? p.keep2 : p.keep;
-  t.layer_id = p.head2 ? 2 : 1;
+  t.B = c.B; t.D = dense.D; t.F = last.F; t.NC = dense.NC;
+  t.keep_prob = head2 ? keep2 : keep;
+  t.layer_id = head2 ? 2 : 1;
   return t;
 }
 
@@ -369,25 +442,32 @@ kws_flat_tail_args tail_args(const GcProgram& p, const GcLayout& lo, const float
 
 int gc_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  if (c.kind == KWS_NET_CONV_1D_TOP_DOWN) return td_build(n);
   GcProgram* p = new GcProgram();
   n->program.reset(p);
-  p->NC = c.num_classes;
+  p->net = n;
+  const int NC = p->dense.NC = c.num_classes;
   p->keep = GC_DROP_KEEP;
   KerasNames kn{n};
+  // the ladder of conv_1d_spec, conv_1d_learned_spec and conv_1d_top_down: four reduce / context pairs, k 3, over [L, C]
+  struct Row { int F, g, nch, stride; };
+  const Row* spec = nullptr;
+  int L = 0, C = 0;
   if (c.kind == KWS_NET_CONV_1D_FAST) {
     KWS_REQUIRE(c.input_size >= 479 && c.input_size % 2 == 0, "net: conv_1d_fast input_size %d (even, >= 479)", c.input_size);
-    p->front = true;
-    p->K0 = 479; p->K0p = 480; p->C0 = 252;
-    p->L0 = (c.input_size - p->K0) / 160 + 1;
-    p->conv0 = kn.conv(p->K0, 1, p->C0, GC_FRONT_L2);
-    // ONE tap of 480 samples (the 480th weight is a zero row): window t starts at 160 t and ends at 160 t + 479 < input_size
-    p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
-    p->g0.x_len = c.input_size; p->g0.x_batch_stride = c.input_size;
-    p->L_in = c.input_size; p->C_in = 1;
+    add_front(kn, p, c.input_size, 252, GC_FRONT_L2, false);
     KWS_TRY(add_block(kn, p, p->L0, p->C0, 300, 15, 6, 252, 2));
     const GcBlock& b1 = p->blocks.back();
     KWS_TRY(add_block(kn, p, b1.d.Lout, b1.F, 360, 7, 5, 300, 2));
+  } else if (c.kind == KWS_NET_CONV_1D_TOP_DOWN) {
+    // the ladder's lengths are 45, 43, 21, 19, 9, 7, 3, 1 at 91 rows, the fewest that leave one: 14879 samples.  The gathered GEMM
+    // loads pairs of samples, so clips must start on even offsets (conv_1d_fast's rule): the first size it takes is 14880
+    KWS_REQUIRE(c.input_size >= 14879 && c.input_size % 2 == 0,
+                "net: conv_1d_top_down input_size %d (even, >= 14879: the ladder needs 91 rows of 160 samples)", c.input_size);
+    p->keep = GC_TOP_DOWN_KEEP;
+    add_front(kn, p, c.input_size, 480, 0.f, true);
+    static const Row rows[8] = {{420, 3, 480, 2}, {420, 2, 420, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
+                                {300, 3, 360, 2}, {300, 2, 300, 1}, {240, 3, 300, 2}, {240, 2, 240, 1}};
+    spec = rows; L = p->L0; C = p->C0;
   } else if (c.kind == KWS_NET_CONV_1D_TIME_STACKED || c.kind == KWS_NET_CONV_1D_HEAVY) {
     const bool heavy = c.kind == KWS_NET_CONV_1D_HEAVY;
     KWS_REQUIRE(c.input_size == 16000, "net: conv_1d_%s input_size %d (the reference reshapes 16000 samples)",
@@ -408,13 +488,12 @@ int gc_build(kws_net* n) {
       p->keep2 = GC_HEAD2_KEEP;
       KWS_TRY(add_block(kn, p, top.d.Lout, top.F, 128, 5, 1, top.F, 1));
       const GcBlock& head = p->blocks.back();
-      p->D = head.F;
-      p->dk = kn.conv(1, head.F, p->NC, 0.f);
-      p->db = -1;
+      p->dense.D = head.F;
+      p->dense.kernel = kn.conv(1, head.F, NC, 0.f);
     } else {
-      p->D = top.d.Lout * top.F;
-      p->dk = kn.conv(top.d.Lout, top.F, p->NC, 0.f);   // [5, 256, NC] = the Dense kernel [1280, NC] over the t-major flatten
-      p->db = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+      p->dense.D = top.d.Lout * top.F;
+      p->dense.kernel = kn.conv(top.d.Lout, top.F, NC, 0.f);   // [5, 256, NC] = the Dense kernel [1280, NC] over the t-major flatten
+      p->dense.bias = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {NC}, false, 0.f, 0, 0, 0.f);
     }
     return KWS_OK;
   } else if (c.kind == KWS_NET_CONV_1D_LEARNED_SPEC) {
@@ -438,45 +517,37 @@ int gc_build(kws_net* n) {
     p->fbank = true;
     p->L_in = c.input_size; p->C_in = 1;
     p->L0 = fb.Lout; p->C0 = fb.nbanks * fb.N;
-    struct { int F, g, nch, stride; } spec[8] = {{300, 3, 240, 2}, {300, 2, 360, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
-                                                 {420, 3, 240, 2}, {420, 2, 420, 1}, {480, 3, 420, 2}, {480, 2, 480, 1}};
-    int L = p->L0, C = p->C0;
-    for (int i = 0; i < 8; ++i) {
-      if (spec[i].nch > C) KWS_TRY(add_ragged_block(kn, p, L, C, spec[i].F, 3, spec[i].nch));
-      else KWS_TRY(add_block(kn, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride));
-      L = p->blocks.back().d.Lout;
-      C = p->blocks.back().F;
-    }
+    static const Row rows[8] = {{300, 3, 240, 2}, {300, 2, 360, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
+                                {420, 3, 240, 2}, {420, 2, 420, 1}, {480, 3, 420, 2}, {480, 2, 480, 1}};
+    spec = rows; L = p->L0; C = p->C0;
   } else {
     p->L_in = 98; p->C_in = 257;   // Input(shape=[98 * 257]) -> Reshape([98, 257]); input_size is not consulted
-    struct { int F, g, nch, stride; } spec[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
-                                                 {420, 4, 360, 2}, {420, 3, 360, 1}, {480, 4, 420, 2}, {480, 3, 480, 1}};
-    int L = p->L_in, C = p->C_in;
-    for (int i = 0; i < 8; ++i) {
-      KWS_TRY(add_block(kn, p, L, C, spec[i].F, 3, spec[i].g, spec[i].nch, spec[i].stride));
-      L = p->blocks.back().d.Lout;
-      C = p->blocks.back().F;
-    }
+    static const Row rows[8] = {{300, 4, 252, 2}, {300, 3, 300, 1}, {360, 4, 300, 2}, {360, 3, 360, 1},
+                                {420, 4, 360, 2}, {420, 3, 360, 1}, {480, 4, 420, 2}, {480, 3, 480, 1}};
+    spec = rows; L = p->L_in; C = p->C_in;
+  }
+  const bool sep = c.kind == KWS_NET_CONV_1D_TOP_DOWN;   // its groups are depthwise-separable, l2 1e-5 on the 1x1 kernels
+  for (int i = 0; spec && i < 8; ++i) {
+    const Row& s = spec[i];
+    if (s.nch > C) KWS_TRY(add_ragged_block(kn, p, L, C, s.F, 3, s.nch));
+    else KWS_TRY(add_block(kn, p, L, C, s.F, 3, s.g, s.nch, s.stride, sep ? KWS_L2_COEF : 0.f, false,
+                           !sep ? GC_NO_DW : s.stride == 1 ? GC_DW_SHARED : GC_DW_SLICED));
+    L = p->blocks.back().d.Lout;
+    C = p->blocks.back().F;
   }
   const GcBlock& last = p->blocks.back();
-  p->D = last.d.Lout * last.F;
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->D, p->NC}, false, 0.f, p->D, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->dense.D = last.d.Lout * last.F;
+  p->dense.kernel = kws_net_add_tensor(n, "dense_1/kernel", {p->dense.D, NC}, false, 0.f, p->dense.D, NC, 0.f);
+  p->dense.bias = kws_net_add_tensor(n, "dense_1/bias", {NC}, false, 0.f, 0, 0, 0.f);
   return KWS_OK;
 }
 
 namespace {
 
-int64_t GcProgram::workspace_bytes(int B, int training) const {
-  GcLayout lo;
-  gc_layout(*this, B, training != 0, &lo);
-  return lo.total;
-}
-
 int GcProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   const GcProgram& p = *this;
   GcLayout lo;
-  gc_layout(p, B, training != 0, &lo);
+  layout(B, training != 0, &lo);
   const int nb = (int)p.blocks.size();
   if (what == 0) {   // pre-BN output of conv stage `index` (conv_1d_fast: 0 = the front convolution)
     const int i = index - (p.has_front() ? 1 : 0);
@@ -488,6 +559,11 @@ int GcProgram::debug_view(int B, int training, int what, int index, int64_t* off
       *offset_floats = lo.y[i];
       *count = (int64_t)B * p.blocks[i].d.Lout * p.blocks[i].F;
     }
+  } else if (what == 1) {   // depthwise output of conv stage `index`, which must be a separable block
+    const int i = index - (p.has_front() ? 1 : 0);
+    KWS_REQUIRE(i >= 0 && i < nb && p.blocks[i].sep, "net_debug_view: z index %d", index);
+    *offset_floats = lo.dwo[i];
+    *count = (int64_t)B * p.blocks[i].d.Lout * p.blocks[i].d.C;
   } else if (what == 2) {   // table of batch_normalization_{index+1}
     for (int i = 0; i < nb; ++i) {
       const GcBlock& b = p.blocks[i];
@@ -506,30 +582,16 @@ int GcProgram::debug_view(int B, int training, int what, int index, int64_t* off
   return KWS_OK;
 }
 
-int GcProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                       hipStream_t st) const {
-  GcLayout lo;
-  gc_layout(*this, B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(gc_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = tail_args(*this, lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int GcProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                     hipStream_t st) const {
+// dA[cur] = gradient wrt the activated output of block i, from the tail's down to the front convolution
+int GcProgram::backward(const GcLayout& lo, const NetCall& c) const {
   const GcProgram& p = *this;
-  GcLayout lo;
-  gc_layout(p, B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  KWS_TRY(gc_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
+  const float* params = c.params;
+  const float* x = c.x;
+  float* grads = c.grads;
+  float* ws = c.ws;
+  const int B = c.B;
+  hipStream_t st = c.st;
   int cur = 0;
-  kws_flat_tail_args t = tail_args(p, lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.dA[cur], ws + lo.per_loss, ws + lo.per_correct, seed, step,
-                              loss_batch, row_offset, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, p.db >= 0 ? grads + p.db : nullptr, B, p.D, p.NC, ws + lo.swg,
-                                 st));
   for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
     const GcBlock& b = p.blocks[i];
     kws_gconv_t d = b.d;
@@ -548,24 +610,35 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
     float* dy = ws + lo.dA[cur];
     if (b.ragged) {   // the windows [0, gs) and [gs, C) together cover dA[cur ^ 1]: the gradient wrt the activated input
       for (int q = 0; q < 2; ++q) {
-        kws_conv1d_t c = b.rc[q];
-        c.B = B;
-        KWS_TRY(kws_conv1d_wgrad_f32(ws + lo.y[i - 1], ws + lo.bnflat, dy, grads + b.rw[q], ws + lo.wws, &c, st));
-        KWS_TRY(kws_conv1d_dgrad_f32(dy, params + b.rw[q], ws + lo.dA[cur ^ 1], 0, &c, st));
+        kws_conv1d_t cv = b.rc[q];
+        cv.B = B;
+        KWS_TRY(kws_conv1d_wgrad_f32(ws + lo.y[i - 1], ws + lo.bnflat, dy, grads + b.rw[q], ws + lo.wws, &cv, st));
+        KWS_TRY(kws_conv1d_dgrad_f32(dy, params + b.rw[q], ws + lo.dA[cur ^ 1], 0, &cv, st));
       }
       cur ^= 1;
       continue;
     }
-    const GcInput gi = gc_input(p, lo, i, x, ws, true);
+    const GcInput gi = gc_input(p, lo, i, c);
+    if (b.sep) {   // the pointwise kernels' gradients and dz, then the depthwise kernels' and the gradient wrt the activated input
+      const GcDwInput di = gc_dw_input(p, i, gi, c);
+      KWS_TRY(kws_gconv_wgrad_f32(ws + lo.dwo[i], nullptr, 0, dy, grads + b.w0, ws + lo.wws, &d, st));
+      KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.dA[cur ^ 1], &d, st));
+      KWS_TRY(kws_gdwconv_bwd_f32(gi.in, di.tab, ws + lo.dA[cur ^ 1], params + b.dw0, ws + lo.dA[cur], grads + b.dw0, nullptr,
+                                  ws + lo.dwws, &di.d, st));
+      continue;
+    }
     KWS_TRY(kws_gconv_wgrad_f32(gi.in, gi.bn, gi.bg, dy, grads + b.w0, ws + lo.wws, &d, st));
     if (p.head2 && i + 1 == (int)p.blocks.size()) {   // back through Dropout(.3): the gradient wrt the activated ladder output
       KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.fa, &d, st));
-      KWS_TRY(kws_dropout_bwd(ws + lo.fa, ws + lo.dA[cur], B, p.Dd, p.keep, seed, step, 1, row_offset, st));
+      KWS_TRY(kws_dropout_bwd(ws + lo.fa, ws + lo.dA[cur], B, p.Dd, p.keep, c.seed, c.step, 1, c.row_offset, st));
     } else if (i > 0 || p.has_front()) {
       KWS_TRY(kws_gconv_dgrad_f32(dy, params + b.w0, ws + lo.dA[cur ^ 1], &d, st));
       cur ^= 1;
     }
   }
+  // a front bias cancels in block 1's BatchNorm on batch statistics: its gradient is exactly 0, not the float32 residue (1e-5)
+  // that the column sum of dA[cur] would leave
+  if (p.bias0 >= 0) KWS_HIP(hipMemsetAsync(grads + p.bias0, 0, sizeof(float) * p.C0, st));
   if (p.front) {   // dA[cur] = gradient wrt the front convolution's output (no BN, no activation in between)
     KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, ws + lo.dA[cur], ws + lo.dw0p, B, p.C0, ws + lo.tnws, st));
     KWS_HIP(hipMemcpyAsync(grads + p.conv0, ws + lo.dw0p, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
@@ -579,313 +652,3 @@ int GcProgram::train(const float* params, float* state, const float* x, const fl
 }
 
 }  // namespace
-
-// ---- conv_1d_top_down ---------------------------------------------------------------------------------------------------------
-namespace {
-
-constexpr float TD_DROP_KEEP = 0.95f;   // Dropout(0.05), model.py:1389
-
-struct TdBlock {
-  kws_gdwconv_t dw;          // B, act and bn_group filled in per call
-  kws_gconv_t pw;            // the g Conv1D(Ng, 1) layers over the depthwise output [B, Lout, g * gs]; B filled in per call
-  int F;
-  int64_t dw0, pw0;          // group 0's depthwise / pointwise kernel (params); group q's at + q * pstride
-  int64_t gamma0, beta_off, mm0, mv_off, pstride, sstride;
-  int bn_idx0;
-};
-
-struct TdProgram : NetProgram {
-  int64_t conv0 = 0, bias0 = 0;
-  int K0 = 479, K0p = 480, L0 = 0, C0 = 480;
-  kws_gather_t g0{};
-  std::vector<TdBlock> blocks;
-  int64_t dk = 0, db = 0;
-  int D = 0, NC = 0;
-
-  int64_t workspace_bytes(int B, int training) const override;
-  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
-};
-
-// _grouped_reduce_conv (shared = false: group q reads the slice [q * nch / g, + nch / g)) or _grouped_context_conv (shared: every
-// group reads all C channels) of F filters; the layers of a group in the reference's order: depthwise, pointwise, BatchNorm
-int td_add_block(KerasNames& kn, TdProgram* p, int L, int C, int F, int g, int num_channels, int stride, bool shared) {
-  KWS_REQUIRE(num_channels % g == 0 && F % g == 0 && num_channels <= C && L >= 3, "net: top-down block F=%d g=%d num_channels=%d C=%d L=%d",
-              F, g, num_channels, C, L);
-  TdBlock b;
-  memset(&b, 0, sizeof(b));
-  const int gs = shared ? C : num_channels / g, Ng = F / g;
-  b.dw.L = L; b.dw.C = C; b.dw.k = 3; b.dw.stride = stride; b.dw.g = g; b.dw.gs = gs;
-  b.dw.Lout = (L - 3) / stride + 1;
-  b.dw.x0 = 0; b.dw.x_step = shared ? 0 : gs;
-  b.pw.L = b.dw.Lout; b.pw.Lout = b.dw.Lout; b.pw.C = g * gs; b.pw.k = 1; b.pw.stride = 1; b.pw.g = g; b.pw.gs = gs; b.pw.Ng = Ng;
-  b.F = F;
-  b.bn_idx0 = kn.n_bn;
-  int64_t prev_dw = 0, prev_m = 0;
-  for (int q = 0; q < g; ++q) {
-    const int64_t dw = kn.dwk(3, gs);
-    const int64_t pw = kn.conv(1, gs, Ng, KWS_L2_COEF);
-    const BnRef r = kn.bn(Ng);
-    if (q == 0) {
-      b.dw0 = dw; b.pw0 = pw; b.gamma0 = r.gamma; b.beta_off = r.beta - r.gamma; b.mm0 = r.mm; b.mv_off = r.mv - r.mm;
-    } else {
-      if (q == 1) {
-        b.pstride = dw - prev_dw;
-        b.sstride = r.mm - prev_m;
-      }
-      KWS_REQUIRE(dw - prev_dw == b.pstride && r.mm - prev_m == b.sstride && pw - dw == b.pw0 - b.dw0 && r.gamma - dw == b.gamma0 - b.dw0,
-                  "net: top-down block layout is not uniform");
-    }
-    prev_dw = dw;
-    prev_m = r.mm;
-  }
-  if (g == 1) b.pstride = 0;
-  b.dw.w_group_stride = b.pstride;
-  b.pw.w_group_stride = b.pstride;
-  p->blocks.push_back(b);
-  return KWS_OK;
-}
-
-struct TdLayout {
-  int64_t total = 0;
-  int64_t w0p = 0, y0 = 0;
-  std::vector<int64_t> z, y, bn;
-  int64_t stats = 0, dA[2] = {0, 0}, part = 0, coef = 0, wws = 0, dwws = 0, tnws = 0, dw0p = 0;
-  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
-};
-
-void td_layout(const TdProgram& p, int B, bool training, TdLayout* lo) {
-  Bump bp;
-  const int nb = (int)p.blocks.size();
-  int64_t max_act = (int64_t)B * p.L0 * p.C0, max_stats = 64, max_part = 64, max_coef = 64, max_wws = 64, max_dwws = 64;
-  lo->w0p = bp.take((int64_t)p.K0p * p.C0);
-  lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
-  lo->z.assign(nb, 0);
-  lo->y.assign(nb, 0);
-  lo->bn.assign(nb, 0);
-  for (int i = 0; i < nb; ++i) {
-    const TdBlock& b = p.blocks[i];
-    kws_gdwconv_t dw = b.dw;
-    kws_gconv_t pw = b.pw;
-    dw.B = pw.B = B;
-    const int64_t M = (int64_t)B * pw.Lout;
-    lo->z[i] = bp.take(M * pw.C);
-    lo->y[i] = bp.take(M * b.F);
-    lo->bn[i] = bp.take((int64_t)4 * b.F);
-    max_act = std::max(max_act, std::max(M * pw.C, std::max(M * b.F, (int64_t)B * dw.L * dw.C)));
-    max_stats = std::max(max_stats, (int64_t)kws_gconv_stats_rows(&pw) * 2 * b.F);
-    max_part = std::max(max_part, (int64_t)kws_gbn_bwd_rows(M) * 2 * b.F);
-    max_coef = std::max(max_coef, (int64_t)2 * b.F);
-    max_wws = std::max(max_wws, kws_gconv_wgrad_workspace_floats(&pw));
-    max_dwws = std::max(max_dwws, kws_gdwconv_bwd_workspace_floats(&dw));
-  }
-  lo->stats = bp.take(max_stats);
-  if (training) {
-    lo->dA[0] = bp.take(max_act);
-    lo->dA[1] = bp.take(max_act);
-    lo->part = bp.take(max_part);
-    lo->coef = bp.take(max_coef);
-    lo->wws = bp.take(max_wws);
-    lo->dwws = bp.take(max_dwws);
-    lo->tnws = bp.take(kws_gemm_tn_workspace_floats((int64_t)B * p.L0, p.K0p, p.C0));
-    lo->dw0p = bp.take((int64_t)p.K0p * p.C0);
-    lo->fd = bp.take((int64_t)B * p.D);
-    lo->dl = bp.take((int64_t)B * p.NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.D * p.NC);
-  }
-  lo->total = bp.cur * 4;
-}
-
-kws_gbn_refs td_refs(const TdBlock& b, const float* params, float* state) {
-  kws_gbn_refs r;
-  r.gamma = params + b.gamma0; r.pstride = b.pstride; r.boff = b.beta_off;
-  r.mm = state ? state + b.mm0 : nullptr; r.sstride = b.sstride; r.voff = b.mv_off;
-  return r;
-}
-
-// block i's depthwise descriptor with what it reads: the front output + its bias, or the producer's raw output through its table
-struct TdInput {
-  kws_gdwconv_t d;
-  const float* in;
-  const float* tab;
-};
-TdInput td_input(const TdProgram& p, const TdLayout& lo, int i, const float* params, const float* ws, int B) {
-  TdInput r;
-  r.d = p.blocks[i].dw;
-  r.d.B = B;
-  if (i == 0) {
-    r.d.act = KWS_GDW_ACT_BIAS;
-    r.in = ws + lo.y0;
-    r.tab = params + p.bias0;
-  } else {
-    r.d.act = KWS_GDW_ACT_BN_RELU6;
-    r.d.bn_group = p.blocks[i - 1].pw.Ng;
-    r.in = ws + lo.y[i - 1];
-    r.tab = ws + lo.bn[i - 1];
-  }
-  return r;
-}
-
-int td_forward(const TdProgram& p, const TdLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-               hipStream_t st) {
-  KWS_HIP(hipMemcpyAsync(ws + lo.w0p, params + p.conv0, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
-  KWS_HIP(hipMemsetAsync(ws + lo.w0p + (int64_t)p.K0 * p.C0, 0, sizeof(float) * (p.K0p - p.K0) * p.C0, st));
-  KWS_TRY(kws_gemm_gather_f32(x, &p.g0, ws + lo.w0p, ws + lo.y0, B, p.C0, nullptr, st));
-  for (size_t i = 0; i < p.blocks.size(); ++i) {
-    const TdBlock& b = p.blocks[i];
-    const TdInput in = td_input(p, lo, (int)i, params, ws, B);
-    kws_gconv_t pw = b.pw;
-    pw.B = B;
-    const kws_gbn_refs r = td_refs(b, params, state);
-    const kws_gbn_cols cols = kws_gbn_grouped(pw.g, pw.Ng);
-    KWS_TRY(kws_gdwconv_fwd_f32(in.in, in.tab, params + b.dw0, ws + lo.z[i], &in.d, st));
-    KWS_TRY(kws_gconv_fwd_f32(ws + lo.z[i], nullptr, 0, params + b.pw0, ws + lo.y[i], training ? ws + lo.stats : nullptr, &pw, st));
-    if (training)
-      KWS_TRY(kws_gbn_finalize(ws + lo.stats, kws_gconv_stats_rows(&pw), (int64_t)B * pw.Lout, &cols, &r, KWS_BN_EPS, KWS_BN_MOMENTUM,
-                               ws + lo.bn[i], st));
-    else
-      KWS_TRY(kws_gbn_infer(&cols, &r, KWS_BN_EPS, ws + lo.bn[i], st));
-  }
-  return KWS_OK;
-}
-
-kws_flat_tail_args td_tail_args(const TdProgram& p, const TdLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const TdBlock& last = p.blocks.back();
-  kws_flat_tail_args t;
-  memset(&t, 0, sizeof(t));
-  t.y = ws + lo.y.back(); t.bn = ws + lo.bn.back(); t.Ng = last.pw.Ng;
-  t.Wd = params + p.dk; t.bd = params + p.db;
-  t.probs = probs;
-  t.B = B; t.D = p.D; t.F = last.F; t.NC = p.NC;
-  t.keep_prob = TD_DROP_KEEP;
-  t.layer_id = 1;
-  return t;
-}
-
-int64_t TdProgram::workspace_bytes(int B, int training) const {
-  TdLayout lo;
-  td_layout(*this, B, training != 0, &lo);
-  return lo.total;
-}
-
-int TdProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
-  TdLayout lo;
-  td_layout(*this, B, training != 0, &lo);
-  const int nb = (int)blocks.size();
-  if (what == 0) {   // index 0: the front convolution's output (its bias not added); i >= 1: block i's pre-BN output
-    KWS_REQUIRE(index >= 0 && index <= nb, "net_debug_view: y index %d", index);
-    if (index == 0) {
-      *offset_floats = lo.y0;
-      *count = (int64_t)B * L0 * C0;
-    } else {
-      *offset_floats = lo.y[index - 1];
-      *count = (int64_t)B * blocks[index - 1].pw.Lout * blocks[index - 1].F;
-    }
-  } else if (what == 1) {   // block i's depthwise output
-    KWS_REQUIRE(index >= 1 && index <= nb, "net_debug_view: z index %d", index);
-    *offset_floats = lo.z[index - 1];
-    *count = (int64_t)B * blocks[index - 1].pw.Lout * blocks[index - 1].pw.C;
-  } else if (what == 2) {   // table of batch_normalization_{index+1}
-    for (int i = 0; i < nb; ++i) {
-      const TdBlock& b = blocks[i];
-      if (index >= b.bn_idx0 && index < b.bn_idx0 + b.pw.g) {
-        *offset_floats = lo.bn[i] + (int64_t)(index - b.bn_idx0) * 4 * b.pw.Ng;
-        *count = 4 * b.pw.Ng;
-        return KWS_OK;
-      }
-    }
-    kws_set_error("net_debug_view: bn index %d", index);
-    return KWS_E_INVALID;
-  } else {
-    kws_set_error("net_debug_view: unknown view %d", what);
-    return KWS_E_INVALID;
-  }
-  return KWS_OK;
-}
-
-int TdProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                       hipStream_t st) const {
-  TdLayout lo;
-  td_layout(*this, B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(td_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, st));
-  kws_flat_tail_args t = td_tail_args(*this, lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int TdProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                     hipStream_t st) const {
-  const TdProgram& p = *this;
-  TdLayout lo;
-  td_layout(p, B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  KWS_TRY(td_forward(p, lo, params, state, x, B, true, ws, st));
-  int cur = 0;
-  kws_flat_tail_args t = td_tail_args(p, lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.dA[cur], ws + lo.per_loss, ws + lo.per_correct, seed, step,
-                              loss_batch, row_offset, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.D, p.NC, ws + lo.swg, st));
-  for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
-    const TdBlock& b = p.blocks[i];
-    kws_gconv_t pw = b.pw;
-    pw.B = B;
-    const int64_t M = (int64_t)B * pw.Lout;
-    const kws_gbn_cols cols = kws_gbn_grouped(pw.g, pw.Ng);
-    // dA[cur]: gradient wrt the block's activated output -> dy (gate + BatchNorm backward) -> the pointwise kernels' gradients and
-    // dz -> the depthwise kernels' gradients and the gradient wrt the block's activated input
-    KWS_TRY(kws_gbn_bwd(ws + lo.dA[cur], ws + lo.y[i], ws + lo.bn[i], nullptr, M, &cols, ws + lo.part, ws + lo.coef, grads + b.gamma0,
-                        b.pstride, b.beta_off, st));
-    KWS_TRY(kws_gconv_wgrad_f32(ws + lo.z[i], nullptr, 0, ws + lo.dA[cur], grads + b.pw0, ws + lo.wws, &pw, st));
-    KWS_TRY(kws_gconv_dgrad_f32(ws + lo.dA[cur], params + b.pw0, ws + lo.dA[cur ^ 1], &pw, st));
-    cur ^= 1;
-    const TdInput in = td_input(p, lo, i, params, ws, B);
-    KWS_TRY(kws_gdwconv_bwd_f32(in.in, in.tab, ws + lo.dA[cur], params + b.dw0, ws + lo.dA[cur ^ 1], grads + b.dw0,
-                                nullptr, ws + lo.dwws, &in.d, st));
-    cur ^= 1;
-  }
-  // the front bias cancels in block 1's BatchNorm on batch statistics: its gradient is exactly 0, not the float32 residue (1e-5)
-  // that the column sum of dA[cur] would leave
-  KWS_HIP(hipMemsetAsync(grads + p.bias0, 0, sizeof(float) * p.C0, st));
-  // dA[cur] = gradient wrt the front convolution's output
-  KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, ws + lo.dA[cur], ws + lo.dw0p, B, p.C0, ws + lo.tnws, st));
-  KWS_HIP(hipMemcpyAsync(grads + p.conv0, ws + lo.dw0p, sizeof(float) * p.K0 * p.C0, hipMemcpyDeviceToDevice, st));
-  return KWS_OK;
-}
-
-}  // namespace
-
-int td_build(kws_net* n) {
-  const kws_net_config_t& c = n->cfg;
-  TdProgram* p = new TdProgram();
-  n->program.reset(p);
-  p->NC = c.num_classes;
-  // the ladder's lengths are 45, 43, 21, 19, 9, 7, 3, 1 at 91 rows, the fewest that leave one: 14879 samples.  The gathered GEMM
-  // loads pairs of samples, so clips must start on even offsets (conv_1d_fast's rule): the first size it takes is 14880
-  KWS_REQUIRE(c.input_size >= 14879 && c.input_size % 2 == 0,
-              "net: conv_1d_top_down input_size %d (even, >= 14879: the ladder needs 91 rows of 160 samples)", c.input_size);
-  KerasNames kn{n};
-  p->L0 = (c.input_size - p->K0) / 160 + 1;
-  p->conv0 = kn.conv(p->K0, 1, p->C0, 0.f);
-  p->bias0 = kws_net_add_tensor(n, "conv1d_1/bias", {p->C0}, false, 0.f, 0, 0, 0.f);
-  p->g0.L_out = p->L0; p->g0.cin = p->K0p; p->g0.taps = 1; p->g0.stride_t = 160; p->g0.stride_j = 0; p->g0.base_off = 0;
-  p->g0.x_len = c.input_size; p->g0.x_batch_stride = c.input_size;
-  struct { int F, g, nch, stride; } spec[8] = {{420, 3, 480, 2}, {420, 2, 420, 1}, {360, 3, 300, 2}, {360, 2, 360, 1},
-                                               {300, 3, 360, 2}, {300, 2, 300, 1}, {240, 3, 300, 2}, {240, 2, 240, 1}};
-  int L = p->L0, C = p->C0;
-  for (int i = 0; i < 8; ++i) {
-    KWS_TRY(td_add_block(kn, p, L, C, spec[i].F, spec[i].g, spec[i].nch, spec[i].stride, spec[i].stride == 1));
-    L = p->blocks.back().dw.Lout;
-    C = p->blocks.back().F;
-  }
-  const TdBlock& last = p->blocks.back();
-  p->D = last.dw.Lout * last.F;
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->D, p->NC}, false, 0.f, p->D, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
-  return KWS_OK;
-}

@@ -62,28 +62,24 @@ struct IncOp {
 struct IncLayout {
   int64_t total = 0;
   std::vector<int64_t> buf, bn, grad, gadd;
-  int64_t stats = 0, part = 0, coef = 0, wws = 0, ident = 0, fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+  int64_t stats = 0, part = 0, coef = 0, wws = 0, ident = 0;
+  FlatTailWs tail;
 };
 
-struct IncProgram : NetProgram {
+struct IncProgram : FlatTailProgram<IncLayout> {
   std::vector<IncTensor> tensors;   // 0 = the network input [800, 20]
   std::vector<IncOp> ops;
   std::vector<int> convs;           // operation of Conv1D i (Keras creation order; BatchNormalization i + 1 is behind it)
-  int64_t dk = 0, db = 0;
-  int D = 0, NC = 0, top = 0;
+  int top = 0;                      // the tensor the tail reads
 
-  void layout(int B, bool training, IncLayout* lo) const;
   kws_gconv_t gdesc(const IncOp& o, int B) const;
   kws_conv1d_t cdesc(const IncOp& o, int B) const;
-  int forward(const IncLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws, hipStream_t st) const;
-  kws_flat_tail_args tail_args(const IncLayout& lo, const float* params, float* ws, int B, float* probs) const;
-
-  int64_t workspace_bytes(int B, int training) const override;
+  void layout(int B, bool training, IncLayout* lo) const override;
+  int forward(const IncLayout& lo, const NetCall& c) const override;
+  kws_flat_tail_args tail_args(const IncLayout& lo, const NetCall& c, float* probs) const override;
+  int64_t tail_grad(const IncLayout& lo) const override { return lo.grad[top]; }
+  int backward(const IncLayout& lo, const NetCall& c) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
 
 kws_gconv_t IncProgram::gdesc(const IncOp& o, int B) const {
@@ -145,17 +141,19 @@ void IncProgram::layout(int B, bool training, IncLayout* lo) const {
     lo->part = bp.take(max_part);
     lo->coef = bp.take(max_coef);
     lo->wws = bp.take(max_wws);
-    lo->fd = bp.take((int64_t)B * D);
-    lo->dl = bp.take((int64_t)B * NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * D * NC);
+    lo->tail.take(bp, B, dense.D, dense.NC);
   }
   lo->total = bp.cur * 4;
 }
 
-int IncProgram::forward(const IncLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-                        hipStream_t st) const {
+int IncProgram::forward(const IncLayout& lo, const NetCall& c) const {
+  const float* params = c.params;
+  float* state = c.state;
+  const float* x = c.x;
+  float* ws = c.ws;
+  const int B = c.B;
+  const bool training = c.training;
+  hipStream_t st = c.st;
   for (const IncOp& o : ops) {
     const IncTensor& ti = tensors[o.in];
     const IncTensor& to = tensors[o.out];
@@ -199,13 +197,13 @@ int IncProgram::forward(const IncLayout& lo, const float* params, float* state, 
   return KWS_OK;
 }
 
-kws_flat_tail_args IncProgram::tail_args(const IncLayout& lo, const float* params, float* ws, int B, float* probs) const {
+kws_flat_tail_args IncProgram::tail_args(const IncLayout& lo, const NetCall& c, float* probs) const {
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.buf[top]; t.bn = ws + lo.ident; t.Ng = tensors[top].C;
-  t.Wd = params + dk; t.bd = params + db;
+  t.y = c.ws + lo.buf[top]; t.bn = c.ws + lo.ident; t.Ng = tensors[top].C;
+  t.Wd = c.params + dense.kernel; t.bd = c.params + dense.bias;
   t.probs = probs;
-  t.B = B; t.D = D; t.F = tensors[top].C; t.NC = NC;
+  t.B = c.B; t.D = dense.D; t.F = tensors[top].C; t.NC = dense.NC;
   t.keep_prob = INC_DROP_KEEP;
   t.layer_id = 1;
   return t;
@@ -290,8 +288,9 @@ int inc_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   IncProgram* p = new IncProgram();
   n->program.reset(p);
+  p->net = n;
   KWS_REQUIRE(c.input_size == 16000, "net: inception_d1 input_size %d (the reference reshapes 16000 samples)", c.input_size);
-  p->NC = c.num_classes;
+  const int NC = p->dense.NC = c.num_classes;
   IncBuilder b{p, KerasNames{n}};
   int x = b.tensor(800, 20, false);   // Reshape([800, 20])
   x = b.conv(OP_GCONV, x, -1, 0, 32, 1, 1, false);
@@ -311,9 +310,9 @@ int inc_build(kws_net* n) {
   p->top = x;
   const IncTensor& top = p->tensors[x];
   KWS_REQUIRE(top.L == 6 && top.C == 496, "net: inception_d1 ends with [%d, %d], the head convolves [6, 496]", top.L, top.C);
-  p->D = top.L * top.C;
-  p->dk = b.kn.conv(top.L, top.C, p->NC, 0.f);   // [6, 496, NC] = the Dense kernel [2976, NC] over the t-major flatten
-  p->db = kws_net_add_tensor(n, "conv1d_" + std::to_string(b.kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->dense.D = top.L * top.C;
+  p->dense.kernel = b.kn.conv(top.L, top.C, NC, 0.f);   // [6, 496, NC] = the Dense kernel [2976, NC] over the t-major flatten
+  p->dense.bias = kws_net_add_tensor(n, "conv1d_" + std::to_string(b.kn.n_conv) + "/bias", {NC}, false, 0.f, 0, 0, 0.f);
   // backward plan: the consumers of a tensor write its gradient in the reverse of the forward order; the first overwrites
   std::vector<char> written(p->tensors.size(), 0);
   for (int i = (int)p->ops.size() - 1; i >= 0; --i) {
@@ -330,12 +329,6 @@ int inc_build(kws_net* n) {
 }
 
 namespace {
-
-int64_t IncProgram::workspace_bytes(int B, int training) const {
-  IncLayout lo;
-  layout(B, training != 0, &lo);
-  return lo.total;
-}
 
 int IncProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   IncLayout lo;
@@ -357,27 +350,14 @@ int IncProgram::debug_view(int B, int training, int what, int index, int64_t* of
   return KWS_OK;
 }
 
-int IncProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                        hipStream_t st) const {
-  IncLayout lo;
-  layout(B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(forward(lo, params, const_cast<float*>(state), x, B, false, ws, st));
-  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int IncProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                      float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                      hipStream_t st) const {
-  IncLayout lo;
-  layout(B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  KWS_TRY(forward(lo, params, state, x, B, true, ws, st));
-  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.grad[top], ws + lo.per_loss, ws + lo.per_correct, seed, step,
-                              loss_batch, row_offset, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + dk, grads + db, B, D, NC, ws + lo.swg, st));
+// the operations in descending order
+int IncProgram::backward(const IncLayout& lo, const NetCall& c) const {
+  const float* params = c.params;
+  const float* x = c.x;
+  float* grads = c.grads;
+  float* ws = c.ws;
+  const int B = c.B;
+  hipStream_t st = c.st;
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
   for (int i = (int)ops.size() - 1; i >= 0; --i) {

@@ -11,6 +11,11 @@
 //   net_mts.hip      conv_1d_multi_time_sliced
 //   net_inception.hip  inception_d1
 //   net_conv2d.hip   conv_2d_mobile, conv_2d_fast
+// The five programs whose head is the flat tail (kws_flat_tail_*) - those of net_grouped.hip, net_dwk.hip, net_time_sliced.hip,
+// net_mts.hip and net_inception.hip (GcProgram, DkProgram, TslProgram, MtProgram, IncProgram) - derive from FlatTailProgram
+// below: it owns workspace_bytes, predict and the order of a training step, and a program supplies its layout, forward,
+// tail_args and backward.  net.hip (attention tail, split step), net_logmfcc.hip and net_conv2d.hip (other tails) implement
+// NetProgram directly.
 // The BatchNorm bookkeeping all but net.hip and net_logmfcc.hip share is bncols.hip (kws_gbn_*, declared in internal.h).
 // Not part of the public C ABI.
 #pragma once
@@ -117,12 +122,98 @@ int kws_flat_tail_train(kws_flat_tail_args* t, const float* labels, float* fd, f
                         float* per_correct, uint64_t seed, uint32_t step, int loss_batch, int64_t row_offset, float* metrics,
                         hipStream_t st);
 
+// ---- the skeleton of the programs that end in the flat tail (kws_flat_tail_*: Dropout -> Dense + softmax -> loss) ------------
+// the tail's training regions: dropped features [B, D], dlogits [B, NC], the per-clip loss and hit, the weight-gradient slices
+struct FlatTailWs {
+  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
+  void take(Bump& bp, int B, int D, int NC) {
+    fd = bp.take((int64_t)B * D);
+    dl = bp.take((int64_t)B * NC);
+    per_loss = bp.take(B);
+    per_correct = bp.take(B);
+    swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * D * NC);
+  }
+};
+// what every forward / backward pass of one call receives (predict: training false, grads NULL, seed = step = row_offset = 0)
+struct NetCall {
+  const float* params;
+  float* state;   // training: moving statistics are updated
+  const float* x;
+  int B;
+  bool training;
+  float* grads;
+  float* ws;
+  uint64_t seed;
+  uint32_t step;
+  int64_t row_offset;
+  hipStream_t st;
+};
+// the Dense + softmax layer the tail ends in: its kernel and bias in params / grads (bias < 0: none), its input width, the classes
+struct FlatTailDense {
+  int64_t kernel = 0, bias = -1;
+  int D = 0, NC = 0;
+};
+// workspace_bytes, predict and train of such a program.  Layout: the program's workspace offsets, with `total` (bytes) and
+// `tail` (a FlatTailWs, taken in training).  One training step is, in stream order: [grads zeroed], forward, the tail with its
+// backward, the Dense layer's weight gradient, backward.
+template <class Layout>
+struct FlatTailProgram : NetProgram {
+  const kws_net* net = nullptr;
+  FlatTailDense dense;
+  bool zero_grads = false;   // train zeroes the net's n_params gradients in front of the forward pass
+
+  virtual void layout(int B, bool training, Layout* lo) const = 0;
+  virtual int forward(const Layout& lo, const NetCall& c) const = 0;
+  virtual kws_flat_tail_args tail_args(const Layout& lo, const NetCall& c, float* probs) const = 0;   // filled for inference
+  virtual int64_t tail_grad(const Layout& lo) const = 0;   // where the tail leaves the gradient wrt its input (float offset)
+  virtual int backward(const Layout& lo, const NetCall& c) const = 0;   // from that gradient down to the first layer
+
+  int64_t workspace_bytes(int B, int training) const override {
+    Layout lo;
+    layout(B, training != 0, &lo);
+    return lo.total;
+  }
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override {
+    Layout lo;
+    layout(B, false, &lo);
+    KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
+    const NetCall c{params, const_cast<float*>(state), x, B, false, nullptr, ws, 0, 0, 0, st};   // state is only read
+    KWS_TRY(forward(lo, c));
+    const kws_flat_tail_args t = tail_args(lo, c, probs);
+    return kws_flat_tail_launch(&t, 0, st);
+  }
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override {
+    Layout lo;
+    layout(B, true, &lo);
+    KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+    const NetCall c{params, state, x, B, true, grads, ws, seed, step, row_offset, st};
+    if (zero_grads) KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
+    KWS_TRY(forward(lo, c));
+    kws_flat_tail_args t = tail_args(lo, c, probs);
+    const FlatTailWs& w = lo.tail;
+    KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + w.fd, ws + w.dl, ws + tail_grad(lo), ws + w.per_loss, ws + w.per_correct, seed, step,
+                                loss_batch, row_offset, metrics, st));
+    KWS_TRY(kws_small_wgrad_launch(ws + w.fd, ws + w.dl, grads + dense.kernel, dense.bias >= 0 ? grads + dense.bias : nullptr, B, dense.D,
+                                   dense.NC, ws + w.swg, st));
+    return backward(lo, c);
+  }
+};
+
 // ---- the hidden Dense layer of conv_1d_gru and conv_1d_time_sliced (net_dwk.hip) ------------------------------------------
 constexpr int DK_BIAS_SLICES = 32;
 // tab [4][n] = 1 | bias (0 without one) | 0 | 1: what the flat tail reads as a BatchNorm table over the layer's output
 int dk_bias_table(const float* bias, int n, float* tab, hipStream_t st);
 // gradient wrt relu6(h + bias) -> gradient wrt h, in place on d [B, n]; bias and dbias may be NULL; part: DK_BIAS_SLICES * n floats
 int dk_bias_relu6_bwd(float* d, const float* h, const float* bias, float* dbias, int B, int n, float* part, hipStream_t st);
+// the whole layer h = in W (+ bias) backwards: d [B, H] = gradient wrt relu6(h + bias) -> wrt h (in place), dW [D, H] and dbias,
+// out [B, D] = gradient wrt in.  Scratch: WT D * H floats, tn kws_gemm_tn_workspace_floats(B, D, H), part as above
+struct DkDenseBwdScratch {
+  float *WT, *tn, *part;
+};
+int dk_dense_bwd(float* d, const float* h, const float* in, const float* W, const float* bias, float* dW, float* dbias, float* out, int B,
+                 int D, int H, const DkDenseBwdScratch& s, hipStream_t st);
 
 // ---- the k-wide depthwise-separable block of net_dwk.hip and net_mts.hip (net_sepblock.hip) ------------------------------
 // DepthwiseConv2D((1, k), strides) -> Conv1D(cout, 1) -> BatchNormalization -> relu6

@@ -35,19 +35,25 @@ struct MtBlock : SepBlock {   // all VALID at stride 1
   int end_col = -1;      // branch end: first column in the feature buffer
 };
 
-struct MtProgram : NetProgram {
-  const kws_net* net = nullptr;
+struct MtLayout {
+  int64_t total = 0;
+  std::vector<int64_t> z, y, bn, a;   // depthwise output, raw pointwise output, table, materialised activation (pool / fork)
+  int64_t stats = 0, red = 0, feat = 0, featd = 0;
+  int64_t G[2] = {0, 0}, FG = 0, DZ = 0, part = 0, coef = 0, tn = 0, WT = 0, stem = 0;
+  FlatTailWs tail;
+};
+
+struct MtProgram : FlatTailProgram<MtLayout> {
   std::vector<MtBlock> blocks;   // blocks.back() is the head's context block
-  int NC = 0, D = 0, H = 0;      // concatenated features, head width
-  int64_t ok = 0, ob = 0;        // classifier kernel and bias
+  int D = 0, H = 0;              // concatenated features, head width (the classifier is `dense`)
   float keep = 0.9f;
 
-  int64_t workspace_bytes(int B, int training) const override;
+  void layout(int B, bool training, MtLayout* lo) const override;
+  int forward(const MtLayout& lo, const NetCall& c) const override;
+  kws_flat_tail_args tail_args(const MtLayout& lo, const NetCall& c, float* probs) const override;
+  int64_t tail_grad(const MtLayout& lo) const override { return lo.G[0]; }
+  int backward(const MtLayout& lo, const NetCall& c) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
 
 constexpr float MT_DROP_KEEP = 0.9f;   // Dropout(0.1), model.py:1144, 1146
@@ -71,15 +77,8 @@ __global__ __launch_bounds__(256) void mt_cols_kernel(const float* __restrict__ 
   out[i] = in[(int64_t)b * pitch + col0 + c];
 }
 
-struct MtLayout {
-  int64_t total = 0;
-  std::vector<int64_t> z, y, bn, a;   // depthwise output, raw pointwise output, table, materialised activation (pool / fork)
-  int64_t stats = 0, red = 0, feat = 0, featd = 0;
-  int64_t G[2] = {0, 0}, FG = 0, DZ = 0, part = 0, coef = 0, tn = 0, WT = 0, stem = 0;
-  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0;
-};
-
-void mt_layout(const MtProgram& p, int B, bool training, MtLayout* lo) {
+void MtProgram::layout(int B, bool training, MtLayout* lo) const {
+  const MtProgram& p = *this;
   Bump bp;
   const int nb = (int)p.blocks.size();
   int64_t max_g = 64, max_z = 64, max_stats = 64, max_part = 64, max_tn = 64, max_w = 64, max_fork = 64, max_stem = 64;
@@ -126,11 +125,7 @@ void mt_layout(const MtProgram& p, int B, bool training, MtLayout* lo) {
     lo->tn = bp.take(max_tn);
     lo->WT = bp.take(max_w);
     lo->stem = bp.take(max_stem);
-    lo->fd = bp.take((int64_t)B * p.H);
-    lo->dl = bp.take((int64_t)B * p.NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.H * p.NC);
+    lo->tail.take(bp, B, p.H, dense.NC);
   }
   lo->total = bp.cur * 4;
 }
@@ -148,8 +143,14 @@ void mt_input(const MtProgram& p, const MtLayout& lo, int i, float* ws, const fl
 }
 
 // forward through the 31 branch blocks, the concatenation and the head's block; training: batch statistics and dropout
-int mt_forward(const MtProgram& p, const MtLayout& lo, const float* params, float* state, const float* x, int B, bool training, float* ws,
-               uint64_t seed, uint32_t step, int64_t row_offset, hipStream_t st) {
+int MtProgram::forward(const MtLayout& lo, const NetCall& c) const {
+  const MtProgram& p = *this;
+  const float* params = c.params;
+  float* state = c.state;
+  float* ws = c.ws;
+  const int B = c.B;
+  const bool training = c.training;
+  hipStream_t st = c.st;
   const int nb = (int)p.blocks.size();
   float* stats = training ? ws + lo.stats : nullptr;
   for (int i = 0; i + 1 < nb; ++i) {
@@ -157,7 +158,7 @@ int mt_forward(const MtProgram& p, const MtLayout& lo, const float* params, floa
     const int64_t M = (int64_t)B * b.Lout;
     int rows;
     if (b.src < 0) {
-      KWS_TRY(kws_stem_fwd_f32(x, params + b.dw, params + b.pw, ws + lo.y[i], B, b.Lin, b.cin, b.cout, stats, st));
+      KWS_TRY(kws_stem_fwd_f32(c.x, params + b.dw, params + b.pw, ws + lo.y[i], B, b.Lin, b.cin, b.cout, stats, st));
       rows = kws_stem_stats_rows(B, b.Lin);
     } else {
       const float *in, *bn_in;
@@ -178,7 +179,7 @@ int mt_forward(const MtProgram& p, const MtLayout& lo, const float* params, floa
   const MtBlock& h = p.blocks[nb - 1];
   const float* feat = ws + lo.feat;
   if (training) {
-    KWS_TRY(kws_dropout_fwd(ws + lo.feat, ws + lo.featd, B, p.D, p.keep, seed, step, 1, row_offset, st));
+    KWS_TRY(kws_dropout_fwd(ws + lo.feat, ws + lo.featd, B, p.D, p.keep, c.seed, c.step, 1, c.row_offset, st));
     feat = ws + lo.featd;
   }
   const int rows = kws_sep_fwd(h, params, feat, nullptr, ws + lo.z[nb - 1], ws + lo.y[nb - 1], stats, B, st);
@@ -187,15 +188,15 @@ int mt_forward(const MtProgram& p, const MtLayout& lo, const float* params, floa
 }
 
 // relu6(bn(.)) of the head's block, Dropout (layer 2), Conv1D(num_classes, 1) + bias + softmax (+ loss and its backward)
-kws_flat_tail_args mt_tail_args(const MtProgram& p, const MtLayout& lo, const float* params, float* ws, int B, float* probs) {
-  const int nb = (int)p.blocks.size();
+kws_flat_tail_args MtProgram::tail_args(const MtLayout& lo, const NetCall& c, float* probs) const {
+  const int nb = (int)blocks.size();
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.y[nb - 1]; t.bn = ws + lo.bn[nb - 1]; t.Ng = p.H;
-  t.Wd = params + p.ok; t.bd = params + p.ob;
+  t.y = c.ws + lo.y[nb - 1]; t.bn = c.ws + lo.bn[nb - 1]; t.Ng = H;
+  t.Wd = c.params + dense.kernel; t.bd = c.params + dense.bias;
   t.probs = probs;
-  t.B = B; t.D = p.H; t.F = p.H; t.NC = p.NC;
-  t.keep_prob = p.keep;
+  t.B = c.B; t.D = H; t.F = H; t.NC = dense.NC;
+  t.keep_prob = keep;
   t.layer_id = 2;
   return t;
 }
@@ -209,7 +210,8 @@ int mt_build(kws_net* n) {
   MtProgram* p = new MtProgram();
   n->program.reset(p);
   p->net = n;
-  p->NC = c.num_classes;
+  p->dense.NC = c.num_classes;
+  p->zero_grads = true;
   p->keep = MT_DROP_KEEP;
   KerasNames kn{n};
   int cur = -1, L = 0, C = 0, col = 0;   // the tensor the next block reads
@@ -260,27 +262,21 @@ int mt_build(kws_net* n) {
   }
   KWS_REQUIRE(!fail && col == 5 * MT_END_WIDTH, "net: conv_1d_multi_time_sliced ladders do not end in five one-step tensors");
   p->D = col;
-  p->H = MT_HEAD_WIDTH;
+  p->H = p->dense.D = MT_HEAD_WIDTH;
   cur = -1; L = 1; C = p->D;
   add(p->H, 1, false);   // _context_conv(128, 1) over the concatenation
   p->blocks.back().onload = false;
-  p->ok = kn.conv(1, p->H, p->NC, 0.f);
-  p->ob = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+  p->dense.kernel = kn.conv(1, p->H, c.num_classes, 0.f);
+  p->dense.bias = kws_net_add_tensor(n, "conv1d_" + std::to_string(kn.n_conv) + "/bias", {c.num_classes}, false, 0.f, 0, 0, 0.f);
   return KWS_OK;
 }
 
 namespace {
 
-int64_t MtProgram::workspace_bytes(int B, int training) const {
-  MtLayout lo;
-  mt_layout(*this, B, training != 0, &lo);
-  return lo.total;
-}
-
 int MtProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   const MtProgram& p = *this;
   MtLayout lo;
-  mt_layout(p, B, training != 0, &lo);
+  layout(B, training != 0, &lo);
   KWS_REQUIRE(index >= 0 && index < (int)p.blocks.size(), "net_debug_view: block index %d", index);
   const MtBlock& b = p.blocks[index];
   if (what == 0) {          // raw pointwise output of block `index` (creation order)
@@ -296,36 +292,21 @@ int MtProgram::debug_view(int B, int training, int what, int index, int64_t* off
   return KWS_OK;
 }
 
-int MtProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                       hipStream_t st) const {
-  MtLayout lo;
-  mt_layout(*this, B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  KWS_TRY(mt_forward(*this, lo, params, const_cast<float*>(state), x, B, false, ws, 0, 0, 0, st));
-  kws_flat_tail_args t = mt_tail_args(*this, lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int MtProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                     hipStream_t st) const {
+// the head's context block, then the 31 branch blocks
+int MtProgram::backward(const MtLayout& lo, const NetCall& c) const {
   const MtProgram& p = *this;
-  MtLayout lo;
-  mt_layout(p, B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
+  const float* params = c.params;
+  const float* x = c.x;
+  float* grads = c.grads;
+  float* ws = c.ws;
+  const int B = c.B;
+  hipStream_t st = c.st;
   const int nb = (int)p.blocks.size();
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
-  KWS_TRY(mt_forward(p, lo, params, state, x, B, true, ws, seed, step, row_offset, st));
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
   float* FG = ws + lo.FG;
   float* part = ws + lo.part;
   float* coef = ws + lo.coef;
   const SepBwdScratch scratch = {ws + lo.WT, ws + lo.DZ, ws + lo.tn, part, coef};
-  // ---- head ----
-  kws_flat_tail_args t = mt_tail_args(p, lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, G[0], ws + lo.per_loss, ws + lo.per_correct, seed, step, loss_batch,
-                              row_offset, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.ok, grads + p.ob, B, p.H, p.NC, ws + lo.swg, st));
   float* dcat = ws + lo.featd;   // gradient wrt the concatenated features [B, 320], over the dropped features once they are spent
   {
     const MtBlock& h = p.blocks[nb - 1];
@@ -333,7 +314,7 @@ int MtProgram::train(const float* params, float* state, const float* x, const fl
     KWS_TRY(kws_gbn_layer_bwd(G[0], ws + lo.y[nb - 1], ws + lo.bn[nb - 1], nullptr, B, kws_gbn_grouped(1, h.cout), part, coef, grads,
                               h.bn, st));
     KWS_TRY(kws_sep_bwd(h, params, grads, G[0], ws + lo.z[nb - 1], ws + lo.featd, nullptr, nullptr, G[0], scratch, B, st));
-    KWS_TRY(kws_dropout_bwd(G[0], dcat, B, p.D, p.keep, seed, step, 1, row_offset, st));
+    KWS_TRY(kws_dropout_bwd(G[0], dcat, B, p.D, p.keep, c.seed, c.step, 1, c.row_offset, st));
   }
   // ---- the 31 branch blocks, descending: `grad` = what arrives at block i, wrt its output (is_dy false) or its raw y (true) ----
   float* grad = nullptr;

@@ -28,16 +28,16 @@ struct TslLayout {
   Dw3Offsets a;                  // the ladder's activations, BatchNorm tables and transposed pointwise kernels
   int64_t part = 0, red = 0, feat = 0, fd1 = 0, h = 0, tab = 0;
   int64_t G[2] = {0, 0}, DZ = 0, coef = 0, tn = 0, tns = 0, tns_cap = 0, WTd = 0, fcws = 0;
-  int64_t fd = 0, dl = 0, per_loss = 0, per_correct = 0, swg = 0, bpart = 0;
+  FlatTailWs tail;
+  int64_t bpart = 0;
 };
 
-struct TslProgram : NetProgram {
-  const kws_net* net = nullptr;
+struct TslProgram : FlatTailProgram<TslLayout> {
   int L_in = 0, pad1 = 0;
   int64_t conv1 = 0;
   Dw3Ladder lad;   // L1, C1, bn1: the first convolution's output
-  int T = 0, C = 0, H = 0, NC = 0;
-  int64_t d1k = 0, d2k = 0;
+  int T = 0, C = 0, H = 0;
+  int64_t d1k = 0;
 
   kws_frame_conv_t frame(int B) const {
     kws_frame_conv_t d;
@@ -45,18 +45,21 @@ struct TslProgram : NetProgram {
     d.N = lad.C1; d.x_batch_stride = L_in;
     return d;
   }
-  void make_layout(int B, bool training, TslLayout* lo) const;
-  int forward(const TslLayout& lo, const Dw3Run& r, const float* x, bool training, uint64_t seed, uint32_t step, int64_t row_offset) const;
-  kws_flat_tail_args tail_args(const TslLayout& lo, const float* params, float* ws, int B, float* probs) const;
-  int64_t workspace_bytes(int B, int training) const override;
+  // the ladder's view of one call; the backward scratch (pass-1 rows = the forward statistics rows, coefficients, DZ) in training only
+  Dw3Run run(const TslLayout& lo, const NetCall& c) const {
+    float* ws = c.ws;
+    return Dw3Run{&lo.a, c.params, c.state, c.grads, ws, c.B, ws + lo.red, c.training ? ws + lo.part : nullptr,
+                  c.training ? ws + lo.coef : nullptr, c.training ? ws + lo.DZ : nullptr, c.st};
+  }
+  void layout(int B, bool training, TslLayout* lo) const override;
+  int forward(const TslLayout& lo, const NetCall& c) const override;
+  kws_flat_tail_args tail_args(const TslLayout& lo, const NetCall& c, float* probs) const override;
+  int64_t tail_grad(const TslLayout& lo) const override { return lo.G[0]; }
+  int backward(const TslLayout& lo, const NetCall& c) const override;
   int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
 };
 
-void TslProgram::make_layout(int B, bool training, TslLayout* lo) const {
+void TslProgram::layout(int B, bool training, TslLayout* lo) const {
   Bump bp;
   const kws_frame_conv_t fc = frame(B);
   const Dw3Sizes s = lad.sizes(B);
@@ -84,25 +87,15 @@ void TslProgram::make_layout(int B, bool training, TslLayout* lo) const {
     for (const Dw3Block& b : lad.blocks) lo->tns_cap += (kws_gemm_tn_workspace_floats((int64_t)B * b.Lout, b.cin, b.cout) + 63) / 64 * 64;
     lo->tns = bp.take(lo->tns_cap);
     lo->fcws = bp.take(kws_frame_conv_wgrad_workspace_floats(&fc));
-    lo->fd = bp.take((int64_t)B * H);
-    lo->dl = bp.take((int64_t)B * NC);
-    lo->per_loss = bp.take(B);
-    lo->per_correct = bp.take(B);
-    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * H * NC);
+    lo->tail.take(bp, B, H, dense.NC);
     lo->bpart = bp.take((int64_t)DK_BIAS_SLICES * H);
   }
   lo->total = bp.cur * 4;
 }
 
-int64_t TslProgram::workspace_bytes(int B, int training) const {
-  TslLayout lo;
-  make_layout(B, training != 0, &lo);
-  return lo.total;
-}
-
 int TslProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
   TslLayout lo;
-  make_layout(B, training != 0, &lo);
+  layout(B, training != 0, &lo);
   if (what >= 0 && what <= 2) return lad.debug_view(lo.a, B, what, index, offset_floats, count);
   if (what == 4) {   // the hidden Dense layer's output before relu6 [B, H]
     *offset_floats = lo.h;
@@ -116,81 +109,62 @@ int TslProgram::debug_view(int B, int training, int what, int index, int64_t* of
 
 // first convolution, blocks, pool + Dropout(.4) and the hidden Dense product; training: batch statistics (moving averages updated)
 // and the masks
-int TslProgram::forward(const TslLayout& lo, const Dw3Run& r, const float* x, bool training, uint64_t seed, uint32_t step,
-                        int64_t row_offset) const {
-  const int nb = lad.nb(), B = r.B;
-  const float* params = r.params;
-  float* ws = r.ws;
-  hipStream_t st = r.st;
-  float* stats = training ? r.part : nullptr;
+int TslProgram::forward(const TslLayout& lo, const NetCall& c) const {
+  const Dw3Run r = run(lo, c);
+  const int nb = lad.nb(), B = c.B;
+  const float* params = c.params;
+  float* ws = c.ws;
+  hipStream_t st = c.st;
+  const bool training = c.training;
+  float* stats = r.part;   // NULL in inference
   if (!training) KWS_TRY(lad.infer_tables(r));
   {
     const kws_frame_conv_t fc = frame(B);
     const BnRef& bn1 = lad.bn1;
-    KWS_TRY(kws_frame_conv_fwd_f32(x, params + conv1, r.y(0), stats, &fc, st));
+    KWS_TRY(kws_frame_conv_fwd_f32(c.x, params + conv1, r.y(0), stats, &fc, st));
     if (training)
       KWS_TRY(kws_bn_stats_finalize(stats, kws_frame_conv_stats_rows(&fc), (int64_t)B * lad.L1, lad.C1, params + bn1.gamma,
                                     params + bn1.beta, KWS_BN_EPS, KWS_BN_MOMENTUM, r.state + bn1.mm, r.state + bn1.mv, r.bn_at(0), r.red, st));
   }
   for (int i = 0; i < nb; ++i) KWS_TRY(lad.fwd_block_f32(i, r, stats, nullptr));
-  KWS_TRY(kws_gap_drop_fwd_f32(r.y(nb), r.bn_at(nb), ws + lo.feat, ws + lo.fd1, B, T, C, training ? TSL_KEEP1 : 1.f, seed, step, 1,
-                               row_offset, st));
+  KWS_TRY(kws_gap_drop_fwd_f32(r.y(nb), r.bn_at(nb), ws + lo.feat, ws + lo.fd1, B, T, C, training ? TSL_KEEP1 : 1.f, c.seed, c.step, 1,
+                               c.row_offset, st));
   KWS_TRY(kws_gemm_nn_f32(ws + lo.fd1, params + d1k, ws + lo.h, B, C, H, nullptr, st));
   return dk_bias_table(nullptr, H, ws + lo.tab, st);
 }
 
 // relu6 + Dropout(.3) of the hidden layer, Dense + softmax (+ loss and its backward): the flat tail over (h, table 1 | 0 | 0 | 1)
-kws_flat_tail_args TslProgram::tail_args(const TslLayout& lo, const float* params, float* ws, int B, float* probs) const {
+kws_flat_tail_args TslProgram::tail_args(const TslLayout& lo, const NetCall& c, float* probs) const {
   kws_flat_tail_args t;
   memset(&t, 0, sizeof(t));
-  t.y = ws + lo.h; t.bn = ws + lo.tab; t.Ng = H;
-  t.Wd = params + d2k; t.bd = nullptr;
+  t.y = c.ws + lo.h; t.bn = c.ws + lo.tab; t.Ng = H;
+  t.Wd = c.params + dense.kernel; t.bd = nullptr;
   t.probs = probs;
-  t.B = B; t.D = H; t.F = H; t.NC = NC;
+  t.B = c.B; t.D = H; t.F = H; t.NC = dense.NC;
   t.keep_prob = TSL_KEEP2;
   t.layer_id = 2;
   return t;
 }
 
-int TslProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                        hipStream_t st) const {
-  TslLayout lo;
-  make_layout(B, false, &lo);
-  KWS_TRY(kws_workspace_check("net_predict", lo.total, ws_bytes, B));
-  const Dw3Run r{&lo.a, params, const_cast<float*>(state), nullptr, ws, B, ws + lo.red, nullptr, nullptr, nullptr, st};   // state is only read
-  KWS_TRY(forward(lo, r, x, false, 0, 0, 0));
-  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
-  return kws_flat_tail_launch(&t, 0, st);
-}
-
-int TslProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                      float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                      hipStream_t st) const {
-  TslLayout lo;
-  make_layout(B, true, &lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", lo.total, ws_bytes, B));
-  const int nb = lad.nb();
-  float* part = ws + lo.part;
-  float* coef = ws + lo.coef;
-  float* DZ = ws + lo.DZ;
+// G[0] = gradient wrt relu6(h) [B, H] -> wrt h; dense_1's gradients; back through Dropout(.4) and the pool; then the blocks
+int TslProgram::backward(const TslLayout& lo, const NetCall& c) const {
+  const Dw3Run r = run(lo, c);
+  const int nb = lad.nb(), B = c.B;
+  const float* params = c.params;
+  float* grads = c.grads;
+  float* ws = c.ws;
+  hipStream_t st = c.st;
+  float* part = r.part;
+  float* coef = r.coef;
+  float* DZ = r.DZ;
   float* G[2] = {ws + lo.G[0], ws + lo.G[1]};
-  const Dw3Run r{&lo.a, params, state, grads, ws, B, ws + lo.red, part, coef, DZ, st};
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
-  KWS_TRY(forward(lo, r, x, true, seed, step, row_offset));
-  // ---- head: G[0] = gradient wrt relu6(h) [B, H] -> wrt h; the two dense kernels' gradients; back through Dropout(.4) and the pool
-  kws_flat_tail_args t = tail_args(lo, params, ws, B, probs);
-  KWS_TRY(kws_flat_tail_train(&t, y_onehot, ws + lo.fd, ws + lo.dl, G[0], ws + lo.per_loss, ws + lo.per_correct, seed, step, loss_batch,
-                              row_offset, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + d2k, nullptr, B, H, NC, ws + lo.swg, st));
-  KWS_TRY(dk_bias_relu6_bwd(G[0], ws + lo.h, nullptr, nullptr, B, H, ws + lo.bpart, st));
-  KWS_TRY(kws_gemm_tn_f32(ws + lo.fd1, G[0], grads + d1k, B, C, H, ws + lo.tn, st));
-  KWS_TRY(kws_transpose_f32(params + d1k, ws + lo.WTd, C, H, st));
-  KWS_TRY(kws_gemm_nn_f32(G[0], ws + lo.WTd, DZ, B, H, C, nullptr, st));
+  KWS_TRY(dk_dense_bwd(G[0], ws + lo.h, ws + lo.fd1, params + d1k, nullptr, grads + d1k, nullptr, DZ, B, C, H,
+                       {ws + lo.WTd, ws + lo.tn, ws + lo.bpart}, st));
   {   // DZ = gradient wrt the dropped features [B, C] (DZ holds B * T * C floats for the last block) -> G[nb % 2] = gated gradient
       // wrt relu6(bn(y)) [B, T, C] -> dy of the last block's pointwise output, in place
     const Dw3Block& b = lad.blocks[nb - 1];
     float* g = G[nb % 2];
-    KWS_TRY(kws_gap_drop_bwd_f32(DZ, r.y(nb), r.bn_at(nb), g, part, B, T, C, TSL_KEEP1, seed, step, 1, row_offset, st));
+    KWS_TRY(kws_gap_drop_bwd_f32(DZ, r.y(nb), r.bn_at(nb), g, part, B, T, C, TSL_KEEP1, c.seed, c.step, 1, c.row_offset, st));
     KWS_TRY(kws_gbn_layer_bwd_finish(g, r.y(nb), r.bn_at(nb), (int64_t)B * T, kws_gbn_grouped(1, b.cout), part,
                                      kws_gap_drop_bwd_part_rows(B, T, C), coef, grads, b.bn, st));
   }
@@ -208,7 +182,7 @@ int TslProgram::train(const float* params, float* state, const float* x, const f
   KWS_TRY(q.flush(st));
   // G[0] = dy of the first convolution; its input is the waveform: no input gradient
   const kws_frame_conv_t fc = frame(B);
-  return kws_frame_conv_wgrad_f32(x, G[0], grads + conv1, ws + lo.fcws, &fc, st);
+  return kws_frame_conv_wgrad_f32(c.x, G[0], grads + conv1, ws + lo.fcws, &fc, st);
 }
 
 }  // namespace
@@ -243,9 +217,11 @@ int tsl_build(kws_net* n) {
   p->T = lad.blocks.back().Lout;
   p->C = lad.blocks.back().cout;
   p->H = 256 * fm;
-  p->NC = c.num_classes;
+  p->dense.NC = c.num_classes;
+  p->dense.D = p->H;
+  p->zero_grads = true;
   KWS_REQUIRE(p->T <= 16, "net: %d time steps at the pool (max 16)", p->T);
   p->d1k = kws_net_add_tensor(n, "dense_1/kernel", {p->C, p->H}, false, 0.f, p->C, p->H, 0.f);
-  p->d2k = kws_net_add_tensor(n, "dense_2/kernel", {p->H, p->NC}, false, KWS_L2_COEF, p->H, p->NC, 0.f);
+  p->dense.kernel = kws_net_add_tensor(n, "dense_2/kernel", {p->H, p->dense.NC}, false, KWS_L2_COEF, p->H, p->dense.NC, 0.f);
   return KWS_OK;
 }

@@ -5,7 +5,8 @@ The Keras tensor names, their order and their offsets in the flat parameter / st
 (DeviceNet.set_weights, the .npz checkpoints, the buffer RCCL all-reduces), so tests/golden/net_tensor_tables.json pins
 them: tests/test_net_tables_cpu.py compares the library's tables with it row by row.  The file was recorded at the commit
 before the residual-family builders were put on one shared block planner; re-record it only when a table is MEANT to
-change, and say so in that commit.
+change, and say so in that commit.  The last six configs were added later, recorded at the commit before the flat-tail
+programs were put on one skeleton; the entries recorded earlier came out byte for byte as they were.
 
 One row per tensor: [name, shape, offset, is_state, l2, fan_in, fan_out, init] (l2 and init as the shortest decimal that
 gives the float32 back)."""
@@ -41,6 +42,12 @@ CONFIGS = {
     'conv_1d_multi_time_sliced': (_lib.KWS_NET_CONV_1D_MULTI_TIME_SLICED, 12, 1, 16000, 0, 0),
     'conv_1d_time_sliced': (_lib.KWS_NET_CONV_1D_TIME_SLICED, 12, 1, 16000, 0, 0),
     'conv_1d_time_sliced_x2': (_lib.KWS_NET_CONV_1D_TIME_SLICED, 12, 2, 12000, 0, 0),
+    'xception_with_attention': (_lib.KWS_NET_XCEPTION_ATTENTION, 12, 1, 16000, 0, 0),
+    'inception_d1': (_lib.KWS_NET_INCEPTION_D1, 12, 1, 16000, 0, 0),
+    'conv_2d_mobile': (_lib.KWS_NET_CONV_2D_MOBILE, 12, 1, 98 * 40, 0, 0),
+    'conv_2d_fast': (_lib.KWS_NET_CONV_2D_FAST, 12, 1, 98 * 40, 0, 0),
+    'conv_1d_learned_spec': (_lib.KWS_NET_CONV_1D_LEARNED_SPEC, 12, 1, 16000, 0, 0),
+    'conv_1d_top_down': (_lib.KWS_NET_CONV_1D_TOP_DOWN, 12, 1, 16000, 0, 0),
 }
 
 

@@ -23,7 +23,9 @@ N_VIEWS = {'ts_attention': (99, 35), 'ts_attention_32_x2': (99, 35), 'log_mfcc_3
            'spectrogram': (241, 241), 'steffe': (256, 256), 'residual': (260, 260), 'residual_x2': (260, 260),
            'mfcc_and_raw': (245, 245), 'conv_1d_fast': (14, 14), 'conv_1d_spec': (36, 36), 'conv_1d_time_stacked': (26, 26),
            'conv_1d_heavy': (32, 32), 'conv_1d_gru': (82, 82), 'conv_1d_simple': (170, 106), 'conv_1d_multi_time_sliced': (64, 64),
-           'conv_1d_time_sliced': (105, 105), 'conv_1d_time_sliced_x2': (105, 105)}
+           'conv_1d_time_sliced': (105, 105), 'conv_1d_time_sliced_x2': (105, 105),
+           'xception_with_attention': (309, 309), 'inception_d1': (192, 192), 'conv_2d_mobile': (32, 32), 'conv_2d_fast': (16, 16),
+           'conv_1d_learned_spec': (29, 29), 'conv_1d_top_down': (37, 37)}
 
 
 def _mismatches(got, gold):

@@ -19,7 +19,9 @@ TABLES = _GOLD['tables']
 N_TENSORS = {'ts_attention': 74, 'ts_attention_32_x2': 74, 'log_mfcc_32': 148, 'log_mfcc_65x40': 148, 'spectrogram': 148,
              'steffe': 186, 'residual': 200, 'residual_x2': 200, 'mfcc_and_raw': 152, 'conv_1d_fast': 58, 'conv_1d_spec': 142,
              'conv_1d_time_stacked': 67, 'conv_1d_heavy': 81, 'conv_1d_gru': 40, 'conv_1d_simple': 92,
-             'conv_1d_multi_time_sliced': 194, 'conv_1d_time_sliced': 85, 'conv_1d_time_sliced_x2': 85}
+             'conv_1d_multi_time_sliced': 194, 'conv_1d_time_sliced': 85, 'conv_1d_time_sliced_x2': 85,
+             'xception_with_attention': 166, 'inception_d1': 397, 'conv_2d_mobile': 50, 'conv_2d_fast': 26,
+             'conv_1d_learned_spec': 108, 'conv_1d_top_down': 124}
 
 
 def _row(t):
