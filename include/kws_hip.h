@@ -204,6 +204,15 @@ int kws_stft_plan_destroy(kws_stft_plan_t* plan);
 int kws_stft_num_frames(const kws_stft_plan_t* plan, int L);
 int kws_stft_mel_f32(const kws_stft_plan_t* plan, const float* x, int B, int L, float* out,
                      int out_kind, void* stream);
+/* Which kernel kws_stft_mel_f32 launches for (plan, x, L, out_kind); host arithmetic only, nothing
+ * is launched and kws_stft_mel_f32 itself decides through this function.  Not an error code:
+ *   0 / 1                  the generic kernel with 4 / 7 waves per workgroup (7: F % 14 == 0)
+ *   10 + 2 * shape + v4    the register-FFT kernel: shape 1..4 = its mel-band instance
+ *                          (80-band form, 5 lane groups at full width, 40-band form, 3 lane groups at
+ *                          full width), v4 = 1 with 16-byte PCM loads (L % 4 == 0, frame_step % 4 == 0,
+ *                          x 16-byte aligned), 0 with 8-byte loads
+ *   -1                     arguments kws_stft_mel_f32 refuses */
+int kws_stft_mel_kernel(const kws_stft_plan_t* plan, const float* x, int L, int out_kind);
 
 /* A/B arm, off by default (csrc/gemm_f16x2.hip; selected per net handle by kws_net_set_gemm_mode(net, 2)): the pointwise
  * GEMMs with every f32 operand scaled by a power of two and split into TWO fp16 parts, three f16 MFMA products

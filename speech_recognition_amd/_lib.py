@@ -170,6 +170,7 @@ SIGNATURES = {
     "kws_stft_plan_destroy": (_I, [_P]),
     "kws_stft_num_frames": (_I, [_P, _I]),
     "kws_stft_mel_f32": (_I, [_P, _P, _I, _I, _P, _I, _P]),
+    "kws_stft_mel_kernel": (_I, [_P, _P, _I, _I]),
     "kws_gemm_num_row_tiles": (_I, [_I64]),
     "kws_gemm_nn_stats_rows": (_I, [_I64, _I, _I]),
     "kws_gemm_gather_stats_rows": (_I, [_I64]),

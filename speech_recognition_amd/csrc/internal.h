@@ -320,5 +320,6 @@ struct kws_stft_plan {
 };
 int kws_stft4_prepare(kws_stft_plan* pl);
 int kws_stft4_lds_bytes(const kws_stft_plan* pl);
+int kws_stft4_kernel_code(const kws_stft_plan* pl, const float* x, int L);   // 10 + 2 shape + v4 (a plan stft4 serves)
 int kws_stft4_launch(const kws_stft_plan* pl, const float* x, int B, int L, int F, float* out, hipStream_t st);
 

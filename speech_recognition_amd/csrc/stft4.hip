@@ -489,7 +489,9 @@ __global__ __launch_bounds__(NW4 * 64, 1) void stft4_kernel(Stft2Args a) {
         }
         // floor: a plain maximum (log_floor = 0 leaves the non-negative sum as it is) - no select on a scalar mask, which
         // issues at 1/7 of the rate of a v_max_f32 here (profiles/r02_probe_valu_rates.txt)
-        const float sm = fmaxf(((s0 + s1) + (s2 + s3)) + pl.log_offset, pl.log_floor);
+        // The maximum is the NaN-propagating one (v_maximum3_f32): fmaxf returns the floor for a NaN sum, which turned a clip
+        // of NaN samples into the features of silence wherever the plan has a floor (mfcc.cc's `if (val < floor)` keeps the NaN).
+        const float sm = __builtin_elementwise_maximum(((s0 + s1) + (s2 + s3)) + pl.log_offset, pl.log_floor);
         // v_log_f32 (log2, 1 ulp) x ln 2: sm >= the offset / floor, so none of logf's denormal handling (15 instructions
         // per band) is needed; with the f16 DCT the row carries that product's 2^9 as well (exact)
         // lanes past n_mel (band 0's weights, see r_mws) store as well: their columns meet zero rows of the DCT operand, and
@@ -682,16 +684,22 @@ static int stft4_launch_w(const Stft2Args& a, hipStream_t st) {
 // 12 waves per workgroup, DCT groups of 4 quads (16 x 2 was measured - 51.4 us against 50.3 - and is not instantiated);
 // 16-byte PCM loads whenever every frame starts on a 16-byte boundary, 8-byte loads otherwise
 template <int NB, int MC, int MCP>
-static int stft4_launch_t(const Stft2Args& a, hipStream_t st) {
-  const bool v4 = a.L % 4 == 0 && a.pl.frame_step % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
+static int stft4_launch_t(const Stft2Args& a, bool v4, hipStream_t st) {
   return v4 ? stft4_launch_w<NB, MC, MCP, true, 12, 4, true>(a, st) : stft4_launch_w<NB, MC, MCP, true, 12, 4, false>(a, st);
+}
+
+// the instance kws_stft4_launch runs, as kws_stft_mel_kernel reports it: 10 + 2 shape + v4 (shape 0: stft4 declines)
+int kws_stft4_kernel_code(const kws_stft_plan* pl, const float* x, int L) {
+  const bool v4 = L % 4 == 0 && pl->frame_step % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  return 10 + 2 * stft4_shape(pl) + (v4 ? 1 : 0);
 }
 
 int kws_stft4_launch(const kws_stft_plan* pl, const float* x, int B, int L, int F, float* out, hipStream_t st) {
   KWS_REQUIRE(pl->n_out <= 64 && pl->n_mel % 4 == 0 && pl->n_mel <= 128, "stft4: n_mel=%d n_out=%d unsupported",
               pl->n_mel, pl->n_out);
   KWS_REQUIRE(F > 0 && (pl->frame_step % 2) == 0 && (L % 2) == 0 && (pl->frame_len % 2) == 0, "stft4: bad geometry");
-  const int sh = stft4_shape(pl);
+  const int code = kws_stft4_kernel_code(pl, x, L), sh = (code - 10) >> 1;
+  const bool v4 = (code & 1) != 0;
   KWS_REQUIRE(pl->img4 != nullptr, "stft4: the plan carries no table image (kws_stft4_prepare)");
   KWS_REQUIRE(sh != 0, "stft4: mel band shape (n_mel=%d, up to %d taps) is not instantiated", pl->n_mel, pl->mel_maxw);
   KWS_REQUIRE((int64_t)B * ((F + 3) / 4) < (1ll << 31), "stft4: %d clips x %d frames exceed 2^31 frame quads", B, F);
@@ -700,8 +708,8 @@ int kws_stft4_launch(const kws_stft_plan* pl, const float* x, int B, int L, int 
   a.x = x; a.out = out; a.B = B; a.L = L; a.F = F;
   a.quads_per_clip = (F + 3) / 4;
   a.total_quads = (int64_t)B * a.quads_per_clip;
-  if (sh == 1) return stft4_launch_t<5, 4, 0x43221>(a, st);
-  if (sh == 2) return stft4_launch_t<5, 4, 0x44444>(a, st);
-  if (sh == 3) return stft4_launch_t<3, 8, 0x852>(a, st);
-  return stft4_launch_t<3, 8, 0x888>(a, st);
+  if (sh == 1) return stft4_launch_t<5, 4, 0x43221>(a, v4, st);
+  if (sh == 2) return stft4_launch_t<5, 4, 0x44444>(a, v4, st);
+  if (sh == 3) return stft4_launch_t<3, 8, 0x852>(a, v4, st);
+  return stft4_launch_t<3, 8, 0x888>(a, v4, st);
 }

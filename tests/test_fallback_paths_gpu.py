@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import stft_cases as SC
 from oracle import features as OF
 from speech_recognition_amd import _lib
 
@@ -79,9 +80,9 @@ def test_stft_features_from_an_unaligned_batch():
         dx.copy_(torch.from_numpy(x))
         assert dx.data_ptr() % 16 == (8 if off == 2 else 0)
         got = _features(plan, dx, B, L, 60)
-        ref = OF.features(x.astype(np.float64), t, 160)
+        _, lm, ref = OF.features(x.astype(np.float64), t, 160, return_all=True)
         assert got.shape == ref.shape and np.all(np.isfinite(got))
-        assert np.abs(got - ref).max() < 2e-3      # the bar of tests/test_kernels_gpu.py::test_stft_mel_features
+        assert np.abs(got - ref).max() <= SC.mfcc_bar(t, lm)      # tests/stft_cases.py: the log-mel bar through the DCT
     _lib.load().kws_stft_plan_destroy(plan)
 
 
@@ -93,6 +94,6 @@ def test_stft_features_of_a_mel_shape_stft4_does_not_instantiate():
     B, L = 4, 16000
     x = (rng.randn(B, L) * 0.0774).astype(np.float32)
     got = _features(plan, torch.from_numpy(x).cuda(), B, L, 32)
-    ref = OF.features(x.astype(np.float64), t, 160)
-    assert np.abs(got - ref).max() < 2e-3      # the bar of tests/test_kernels_gpu.py::test_stft_mel_features
+    _, lm, ref = OF.features(x.astype(np.float64), t, 160, return_all=True)
+    assert np.abs(got - ref).max() <= SC.mfcc_bar(t, lm)      # tests/stft_cases.py: the log-mel bar through the DCT
     _lib.load().kws_stft_plan_destroy(plan)
