@@ -137,6 +137,34 @@ int kws_time_stretch_f32(const kws_stretch_plan_t* plan, const float* x, float i
 int kws_time_stretch_i16(const kws_stretch_plan_t* plan, const int16_t* x, float* out, int B, int keep,
                          int quantize, void* stream);
 
+/* Rational polyphase resampling of wav rows (csrc/resample.hip): scipy.signal.resample_poly(x, up, down) at its defaults
+ * (window ('kaiser', 5.0), padtype 'constant').  g = gcd(rate_out, rate_in), up = rate_out / g, down = rate_in / g,
+ * mx = max(up, down), half = 10 mx; the prototype has 2 half + 1 taps h[j] = up w[j] fc sinc(fc (j - half)) / S with
+ * fc = 1 / mx, w = kaiser(2 half + 1, 5.0) and S the sum of the unscaled windowed taps;
+ *   y[n] = sum_j h[j] xu[n down + half - j],  xu[i up] = x[i], zero elsewhere;  n_out = ceil(n_in up / down);
+ * taps_per_phase = ceil((2 half + 1) / up) taps meet a sample per output.  Equal rates (up = down = 1) are a copy.
+ * Rates < 1 or max(up, down) > 65536 are KWS_E_INVALID.
+ * The first three calls are host-only (no device is touched).  The design and out_samples calls write / return the numbers
+ * above (NULL pointers are skipped); the taps call returns the prototype in natural order, designed in double and rounded to
+ * float once - the floats the kernels multiply with; n must be 2 half + 1. */
+int kws_resample_design(int rate_in, int rate_out, int* up, int* down, int* half_len, int* taps_per_phase);
+int kws_resample_taps(int rate_in, int rate_out, float* h, int64_t n);
+int64_t kws_resample_out_samples(int rate_in, int rate_out, int64_t n_in);
+/* The plan holds the phase-major device table of one rate pair (create it on the device that runs the launches).
+ *   x        [B] rows x_pitch (>= n_in) elements apart; row b is read at [0, n_valid[b]) only
+ *   n_valid  device [B] (clamped to [0, n_in]), or NULL = n_in for every row
+ *   out      [B, keep]: the first `keep` resampled samples, zeros from ceil(n_valid up / down) on (a zero row for n_valid = 0)
+ * int16 samples enter as integers (no 1 / 32768 scale).  out_i16 = clamp(rintf(v), -32768, 32767) (round half to even) of the
+ * very v stored to out_f32; either may be NULL, not both.  Inputs must be finite.  No atomics, every element written once;
+ * a row's bits do not depend on the batch around it. */
+typedef struct kws_resample_plan kws_resample_plan_t;
+int kws_resample_plan_create(int rate_in, int rate_out, kws_resample_plan_t** plan);
+int kws_resample_plan_destroy(kws_resample_plan_t* plan);
+int kws_resample_i16(const kws_resample_plan_t* plan, const int16_t* x, int64_t x_pitch, const int32_t* n_valid, int n_in,
+                     int16_t* out_i16, float* out_f32, int B, int keep, void* stream);
+int kws_resample_f32(const kws_resample_plan_t* plan, const float* x, int64_t x_pitch, const int32_t* n_valid, int n_in,
+                     float* out, int B, int keep, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Stand-alone forms of the classifier-tail ops (the network programs below run them fused in one
  * kernel; these bind ONE reference call site each).

@@ -166,6 +166,13 @@ SIGNATURES = {
     "kws_stretch_out_samples": (_I, [_P]),
     "kws_time_stretch_f32": (_I, [_P, _P, _F, _P, _I, _I, _I, _P]),
     "kws_time_stretch_i16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "kws_resample_design": (_I, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "kws_resample_taps": (_I, [_I, _I, _P, _I64]),
+    "kws_resample_out_samples": (_I64, [_I, _I, _I64]),
+    "kws_resample_plan_create": (_I, [_I, _I, ctypes.POINTER(_P)]),
+    "kws_resample_plan_destroy": (_I, [_P]),
+    "kws_resample_i16": (_I, [_P, _P, _I64, _P, _I, _P, _P, _I, _I, _P]),
+    "kws_resample_f32": (_I, [_P, _P, _I64, _P, _I, _P, _I, _I, _P]),
     "kws_stft_plan_create": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _F, _F, ctypes.POINTER(_P)]),
     "kws_stft_plan_destroy": (_I, [_P]),
     "kws_stft_num_frames": (_I, [_P, _I]),

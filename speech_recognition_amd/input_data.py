@@ -91,6 +91,83 @@ def bank_from_files(file_row, desired_samples):
     return bank
 
 
+RATE_POLICIES = ('decode_wav', 'error', 'resample')
+RESAMPLE_CHUNK_FILES = 2048      # files per kws_resample_i16 launch of decode_wav_files
+
+
+def group_files_by_rate(filenames):
+    """[(rate, [(position in `filenames`, int16 samples)])] in ascending rate order; every file is read once."""
+    groups = {}
+    for k, fn in enumerate(filenames):
+        a, rate = _read_wav_int16(fn)
+        groups.setdefault(int(rate), []).append((k, a))
+    return sorted(groups.items())
+
+
+def check_wav_rates(filenames, sample_rate):
+    """rate_policy='error': ValueError naming the first file whose header rate differs from `sample_rate`."""
+    for fn in filenames:
+        rate = _read_wav_int16(fn)[1]
+        if rate != sample_rate:
+            raise ValueError('%s has a sample rate of %d Hz, not %d (wav_rate_policy=\'error\'; \'resample\' converts it, '
+                             '\'decode_wav\' ignores the header like DecodeWav)' % (fn, rate, sample_rate))
+
+
+def decode_wav_files(filenames, desired_samples, sample_rate, device, rate_policy='decode_wav'):
+    """The int16 clip bank rows of `filenames` as a device tensor [n, desired_samples] (row k = file k, first channel,
+    cropped / zero padded).  rate_policy:
+      'decode_wav'  the header's sample rate is ignored (DecodeWav; the bytes of bank_from_files);
+      'error'       ValueError for the first file whose rate is not `sample_rate`;
+      'resample'    files at another rate are resampled to `sample_rate` on the device (resample.py): each rate's files
+                    go up padded, with their lengths, in chunks of at most RESAMPLE_CHUNK_FILES and every chunk is one
+                    kws_resample_i16 launch that crops / pads to desired_samples; files already at `sample_rate` take the
+                    'decode_wav' path."""
+    if rate_policy not in RATE_POLICIES:
+        raise ValueError('rate_policy must be one of %r, not %r' % (RATE_POLICIES, rate_policy))
+    filenames = list(filenames)
+    if rate_policy == 'error':
+        check_wav_rates(filenames, sample_rate)
+    if rate_policy != 'resample':
+        bank = bank_from_files({fn: k for k, fn in enumerate(filenames)}, desired_samples)[:len(filenames)]
+        return torch.from_numpy(bank).to(device)
+    from . import resample as rs
+    out = torch.zeros((len(filenames), desired_samples), dtype=torch.int16, device=device)
+    for rate, files in group_files_by_rate(filenames):
+        if rate != sample_rate:
+            rs.design(rate, sample_rate)          # a rate the library refuses fails before anything is uploaded
+        for c in range(0, len(files), RESAMPLE_CHUNK_FILES):
+            chunk = files[c:c + RESAMPLE_CHUNK_FILES]
+            rows = torch.tensor([k for k, _ in chunk], dtype=torch.int64, device=device)
+            if rate == sample_rate:
+                host = np.zeros((len(chunk), desired_samples), dtype=np.int16)
+                for i, (_, a) in enumerate(chunk):
+                    host[i, :min(len(a), desired_samples)] = a[:desired_samples]
+                out[rows] = torch.from_numpy(host).to(device)
+                continue
+            # only the samples the first desired_samples outputs depend on travel: ceil(desired_samples down / up) plus the
+            # filter's reach on the right; the row's true length (capped there) still decides where the zeros start
+            up, down, half, _ = rs.design(rate, sample_rate)
+            need = -(-(desired_samples * down + half) // up) + 1
+            lens = np.array([min(len(a), need) for _, a in chunk], dtype=np.int32)
+            host = np.zeros((len(chunk), max(int(lens.max()), 1)), dtype=np.int16)
+            for i, (_, a) in enumerate(chunk):
+                host[i, :lens[i]] = a[:lens[i]]
+            o16, _ = rs.resample_rows(torch.from_numpy(host).to(device), torch.from_numpy(lens).to(device), rate, sample_rate,
+                                      desired_samples)
+            out[rows] = o16
+    return out
+
+
+def resample_recording(samples_i16, rate, sample_rate, device):
+    """One int16 recording of any length (a background noise file) at `sample_rate`, resampled as ONE long row: the int16
+    host array a file converted to `sample_rate` would hold (rounded half to even, saturated)."""
+    from . import resample as rs
+    x = torch.from_numpy(np.ascontiguousarray(samples_i16, dtype=np.int16).reshape(1, -1)).to(device)
+    keep = rs.resampled_samples(x.shape[1], rate, sample_rate)
+    o16, _ = rs.resample_rows(x, None, rate, sample_rate, keep)
+    return o16.reshape(-1).cpu().numpy()
+
+
 class _Placeholder(object):
     """Opaque feed key standing in for a tf.placeholder of the reference's processing graph."""
 
@@ -134,7 +211,14 @@ class AudioProcessor(object):
     input_data.py:159-610); see the module docstring for what runs where."""
 
     def __init__(self, data_dirs, silence_percentage, unknown_percentage, wanted_words, validation_percentage,
-                 testing_percentage, model_settings, output_representation=False, device=None):
+                 testing_percentage, model_settings, output_representation=False, device=None,
+                 wav_rate_policy='decode_wav'):
+        """wav_rate_policy (not in the reference): what a wav whose header rate is not model_settings['sample_rate'] means -
+        'decode_wav' ignores the header like the reference's DecodeWav (the default), 'error' refuses the file, 'resample'
+        converts it on the device (decode_wav_files)."""
+        if wav_rate_policy not in RATE_POLICIES:
+            raise ValueError('wav_rate_policy must be one of %r, not %r' % (RATE_POLICIES, wav_rate_policy))
+        self.wav_rate_policy = wav_rate_policy
         if not torch.cuda.is_available():
             raise _lib.KwsError("AudioProcessor needs an MI355X: augmentation and features run on the GPU "
                                 "(no CPU fallback)")
@@ -231,15 +315,34 @@ class AudioProcessor(object):
         if not os.path.exists(background_dir):
             return self.background_data
         search_path = os.path.join(background_dir, '*.wav')
-        for wav_path in sorted(glob.glob(search_path)):
-            self.background_data.append(load_wav_file(wav_path))
+        paths = sorted(glob.glob(search_path))
+        policy = getattr(self, 'wav_rate_policy', 'decode_wav')
+        rate_out = self.model_settings['sample_rate'] if policy != 'decode_wav' else None
+        if policy == 'error':
+            check_wav_rates(paths, rate_out)
+        for wav_path in paths:
+            if policy == 'resample':
+                a, rate = _read_wav_int16(wav_path)
+                if rate != rate_out:
+                    a = resample_recording(a, rate, rate_out, self.device)
+                self.background_data.append(a.astype(np.float32) / np.float32(32768.0))
+            else:
+                self.background_data.append(load_wav_file(wav_path))
         if not self.background_data:
             raise Exception('No background wav files were found in ' + search_path)
 
     def _build_bank(self):
         """Decode every distinct file of the index once into the int16 HBM clip bank."""
-        bank = bank_from_files(self._file_row, self.model_settings['desired_samples'])
-        self.bank = ClipBank(torch.from_numpy(bank).to(self.device), self.background_data, self.device)
+        L = self.model_settings['desired_samples']
+        if self.wav_rate_policy == 'decode_wav':
+            clips = torch.from_numpy(bank_from_files(self._file_row, L)).to(self.device)
+        else:
+            files = sorted(self._file_row, key=self._file_row.get)          # row r = file r
+            assert [self._file_row[fn] for fn in files] == list(range(len(files)))
+            clips = decode_wav_files(files, L, self.model_settings['sample_rate'], self.device, self.wav_rate_policy)
+            if not files:
+                clips = torch.zeros((1, L), dtype=torch.int16, device=self.device)
+        self.bank = ClipBank(clips, self.background_data, self.device)
 
     def _init_synthetic(self, spec, wanted_words):
         """Synthetic source (bench.py / tests): spec = {'bank': ClipBank, 'index': {set: [(row, word)]}}.
