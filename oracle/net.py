@@ -377,7 +377,7 @@ class ResidualFamilyNet(object):
                     pad=(pl, pr), Lin=Lin, Lout=Lout)
 
     def _add_dense(self, fin, bias=True):
-        """Dense(num_classes) over the pooled features; closes the table (twin of lm_add_dense)."""
+        """Dense(num_classes) over the pooled features; closes the table (twin of LmHead::add_dense)."""
         self.params['dense_1/kernel'] = glorot_uniform(self.kn.rng, (fin, self.num_classes), fin, self.num_classes)
         if bias:
             self.params['dense_1/bias'] = np.zeros((self.num_classes,), np.float32)

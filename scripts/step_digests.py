@@ -10,7 +10,9 @@ and conv_1d_time_sliced under modes 0 and 1.
 for pool2d.hip and conv_1d_time_sliced for gap.hip.
 --set flat_tail: the twelve configs of the five programs on the flat-tail skeleton (FlatTailProgram, csrc/net_internal.h): the eight
 models above, conv_1d_learned_spec, conv_1d_top_down and conv_1d_time_sliced at filter_mult 1 / 16000 and filter_mult 2 / 12000.
-usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder|pools|flat_tail] [--out FILE]"""
+--set residual: the eight residual-family configs of tests/golden/make_golden_net_tables.py (LmProgram, csrc/net_logmfcc.hip), each under
+GEMM modes 0 and 1 (mode 1, the reference schedule, takes the unfused, unpaired branches) and log_mfcc_32 under mode 2 as well.
+usage: [KWS_LIB_PATH=other/libkws_hip.so] python3 scripts/step_digests.py [--set bncols|ladder|pools|flat_tail|residual] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -52,6 +54,16 @@ FLAT_TAIL = [m + (1,) for m in MODELS] + [  # (name, kind, input_size, filter_mu
     ('conv_1d_time_sliced_fm1_16000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 16000, 1),
     ('conv_1d_time_sliced_fm2_12000', _lib.KWS_NET_CONV_1D_TIME_SLICED, 12000, 2),
 ]
+RESIDUAL = [  # (name, kind, num_classes, filter_mult, input_size, spectrogram_length, num_features, gemm modes)
+    ('log_mfcc_32', _lib.KWS_NET_LOG_MFCC, 32, 1, 98 * 40, 98, 40, (0, 1, 2)),
+    ('log_mfcc_65x40', _lib.KWS_NET_LOG_MFCC, 12, 1, 65 * 40, 65, 40, (0, 1)),
+    ('spectrogram', _lib.KWS_NET_LOG_MFCC, 12, 1, 98 * 257, 98, 257, (0, 1)),
+    ('steffe', _lib.KWS_NET_STEFFE, 12, 1, 16000, 0, 0, (0, 1)),
+    ('residual', _lib.KWS_NET_RESIDUAL, 12, 1, 16000, 0, 0, (0, 1)),
+    ('residual_x2', _lib.KWS_NET_RESIDUAL, 12, 2, 16000, 0, 0, (0, 1)),
+    ('mfcc_and_raw', _lib.KWS_NET_MFCC_AND_RAW, 12, 1, 98 * 40 + 16000, 98, 40, (0, 1)),
+    ('xception_with_attention', _lib.KWS_NET_XCEPTION_ATTENTION, 12, 1, 16000, 0, 0, (0, 1)),
+]
 SPLITS = (1, 6)
 NC = 12
 
@@ -82,21 +94,22 @@ def digests(net, probs):
     return {'probs': sha(probs), 'grads': sha(net.grads), 'state': sha(net.state), 'metrics': sha(net.metrics), 'finite': finite}
 
 
-def batch(B, input_size, seed):
+def batch(B, input_size, seed, nc=NC):
     rng = np.random.RandomState(seed)
     x = (rng.randn(B, input_size) * 0.0774).astype(np.float32)
-    y = np.eye(NC, dtype=np.float32)[rng.randint(0, NC, B)]
+    y = np.eye(nc, dtype=np.float32)[rng.randint(0, nc, B)]
     return torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
 
 
-def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=False):
-    net = DeviceNet(kind, NC, filter_mult=filter_mult, input_size=input_size, seed=1234, gemm_mode=gemm_mode)
+def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=False, nc=NC, spectrogram_length=0, num_features=0):
+    net = DeviceNet(kind, nc, filter_mult=filter_mult, input_size=input_size, spectrogram_length=spectrogram_length,
+                    num_features=num_features, seed=1234, gemm_mode=gemm_mode)
     net.set_weights(perturbed_weights(net, 99))
     out = {}
-    x, y = batch(3, input_size, 7)
+    x, y = batch(3, input_size, 7, nc)
     out['predict_b3'] = digests(net, net.predict(x))
     out['train_b3'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=1))
-    x, y = batch(16, input_size, 8)
+    x, y = batch(16, input_size, 8, nc)
     out['train_b16'] = digests(net, net.train_fwd_bwd(x, y, seed=5, step=2))
     if split:
         x, y = batch(3, input_size, 9)
@@ -111,12 +124,15 @@ def model_digests(name, kind, input_size, filter_mult=1, gemm_mode=0, split=Fals
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder', 'pools', 'flat_tail'))
+    ap.add_argument('--set', default='bncols', choices=('bncols', 'ladder', 'pools', 'flat_tail', 'residual'))
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.set == 'ladder':
         res = dict(('%s_mode%d' % (name, m), model_digests(name, kind, size, fm, m, split and m != 2))
                    for name, kind, fm, size, modes, split in LADDER for m in modes)
+    elif a.set == 'residual':
+        res = dict(('%s_mode%d' % (name, m), model_digests(name, kind, size, fm, m, nc=nc, spectrogram_length=T, num_features=F))
+                   for name, kind, nc, fm, size, T, F, modes in RESIDUAL for m in modes)
     elif a.set in ('pools', 'flat_tail'):
         res = dict((name, model_digests(name, kind, size, fm)) for name, kind, size, fm in (POOLS if a.set == 'pools' else FLAT_TAIL))
     else:

@@ -2,8 +2,8 @@
 // (the switch there maps a kind to its builder) plus the launch sequences over it.  Each family keeps its program class in
 // its own file and exports only its builder(s):
 //   net.hip          conv_1d_time_sliced_with_attention
-//   net_logmfcc.hip  the residual-block family: conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual,
-//                    conv_1d_mfcc_and_raw, xception_with_attention
+//   net_logmfcc.hip  the residual-block family (LmProgram: a stem, units of depthwise k 3 -> pointwise -> BN, residual blocks, a head):
+//                    conv_1d_log_mfcc / conv_1d_spectrogram, steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw, xception_with_attention
 //   net_grouped.hip  conv_1d_fast, conv_1d_spec, conv_1d_time_stacked, conv_1d_heavy, conv_1d_learned_spec, conv_1d_top_down
 //   net_dwk.hip      conv_1d_gru, conv_1d_simple
 //   net_time_sliced.hip  conv_1d_time_sliced
@@ -14,8 +14,8 @@
 // The five programs whose head is the flat tail (kws_flat_tail_*) - those of net_grouped.hip, net_dwk.hip, net_time_sliced.hip,
 // net_mts.hip and net_inception.hip (GcProgram, DkProgram, TslProgram, MtProgram, IncProgram) - derive from FlatTailProgram
 // below: it owns workspace_bytes, predict and the order of a training step, and a program supplies its layout, forward,
-// tail_args and backward.  net.hip (attention tail, split step), net_logmfcc.hip and net_conv2d.hip (other tails) implement
-// NetProgram directly.
+// tail_args and backward.  net.hip (attention tail, split step), net_logmfcc.hip (three heads behind its own LmHead; it shares NetCall
+// and kws_flat_tail_train) and net_conv2d.hip (another tail) implement NetProgram directly.
 // The BatchNorm bookkeeping all but net.hip and net_logmfcc.hip share is bncols.hip (kws_gbn_*, declared in internal.h).
 // Not part of the public C ABI.
 #pragma once

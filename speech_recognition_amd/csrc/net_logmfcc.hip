@@ -1,279 +1,319 @@
-// Residual-block network programs.  One layer table (LmProgram) drives five reference models:
-//   LM_ATTENTION     conv_1d_log_mfcc_model (model.py:1400-1479) and conv_1d_spectrogram_model
-//                    (model.py:1482-1561: the same program on 257-bin input, first convolution on re-pitched copies)
-//   LM_STEFFE        steffeNet (model.py:1663-1726): stride in the block's first depthwise convolution, context block,
-//                    global max ++ average pooling tail
-//   LM_RESIDUAL      conv_1d_residual_model (model.py:841-908): 3-wide SAME max-pool joins, plain blocks after the
-//                    stack, global-average tail
-//   LM_MFCC_AND_RAW  conv_1d_mfcc_and_raw_model (model.py:1563-1660): two stems on packed [mfcc | raw] rows, concatenated
-//   LM_XCEPTION      xception_with_attention_model (model.py:911-983): conv_1d_residual's stem and a shorter block list, then the
-//                    attention gate (attgate.hip) feeding Bidirectional(GRU(192)) (gru.hip) and the flat tail's raw arm
-// The original description of LM_ATTENTION follows.
-// Network program of conv_1d_log_mfcc_model (reference model.py:1400-1479; SURVEY 8a row a19, layer
-// table Appendix B.2): Conv1D(64,3)+BN+ReLU6 on [98,40] features, 10 residual blocks of
-// 2 x [depthwise k3 SAME -> pointwise -> BN -> ReLU6] + MaxPool1D(pool=stride) + Add (1x1 stride-2
-// Conv1D + BN shortcut on the strided blocks), softmax-over-time attention, GAP, Dropout(.2),
-// Dense(num_classes)+softmax, categorical cross-entropy.
-//
-// Same building blocks as the raw-waveform net (f32-MFMA GEMMs with BN statistics in the epilogue,
-// depthwise kernels applying BN+ReLU6 on load, fixed-order partial-slab reductions) plus resblock.hip.
-// Keras variable names follow per-class auto-numbering in layer creation order.
+// Residual-block network programs.  One program class (LmProgram) runs one layer table, and the table is a composition:
+//   stem -> [context unit] -> residual blocks -> [plain units] -> head
+//   LmUnit   depthwise k 3 -> pointwise -> BatchNorm: the context unit, both halves of a block, a plain unit (unit_fwd / unit_bwd)
+//   LmBlock  two units, the shortcut (identity, or a strided 1 x 1 Conv1D + BN), where the stride sits, and the join
+//   LmStem   one gathered convolution; LmPaddedStem: on padded copies; LmStem2: two of them, concatenated
+//   LmHead   LmAttentionHead (kws_lm_tail_*), LmPoolHead (kws_gp_tail_launch), LmGruHead (attention gate + BiGRU + kws_flat_tail_*)
+// A training step is, in stream order: [grads zeroed], stem forward, body forward, the pointwise kernels transposed, the head with its
+// backward (it leaves the gradient wrt the last activation in dO), body backward, stem backward; inference is the first, the second
+// and the head.  Only the five builders at the end of the file know which model they build: conv_1d_log_mfcc / conv_1d_spectrogram,
+// steffeNet, conv_1d_residual, conv_1d_mfcc_and_raw, xception_with_attention.
+// Same building blocks as the raw-waveform net (f32-MFMA GEMMs with BN statistics in the epilogue, depthwise kernels applying
+// BN + ReLU6 on load, fixed-order partial-slab reductions) plus resblock.hip.  Keras variable names follow per-class auto-numbering
+// in layer creation order.
 #include "net_internal.h"
 
 namespace {
 
+// depthwise k 3 -> pointwise -> BatchNorm over [Lin, cin] -> [Lout, cout]; whoever reads y applies the table and ReLU6
+struct LmUnit {
+  int64_t dw, pw;
+  BnRef bn;
+  int bn_idx, cin, cout, Lin, Lout, stride, pad_l;
+  int slot;   // its workspace offsets: LmLayout::u[slot]
+};
+struct LmUnitWs { int64_t z = 0, y = 0, wt = 0; };   // depthwise output, pointwise output (pre-BN), pointwise kernel transposed (dgrad GEMM)
+
 struct LmBlock {
   int nf, stride, cin, Lin, Lout;
-  // where the stride sits: log-mfcc blocks pool after the second pointwise (s1 = 1, pool = stride, Lmid = Lin);
-  // steffeNet blocks stride their FIRST depthwise convolution (s1 = stride, pool = 1, Lmid = Lout)
-  int s1, pool, Lmid, pad1;
+  // where the stride sits: log-mfcc blocks pool after the second pointwise (pool = stride, Lmid = Lin); steffeNet blocks stride
+  // their FIRST depthwise convolution (u1.stride = stride, pool = 1, Lmid = Lout)
+  int pool, Lmid;
   int pool3 = 0, ppad = 0;  // conv_1d_residual: MaxPool1D(3, stride, 'same') join, window of output t starts at t*stride - ppad
   bool has_short;
-  int64_t ws;
+  int64_t ws;          // the shortcut Conv1D(nf, 1, strides) over the rows gs gathers, and its BatchNorm
   BnRef bns;
   int bns_idx;
   kws_gather_t gs;
-  int64_t dw1, pw1, dw2, pw2;
-  BnRef bn1, bn2;
-  int bn1_idx, bn2_idx;
+  LmUnit u1, u2;
+  int slot;   // LmLayout::b[slot]
+};
+struct LmBlockWs { int64_t ys = 0, o = 0, wt_ws = 0; };   // shortcut convolution's output, the join's output, the shortcut kernel transposed
+
+constexpr int64_t round64(int64_t floats) { return (floats + 63) / 64 * 64; }
+
+// what the table's layers ask of the shared regions at batch B (floats)
+struct LmSizes {
+  int B = 0;
+  int64_t o = 0, y = 0, z = 0, xs = 64, part = 0, wt = 0, tn = 0;
+  int64_t tnq = 0;   // the pointwise weight gradients keep their slabs until one batched sum
+  int64_t dwq = 0;   // depthwise backward kernels whose rows hold only a weight gradient: folded at the end
+  void parts(int64_t floats) { part = std::max(part, floats); }
+  void pw(int64_t M, int K, int N) {   // a GEMM with statistics rows whose weight gradient queues its slabs
+    parts((int64_t)kws_gemm_num_row_tiles(M) * 2 * N);
+    wt = std::max(wt, (int64_t)K * N);
+    tn = std::max(tn, kws_gemm_tn_workspace_floats(M, K, N));
+    tnq += round64(kws_gemm_tn_workspace_floats(M, K, N));
+  }
+  void unit(const LmUnit& u, bool parked) {   // parked: its backward takes the form that parks its rows in DwFinQueue
+    z = std::max(z, (int64_t)B * u.Lout * u.cin);
+    y = std::max(y, (int64_t)B * u.Lout * u.cout);
+    pw((int64_t)B * u.Lout, u.cin, u.cout);
+    parts(kws_dwconv_bwd_part_floats(B, u.Lin, u.cin));
+    if (parked) dwq += round64(kws_dwconv_bwd_part_floats(B, u.Lin, u.cin));
+  }
 };
 
-// a depthwise block without a residual (conv_1d_residual's _reduce_block: strided SAME, then VALID)
-struct LmPlain {
-  int64_t dw, pw;
-  BnRef bn;
-  int bn_idx, cin, cout, stride, pad_l, Lin, Lout;
+struct LmStemWs {
+  int64_t y0 = 0, a0 = 0;                  // raw output(s) of the first convolution(s), the activation the body reads
+  int64_t a0m = 0, a0r = 0;                // LmStem2: activated branch outputs before the concatenation
+  int64_t xpad = 0, wpad = 0, gwpad = 0;   // LmPaddedStem: re-pitched input, padded kernel and its gradient
 };
-
-// which model the table was built for; forward / backward ask it only for structure no field below describes
-enum LmStyle { LM_ATTENTION, LM_STEFFE, LM_RESIDUAL, LM_MFCC_AND_RAW, LM_XCEPTION };
-
-struct LmProgram : NetProgram {
-  const kws_net* net = nullptr;
-  LmStyle style = LM_ATTENTION;
-  int T0, F, C0, L0;
-  int Fp;  // F rounded up to the 16-byte vectors of the gathered GEMM (spectrogram input: 257 -> 260)
-  int64_t conv1;
-  BnRef bn0;
-  kws_gather_t g0;
-  std::vector<LmBlock> blocks;
-  int T, C, NC;   // [T, C]: the running activation while the table is built, the tail's input afterwards
-  int64_t att_dw, att_pw, dk, db = 0;
-  BnRef att_bn;
-  int att_bn_idx;
-  int n_bn;
-  int maxC;       // widest BatchNormalization of the table
-  // the dense layer and, for every style but LM_ATTENTION (softmax-over-time attention), the global-pooling tail in front of it
-  bool has_bias = true;    // dense_1/bias
-  bool pool_max = false;   // GlobalMaxPooling1D ++ GlobalAveragePooling1D (else the average alone)
-  int feat = 0;            // width of the dense layer's input: 2 C with pool_max, else C
-  int loss_kind = 1;       // kws_gp_tail_args::loss_kind: 0 = label-smoothed CE, 1 = keras categorical_crossentropy
-  float label_smoothing = 0.f;
-  float drop_keep = 0.5f;
-  // steffeNet: raw input, first convolution of K0 = 75 taps on one channel (gathered as ONE tap of
-  // K0p = 76 samples against a zero-padded kernel), a context block between the first convolution and the
-  // residual stack, global max ++ average pooling tail
-  int K0 = 0, K0p = 0;
-  // conv_1d_residual: raw input through the time-slice gather, 3-wide max-pool joins, plain blocks after the
-  // residual stack, global average pooling tail with bias and plain CE
-  std::vector<LmPlain> plain;
-  // conv_1d_mfcc_and_raw: input rows are [mfcc T0*F | raw L_raw]; two first convolutions (Cm + Cr = C0
-  // channels, concatenated after BN + ReLU6), conv_1d_residual's blocks, global-average tail
-  int Cm = 0, Cr = 0, Din = 0;
-  int64_t conv1r = 0;
-  BnRef bn0r;
-  kws_gather_t g0r;
-  int64_t ctx_dw = 0, ctx_pw = 0;
-  BnRef ctx_bn;
-  int ctx_bn_idx = 0;
-  // xception_with_attention: the gate's kernels are att_dw [1, 5, C, 1] / att_pw / att_bn; a bidirectional GRU of gH units reads the
-  // gated sequence [T, C]; the dense layer reads its [2 gH] output
-  int gH = 0;
-  int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
-
-  int64_t workspace_bytes(int B, int training) const override;
-  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override;
-  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-              hipStream_t st) const override;
-  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
-            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override;
+struct LmHeadWs {
+  int64_t u = 0, fd = 0, dl = 0, gu = 0, coef2 = 0, per_loss = 0, per_correct = 0, att = 0;
+  // LmGruHead: gate output, gate workspaces, GRU masks / output / saved steps / workspace / output gradient
+  int64_t xgy = 0, xagf = 0, xagb = 0, gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;
 };
-
 struct LmLayout {
   int64_t total = 0;
-  int64_t y0 = 0, a0 = 0;
-  std::vector<int64_t> ys, z1, y1, z2, y2, o;
+  LmStemWs stem;
+  std::vector<LmUnitWs> u;
+  std::vector<LmBlockWs> b;
+  int64_t ac = 0, alast = 0;               // the context unit's and the last plain unit's activated output
   int64_t bn = 0, bn_stride = 0, part = 0, red = 0, coef = 0, WT = 0, tn = 0, swg = 0;
   int64_t tnq = 0, tnq_floats = 0;         // slabs of the pointwise weight gradients of one backward pass (KwsSlabQueue)
   int64_t dwq = 0, dwq_floats = 0;         // partial rows of the depthwise weight gradients folded by one launch (DwFinQueue)
   int64_t dOa = 0, dOb = 0, G = 0, DZ = 0, DXS = 0;
-  int64_t u = 0, fd = 0, dl = 0, gu = 0, coef2 = 0, per_loss = 0, per_correct = 0, att = 0;
-  int64_t xpad = 0, wpad = 0, gwpad = 0;  // only when Fp != F (spectrogram input) / always (steffeNet: padded first kernel)
-  int64_t zc = 0, yc = 0, ac = 0;          // steffeNet context block
-  std::vector<int64_t> pz, py;             // plain blocks (conv_1d_residual)
-  int64_t alast = 0;
-  int64_t a0m = 0, a0r = 0;                // conv_1d_mfcc_and_raw: activated branch outputs before the concatenation
-  // xception_with_attention: gate output, gate workspaces, GRU masks / output / saved steps / workspace / output gradient
-  int64_t xgy = 0, xagf = 0, xagb = 0, gmx = 0, gmh = 0, gout = 0, gsave = 0, gws = 0, gdout = 0;
-  std::vector<int64_t> wt_pw1, wt_pw2, wt_ws, wt_plain;   // transposed pointwise kernels for the dgrad GEMMs
-  int64_t wt_ctx = 0;
+  LmHeadWs head;
 };
 
-constexpr int XC_GATE_K = 5;          // _context_conv(x, 1, 5, padding='same'), model.py:973
-constexpr int XC_GRU_UNITS = 192;     // GRU(192, ...), model.py:976
-constexpr float XC_GRU_KEEP = 0.8f;   // dropout=0.2, recurrent_dropout=0.2
-
-void lm_layout(const LmProgram& p, int B, LmLayout* lo) {
-  Bump bp;
-  const int nb = (int)p.blocks.size();
-  lo->ys.assign(nb, 0); lo->z1.assign(nb, 0); lo->y1.assign(nb, 0); lo->z2.assign(nb, 0); lo->y2.assign(nb, 0);
-  lo->o.assign(nb, 0);
-  lo->y0 = bp.take((int64_t)B * p.L0 * p.C0);
-  lo->a0 = bp.take((int64_t)B * p.L0 * p.C0);
-  int64_t max_o = (int64_t)B * p.L0 * p.C0, max_y = max_o, max_z = 0, max_xs = 64, max_part = 0, max_wt = 0, max_tn = 0;
-  auto upd_gemm = [&](int64_t M, int K, int N) {
-    max_part = std::max(max_part, (int64_t)kws_gemm_num_row_tiles(M) * 2 * N);
-    max_wt = std::max(max_wt, (int64_t)K * N);
-    max_tn = std::max(max_tn, kws_gemm_tn_workspace_floats(M, K, N));
-  };
-  int64_t sum_tnq = 0;                     // the pointwise weight gradients keep their slabs until one batched sum
-  int64_t sum_dwq = 0;                     // depthwise backward kernels whose rows hold only a weight gradient: folded at the end
-  auto upd_dwq = [&](int L, int C) { sum_dwq += (kws_dwconv_bwd_part_floats(B, L, C) + 63) / 64 * 64; };
-  auto upd_pw = [&](int64_t M, int K, int N) {
-    upd_gemm(M, K, N);
-    sum_tnq += (kws_gemm_tn_workspace_floats(M, K, N) + 63) / 64 * 64;
-  };
-  upd_pw((int64_t)B * p.L0, p.g0.taps * p.g0.cin, p.C0);    // (gathered weight gradients queue their slabs too: round 5)
-  if (p.style == LM_MFCC_AND_RAW) {
-    upd_pw((int64_t)B * p.L0, p.g0r.taps * p.g0r.cin, p.Cr);
-    lo->a0m = bp.take((int64_t)B * p.L0 * p.Cm);
-    lo->a0r = bp.take((int64_t)B * p.L0 * p.Cr);
-  }
-  max_part = std::max(max_part, kws_block_out_bwd_part_floats(B, p.L0, p.C0, 1));
-  if (p.style == LM_STEFFE) {
-    lo->zc = bp.take((int64_t)B * p.L0 * p.C0);
-    lo->yc = bp.take((int64_t)B * p.L0 * p.C0);
-    lo->ac = bp.take((int64_t)B * p.L0 * p.C0);
-    max_z = (int64_t)B * p.L0 * p.C0;
-    upd_pw((int64_t)B * p.L0, p.C0, p.C0);
-    max_part = std::max(max_part, kws_dwconv_bwd_part_floats(B, p.L0, p.C0));
-    upd_dwq(p.L0, p.C0);
-  }
-  for (int i = 0; i < nb; ++i) {
-    const LmBlock& b = p.blocks[i];
-    if (b.has_short) lo->ys[i] = bp.take((int64_t)B * b.Lout * b.nf);
-    lo->z1[i] = bp.take((int64_t)B * b.Lmid * b.cin);
-    lo->y1[i] = bp.take((int64_t)B * b.Lmid * b.nf);
-    lo->z2[i] = bp.take((int64_t)B * b.Lmid * b.nf);
-    lo->y2[i] = bp.take((int64_t)B * b.Lmid * b.nf);
-    lo->o[i] = bp.take((int64_t)B * b.Lout * b.nf);
-    max_o = std::max(max_o, std::max((int64_t)B * b.Lout * b.nf, (int64_t)B * b.Lin * b.cin));
-    max_y = std::max(max_y, (int64_t)B * b.Lmid * b.nf);
-    max_z = std::max(max_z, std::max((int64_t)B * b.Lmid * b.cin, (int64_t)B * b.Lmid * b.nf));
-    max_xs = std::max(max_xs, (int64_t)B * b.Lout * b.cin);
-    upd_pw((int64_t)B * b.Lmid, b.cin, b.nf);
-    upd_pw((int64_t)B * b.Lmid, b.nf, b.nf);
-    if (b.has_short) upd_pw((int64_t)B * b.Lout, b.cin, b.nf);
-    max_part = std::max(max_part, kws_dwconv_bwd_part_floats(B, b.Lin, b.cin));
-    upd_dwq(b.Lin, b.cin);
-    max_part = std::max(max_part, kws_dwconv_bwd_part_floats(B, b.Lmid, b.nf));
-    max_part = std::max(max_part, b.pool3 ? kws_block_out3_bwd_part_floats(B, b.Lmid, b.nf)
-                                          : kws_block_out_bwd_part_floats(B, b.Lmid, b.nf, b.pool));
-    max_part = std::max(max_part, kws_block_out_bwd_part_floats(B, b.Lout, b.nf, 1));
-  }
-  lo->pz.assign(p.plain.size(), 0); lo->py.assign(p.plain.size(), 0);
-  for (size_t j = 0; j < p.plain.size(); ++j) {
-    const LmPlain& q = p.plain[j];
-    lo->pz[j] = bp.take((int64_t)B * q.Lout * q.cin);
-    lo->py[j] = bp.take((int64_t)B * q.Lout * q.cout);
-    max_y = std::max(max_y, (int64_t)B * q.Lout * q.cout);
-    max_z = std::max(max_z, (int64_t)B * q.Lout * q.cin);
-    max_o = std::max(max_o, std::max((int64_t)B * q.Lin * q.cin, (int64_t)B * q.Lout * q.cout));
-    upd_pw((int64_t)B * q.Lout, q.cin, q.cout);
-    max_part = std::max(max_part, kws_dwconv_bwd_part_floats(B, q.Lin, q.cin));
-    if (j == 0) upd_dwq(q.Lin, q.cin);
-    max_part = std::max(max_part, kws_block_out_bwd_part_floats(B, q.Lout, q.cout, 1));
-  }
-  if (!p.plain.empty()) lo->alast = bp.take((int64_t)B * p.T * p.C);
-  max_part = std::max(max_part, (int64_t)B * 5 * p.C);
-  lo->bn_stride = 4 * p.maxC;
-  lo->bn = bp.take(lo->bn_stride * (p.n_bn + 1));
-  lo->part = bp.take(max_part);
-  lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * p.maxC);
-  lo->coef = bp.take(2 * p.maxC);
-  lo->WT = bp.take(max_wt);
-  lo->wt_pw1.assign(nb, 0); lo->wt_pw2.assign(nb, 0); lo->wt_ws.assign(nb, 0); lo->wt_plain.assign(p.plain.size(), 0);
-  for (int i = 0; i < nb; ++i) {
-    const LmBlock& b = p.blocks[i];
-    lo->wt_pw1[i] = bp.take((int64_t)b.cin * b.nf);
-    lo->wt_pw2[i] = bp.take((int64_t)b.nf * b.nf);
-    if (b.has_short) lo->wt_ws[i] = bp.take((int64_t)b.cin * b.nf);
-  }
-  for (size_t j = 0; j < p.plain.size(); ++j) lo->wt_plain[j] = bp.take((int64_t)p.plain[j].cin * p.plain[j].cout);
-  if (p.style == LM_STEFFE) lo->wt_ctx = bp.take((int64_t)p.C0 * p.C0);
-  lo->tn = bp.take(max_tn);
-  lo->tnq_floats = sum_tnq;
-  lo->tnq = bp.take(sum_tnq);
-  lo->dwq_floats = sum_dwq;
-  lo->dwq = bp.take(sum_dwq);
-  lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * p.feat * p.NC);
-  lo->dOa = bp.take(max_o);
-  lo->dOb = bp.take(max_o);
-  lo->G = bp.take(max_y);
-  lo->DZ = bp.take(max_z);
-  lo->DXS = bp.take(max_xs);
-  const int tail_T = p.style == LM_XCEPTION ? p.T : 16;   // u / att: [B, T]
-  lo->u = bp.take((int64_t)B * tail_T);
-  lo->fd = bp.take((int64_t)B * p.feat);
-  lo->dl = bp.take((int64_t)B * p.NC);
-  lo->gu = bp.take((int64_t)B * 16);
-  lo->coef2 = bp.take(4);
-  lo->per_loss = bp.take(B);
-  lo->per_correct = bp.take(B);
-  lo->att = bp.take((int64_t)B * tail_T);
-  if (p.style == LM_XCEPTION) {
-    lo->xgy = bp.take((int64_t)B * p.T * p.C);
-    lo->xagf = bp.take(kws_attn_gate_fwd_floats(B, p.T, p.C, XC_GATE_K));
-    lo->xagb = bp.take(kws_attn_gate_bwd_floats(B, p.T, p.C, XC_GATE_K));
-    lo->gmx = bp.take((int64_t)6 * B * p.C);
-    lo->gmh = bp.take((int64_t)6 * B * p.gH);
-    lo->gout = bp.take((int64_t)B * 2 * p.gH);
-    lo->gdout = bp.take((int64_t)B * 2 * p.gH);
-    lo->gsave = bp.take(kws_gru_save_floats(B, p.T, p.gH));
-    lo->gws = bp.take(kws_gru_workspace_floats(B, p.T, p.C, p.gH, 1));
-  }
-  if (p.style == LM_STEFFE) {
-    lo->wpad = bp.take((int64_t)p.K0p * p.C0);
-    lo->gwpad = bp.take((int64_t)p.K0p * p.C0);
-  } else if (p.Fp != p.F) {
-    lo->xpad = bp.take((int64_t)B * p.T0 * p.Fp);
-    lo->wpad = bp.take((int64_t)3 * p.Fp * p.C0);
-    lo->gwpad = bp.take((int64_t)3 * p.Fp * p.C0);
-  }
-  lo->total = bp.cur * 4;
-}
-
-struct Ctx {
-  const LmProgram* p;
-  const float* params;
-  float* state;        // may be written (training)
-  float* ws;
+// one call: what it received and the program's layout at its batch size
+struct LmProgram;
+struct Ctx : NetCall {
   LmLayout lo;
-  int B;
-  bool training;
-  hipStream_t st;
+  bool ref_schedule;   // gemm mode 1, the A/B reference schedule: no fused depthwise passes, separate input- / weight-gradient launches
+  Ctx(const LmProgram& p, const NetCall& n);
   float* bn_at(int idx) const { return ws + lo.bn + lo.bn_stride * idx; }
+  float* stats() const { return training ? ws + lo.part : nullptr; }
+  float* z(const LmUnit& u) const { return ws + lo.u[u.slot].z; }
+  float* y(const LmUnit& u) const { return ws + lo.u[u.slot].y; }
+  float* wt(const LmUnit& u) const { return ws + lo.u[u.slot].wt; }
 };
 
 // BN statistics -> table (training) or moving statistics -> table (inference)
 int bn_table(const Ctx& c, const BnRef& r, int idx, int64_t M, int stat_rows) {
   if (c.training)
-    return kws_bn_stats_finalize(c.ws + c.lo.part, stat_rows, M, r.C, c.params + r.gamma,
-                                 c.params + r.beta, KWS_BN_EPS, KWS_BN_MOMENTUM, c.state + r.mm, c.state + r.mv,
-                                 c.bn_at(idx), c.ws + c.lo.red, c.st);
-  return kws_bn_infer_prepare(c.params + r.gamma, c.params + r.beta, c.state + r.mm, c.state + r.mv, KWS_BN_EPS, r.C,
-                              c.bn_at(idx), c.st);
+    return kws_bn_stats_finalize(c.ws + c.lo.part, stat_rows, M, r.C, c.params + r.gamma, c.params + r.beta, KWS_BN_EPS, KWS_BN_MOMENTUM,
+                                 c.state + r.mm, c.state + r.mv, c.bn_at(idx), c.ws + c.lo.red, c.st);
+  return kws_bn_infer_prepare(c.params + r.gamma, c.params + r.beta, c.state + r.mm, c.state + r.mv, KWS_BN_EPS, r.C, c.bn_at(idx), c.st);
 }
+
+// Depthwise backward kernels that leave ONLY a weight gradient behind (a block's first depthwise convolution, the context unit's, the
+// first plain unit's: their input is a materialised activation, no BatchNorm in front): nothing on the dependency chain needs the fold of
+// their partial rows, so the rows stay in regions of their own and one launch folds up to KWS_DW_FIN_BATCH layers at the end of the pass.
+struct DwFinQueue {
+  const float* part[KWS_DW_FIN_BATCH];
+  float* dw[KWS_DW_FIN_BATCH];
+  int n_parts[KWS_DW_FIN_BATCH], C[KWS_DW_FIN_BATCH];
+  int count = 0;
+  float* base = nullptr;
+  int64_t used = 0, cap = 0;
+  hipStream_t st = nullptr;
+  int flush() {
+    if (count == 0) return KWS_OK;
+    const int rc = kws_dw_grad_finalize_batch(part, n_parts, C, dw, count, st);
+    count = 0; used = 0;
+    return rc;
+  }
+  // a region for the rows of one depthwise backward launch (floats = kws_dwconv_bwd_part_floats) whose fold writes dW
+  int take(int64_t floats, int Cc, float* dW, float** out) {
+    const int64_t need = round64(floats);
+    if (count == KWS_DW_FIN_BATCH || used + need > cap) KWS_TRY(flush());
+    if (need > cap) return KWS_E_WORKSPACE;
+    *out = base + used;
+    part[count] = base + used; dw[count] = dW; n_parts[count] = (int)(floats / (5 * Cc)); C[count] = Cc;
+    used += need; ++count;
+    return KWS_OK;
+  }
+};
+
+// one backward pass: its scratch, the two gradient buffers that trade places layer by layer (dO: wrt the current layer's output) and
+// the two queues of deferred weight-gradient sums
+struct LmBwd {
+  const Ctx& c;
+  float *part, *red, *coef, *G, *DZ, *DXS, *dO, *dX;
+  KwsSlabQueue sq;
+  DwFinQueue dq;
+  explicit LmBwd(const Ctx& c_) : c(c_) {
+    const LmLayout& lo = c.lo;
+    part = c.ws + lo.part; red = c.ws + lo.red; coef = c.ws + lo.coef; G = c.ws + lo.G; DZ = c.ws + lo.DZ; DXS = c.ws + lo.DXS;
+    dO = c.ws + lo.dOa; dX = c.ws + lo.dOb;
+    sq.base = c.ws + lo.tnq; sq.cap = lo.tnq_floats; sq.allow_pair = !c.ref_schedule;
+    dq.base = c.ws + lo.dwq; dq.cap = lo.dwq_floats; dq.st = c.st;
+  }
+  // join backward + BatchNorm backward in two passes (round 4): reductions, fold (dgamma, dbeta, c1 | c2), then the masked /
+  // pool-routed gradient is recomputed and dy written directly - 5 tensor passes instead of the 6 of "kws_block_out_bwd,
+  // fold, kws_bn_bwd_apply", <= 256 partial rows (no slice fold), one launch less per join.  `outp` may be `dOin` (pool 1).
+  int join_bwd(const float* dOin, const float* yv, const BnRef& r, int bn_idx, float* outp, int L, int C, int pool, int relu) {
+    const float* bn = c.bn_at(bn_idx);
+    KWS_TRY(kws_block_join_bwd(dOin, yv, bn, nullptr, nullptr, nullptr, part, 1, c.B, L, C, pool, relu, c.st));
+    KWS_TRY(kws_dw_bwd_finalize(part, kws_block_join_bwd_parts(c.B, L, C, pool), (int64_t)c.B * L, C, nullptr, c.grads + r.gamma,
+                                c.grads + r.beta, coef, red, c.st));
+    return kws_block_join_bwd(dOin, yv, bn, c.params + r.gamma, coef, outp, nullptr, 2, c.B, L, C, pool, relu, c.st);
+  }
+};
+
+// ---- the unit's two steps -----------------------------------------------------------------------------------------------------------
+// `prod`: `in` is that unit's raw output, read through its BatchNorm + ReLU6; NULL: a materialised activation.
+// z_ready: a fused pass in front wrote the depthwise output already
+int unit_fwd(const Ctx& c, const LmUnit& u, const float* in, const LmUnit* prod, bool z_ready = false) {
+  const int64_t M = (int64_t)c.B * u.Lout;
+  if (!z_ready)
+    KWS_TRY(kws_dwconv_fwd_f32(in, prod ? c.bn_at(prod->bn_idx) : nullptr, c.params + u.dw, c.z(u), c.B, u.Lin, u.Lout, u.cin, u.stride,
+                               u.pad_l, c.st));
+  KWS_TRY(kws_gemm_nn_f32(c.z(u), c.params + u.pw, c.y(u), M, u.cin, u.cout, c.stats(), c.st));
+  return bn_table(c, u.bn, u.bn_idx, M, kws_gemm_nn_stats_rows(M, u.cin, u.cout));
+}
+
+// a strided block's shortcut branch: its BN (no mask, in place on dO), the 1 x 1 convolution's weight gradient (slabs queued: summed
+// with the pass's other weight gradients) and its input gradient on the Lout strided rows, left in DXS
+int short_bwd(LmBwd& k, const LmBlock& b, const float* xin) {
+  const Ctx& c = k.c;
+  const LmBlockWs& w = c.lo.b[b.slot];
+  KWS_TRY(k.join_bwd(k.dO, c.ws + w.ys, b.bns, b.bns_idx, k.dO, b.Lout, b.nf, 1, 0));
+  KWS_TRY(k.sq.gemm_gather(xin, &b.gs, k.dO, c.grads + b.ws, c.B, b.nf, c.st));
+  return kws_gemm_nn_f32(k.dO, c.ws + w.wt_ws, k.DXS, (int64_t)c.B * b.Lout, b.nf, b.cin, nullptr, c.st);
+}
+
+// what joins the input gradient while the parked-rows form writes it: nothing; `add`, elementwise (an identity shortcut); or the input
+// gradient of block sc's shortcut branch on every sc->stride-th row - that branch then runs here, after the rows are parked
+struct LmDxJoin { const float* add = nullptr; const LmBlock* sc = nullptr; };
+// k.G = the gradient wrt y -> the pointwise kernel's gradient and dz (one launch where the pair kernel takes the shape), then the
+// depthwise backward.  prod != NULL: two passes over dz and the producer's raw output - the producer's BatchNorm backward rides
+// along, its masked gradient is never stored, k.G becomes the producer's dy.  prod NULL: k.dX = the gradient wrt `in`.
+int unit_bwd(LmBwd& k, const LmUnit& u, const float* in, const LmUnit* prod, const LmDxJoin& j = LmDxJoin()) {
+  const Ctx& c = k.c;
+  const int B = c.B;
+  const float* w = c.params + u.dw;
+  KWS_TRY(k.sq.pair(k.G, c.wt(u), k.DZ, c.z(u), c.grads + u.pw, (int64_t)B * u.Lout, u.cin, u.cout, c.st));
+  const int64_t rows = kws_dwconv_bwd_part_floats(B, u.Lin, u.cin);
+  if (prod) {
+    const float* bn = c.bn_at(prod->bn_idx);
+    KWS_TRY(kws_dwconv_bwd_bn_f32(k.DZ, in, bn, w, nullptr, nullptr, k.part, 1, B, u.Lin, u.Lout, u.cin, u.stride, u.pad_l, c.st));
+    KWS_TRY(kws_dw_bwd_finalize(k.part, (int)(rows / (5 * u.cin)), (int64_t)B * u.Lin, u.cin, c.grads + u.dw, c.grads + prod->bn.gamma,
+                                c.grads + prod->bn.beta, k.coef, k.red, c.st));
+    return kws_dwconv_bwd_bn_f32(k.DZ, in, bn, w, k.coef, k.G, nullptr, 2, B, u.Lin, u.Lout, u.cin, u.stride, u.pad_l, c.st);
+  }
+  float* dpart;   // only a weight gradient comes out of these rows: folded with the other layers' at the end of the pass
+  KWS_TRY(k.dq.take(rows, u.cin, c.grads + u.dw, &dpart));
+  if (j.sc) {
+    KWS_TRY(short_bwd(k, *j.sc, in));
+    return kws_dwconv_bwd_acc_strided_f32(k.DZ, in, w, k.DXS, j.sc->stride, j.sc->Lout, k.dX, dpart, B, u.Lin, u.Lout, u.cin, u.stride,
+                                          u.pad_l, c.st);
+  }
+  if (j.add) return kws_dwconv_bwd_acc_f32(k.DZ, in, w, j.add, k.dX, dpart, B, u.Lin, u.Lout, u.cin, u.stride, u.pad_l, c.st);
+  return kws_dwconv_bwd_f32(k.DZ, in, nullptr, w, k.dX, dpart, B, u.Lin, u.Lout, u.cin, u.stride, u.pad_l, c.st);
+}
+// a k 3 / stride 1 / 'same' depthwise convolution over exactly [L, C]: the pass that writes that tensor can write its output too
+bool dw_follows(const LmUnit& u, int L, int C) { return u.stride == 1 && u.pad_l == 1 && u.Lout == u.Lin && u.Lin == L && u.cin == C; }
+
+// ---- stems ----------------------------------------------------------------------------------------------------------------------------
+// The base is the first form: ONE gathered convolution + BN (index 1) + ReLU6 -> a0 [B, L0, C0].
+struct LmStem {
+  int L0 = 0, C0 = 0;
+  int64_t conv1 = 0;
+  BnRef bn0;
+  kws_gather_t g0;
+  virtual ~LmStem() {}
+  virtual void sizes(LmSizes* s) const { s->pw((int64_t)s->B * L0, g0.taps * g0.cin, C0); }   // (gathered weight gradients queue their slabs too)
+  virtual void take_front(Bump& bp, int B, LmStemWs* w) const { w->y0 = bp.take((int64_t)B * L0 * C0); w->a0 = bp.take((int64_t)B * L0 * C0); }
+  virtual void take_back(Bump&, int, LmStemWs*) const {}
+  // the pre-BN tensor of BatchNorm `index`, where it is the stem's
+  virtual bool view(const LmStemWs& w, int B, int index, int64_t* offset_floats, int64_t* count) const {
+    if (index == 1) { *offset_floats = w.y0; *count = (int64_t)B * L0 * C0; }
+    return index == 1;
+  }
+  // the gathered GEMM's operands: the input and the kernel as they are
+  virtual int operands(const Ctx& c, const float** x0, const float** w0) const { *x0 = c.x; *w0 = c.params + conv1; return KWS_OK; }
+  // dw_next != NULL: the activation pass writes that unit's depthwise output as well (kws_block_out_dw_fwd without a residual: bit-identical)
+  virtual int forward(const Ctx& c, const LmUnit* dw_next) const {
+    const int64_t M = (int64_t)c.B * L0;
+    float *y0 = c.ws + c.lo.stem.y0, *a0 = c.ws + c.lo.stem.a0;
+    const float *x0, *w0;
+    KWS_TRY(operands(c, &x0, &w0));
+    KWS_TRY(kws_gemm_gather_f32(x0, &g0, w0, y0, c.B, C0, c.stats(), c.st));
+    KWS_TRY(bn_table(c, bn0, 1, M, kws_gemm_gather_stats_rows(M)));
+    if (dw_next) return kws_block_out_dw_fwd(y0, c.bn_at(1), nullptr, nullptr, c.params + dw_next->dw, a0, c.z(*dw_next), c.B, L0, C0, 1, c.st);
+    return kws_bn_relu6_apply(y0, c.bn_at(1), a0, M, C0, 1, c.st);
+  }
+  // k.dO = the gradient wrt a0.  Ends the pass: both queues are flushed, each form in its own stream order
+  virtual int backward(LmBwd& k) const {
+    const Ctx& c = k.c;
+    KWS_TRY(k.dq.flush());     // the depthwise weight gradients whose rows were parked
+    KWS_TRY(k.join_bwd(k.dO, c.ws + c.lo.stem.y0, bn0, 1, k.G, L0, C0, 1, 1));
+    KWS_TRY(k.sq.gemm_gather(c.x, &g0, k.G, c.grads + conv1, c.B, C0, c.st));   // written in place: the slabs join the pass's batched sum
+    return k.sq.flush(c.st);   // the pointwise weight gradients of the whole pass: one sum (two past 16 layers)
+  }
+};
+
+// rows of F floats -> rows of Fp floats (Fp % 4 == 0), zero filled; one 16-byte store per thread
+__global__ __launch_bounds__(256) void repitch_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t rows,
+                                                      int F, int Fp) {
+  const int q = Fp / 4;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < rows * q; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / q;
+    const int f = (int)(i - r * q) * 4;
+    const float* src = in + r * F + f;
+    float4 v;
+    v.x = f + 0 < F ? src[0] : 0.f;
+    v.y = f + 1 < F ? src[1] : 0.f;
+    v.z = f + 2 < F ? src[2] : 0.f;
+    v.w = f + 3 < F ? src[3] : 0.f;
+    *reinterpret_cast<float4*>(out + r * Fp + f) = v;
+  }
+}
+
+// The second form: the gathered GEMM reads 16-byte vectors, so the kernel [taps, K, C0] runs as a zero-padded copy [taps, Kp, C0]
+// and the padded weight gradient is copied back without the padding.
+//   T0 > 0 (conv_1d_spectrogram, K = 257 bins): the input rows [T0, K] are re-pitched to Kp as well (plain 2-D copies)
+//   T0 = 0 (steffeNet, one tap of K = 75 samples): the gather reads Kp = 76 samples per output row of the input as it is
+struct LmPaddedStem : LmStem {
+  int K = 0, Kp = 0, T0 = 0;
+  void take_back(Bump& bp, int B, LmStemWs* w) const override {
+    if (T0) w->xpad = bp.take((int64_t)B * T0 * Kp);
+    w->wpad = bp.take((int64_t)g0.taps * Kp * C0);
+    w->gwpad = bp.take((int64_t)g0.taps * Kp * C0);
+  }
+  int operands(const Ctx& c, const float** x0, const float** w0) const override {
+    float *wp = c.ws + c.lo.stem.wpad, *xp = c.ws + c.lo.stem.xpad;
+    *x0 = T0 ? xp : c.x; *w0 = wp;
+    if (!T0) {
+      KWS_HIP(hipMemcpyAsync(wp, c.params + conv1, (size_t)K * C0 * 4, hipMemcpyDeviceToDevice, c.st));
+      KWS_HIP(hipMemsetAsync(wp + (size_t)K * C0, 0, (size_t)(Kp - K) * C0 * 4, c.st));
+      return KWS_OK;
+    }
+    const int64_t rows = (int64_t)c.B * T0, n4 = rows * (Kp / 4);
+    hipLaunchKernelGGL(repitch_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, c.st, c.x, xp, rows, K, Kp);
+    KWS_LAUNCH_CHECK("repitch_kernel");
+    KWS_HIP(hipMemsetAsync(wp, 0, (size_t)g0.taps * Kp * C0 * 4, c.st));
+    KWS_HIP(hipMemcpy2DAsync(wp, (size_t)Kp * C0 * 4, c.params + conv1, (size_t)K * C0 * 4, (size_t)K * C0 * 4, g0.taps,
+                             hipMemcpyDeviceToDevice, c.st));
+    return KWS_OK;
+  }
+  int backward(LmBwd& k) const override {
+    const Ctx& c = k.c;
+    float* gw = c.ws + c.lo.stem.gwpad;
+    KWS_TRY(k.dq.flush());
+    KWS_TRY(k.join_bwd(k.dO, c.ws + c.lo.stem.y0, bn0, 1, k.G, L0, C0, 1, 1));
+    KWS_TRY(k.sq.flush(c.st));
+    // the gradient of the padded kernel (the forward of this step left the padded input in xpad), then its K rows per tap
+    KWS_TRY(kws_gemm_tn_gather_f32(T0 ? c.ws + c.lo.stem.xpad : c.x, &g0, k.G, gw, c.B, C0, c.ws + c.lo.tn, c.st));
+    if (!T0) KWS_HIP(hipMemcpyAsync(c.grads + conv1, gw, (size_t)K * C0 * 4, hipMemcpyDeviceToDevice, c.st));
+    else KWS_HIP(hipMemcpy2DAsync(c.grads + conv1, (size_t)K * C0 * 4, gw, (size_t)Kp * C0 * 4, (size_t)K * C0 * 4, g0.taps,
+                                  hipMemcpyDeviceToDevice, c.st));
+    return KWS_OK;
+  }
+};
 
 // out[r, 0:cols] = in[r, 0:cols] for row pitches ld_in / ld_out (channel concatenation and its backward split)
 __global__ __launch_bounds__(256) void copy_cols_kernel(const float* __restrict__ in, int ld_in, float* __restrict__ out,
@@ -293,207 +333,538 @@ int copy_cols(const float* in, int ld_in, float* out, int ld_out, int64_t rows, 
   return KWS_OK;
 }
 
-// rows of F floats -> rows of Fp floats (Fp % 4 == 0), zero filled; one 16-byte store per thread
-__global__ __launch_bounds__(256) void repitch_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t rows,
-                                                      int F, int Fp) {
-  const int q = Fp / 4;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < rows * q; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / q;
-    const int f = (int)(i - r * q) * 4;
-    const float* src = in + r * F + f;
-    float4 v;
-    v.x = f + 0 < F ? src[0] : 0.f;
-    v.y = f + 1 < F ? src[1] : 0.f;
-    v.z = f + 2 < F ? src[2] : 0.f;
-    v.w = f + 3 < F ? src[3] : 0.f;
-    *reinterpret_cast<float4*>(out + r * Fp + f) = v;
+// The third form (conv_1d_mfcc_and_raw): input rows are [mfcc | raw]; the base's convolution gives Cm channels, a second one
+// (BN index 2) Cr, and a0 is their concatenation after BN + ReLU6: C0 = Cm + Cr.  y0 holds [B L0, Cm] then [B L0, Cr].
+struct LmStem2 : LmStem {
+  int Cm = 0, Cr = 0;
+  int64_t conv1r = 0;
+  BnRef bn0r;
+  kws_gather_t g0r;
+  void sizes(LmSizes* s) const override { LmStem::sizes(s); s->pw((int64_t)s->B * L0, g0r.taps * g0r.cin, Cr); }
+  void take_front(Bump& bp, int B, LmStemWs* w) const override {
+    LmStem::take_front(bp, B, w);
+    w->a0m = bp.take((int64_t)B * L0 * Cm); w->a0r = bp.take((int64_t)B * L0 * Cr);
   }
-}
+  bool view(const LmStemWs& w, int B, int index, int64_t* offset_floats, int64_t* count) const override {
+    if (index > 2) return false;
+    *offset_floats = w.y0 + (index == 2 ? (int64_t)B * L0 * Cm : 0);
+    *count = (int64_t)B * L0 * (index == 2 ? Cr : Cm);
+    return true;
+  }
+  int forward(const Ctx& c, const LmUnit* dw_next) const override {
+    KWS_REQUIRE(!dw_next, "net: the concatenating stem has no fused activation pass");
+    const LmStemWs& w = c.lo.stem;
+    const int64_t M = (int64_t)c.B * L0;
+    float *ws = c.ws, *y0m = ws + w.y0, *y0r = y0m + M * Cm;
+    KWS_TRY(kws_gemm_gather_f32(c.x, &g0, c.params + conv1, y0m, c.B, Cm, c.stats(), c.st));
+    KWS_TRY(bn_table(c, bn0, 1, M, kws_gemm_gather_stats_rows(M)));
+    KWS_TRY(kws_gemm_gather_f32(c.x, &g0r, c.params + conv1r, y0r, c.B, Cr, c.stats(), c.st));
+    KWS_TRY(bn_table(c, bn0r, 2, M, kws_gemm_gather_stats_rows(M)));
+    KWS_TRY(kws_bn_relu6_apply(y0m, c.bn_at(1), ws + w.a0m, M, Cm, 1, c.st));
+    KWS_TRY(kws_bn_relu6_apply(y0r, c.bn_at(2), ws + w.a0r, M, Cr, 1, c.st));
+    KWS_TRY(copy_cols(ws + w.a0m, Cm, ws + w.a0, C0, M, Cm, c.st));
+    return copy_cols(ws + w.a0r, Cr, ws + w.a0 + Cm, C0, M, Cr, c.st);
+  }
+  int backward(LmBwd& k) const override {   // split the gradient of the concatenation, then each like a first convolution
+    const Ctx& c = k.c;
+    const int64_t M = (int64_t)c.B * L0;
+    float *y0m = c.ws + c.lo.stem.y0, *dOm = k.dX, *dOr = k.dX + M * Cm;
+    KWS_TRY(copy_cols(k.dO, C0, dOm, Cm, M, Cm, c.st));
+    KWS_TRY(copy_cols(k.dO + Cm, C0, dOr, Cr, M, Cr, c.st));
+    KWS_TRY(k.join_bwd(dOm, y0m, bn0, 1, k.G, L0, Cm, 1, 1));
+    KWS_TRY(k.sq.gemm_gather(c.x, &g0, k.G, c.grads + conv1, c.B, Cm, c.st));
+    KWS_TRY(k.join_bwd(dOr, y0m + M * Cm, bn0r, 2, k.G, L0, Cr, 1, 1));
+    KWS_TRY(k.sq.gemm_gather(c.x, &g0r, k.G, c.grads + conv1r, c.B, Cr, c.st));
+    KWS_TRY(k.sq.flush(c.st));
+    return k.dq.flush();
+  }
+};
 
-// Feature counts that are not a multiple of 4 (conv_1d_spectrogram: 257 bins): the gathered GEMM reads 16-byte
-// vectors, so the input rows and the [3, F, 64] kernel are re-pitched to Fp with zero columns / rows (plain 2-D
-// copies), and the padded weight gradient is copied back without them.
-int pad_first_conv(const Ctx& c, const float* x, const float** x_used, const float** w_used) {
-  const LmProgram& p = *c.p;
-  *x_used = x;
-  *w_used = c.params + p.conv1;
-  if (p.style == LM_STEFFE) {  // [75, 1, C0] kernel + one zero row: the gather reads 76 samples per output row
-    float* wp = c.ws + c.lo.wpad;
-    KWS_HIP(hipMemcpyAsync(wp, c.params + p.conv1, (size_t)p.K0 * p.C0 * 4, hipMemcpyDeviceToDevice, c.st));
-    KWS_HIP(hipMemsetAsync(wp + (size_t)p.K0 * p.C0, 0, (size_t)(p.K0p - p.K0) * p.C0 * 4, c.st));
-    *w_used = wp;
+// ---- heads ----------------------------------------------------------------------------------------------------------------------------
+// From the last activation x [B, T, C] to the class probabilities, through a Dense(NC) + softmax over `feat` values per clip.
+struct LmHead {
+  int T = 0, C = 0, NC = 0, feat = 0;
+  int tail_T = 16;           // u / att: [B, tail_T]
+  int64_t dk = 0, db = -1;   // dense_1/kernel, dense_1/bias (< 0: none)
+  virtual ~LmHead() {}
+  void add_dense(kws_net* n, int feat_, bool bias) {
+    NC = n->cfg.num_classes; feat = feat_;
+    dk = kws_net_add_tensor(n, "dense_1/kernel", {feat, NC}, false, KWS_L2_COEF, feat, NC, 0.f);
+    if (bias) db = kws_net_add_tensor(n, "dense_1/bias", {NC}, false, 0.f, 0, 0, 0.f);
+  }
+  virtual void take(Bump& bp, int B, LmHeadWs* w) const {
+    w->u = bp.take((int64_t)B * tail_T); w->fd = bp.take((int64_t)B * feat); w->dl = bp.take((int64_t)B * NC);
+    w->gu = bp.take((int64_t)B * 16); w->coef2 = bp.take(4);
+    w->per_loss = bp.take(B); w->per_correct = bp.take(B);
+    w->att = bp.take((int64_t)B * tail_T);
+  }
+  // debug views 3 = attention weights, 4 = attention logits u; 1: not one of the head's
+  virtual int view(const LmLayout& lo, int B, int training, int what, int64_t* offset_floats, int64_t* count) const {
+    if (what != 3 && what != 4) return 1;
+    *offset_floats = what == 3 ? lo.head.att : lo.head.u; *count = (int64_t)B * T;
     return KWS_OK;
   }
-  if (p.Fp == p.F) return KWS_OK;
-  float* xp = c.ws + c.lo.xpad;
-  float* wp = c.ws + c.lo.wpad;
-  const size_t rows = (size_t)c.B * p.T0;
-  const int64_t n4 = (int64_t)rows * (p.Fp / 4);
-  hipLaunchKernelGGL(repitch_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 8192)), dim3(256), 0, c.st, x, xp,
-                     (int64_t)rows, p.F, p.Fp);
-  KWS_LAUNCH_CHECK("repitch_kernel");
-  KWS_HIP(hipMemsetAsync(wp, 0, (size_t)3 * p.Fp * p.C0 * 4, c.st));
-  KWS_HIP(hipMemcpy2DAsync(wp, (size_t)p.Fp * p.C0 * 4, c.params + p.conv1, (size_t)p.F * p.C0 * 4, (size_t)p.F * p.C0 * 4, 3,
-                           hipMemcpyDeviceToDevice, c.st));
-  *x_used = xp;
-  *w_used = wp;
-  return KWS_OK;
-}
+  virtual int predict(const Ctx& c, const float* x, float* probs) const = 0;
+  // probs, metrics, the head's own gradients (the Dense weight gradient launched), and the gradient wrt x in k.dO
+  virtual int train(LmBwd& k, const float* x, const float* labels, float* probs, float* metrics, int loss_batch) const = 0;
+  int dense_wgrad(const Ctx& c) const {
+    return kws_small_wgrad_launch(c.ws + c.lo.head.fd, c.ws + c.lo.head.dl, c.grads + dk, db >= 0 ? c.grads + db : nullptr, c.B, feat, NC,
+                                  c.ws + c.lo.swg, c.st);
+  }
+};
+// the attention branch of two heads: a depthwise kernel and a pointwise kernel to one channel, with its BatchNorm
+struct LmAttLayers { int64_t dw = 0, pw = 0; BnRef bn; int bn_idx = 0; };
 
-int forward(const Ctx& c, const float* x, kws_lm_tail_args* t) {
-  const LmProgram& p = *c.p;
-  const LmLayout& lo = c.lo;
-  float* ws = c.ws;
-  const int B = c.B;
-  float* stats = c.training ? ws + lo.part : nullptr;
-  bool z1_first = false;      // the first block's first depthwise output already written (see below)
-  if (p.style == LM_MFCC_AND_RAW) {  // two stems on the packed [mfcc | raw] rows, concatenated after BN + ReLU6
-    const int64_t M = (int64_t)B * p.L0;
-    float* y0m = ws + lo.y0;
-    float* y0r = ws + lo.y0 + M * p.Cm;
-    KWS_TRY(kws_gemm_gather_f32(x, &p.g0, c.params + p.conv1, y0m, B, p.Cm, stats, c.st));
-    KWS_TRY(bn_table(c, p.bn0, 1, M, kws_gemm_gather_stats_rows(M)));
-    KWS_TRY(kws_gemm_gather_f32(x, &p.g0r, c.params + p.conv1r, y0r, B, p.Cr, stats, c.st));
-    KWS_TRY(bn_table(c, p.bn0r, 2, M, kws_gemm_gather_stats_rows(M)));
-    KWS_TRY(kws_bn_relu6_apply(y0m, c.bn_at(1), ws + lo.a0m, M, p.Cm, 1, c.st));
-    KWS_TRY(kws_bn_relu6_apply(y0r, c.bn_at(2), ws + lo.a0r, M, p.Cr, 1, c.st));
-    KWS_TRY(copy_cols(ws + lo.a0m, p.Cm, ws + lo.a0, p.C0, M, p.Cm, c.st));
-    KWS_TRY(copy_cols(ws + lo.a0r, p.Cr, ws + lo.a0 + p.Cm, p.C0, M, p.Cr, c.st));
-  } else {
-  const float *x0, *w0;
-  KWS_TRY(pad_first_conv(c, x, &x0, &w0));
-  KWS_TRY(kws_gemm_gather_f32(x0, &p.g0, w0, ws + lo.y0, B, p.C0, stats, c.st));
-  KWS_TRY(bn_table(c, p.bn0, 1, (int64_t)B * p.L0, kws_gemm_gather_stats_rows((int64_t)B * p.L0)));
-  // the first convolution's activation - and, where the first block starts with a k 3 / stride 1 / 'same' depthwise convolution over it
-  // (conv_1d_log_mfcc), that convolution's output in the same pass (round 6, kws_block_out_dw_fwd without a residual: bit-identical)
-  if (p.style == LM_ATTENTION && !p.blocks.empty() && kws_net_get_gemm_mode(c.p->net) != 1) {
-    const LmBlock& b0 = p.blocks[0];
-    if (b0.s1 == 1 && b0.pad1 == 1 && b0.Lmid == b0.Lin && b0.Lin == p.L0 && b0.cin == p.C0) {
-      KWS_TRY(kws_block_out_dw_fwd(ws + lo.y0, c.bn_at(1), nullptr, nullptr, c.params + b0.dw1, ws + lo.a0, ws + lo.z1[0], B, p.L0, p.C0, 1, c.st));
-      z1_first = true;
+// softmax-over-time attention (depthwise k 3 -> pointwise to 1 channel -> BN), weighted sum over time, Dropout, Dense + softmax, CE
+struct LmAttentionHead : LmHead {
+  LmAttLayers att;
+  float drop_keep = 1.f;
+  kws_lm_tail_args args(const Ctx& c, const float* x, float* probs) const {
+    kws_lm_tail_args t;
+    memset(&t, 0, sizeof(t));
+    t.x = x; t.probs = probs;
+    t.wa = c.params + att.dw; t.Wa = c.params + att.pw; t.bn_gamma = c.params + att.bn.gamma; t.bn_beta = c.params + att.bn.beta;
+    t.mm = c.state + att.bn.mm; t.mv = c.state + att.bn.mv;
+    t.Wd = c.params + dk; t.bd = c.params + db;
+    t.u = c.ws + c.lo.head.u; t.bn = c.bn_at(att.bn_idx);
+    t.B = c.B; t.T = T; t.C = C; t.NC = NC; t.keep_prob = c.training ? drop_keep : 1.f; t.loss_batch = 1;
+    return t;
+  }
+  int predict(const Ctx& c, const float* x, float* probs) const override {
+    const kws_lm_tail_args t = args(c, x, probs);
+    return kws_lm_tail_fwd(&t, 0, c.st);
+  }
+  int train(LmBwd& k, const float* x, const float* labels, float* probs, float* metrics, int loss_batch) const override {
+    const Ctx& c = k.c;
+    const LmHeadWs& w = c.lo.head;
+    float* ws = c.ws;
+    kws_lm_tail_args t = args(c, x, probs);
+    t.labels = labels; t.dX = k.dO; t.fd = ws + w.fd; t.dl = ws + w.dl; t.gu = ws + w.gu;
+    t.part = k.part; t.coef = ws + w.coef2; t.d_gamma = c.grads + att.bn.gamma; t.d_beta = c.grads + att.bn.beta;
+    t.per_loss = ws + w.per_loss; t.per_correct = ws + w.per_correct; t.att = ws + w.att;
+    t.seed = c.seed; t.step = c.step; t.loss_batch = loss_batch; t.row_offset = c.row_offset;
+    KWS_TRY(kws_lm_tail_fwd(&t, 1, c.st));
+    KWS_TRY(kws_metrics_launch(t.per_loss, t.per_correct, c.B, metrics, c.st));
+    KWS_TRY(dense_wgrad(c));
+    KWS_TRY(kws_lm_tail_bwd(&t, c.st));
+    return kws_dw_bwd_finalize(k.part, c.B, 1, C, c.grads + att.dw, nullptr, c.grads + att.pw, nullptr, k.red, c.st);
+  }
+};
+
+// GlobalAveragePooling1D, or GlobalMaxPooling1D ++ it, then Dropout, Dense + softmax and the loss (kws_gp_tail_args)
+struct LmPoolHead : LmHead {
+  bool pool_max = false;
+  int loss_kind = 1;       // 0 = label-smoothed CE, 1 = keras categorical_crossentropy
+  float label_smoothing = 0.f, drop_keep = 0.5f;
+  kws_gp_tail_args args(const Ctx& c, const float* x, float* probs) const {   // inference as it stands
+    kws_gp_tail_args g;
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.Wd = c.params + dk; g.bd = db >= 0 ? c.params + db : nullptr; g.probs = probs;
+    g.B = c.B; g.T = T; g.C = C; g.NC = NC;
+    g.pool_max = pool_max; g.loss_kind = loss_kind; g.label_smoothing = label_smoothing; g.keep_prob = 1.f; g.loss_batch = 1;
+    return g;
+  }
+  int predict(const Ctx& c, const float* x, float* probs) const override {
+    const kws_gp_tail_args g = args(c, x, probs);
+    return kws_gp_tail_launch(&g, 0, c.st);
+  }
+  int train(LmBwd& k, const float* x, const float* labels, float* probs, float* metrics, int loss_batch) const override {
+    const Ctx& c = k.c;
+    const LmHeadWs& w = c.lo.head;
+    kws_gp_tail_args g = args(c, x, probs);
+    g.labels = labels; g.dX = k.dO; g.fd = c.ws + w.fd; g.dl = c.ws + w.dl;
+    g.per_loss = c.ws + w.per_loss; g.per_correct = c.ws + w.per_correct;
+    g.seed = c.seed; g.step = c.step; g.keep_prob = drop_keep; g.loss_batch = loss_batch; g.row_offset = c.row_offset;
+    KWS_TRY(kws_gp_tail_launch(&g, 1, c.st));
+    KWS_TRY(kws_metrics_launch(g.per_loss, g.per_correct, c.B, metrics, c.st));
+    return dense_wgrad(c);
+  }
+};
+
+constexpr int XC_GATE_K = 5;          // _context_conv(x, 1, 5, padding='same'), model.py:973
+constexpr int XC_GRU_UNITS = 192;     // GRU(192, ...), model.py:976
+constexpr float XC_GRU_KEEP = 0.8f;   // dropout=0.2, recurrent_dropout=0.2
+
+// xception_with_attention: the attention gate (depthwise kernel [1, 5, C, 1]) over x, a bidirectional GRU of H units on the gated
+// sequence as it is, Dense + softmax over its signed [2 H] output (the flat tail's raw arm); the GRU carries the dropout
+struct LmGruHead : LmHead {
+  LmAttLayers att;
+  int H = 0;
+  int64_t gW[2] = {0, 0}, gU[2] = {0, 0}, gb[2] = {0, 0};
+  void take(Bump& bp, int B, LmHeadWs* w) const override {
+    LmHead::take(bp, B, w);
+    w->xgy = bp.take((int64_t)B * T * C);
+    w->xagf = bp.take(kws_attn_gate_fwd_floats(B, T, C, XC_GATE_K)); w->xagb = bp.take(kws_attn_gate_bwd_floats(B, T, C, XC_GATE_K));
+    w->gmx = bp.take((int64_t)6 * B * C); w->gmh = bp.take((int64_t)6 * B * H);
+    w->gout = bp.take((int64_t)B * 2 * H); w->gdout = bp.take((int64_t)B * 2 * H);
+    w->gsave = bp.take(kws_gru_save_floats(B, T, H));
+    w->gws = bp.take(kws_gru_workspace_floats(B, T, C, H, 1));
+  }
+  // 6 = gate output, 7 = the GRU's saved steps [2][4: z, r, c, h][B, T, H], 8 = GRU output, 9 = attention BN table
+  int view(const LmLayout& lo, int B, int training, int what, int64_t* offset_floats, int64_t* count) const override {
+    const LmHeadWs& w = lo.head;
+    if (what == 6) { *offset_floats = w.xgy; *count = (int64_t)B * T * C; return KWS_OK; }
+    KWS_REQUIRE(what != 7 || training, "lm_debug_view: view 7 exists in training only");
+    if (what == 7) { *offset_floats = w.gsave; *count = kws_gru_save_floats(B, T, H); return KWS_OK; }
+    if (what == 8) { *offset_floats = w.gout; *count = (int64_t)B * 2 * H; return KWS_OK; }
+    if (what == 9) { *offset_floats = lo.bn + lo.bn_stride * att.bn_idx; *count = 4; return KWS_OK; }
+    return LmHead::view(lo, B, training, what, offset_floats, count);
+  }
+  int gate_gru_fwd(const Ctx& c, const float* x) const {
+    const LmHeadWs& w = c.lo.head;
+    float* ws = c.ws;
+    const float* p = c.params;
+    KWS_TRY(kws_attn_gate_fwd_f32(x, p + att.dw, p + att.pw, p + att.bn.gamma, p + att.bn.beta, c.state + att.bn.mm, c.state + att.bn.mv,
+                                  ws + w.u, c.bn_at(att.bn_idx), ws + w.att, ws + w.xgy, ws + w.xagf, c.B, T, C, XC_GATE_K,
+                                  c.training ? 1 : 0, c.st));
+    if (c.training) KWS_TRY(kws_gru_masks(ws + w.gmx, ws + w.gmh, c.B, C, H, XC_GRU_KEEP, c.seed, c.step, c.row_offset, c.st));
+    return kws_gru_fwd_f32(ws + w.xgy, p + gW[0], p + gU[0], p + gb[0], p + gW[1], p + gU[1], p + gb[1], c.training ? ws + w.gmx : nullptr,
+                           c.training ? ws + w.gmh : nullptr, ws + w.gout, c.training ? ws + w.gsave : nullptr, ws + w.gws, c.B, T, C, H,
+                           c.st);
+  }
+  kws_flat_tail_args tail_args(const Ctx& c, float* probs) const {
+    kws_flat_tail_args t;
+    memset(&t, 0, sizeof(t));
+    t.y = c.ws + c.lo.head.gout; t.Ng = feat; t.raw = 1;
+    t.Wd = c.params + dk; t.bd = c.params + db; t.probs = probs;
+    t.B = c.B; t.D = feat; t.F = feat; t.NC = NC; t.keep_prob = 1.f;
+    return t;
+  }
+  int predict(const Ctx& c, const float* x, float* probs) const override {
+    KWS_TRY(gate_gru_fwd(c, x));
+    const kws_flat_tail_args t = tail_args(c, probs);
+    return kws_flat_tail_launch(&t, 0, c.st);
+  }
+  // ... and back: the GRU's dx (in k.G) is the gate's dy, the gate's dx the last block's dO
+  int train(LmBwd& k, const float* x, const float* labels, float* probs, float* metrics, int loss_batch) const override {
+    const Ctx& c = k.c;
+    const LmHeadWs& w = c.lo.head;
+    float *ws = c.ws, *g = c.grads;
+    const float* p = c.params;
+    KWS_TRY(gate_gru_fwd(c, x));
+    kws_flat_tail_args t = tail_args(c, probs);
+    KWS_TRY(kws_flat_tail_train(&t, labels, ws + w.fd, ws + w.dl, ws + w.gdout, ws + w.per_loss, ws + w.per_correct, c.seed, c.step,
+                                loss_batch, c.row_offset, metrics, c.st));
+    KWS_TRY(dense_wgrad(c));
+    KWS_TRY(kws_gru_bwd_f32(ws + w.gdout, ws + w.xgy, p + gW[0], p + gU[0], p + gW[1], p + gU[1], ws + w.gmx, ws + w.gmh, ws + w.gsave, k.G,
+                            g + gW[0], g + gU[0], g + gb[0], g + gW[1], g + gU[1], g + gb[1], ws + w.gws, c.B, T, C, H, c.st));
+    return kws_attn_gate_bwd_f32(k.G, x, ws + w.u, ws + w.att, c.bn_at(att.bn_idx), p + att.dw, p + att.pw, p + att.bn.gamma, k.dO,
+                                 g + att.dw, g + att.pw, g + att.bn.gamma, g + att.bn.beta, ws + w.xagb, c.B, T, C, XC_GATE_K, 1, c.st);
+  }
+};
+
+// ---- the program ----------------------------------------------------------------------------------------------------------------------
+struct LmProgram : NetProgram {
+  const kws_net* net = nullptr;
+  std::unique_ptr<LmStem> stem;
+  bool fuse_first_dw = false;   // the stem's activation pass also writes block 0's first depthwise output, where that follows it
+  bool has_ctx = false;         // a unit between the stem and the blocks whose activated output is materialised (steffeNet's _context_conv)
+  LmUnit ctx;
+  std::vector<LmBlock> blocks;
+  std::vector<LmUnit> plain;    // units without a residual after the blocks (conv_1d_residual's _reduce_block); the last activation is materialised
+  std::unique_ptr<LmHead> head;
+  int T = 0, C = 0;             // [T, C]: the running activation while the table is built, the head's input afterwards
+  int n_units = 0, n_bn = 0, maxC = 0;   // maxC: the widest BatchNormalization of the table
+
+  void layout(int B, LmLayout* lo) const {
+    Bump bp;
+    const LmStem& s = *stem;
+    LmSizes m;
+    m.B = B; m.o = m.y = (int64_t)B * s.L0 * s.C0;
+    lo->u.assign(n_units, LmUnitWs());
+    lo->b.assign(blocks.size(), LmBlockWs());
+    auto take_acts = [&](const LmUnit& u) {
+      lo->u[u.slot].z = bp.take((int64_t)B * u.Lout * u.cin);
+      lo->u[u.slot].y = bp.take((int64_t)B * u.Lout * u.cout);
+    };
+    auto take_wt = [&](const LmUnit& u) { lo->u[u.slot].wt = bp.take((int64_t)u.cin * u.cout); };
+    s.take_front(bp, B, &lo->stem);
+    s.sizes(&m);
+    m.parts(kws_block_out_bwd_part_floats(B, s.L0, s.C0, 1));
+    if (has_ctx) {
+      take_acts(ctx);
+      lo->ac = bp.take((int64_t)B * ctx.Lout * ctx.cout);
+      m.unit(ctx, true);
     }
+    for (const LmBlock& b : blocks) {
+      LmBlockWs& w = lo->b[b.slot];
+      if (b.has_short) w.ys = bp.take((int64_t)B * b.Lout * b.nf);
+      take_acts(b.u1); take_acts(b.u2);
+      w.o = bp.take((int64_t)B * b.Lout * b.nf);
+      m.o = std::max(m.o, std::max((int64_t)B * b.Lout * b.nf, (int64_t)B * b.Lin * b.cin));
+      m.xs = std::max(m.xs, (int64_t)B * b.Lout * b.cin);
+      m.unit(b.u1, true); m.unit(b.u2, false);
+      if (b.has_short) m.pw((int64_t)B * b.Lout, b.cin, b.nf);
+      m.parts(b.pool3 ? kws_block_out3_bwd_part_floats(B, b.Lmid, b.nf) : kws_block_out_bwd_part_floats(B, b.Lmid, b.nf, b.pool));
+      m.parts(kws_block_out_bwd_part_floats(B, b.Lout, b.nf, 1));
+    }
+    for (size_t j = 0; j < plain.size(); ++j) {
+      const LmUnit& q = plain[j];
+      take_acts(q);
+      m.o = std::max(m.o, std::max((int64_t)B * q.Lin * q.cin, (int64_t)B * q.Lout * q.cout));
+      m.unit(q, j == 0);
+      m.parts(kws_block_out_bwd_part_floats(B, q.Lout, q.cout, 1));
+    }
+    if (!plain.empty()) lo->alast = bp.take((int64_t)B * T * C);
+    m.parts((int64_t)B * 5 * C);
+    lo->bn_stride = 4 * maxC;
+    lo->bn = bp.take(lo->bn_stride * (n_bn + 1));
+    lo->part = bp.take(m.part);
+    lo->red = bp.take((int64_t)KWS_REDUCE_SLICES * 5 * maxC);
+    lo->coef = bp.take(2 * maxC);
+    lo->WT = bp.take(m.wt);
+    for (const LmBlock& b : blocks) {
+      take_wt(b.u1); take_wt(b.u2);
+      if (b.has_short) lo->b[b.slot].wt_ws = bp.take((int64_t)b.cin * b.nf);
+    }
+    for (const LmUnit& q : plain) take_wt(q);
+    if (has_ctx) take_wt(ctx);
+    lo->tn = bp.take(m.tn);
+    lo->tnq_floats = m.tnq; lo->tnq = bp.take(m.tnq);
+    lo->dwq_floats = m.dwq; lo->dwq = bp.take(m.dwq);
+    lo->swg = bp.take((int64_t)KWS_SMALL_WGRAD_SLICES * head->feat * head->NC);
+    lo->dOa = bp.take(m.o); lo->dOb = bp.take(m.o);
+    lo->G = bp.take(m.y); lo->DZ = bp.take(m.z); lo->DXS = bp.take(m.xs);
+    head->take(bp, B, &lo->head);
+    s.take_back(bp, B, &lo->stem);
+    lo->total = bp.cur * 4;
   }
-  if (!z1_first) KWS_TRY(kws_bn_relu6_apply(ws + lo.y0, c.bn_at(1), ws + lo.a0, (int64_t)B * p.L0, p.C0, 1, c.st));
+
+  // block 0's first unit where the stem's activation pass writes its depthwise output
+  const LmUnit* fused_first_dw(const Ctx& c) const {
+    if (!fuse_first_dw || c.ref_schedule || blocks.empty()) return nullptr;
+    return dw_follows(blocks[0].u1, stem->L0, stem->C0) ? &blocks[0].u1 : nullptr;
   }
-  const float* xin = ws + lo.a0;
-  if (p.style == LM_STEFFE) {  // _context_conv(x, 256, 3, 'same'): depthwise -> pointwise -> BN -> ReLU6, materialised
-    const int64_t M = (int64_t)B * p.L0;
-    KWS_TRY(kws_dwconv_fwd_f32(xin, nullptr, c.params + p.ctx_dw, ws + lo.zc, B, p.L0, p.L0, p.C0, 1, 1, c.st));
-    KWS_TRY(kws_gemm_nn_f32(ws + lo.zc, c.params + p.ctx_pw, ws + lo.yc, M, p.C0, p.C0, stats, c.st));
-    KWS_TRY(bn_table(c, p.ctx_bn, p.ctx_bn_idx, M, kws_gemm_nn_stats_rows(M, p.C0, p.C0)));
-    KWS_TRY(kws_bn_relu6_apply(ws + lo.yc, c.bn_at(p.ctx_bn_idx), ws + lo.ac, M, p.C0, 1, c.st));
-    xin = ws + lo.ac;
-  }
-  bool z1_ready = z1_first;
-  const bool fuse_join_dw = kws_net_get_gemm_mode(c.p->net) != 1;
-  for (size_t i = 0; i < p.blocks.size(); ++i) {
-    const LmBlock& b = p.blocks[i];
-    const int64_t M = (int64_t)B * b.Lmid;
-    if (b.has_short) {
-      // the shortcut convolution (1 x 1, stride s): over an even-length input it is every s-th ROW of the block input - a plain GEMM
-      // with a row pitch on the wave-specialised kernel (round 6); the gathered kernel otherwise
-      const int64_t Ms = (int64_t)B * b.Lout;
-      int lda = 0, srows = kws_gemm_gather_stats_rows(Ms);
-      int rs = 1;
-      if (kws_gather_strided_rows(&b.gs, &lda)) {
-        rs = kws_gemm_nn_strided_f32(xin, lda, c.params + b.ws, ws + lo.ys[i], Ms, b.gs.cin, b.nf, stats, c.st);
-        if (rs < 0) return rs;
-        if (rs == 0 && stats) srows = kws_gemm_nn_stats_rows(Ms, b.gs.cin, b.nf);
+
+  // from the stem's activation a0 to the last activation *x_last
+  int body_forward(const Ctx& c, const float** x_last) const {
+    const LmLayout& lo = c.lo;
+    float* ws = c.ws;
+    const int B = c.B;
+    const float* xin = ws + lo.stem.a0;
+    if (has_ctx) {
+      KWS_TRY(unit_fwd(c, ctx, xin, nullptr));
+      KWS_TRY(kws_bn_relu6_apply(c.y(ctx), c.bn_at(ctx.bn_idx), ws + lo.ac, (int64_t)B * ctx.Lout, ctx.cout, 1, c.st));
+      xin = ws + lo.ac;
+    }
+    bool z1_ready = fused_first_dw(c) != nullptr;   // the first block's first depthwise output already written by the stem
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      const LmBlock& b = blocks[i];
+      const LmBlockWs& w = lo.b[i];
+      if (b.has_short) {
+        // the shortcut convolution (1 x 1, stride s): over an even-length input it is every s-th ROW of the block input - a plain GEMM
+        // with a row pitch on the wave-specialised kernel (round 6); the gathered kernel otherwise
+        const int64_t Ms = (int64_t)B * b.Lout;
+        int lda = 0, srows = kws_gemm_gather_stats_rows(Ms);
+        int rs = 1;
+        if (kws_gather_strided_rows(&b.gs, &lda)) {
+          rs = kws_gemm_nn_strided_f32(xin, lda, c.params + b.ws, ws + w.ys, Ms, b.gs.cin, b.nf, c.stats(), c.st);
+          if (rs < 0) return rs;
+          if (rs == 0 && c.training) srows = kws_gemm_nn_stats_rows(Ms, b.gs.cin, b.nf);
+        }
+        if (rs != 0) KWS_TRY(kws_gemm_gather_f32(xin, &b.gs, c.params + b.ws, ws + w.ys, B, b.nf, c.stats(), c.st));
+        KWS_TRY(bn_table(c, b.bns, b.bns_idx, Ms, srows));
       }
-      if (rs != 0) KWS_TRY(kws_gemm_gather_f32(xin, &b.gs, c.params + b.ws, ws + lo.ys[i], B, b.nf, stats, c.st));
-      KWS_TRY(bn_table(c, b.bns, b.bns_idx, Ms, srows));
+      KWS_TRY(unit_fwd(c, b.u1, xin, nullptr, z1_ready));   // (z1_ready: written by the previous block's join, below)
+      KWS_TRY(unit_fwd(c, b.u2, c.y(b.u1), &b.u1));
+      const float* y2 = c.y(b.u2);
+      const float* bn2 = c.bn_at(b.u2.bn_idx);
+      const float* res = b.has_short ? ws + w.ys : xin;
+      const float* res_bn = b.has_short ? c.bn_at(b.bns_idx) : nullptr;
+      // round 6: the join writes the NEXT block's first depthwise output too where that is a k 3 / stride 1 / 'same' convolution over this
+      // block's output (every log-mfcc block): one tensor pass and one launch less per block, bit-identical (not in the reference schedule)
+      const LmUnit* nx = i + 1 < blocks.size() ? &blocks[i + 1].u1 : nullptr;
+      z1_ready = !b.pool3 && nx && !c.ref_schedule && dw_follows(*nx, b.Lout, b.nf);
+      if (b.pool3) KWS_TRY(kws_block_out3_fwd(y2, bn2, res, res_bn, ws + w.o, B, b.Lmid, b.Lout, b.nf, b.stride, b.ppad, c.st));
+      else if (z1_ready) KWS_TRY(kws_block_out_dw_fwd(y2, bn2, res, res_bn, c.params + nx->dw, ws + w.o, c.z(*nx), B, b.Lmid, b.nf, b.pool, c.st));
+      else KWS_TRY(kws_block_out_fwd(y2, bn2, res, res_bn, ws + w.o, B, b.Lmid, b.nf, b.pool, c.st));
+      xin = ws + w.o;
     }
-    if (!z1_ready)      // (else: written by the previous block's join, kws_block_out_dw_fwd below)
-      KWS_TRY(kws_dwconv_fwd_f32(xin, nullptr, c.params + b.dw1, ws + lo.z1[i], B, b.Lin, b.Lmid, b.cin, b.s1, b.pad1, c.st));
-    z1_ready = false;
-    KWS_TRY(kws_gemm_nn_f32(ws + lo.z1[i], c.params + b.pw1, ws + lo.y1[i], M, b.cin, b.nf, stats, c.st));
-    KWS_TRY(bn_table(c, b.bn1, b.bn1_idx, M, kws_gemm_nn_stats_rows(M, b.cin, b.nf)));
-    KWS_TRY(kws_dwconv_fwd_f32(ws + lo.y1[i], c.bn_at(b.bn1_idx), c.params + b.dw2, ws + lo.z2[i], B, b.Lmid, b.Lmid,
-                               b.nf, 1, 1, c.st));
-    KWS_TRY(kws_gemm_nn_f32(ws + lo.z2[i], c.params + b.pw2, ws + lo.y2[i], M, b.nf, b.nf, stats, c.st));
-    KWS_TRY(bn_table(c, b.bn2, b.bn2_idx, M, kws_gemm_nn_stats_rows(M, b.nf, b.nf)));
-    if (b.pool3)
-      KWS_TRY(kws_block_out3_fwd(ws + lo.y2[i], c.bn_at(b.bn2_idx), b.has_short ? ws + lo.ys[i] : xin,
-                                 b.has_short ? c.bn_at(b.bns_idx) : nullptr, ws + lo.o[i], B, b.Lmid, b.Lout, b.nf, b.stride,
-                                 b.ppad, c.st));
-    else {
-      // round 6: the join writes the NEXT block's first depthwise output too where that is a k 3 / stride 1 / 'same' convolution over
-      // this block's output (every log-mfcc block): one tensor pass and one launch less per block, bit-identical (gemm mode 1, the A/B
-      // reference schedule, keeps the two launches)
-      const LmBlock* nx = i + 1 < p.blocks.size() ? &p.blocks[i + 1] : nullptr;
-      const bool fuse = nx && fuse_join_dw && nx->s1 == 1 && nx->pad1 == 1 && nx->Lmid == nx->Lin && nx->Lin == b.Lout && nx->cin == b.nf;
-      if (fuse) {
-        KWS_TRY(kws_block_out_dw_fwd(ws + lo.y2[i], c.bn_at(b.bn2_idx), b.has_short ? ws + lo.ys[i] : xin,
-                                     b.has_short ? c.bn_at(b.bns_idx) : nullptr, c.params + nx->dw1, ws + lo.o[i], ws + lo.z1[i + 1], B,
-                                     b.Lmid, b.nf, b.pool, c.st));
-        z1_ready = true;
+    for (size_t j = 0; j < plain.size(); ++j) {
+      KWS_TRY(unit_fwd(c, plain[j], j ? c.y(plain[j - 1]) : xin, j ? &plain[j - 1] : nullptr));
+      if (j + 1 == plain.size()) {
+        KWS_TRY(kws_bn_relu6_apply(c.y(plain[j]), c.bn_at(plain[j].bn_idx), ws + lo.alast, (int64_t)B * T, C, 1, c.st));
+        xin = ws + lo.alast;
+      }
+    }
+    *x_last = xin;
+    return KWS_OK;
+  }
+
+  // every pointwise kernel transposed for its dgrad GEMM, KWS_TRANSPOSE_BATCH matrices per launch
+  int transpose_pointwise(const Ctx& c) const {
+    std::vector<const float*> tin;
+    std::vector<float*> tout;
+    std::vector<int> trows, tcols;
+    auto add = [&](int64_t src, float* dst, int rows, int cols) {
+      tin.push_back(c.params + src); tout.push_back(dst); trows.push_back(rows); tcols.push_back(cols);
+    };
+    auto add_unit = [&](const LmUnit& u) { add(u.pw, c.wt(u), u.cin, u.cout); };
+    for (const LmBlock& b : blocks) {
+      add_unit(b.u1); add_unit(b.u2);
+      if (b.has_short) add(b.ws, c.ws + c.lo.b[b.slot].wt_ws, b.cin, b.nf);
+    }
+    for (const LmUnit& q : plain) add_unit(q);
+    if (has_ctx) add_unit(ctx);
+    for (size_t o = 0; o < tin.size(); o += KWS_TRANSPOSE_BATCH) {
+      const int nbat = (int)std::min<size_t>(KWS_TRANSPOSE_BATCH, tin.size() - o);
+      KWS_TRY(kws_transpose_batch_f32(tin.data() + o, tout.data() + o, trows.data() + o, tcols.data() + o, nbat, c.st));
+    }
+    return KWS_OK;
+  }
+
+  // k.dO = the gradient wrt the last activation -> k.dO = the gradient wrt the stem's activation a0
+  int body_backward(LmBwd& k) const {
+    const Ctx& c = k.c;
+    const LmLayout& lo = c.lo;
+    float* ws = c.ws;
+    const int B = c.B;
+    // ---- plain units, last to first: dO is the gradient wrt the materialised activation; below it k.G carries dy from unit to unit
+    for (int j = (int)plain.size() - 1; j >= 0; --j) {
+      const LmUnit& q = plain[j];
+      if (j + 1 == (int)plain.size()) KWS_TRY(k.join_bwd(k.dO, c.y(q), q.bn, q.bn_idx, k.G, q.Lout, q.cout, 1, 1));
+      KWS_TRY(unit_bwd(k, q, j ? c.y(plain[j - 1]) : ws + lo.b[blocks.size() - 1].o, j ? &plain[j - 1] : nullptr));
+      if (j == 0) std::swap(k.dO, k.dX);
+    }
+    // ---- residual blocks, last to first ----
+    for (int i = (int)blocks.size() - 1; i >= 0; --i) {
+      const LmBlock& b = blocks[i];
+      const float* xin = i ? ws + lo.b[i - 1].o : has_ctx ? ws + lo.ac : ws + lo.stem.a0;
+      // main branch: join backward (maxpool routing + ReLU6 mask) -> BN2, then the second unit and the first
+      if (b.pool3) {   // the 3-wide SAME join keeps the one-pass form (an input position collects up to three windows)
+        const int64_t M = (int64_t)B * b.Lmid;
+        const float* bn2 = c.bn_at(b.u2.bn_idx);
+        KWS_TRY(kws_block_out3_bwd(k.dO, c.y(b.u2), bn2, k.G, k.part, B, b.Lmid, b.Lout, b.nf, b.stride, b.ppad, c.st));
+        const int np = (int)(kws_block_out3_bwd_part_floats(B, b.Lmid, b.nf) / (5 * b.nf));
+        KWS_TRY(kws_dw_bwd_finalize(k.part, np, M, b.nf, nullptr, c.grads + b.u2.bn.gamma, c.grads + b.u2.bn.beta, k.coef, k.red, c.st));
+        KWS_TRY(kws_bn_bwd_apply(k.G, c.y(b.u2), bn2, c.params + b.u2.bn.gamma, k.coef, M, b.nf, c.st));
       } else {
-        KWS_TRY(kws_block_out_fwd(ws + lo.y2[i], c.bn_at(b.bn2_idx), b.has_short ? ws + lo.ys[i] : xin,
-                                  b.has_short ? c.bn_at(b.bns_idx) : nullptr, ws + lo.o[i], B, b.Lmid, b.nf, b.pool, c.st));
+        KWS_TRY(k.join_bwd(k.dO, c.y(b.u2), b.u2.bn, b.u2.bn_idx, k.G, b.Lmid, b.nf, b.pool, 1));
+      }
+      KWS_TRY(unit_bwd(k, b.u2, c.y(b.u1), &b.u1));
+      // round 6: with a strided shortcut whose rows sit at whole multiples of the stride, the shortcut branch runs FIRST and its input
+      // gradient joins the depthwise input gradient inside that kernel (same single addition per element: bit-identical) instead of an
+      // add_strided pass afterwards; the reference schedule keeps the order and the launches of rounds 3 - 5
+      const bool short_first = b.has_short && !c.ref_schedule && b.stride >= 2 && (int64_t)(b.Lout - 1) * b.stride < b.Lin;
+      if (!b.has_short) {   // identity shortcut: the join's other gradient is added while the depthwise input gradient is written
+        KWS_TRY(unit_bwd(k, b.u1, xin, nullptr, LmDxJoin{k.dO, nullptr}));
+      } else if (short_first) {
+        KWS_TRY(unit_bwd(k, b.u1, xin, nullptr, LmDxJoin{nullptr, &b}));
+      } else {
+        KWS_TRY(unit_bwd(k, b.u1, xin, nullptr));
+        KWS_TRY(short_bwd(k, b, xin));   // residual branch
+        KWS_TRY(kws_add_strided_f32(k.dX, k.DXS, B, b.Lin, b.Lout, b.cin, b.stride, c.st));
+      }
+      std::swap(k.dO, k.dX);
+    }
+    if (has_ctx) {   // dO is the gradient wrt the context unit's activated output
+      KWS_TRY(k.join_bwd(k.dO, c.y(ctx), ctx.bn, ctx.bn_idx, k.G, ctx.Lout, ctx.cout, 1, 1));
+      KWS_TRY(unit_bwd(k, ctx, ws + lo.stem.a0, nullptr));
+      std::swap(k.dO, k.dX);
+    }
+    return KWS_OK;
+  }
+
+  int64_t workspace_bytes(int B, int) const override {
+    LmLayout lo;
+    layout(B, &lo);
+    return lo.total;
+  }
+  // what: 0 = pre-BN tensor of BN `index` (1-based Keras numbering), 2 = BN table of BN `index`, 5 = the last block's output,
+  //       the rest are the head's
+  int debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const override {
+    LmLayout lo;
+    layout(B, &lo);
+    if (what == 2) {
+      KWS_REQUIRE(index >= 1 && index <= n_bn, "lm_debug_view: bn index %d", index);
+      *offset_floats = lo.bn + lo.bn_stride * index; *count = 4 * maxC;
+      return KWS_OK;
+    }
+    if (what == 5) { *offset_floats = lo.b[blocks.size() - 1].o; *count = (int64_t)B * T * C; return KWS_OK; }
+    const int rc = head->view(lo, B, training, what, offset_floats, count);
+    if (rc != 1) return rc;
+    auto unit_view = [&](const LmUnit& u) {
+      if (index == u.bn_idx) { *offset_floats = lo.u[u.slot].y; *count = (int64_t)B * u.Lout * u.cout; }
+      return index == u.bn_idx;
+    };
+    if (what == 0) {
+      if (stem->view(lo.stem, B, index, offset_floats, count) || (has_ctx && unit_view(ctx))) return KWS_OK;
+      for (const LmUnit& q : plain)
+        if (unit_view(q)) return KWS_OK;
+      for (const LmBlock& b : blocks) {
+        if (b.has_short && index == b.bns_idx) { *offset_floats = lo.b[b.slot].ys; *count = (int64_t)B * b.Lout * b.nf; return KWS_OK; }
+        if (unit_view(b.u1) || unit_view(b.u2)) return KWS_OK;
       }
     }
-    xin = ws + lo.o[i];
+    kws_set_error("lm_debug_view: unknown view %d/%d", what, index);
+    return KWS_E_INVALID;
   }
-  if (!p.plain.empty()) {  // _reduce_block: depthwise -> pointwise -> BN -> ReLU6, twice; the last activation is materialised
-    const float* pbn = nullptr;
-    for (size_t j = 0; j < p.plain.size(); ++j) {
-      const LmPlain& q = p.plain[j];
-      const int64_t M = (int64_t)B * q.Lout;
-      KWS_TRY(kws_dwconv_fwd_f32(xin, pbn, c.params + q.dw, ws + lo.pz[j], B, q.Lin, q.Lout, q.cin, q.stride, q.pad_l, c.st));
-      KWS_TRY(kws_gemm_nn_f32(ws + lo.pz[j], c.params + q.pw, ws + lo.py[j], M, q.cin, q.cout, stats, c.st));
-      KWS_TRY(bn_table(c, q.bn, q.bn_idx, M, kws_gemm_nn_stats_rows(M, q.cin, q.cout)));
-      xin = ws + lo.py[j];
-      pbn = c.bn_at(q.bn_idx);
-    }
-    KWS_TRY(kws_bn_relu6_apply(xin, pbn, ws + lo.alast, (int64_t)B * p.T, p.C, 1, c.st));
-    xin = ws + lo.alast;
+  int predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
+              hipStream_t st) const override {
+    const Ctx c(*this, NetCall{params, const_cast<float*>(state), x, B, false, nullptr, ws, 0, 0, 0, st});   // state is only read
+    KWS_TRY(kws_workspace_check("net_predict", c.lo.total, ws_bytes, B));
+    const float* x_last = nullptr;
+    KWS_TRY(stem->forward(c, fused_first_dw(c)));
+    KWS_TRY(body_forward(c, &x_last));
+    return head->predict(c, x_last, probs);
   }
-  memset(t, 0, sizeof(*t));
-  t->x = xin;
-  if (p.style != LM_ATTENTION) return KWS_OK;  // the caller sets up the global-pooling tail
-  t->wa = c.params + p.att_dw; t->Wa = c.params + p.att_pw;
-  t->bn_gamma = c.params + p.att_bn.gamma; t->bn_beta = c.params + p.att_bn.beta;
-  t->mm = c.state + p.att_bn.mm; t->mv = c.state + p.att_bn.mv;
-  t->Wd = c.params + p.dk; t->bd = c.params + p.db;
-  t->u = ws + lo.u; t->bn = c.bn_at(p.att_bn_idx);
-  t->B = B; t->T = p.T; t->C = p.C; t->NC = p.NC; t->keep_prob = c.training ? p.drop_keep : 1.f; t->loss_batch = 1;
-  return KWS_OK;
-}
+  int train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs, float* metrics,
+            uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes, hipStream_t st) const override {
+    const Ctx c(*this, NetCall{params, state, x, B, true, grads, ws, seed, step, row_offset, st});
+    KWS_TRY(kws_workspace_check("net_train_fwd_bwd", c.lo.total, ws_bytes, B));
+    KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
+    const float* x_last = nullptr;
+    KWS_TRY(stem->forward(c, fused_first_dw(c)));
+    KWS_TRY(body_forward(c, &x_last));
+    KWS_TRY(transpose_pointwise(c));
+    LmBwd k(c);
+    KWS_TRY(head->train(k, x_last, y_onehot, probs, metrics, loss_batch));   // leaves the gradient wrt x_last in k.dO
+    KWS_TRY(body_backward(k));
+    return stem->backward(k);
+  }
+};
 
-// Where a residual block's stride sits (LmBlock::s1 / pool / Lmid / pad1 / pool3 / ppad follow from it)
+Ctx::Ctx(const LmProgram& p, const NetCall& n) : NetCall(n), ref_schedule(kws_net_get_gemm_mode(p.net) == 1) { p.layout(B, &lo); }
+
+// ---- what the builders share ----------------------------------------------------------------------------------------------------------
+// Where a residual block's stride sits (LmBlock::pool / Lmid / pool3 / ppad and its first unit's stride follow from it)
 enum LmStridePlace {
   LM_POOL_AFTER,   // MaxPool1D(stride, stride) after the second pointwise convolution (conv_1d_log_mfcc)
   LM_STRIDED_DW,   // the block's first depthwise convolution is strided, 'same' (steffeNet)
   LM_POOL3_SAME,   // MaxPool1D(3, stride, 'same') after the second pointwise (conv_1d_residual, conv_1d_mfcc_and_raw)
 };
 
-LmProgram* lm_new(kws_net* n, LmStyle style, float drop_keep) {
+// Installs the program with its stem (L0 and C0 set): the running activation is the stem's [L0, C0]
+LmProgram* lm_new(kws_net* n, LmStem* stem) {
   LmProgram* p = new LmProgram();
   n->program.reset(p);   // freed with the net when the builder fails
-  p->net = n;
-  p->style = style;
-  p->drop_keep = drop_keep;
+  p->net = n; p->stem.reset(stem);
+  p->T = stem->L0; p->C = p->maxC = stem->C0;
   return p;
 }
 
-// The stem is done: the running activation is [L0, C0]
-void lm_begin_stack(LmProgram* p) {
-  p->T = p->L0;
-  p->C = p->C0;
-  p->maxC = p->C0;
+// Creates one unit's layers (Keras creation order: depthwise, pointwise, BatchNormalization) for the given geometry
+LmUnit lm_unit(KerasNames& kn, LmProgram* p, int cin, int cout, int Lin, int Lout, int stride, int pad_l) {
+  LmUnit u;
+  u.cin = cin; u.cout = cout; u.Lin = Lin; u.Lout = Lout; u.stride = stride; u.pad_l = pad_l;
+  u.dw = kn.dw(cin); u.pw = kn.conv(1, cin, cout, KWS_L2_COEF);
+  u.bn = kn.bn(cout, &u.bn_idx);
+  u.slot = p->n_units++;
+  p->maxC = std::max(p->maxC, cout);
+  return u;
 }
 
 // Appends one residual block of nf filters over the running activation [p->T, p->C] and moves that on to the block's
-// output.  Keras creation order: shortcut Conv1D + BN (strided blocks only), then 2 x (depthwise, pointwise, BN).
+// output.  Keras creation order: shortcut Conv1D + BN (strided blocks only), then the two units.
 int lm_add_block(KerasNames& kn, LmProgram* p, LmStridePlace place, int nf, int stride) {
   const int cin = p->C, L = p->T;
   LmBlock b{};
-  b.nf = nf; b.stride = stride; b.cin = cin; b.Lin = L;
-  b.s1 = 1; b.pool = stride; b.Lmid = L; b.pad1 = 1;
+  b.nf = nf; b.stride = stride; b.cin = cin; b.Lin = L; b.pool = stride; b.Lmid = L;
   b.Lout = (L + stride - 1) / stride;   // Keras 'same' whichever layer carries the stride: ceil(L / stride)
+  int s1 = 1, pad1 = 1;
   if (place == LM_STRIDED_DW) {
-    kws_same_pad(L, 3, stride, &b.Lout, &b.pad1);
-    b.s1 = stride; b.pool = 1; b.Lmid = b.Lout;
+    kws_same_pad(L, 3, stride, &b.Lout, &pad1);
+    s1 = stride; b.pool = 1; b.Lmid = b.Lout;
   } else if (place == LM_POOL3_SAME) {
     b.pool3 = 1;
     kws_same_pad(L, 3, stride, &b.Lout, &b.ppad);
@@ -507,146 +878,93 @@ int lm_add_block(KerasNames& kn, LmProgram* p, LmStridePlace place, int nf, int 
   } else {
     KWS_REQUIRE(cin == nf, "net: identity shortcut needs cin == nf");
   }
-  b.dw1 = kn.dw(cin);
-  b.pw1 = kn.conv(1, cin, nf, KWS_L2_COEF);
-  b.bn1 = kn.bn(nf, &b.bn1_idx);
-  b.dw2 = kn.dw(nf);
-  b.pw2 = kn.conv(1, nf, nf, KWS_L2_COEF);
-  b.bn2 = kn.bn(nf, &b.bn2_idx);
+  b.u1 = lm_unit(kn, p, cin, nf, L, b.Lmid, s1, pad1);
+  b.u2 = lm_unit(kn, p, nf, nf, b.Lmid, b.Lmid, 1, 1);
+  b.slot = (int)p->blocks.size();
   p->blocks.push_back(b);
-  p->C = nf;
-  p->T = b.Lout;
-  p->maxC = std::max(p->maxC, nf);
+  p->C = nf; p->T = b.Lout;
   return KWS_OK;
 }
 
-// Appends a depthwise block without a residual: _reduce_conv (strides 2, 'same') or _context_conv ('valid')
+// Appends a unit without a residual: _reduce_conv (strides 2, 'same') or _context_conv ('valid')
 int lm_add_plain(KerasNames& kn, LmProgram* p, int cout, int stride) {
-  LmPlain q;
-  q.cin = p->C; q.cout = cout; q.Lin = p->T; q.stride = stride;
-  if (stride == 1) { q.pad_l = 0; q.Lout = q.Lin - 2; }
-  else kws_same_pad(q.Lin, 3, stride, &q.Lout, &q.pad_l);
-  KWS_REQUIRE(q.Lout >= 1, "net: conv_1d_residual input too short");
-  q.dw = kn.dw(q.cin);
-  q.pw = kn.conv(1, q.cin, cout, KWS_L2_COEF);
-  q.bn = kn.bn(cout, &q.bn_idx);
-  p->plain.push_back(q);
-  p->C = cout;
-  p->T = q.Lout;
-  p->maxC = std::max(p->maxC, cout);
+  int Lout = p->T - 2, pad_l = 0;
+  if (stride != 1) kws_same_pad(p->T, 3, stride, &Lout, &pad_l);
+  KWS_REQUIRE(Lout >= 1, "net: conv_1d_residual input too short");
+  p->plain.push_back(lm_unit(kn, p, p->C, cout, p->T, Lout, stride, pad_l));
+  p->C = cout; p->T = Lout;
   return KWS_OK;
 }
 
-// Dense(num_classes) over the pooled features of the running activation; closes the table
-void lm_add_dense(KerasNames& kn, LmProgram* p) {
-  p->NC = kn.n->cfg.num_classes;
-  p->feat = p->pool_max ? 2 * p->C : p->C;
-  p->dk = kws_net_add_tensor(kn.n, "dense_1/kernel", {p->feat, p->NC}, false, KWS_L2_COEF, p->feat, p->NC, 0.f);
-  if (p->has_bias) p->db = kws_net_add_tensor(kn.n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
+// Closes the table with head h over the running activation; feat: the width of the dense layer's input
+void lm_add_head(KerasNames& kn, LmProgram* p, LmHead* h, int feat, bool bias) {
+  p->head.reset(h);
+  h->T = p->T; h->C = p->C;
+  h->add_dense(kn.n, feat, bias);
   p->n_bn = kn.n_bn;
 }
-
-// Depthwise backward kernels that leave ONLY a weight gradient behind (a block's first depthwise convolution, the context
-// block's, the first plain block's: their input is a materialised activation, no BatchNorm in front): nothing on the
-// dependency chain needs the fold of their partial rows, so the rows stay in regions of their own and one launch folds up to
-// KWS_DW_FIN_BATCH layers at the end of the pass (round 4: one small launch per block off the chain).
-struct DwFinQueue {
-  const float* part[KWS_DW_FIN_BATCH];
-  float* dw[KWS_DW_FIN_BATCH];
-  int n_parts[KWS_DW_FIN_BATCH], C[KWS_DW_FIN_BATCH];
-  int count = 0;
-  float* base = nullptr;
-  int64_t used = 0, cap = 0;
-  hipStream_t st = nullptr;
-  int flush() {
-    if (count == 0) return KWS_OK;
-    const int rc = kws_dw_grad_finalize_batch(part, n_parts, C, dw, count, st);
-    count = 0;
-    used = 0;
-    return rc;
-  }
-  // a region for the rows of one depthwise backward launch (floats = kws_dwconv_bwd_part_floats) whose fold writes dW
-  int take(int64_t floats, int Cc, float* dW, float** out) {
-    const int64_t need = (floats + 63) / 64 * 64;
-    if (count == KWS_DW_FIN_BATCH || used + need > cap) KWS_TRY(flush());
-    if (need > cap) return KWS_E_WORKSPACE;
-    *out = base + used;
-    part[count] = base + used; dw[count] = dW; n_parts[count] = (int)(floats / (5 * Cc)); C[count] = Cc;
-    used += need;
-    ++count;
-    return KWS_OK;
-  }
-};
-
-// The global-pooling tail's arguments as the program fixes them (inference as it stands; training adds its buffers and the
-// dropout draw)
-kws_gp_tail_args gp_tail_args(const Ctx& c, const float* x, float* probs) {
-  const LmProgram& p = *c.p;
-  kws_gp_tail_args g;
-  memset(&g, 0, sizeof(g));
-  g.x = x; g.Wd = c.params + p.dk; g.bd = p.has_bias ? c.params + p.db : nullptr; g.probs = probs;
-  g.B = c.B; g.T = p.T; g.C = p.C; g.NC = p.NC;
-  g.pool_max = p.pool_max; g.loss_kind = p.loss_kind; g.label_smoothing = p.label_smoothing;
-  g.keep_prob = 1.f; g.loss_batch = 1;
-  return g;
+LmPoolHead* lm_add_pool_head(KerasNames& kn, LmProgram* p, bool pool_max, bool bias, float drop_keep) {
+  LmPoolHead* h = new LmPoolHead();
+  h->pool_max = pool_max; h->drop_keep = drop_keep;
+  lm_add_head(kn, p, h, pool_max ? 2 * p->C : p->C, bias);
+  return h;
+}
+// the attention branch over the running activation: a k-wide depthwise kernel, Conv1D(1, 1) and its BatchNormalization
+LmAttLayers lm_att_layers(KerasNames& kn, const LmProgram* p, int k) {
+  LmAttLayers a;
+  a.dw = kn.dwk(k, p->C); a.pw = kn.conv(1, p->C, 1, KWS_L2_COEF);
+  a.bn = kn.bn(1, &a.bn_idx);
+  return a;
 }
 
-// xception_with_attention: the gate over the last join's output, then the bidirectional GRU on the gated sequence as it is
-int xc_gate_gru_fwd(const Ctx& c, const float* xin, uint64_t seed, uint32_t step, int64_t row_offset) {
-  const LmProgram& p = *c.p;
-  const LmLayout& lo = c.lo;
-  float* ws = c.ws;
-  const int H = p.gH;
-  KWS_TRY(kws_attn_gate_fwd_f32(xin, c.params + p.att_dw, c.params + p.att_pw, c.params + p.att_bn.gamma, c.params + p.att_bn.beta,
-                                c.state + p.att_bn.mm, c.state + p.att_bn.mv, ws + lo.u, c.bn_at(p.att_bn_idx), ws + lo.att, ws + lo.xgy,
-                                ws + lo.xagf, c.B, p.T, p.C, XC_GATE_K, c.training ? 1 : 0, c.st));
-  if (c.training) KWS_TRY(kws_gru_masks(ws + lo.gmx, ws + lo.gmh, c.B, p.C, H, XC_GRU_KEEP, seed, step, row_offset, c.st));
-  return kws_gru_fwd_f32(ws + lo.xgy, c.params + p.gW[0], c.params + p.gU[0], c.params + p.gb[0], c.params + p.gW[1], c.params + p.gU[1],
-                         c.params + p.gb[1], c.training ? ws + lo.gmx : nullptr, c.training ? ws + lo.gmh : nullptr, ws + lo.gout,
-                         c.training ? ws + lo.gsave : nullptr, ws + lo.gws, c.B, p.T, p.C, H, c.st);
-}
-
-// Dense + softmax over the signed GRU output: the flat tail's raw arm
-kws_flat_tail_args xc_tail_args(const Ctx& c, float* probs) {
-  const LmProgram& p = *c.p;
-  kws_flat_tail_args t;
-  memset(&t, 0, sizeof(t));
-  t.y = c.ws + c.lo.gout; t.Ng = p.feat; t.raw = 1;
-  t.Wd = c.params + p.dk; t.bd = c.params + p.db;
-  t.probs = probs;
-  t.B = c.B; t.D = p.feat; t.F = p.feat; t.NC = p.NC;
-  t.keep_prob = 1.f;
-  return t;
+// overlapping_time_slice_stack(x, 40, 20) SAME fused with Conv1D(64 fm, 3, strides=2) (model.py:881-884, 957-960), as the
+// raw-waveform net's first convolution: the stem of conv_1d_residual and xception_with_attention
+LmStem* time_slice_stem(KerasNames& kn, int input_size, int fm) {
+  LmStem* s = new LmStem();
+  int Lf, plf;
+  kws_same_pad(input_size, 40, 20, &Lf, &plf);
+  s->C0 = 64 * fm; s->L0 = (Lf - 3) / 2 + 1;
+  s->conv1 = kn.conv(3, 40, s->C0, KWS_L2_COEF);
+  s->bn0 = kn.bn(s->C0);
+  kws_gather_t& g0 = s->g0;
+  g0.L_out = s->L0; g0.cin = 40; g0.taps = 3; g0.stride_t = 2 * 20; g0.stride_j = 20; g0.base_off = -plf;
+  g0.x_len = input_size; g0.x_batch_stride = input_size;
+  return s;
 }
 
 }  // namespace
 
+// conv_1d_log_mfcc_model (reference model.py:1400-1479; SURVEY 8a row a19, layer table Appendix B.2): Conv1D(64, 3) + BN + ReLU6 on
+// [98, 40] features, 10 residual blocks, softmax-over-time attention, Dropout(.2), Dense(num_classes) + softmax, categorical
+// cross-entropy.  conv_1d_spectrogram_model (model.py:1482-1561) is the same table on 257-bin input, its stem on re-pitched copies.
 int lm_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
-  KWS_REQUIRE(c.spectrogram_length >= 19 && c.num_features >= 4 &&
-                  c.input_size == c.spectrogram_length * c.num_features,
+  KWS_REQUIRE(c.spectrogram_length >= 19 && c.num_features >= 4 && c.input_size == c.spectrogram_length * c.num_features,
               "net: log-mfcc input %d != %d x %d", c.input_size, c.spectrogram_length, c.num_features);
-  LmProgram* p = lm_new(n, LM_ATTENTION, 0.8f);  // Dropout(0.2), model.py:1471
   KerasNames kn{n};
-  p->T0 = c.spectrogram_length; p->F = c.num_features; p->C0 = 64; p->L0 = p->T0 - 2;
-  p->conv1 = kn.conv(3, p->F, p->C0, KWS_L2_COEF);
-  p->bn0 = kn.bn(p->C0);
-  kws_gather_t g0;
-  p->Fp = (p->F + 3) & ~3;
-  g0.L_out = p->L0; g0.cin = p->Fp; g0.taps = 3; g0.stride_t = p->Fp; g0.stride_j = p->Fp; g0.base_off = 0;
-  g0.x_len = p->T0 * p->Fp; g0.x_batch_stride = p->T0 * p->Fp;
-  p->g0 = g0;
+  const int T0 = c.spectrogram_length, F = c.num_features;
+  const int Fp = (F + 3) & ~3;   // F rounded up to the 16-byte vectors of the gathered GEMM (spectrogram input: 257 -> 260)
+  LmPaddedStem* ps = Fp != F ? new LmPaddedStem() : nullptr;
+  if (ps) { ps->K = F; ps->Kp = Fp; ps->T0 = T0; }
+  LmStem* s = ps ? ps : new LmStem();
+  s->C0 = 64; s->L0 = T0 - 2;
+  LmProgram* p = lm_new(n, s);
+  s->conv1 = kn.conv(3, F, s->C0, KWS_L2_COEF);
+  s->bn0 = kn.bn(s->C0);
+  kws_gather_t& g0 = s->g0;
+  g0.L_out = s->L0; g0.cin = Fp; g0.taps = 3; g0.stride_t = Fp; g0.stride_j = Fp; g0.base_off = 0;
+  g0.x_len = T0 * Fp; g0.x_batch_stride = T0 * Fp;
+  p->fuse_first_dw = true;   // (round 6) block 0 starts with a k 3 / stride 1 / 'same' depthwise convolution over the stem's activation
   // any length: the strided blocks are Keras 'same' layers - MaxPool1D(2, 2) and Conv1D(nf, 1, strides=2) both give
   // ceil(L / 2), e.g. the function's own default spectrogram_length = 65 -> 63 -> 32 -> 16 -> 8 (model.py:1410)
   static const int spec[10][2] = {{64, 1}, {64, 1}, {128, 2}, {128, 1}, {192, 2}, {192, 1}, {192, 1}, {256, 2},
                                   {256, 1}, {256, 1}};  // model.py:1453-1462
-  lm_begin_stack(p);
-  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL_AFTER, s[0], s[1]));
+  for (const int* b : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL_AFTER, b[0], b[1]));
   KWS_REQUIRE(p->T <= 16, "net: %d time steps at the tail (max 16)", p->T);
-  p->att_dw = kn.dw(p->C);
-  p->att_pw = kn.conv(1, p->C, 1, KWS_L2_COEF);
-  p->att_bn = kn.bn(1, &p->att_bn_idx);
-  lm_add_dense(kn, p);
+  LmAttentionHead* h = new LmAttentionHead();
+  h->drop_keep = 0.8f;   // Dropout(0.2), model.py:1471
+  h->att = lm_att_layers(kn, p, 3);
+  lm_add_head(kn, p, h, p->C, true);
   return KWS_OK;
 }
 
@@ -654,30 +972,29 @@ int lm_build(kws_net* n) {
 int steffe_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   KWS_REQUIRE(c.input_size >= 3200 && c.input_size % 2 == 0, "net: steffeNet input_size %d", c.input_size);
-  LmProgram* p = lm_new(n, LM_STEFFE, 0.5f);     // Dropout(0.5), model.py:1716
-  p->pool_max = true; p->has_bias = false;       // GlobalMaxPooling1D ++ GlobalAveragePooling1D -> Dense(use_bias=False), model.py:1712-1718
-  p->loss_kind = 0; p->label_smoothing = 0.1f;   // model.py:1722-1724
   KerasNames kn{n};
-  // Conv1D(256, 75, strides=50, padding='same', use_bias=False): no kernel_regularizer (model.py:1705)
-  p->K0 = 75; p->K0p = 76; p->C0 = 256; p->T0 = c.input_size; p->F = 1; p->Fp = 1;
+  // Conv1D(256, 75, strides=50, padding='same', use_bias=False): no kernel_regularizer (model.py:1705); its 75 taps on one channel are
+  // gathered as ONE tap of 76 samples against a zero-padded kernel
+  LmPaddedStem* s = new LmPaddedStem();
+  s->K = 75; s->Kp = 76; s->C0 = 256;
   int pl0;
-  kws_same_pad(c.input_size, p->K0, 50, &p->L0, &pl0);
+  kws_same_pad(c.input_size, s->K, 50, &s->L0, &pl0);
+  LmProgram* p = lm_new(n, s);
   KWS_REQUIRE(pl0 % 2 == 0, "net: steffeNet left padding %d must be even (8-byte gather loads)", pl0);
-  p->conv1 = kn.conv(p->K0, 1, p->C0, 0.f);
-  p->bn0 = kn.bn(p->C0);
-  kws_gather_t g0;
-  g0.L_out = p->L0; g0.cin = p->K0p; g0.taps = 1; g0.stride_t = 50; g0.stride_j = 0; g0.base_off = -pl0;
+  s->conv1 = kn.conv(s->K, 1, s->C0, 0.f);
+  s->bn0 = kn.bn(s->C0);
+  kws_gather_t& g0 = s->g0;
+  g0.L_out = s->L0; g0.cin = s->Kp; g0.taps = 1; g0.stride_t = 50; g0.stride_j = 0; g0.base_off = -pl0;
   g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
-  p->g0 = g0;
-  p->ctx_dw = kn.dw(p->C0);                                  // _context_conv(x, 256, 3, padding='same'), model.py:1708
-  p->ctx_pw = kn.conv(1, p->C0, p->C0, KWS_L2_COEF);
-  p->ctx_bn = kn.bn(p->C0, &p->ctx_bn_idx);
+  p->has_ctx = true;   // _context_conv(x, 256, 3, padding='same'), model.py:1708
+  p->ctx = lm_unit(kn, p, s->C0, s->C0, s->L0, s->L0, 1, 1);
   static const int widths[6] = {320, 384, 512, 768, 1024, 1536};  // model.py:1709
-  lm_begin_stack(p);
   for (int nf : widths)
     for (int stride = 2; stride >= 1; --stride) KWS_TRY(lm_add_block(kn, p, LM_STRIDED_DW, nf, stride));
   KWS_REQUIRE(p->T >= 1 && p->T <= 64, "net: %d time steps at the tail", p->T);
-  lm_add_dense(kn, p);
+  // GlobalMaxPooling1D ++ GlobalAveragePooling1D -> Dropout(0.5) -> Dense(use_bias=False), model.py:1712-1718; loss: model.py:1722-1724
+  LmPoolHead* h = lm_add_pool_head(kn, p, true, false, 0.5f);
+  h->loss_kind = 0; h->label_smoothing = 0.1f;
   return KWS_OK;
 }
 
@@ -686,28 +1003,16 @@ int residual_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   KWS_REQUIRE(c.input_size >= 4000 && c.input_size % 2 == 0, "net: conv_1d_residual input_size %d", c.input_size);
   const int fm = c.filter_mult > 0 ? c.filter_mult : 1;
-  LmProgram* p = lm_new(n, LM_RESIDUAL, 0.5f);   // Dropout(0.5), model.py:899
   KerasNames kn{n};
-  // overlapping_time_slice_stack(x, 40, 20) SAME fused with Conv1D(64, 3, strides=2) (model.py:881-884), as the
-  // raw-waveform net's first convolution
-  int Lf, plf;
-  kws_same_pad(c.input_size, 40, 20, &Lf, &plf);
-  p->T0 = c.input_size; p->F = 40; p->Fp = 40; p->C0 = 64 * fm; p->L0 = (Lf - 3) / 2 + 1;
-  p->conv1 = kn.conv(3, 40, p->C0, KWS_L2_COEF);
-  p->bn0 = kn.bn(p->C0);
-  kws_gather_t g0;
-  g0.L_out = p->L0; g0.cin = 40; g0.taps = 3; g0.stride_t = 2 * 20; g0.stride_j = 20; g0.base_off = -plf;
-  g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
-  p->g0 = g0;
+  LmProgram* p = lm_new(n, time_slice_stem(kn, c.input_size, fm));
   static const int spec[13][2] = {{128, 2}, {256, 2}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1},
                                   {256, 1}, {256, 1}, {512, 2}, {728, 2}, {728, 2}};  // model.py:888-894
-  lm_begin_stack(p);
-  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0] * fm, s[1]));
+  for (const int* b : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, b[0] * fm, b[1]));
   // _reduce_block(x, 1024, 3): _reduce_conv (strides 2, 'same') then _context_conv ('valid'), model.py:895
   KWS_TRY(lm_add_plain(kn, p, 1024 * fm, 2));
   KWS_TRY(lm_add_plain(kn, p, 1024 * fm, 1));
   KWS_REQUIRE(p->T <= 64, "net: %d time steps at the tail", p->T);
-  lm_add_dense(kn, p);
+  lm_add_pool_head(kn, p, false, true, 0.5f);   // GlobalAveragePooling1D -> Dropout(0.5) -> Dense, model.py:898-905
   return KWS_OK;
 }
 
@@ -716,39 +1021,25 @@ int xception_build(kws_net* n) {
   const kws_net_config_t& c = n->cfg;
   KWS_REQUIRE(c.input_size >= 4000 && c.input_size % 2 == 0, "net: xception_with_attention input_size %d", c.input_size);
   const int fm = c.filter_mult > 0 ? c.filter_mult : 1;
-  LmProgram* p = lm_new(n, LM_XCEPTION, 1.f);    // no Dropout layer: the GRU carries the model's dropout
   KerasNames kn{n};
-  int Lf, plf;
-  kws_same_pad(c.input_size, 40, 20, &Lf, &plf);   // overlapping_time_slice_stack(x, 40, 20) fused with Conv1D(64, 3, strides=2), model.py:957-960
-  p->T0 = c.input_size; p->F = 40; p->Fp = 40; p->C0 = 64 * fm; p->L0 = (Lf - 3) / 2 + 1;
-  p->conv1 = kn.conv(3, 40, p->C0, KWS_L2_COEF);
-  p->bn0 = kn.bn(p->C0);
-  kws_gather_t g0;
-  g0.L_out = p->L0; g0.cin = 40; g0.taps = 3; g0.stride_t = 2 * 20; g0.stride_j = 20; g0.base_off = -plf;
-  g0.x_len = c.input_size; g0.x_batch_stride = c.input_size;
-  p->g0 = g0;
+  LmProgram* p = lm_new(n, time_slice_stem(kn, c.input_size, fm));
   static const int spec[11][2] = {{128, 2}, {256, 2}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1}, {256, 1},
                                   {256, 1}, {256, 1}, {384, 2}};  // model.py:964-968
-  lm_begin_stack(p);
-  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0] * fm, s[1]));
+  for (const int* b : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, b[0] * fm, b[1]));
   KWS_REQUIRE(kws_attn_gate_fwd_floats(1, p->T, p->C, XC_GATE_K) > 0, "net: xception_with_attention tail [%d, %d] is outside the attention gate's domain",
               p->T, p->C);
-  p->att_dw = kn.dwk(XC_GATE_K, p->C);                 // _context_conv(x, 1, 5, padding='same'), model.py:973
-  p->att_pw = kn.conv(1, p->C, 1, KWS_L2_COEF);
-  p->att_bn = kn.bn(1, &p->att_bn_idx);
-  p->gH = XC_GRU_UNITS;
-  const int H = p->gH;
+  LmGruHead* h = new LmGruHead();
+  h->tail_T = p->T;
+  h->att = lm_att_layers(kn, p, XC_GATE_K);   // _context_conv(x, 1, 5, padding='same'), model.py:973
+  h->H = XC_GRU_UNITS;
+  const int H = h->H;
   for (int d = 0; d < 2; ++d) {   // kernel_regularizer=l2(1e-5) reaches `kernel` only; recurrent_kernel: Orthogonal, drawn by the host
     const std::string base = std::string("bidirectional_1/") + (d ? "backward" : "forward") + "_gru_1/";
-    p->gW[d] = kws_net_add_tensor(n, base + "kernel", {p->C, 3 * H}, false, KWS_L2_COEF, p->C, 3 * H, 0.f);
-    p->gU[d] = kws_net_add_tensor(n, base + "recurrent_kernel", {H, 3 * H}, false, 0.f, 0, 0, 0.f);
-    p->gb[d] = kws_net_add_tensor(n, base + "bias", {3 * H}, false, 0.f, 0, 0, 0.f);
+    h->gW[d] = kws_net_add_tensor(n, base + "kernel", {p->C, 3 * H}, false, KWS_L2_COEF, p->C, 3 * H, 0.f);
+    h->gU[d] = kws_net_add_tensor(n, base + "recurrent_kernel", {H, 3 * H}, false, 0.f, 0, 0, 0.f);
+    h->gb[d] = kws_net_add_tensor(n, base + "bias", {3 * H}, false, 0.f, 0, 0, 0.f);
   }
-  p->NC = c.num_classes;
-  p->feat = 2 * H;
-  p->dk = kws_net_add_tensor(n, "dense_1/kernel", {p->feat, p->NC}, false, KWS_L2_COEF, p->feat, p->NC, 0.f);
-  p->db = kws_net_add_tensor(n, "dense_1/bias", {p->NC}, false, 0.f, 0, 0, 0.f);
-  p->n_bn = kn.n_bn;
+  lm_add_head(kn, p, h, 2 * H, true);   // no Dropout layer: the GRU carries the model's dropout
   return KWS_OK;
 }
 
@@ -762,319 +1053,24 @@ int mfcc_raw_build(kws_net* n) {
   const int frame_len = 480, frame_step = 160;   // window_size_samples / window_stride_samples of prepare_model_settings
   KWS_REQUIRE(1 + (Lraw - frame_len) / frame_step == T && (T * F) % 4 == 0 && Lraw % 2 == 0,
               "net: mfcc_and_raw needs 1 + (raw %d - 480) / 160 == spectrogram_length %d", Lraw, T);
-  LmProgram* p = lm_new(n, LM_MFCC_AND_RAW, 0.7f);   // Dropout(0.3), model.py:1648
   KerasNames kn{n};
-  p->T0 = T; p->F = F; p->Fp = F; p->Cm = 64; p->Cr = 96; p->C0 = p->Cm + p->Cr; p->L0 = T - 2; p->Din = c.input_size;
-  p->conv1 = kn.conv(3, F, p->Cm, KWS_L2_COEF);            // model.py:1615
-  p->bn0 = kn.bn(p->Cm);
-  p->conv1r = kn.conv(3, frame_len, p->Cr, KWS_L2_COEF);   // model.py:1625
-  p->bn0r = kn.bn(p->Cr);
+  LmStem2* s = new LmStem2();
+  s->Cm = 64; s->Cr = 96; s->C0 = s->Cm + s->Cr; s->L0 = T - 2;
+  LmProgram* p = lm_new(n, s);
+  s->conv1 = kn.conv(3, F, s->Cm, KWS_L2_COEF);            // model.py:1615
+  s->bn0 = kn.bn(s->Cm);
+  s->conv1r = kn.conv(3, frame_len, s->Cr, KWS_L2_COEF);   // model.py:1625
+  s->bn0r = kn.bn(s->Cr);
   kws_gather_t g;
-  g.L_out = p->L0; g.cin = F; g.taps = 3; g.stride_t = F; g.stride_j = F; g.base_off = 0;
-  g.x_len = T * F; g.x_batch_stride = p->Din;
-  p->g0 = g;
+  g.L_out = s->L0; g.cin = F; g.taps = 3; g.stride_t = F; g.stride_j = F; g.base_off = 0;
+  g.x_len = T * F; g.x_batch_stride = c.input_size;
+  s->g0 = g;
   // overlapping_time_slice_stack(x, 480, 160, 'VALID') fused with Conv1D(96, 3): row t reads 3 frames 160 apart
-  g.cin = frame_len; g.stride_t = frame_step; g.stride_j = frame_step; g.base_off = T * F; g.x_len = p->Din;
-  p->g0r = g;
+  g.cin = frame_len; g.stride_t = frame_step; g.stride_j = frame_step; g.base_off = T * F; g.x_len = c.input_size;
+  s->g0r = g;
   static const int spec[10][2] = {{160, 1}, {160, 1}, {192, 2}, {192, 1}, {256, 2}, {256, 1}, {320, 2}, {320, 1},
                                   {384, 2}, {384, 1}};  // model.py:1632-1641
-  lm_begin_stack(p);
-  for (const int* s : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, s[0], s[1]));
-  lm_add_dense(kn, p);
+  for (const int* b : spec) KWS_TRY(lm_add_block(kn, p, LM_POOL3_SAME, b[0], b[1]));
+  lm_add_pool_head(kn, p, false, true, 0.7f);   // GlobalAveragePooling1D -> Dropout(0.3) -> Dense, model.py:1648
   return KWS_OK;
 }
-
-namespace {
-
-int64_t LmProgram::workspace_bytes(int B, int training) const {
-  (void)training;
-  LmLayout lo;
-  lm_layout(*this, B, &lo);
-  return lo.total;
-}
-
-int LmProgram::debug_view(int B, int training, int what, int index, int64_t* offset_floats, int64_t* count) const {
-  LmLayout lo;
-  lm_layout(*this, B, &lo);
-  const LmProgram& p = *this;
-  const int nb = (int)p.blocks.size();
-  // what: 0 = pre-BN tensor of BN `index` (1-based Keras numbering), 2 = BN table of BN `index`,
-  //       3 = attention weights, 4 = attention logits u
-  if (what == 2) {
-    KWS_REQUIRE(index >= 1 && index <= p.n_bn, "lm_debug_view: bn index %d", index);
-    *offset_floats = lo.bn + lo.bn_stride * index;
-    *count = 4 * p.maxC;
-    return KWS_OK;
-  }
-  if (what == 3) { *offset_floats = lo.att; *count = (int64_t)B * p.T; return KWS_OK; }
-  if (what == 4) { *offset_floats = lo.u; *count = (int64_t)B * p.T; return KWS_OK; }
-  if (what == 5) { *offset_floats = lo.o[nb - 1]; *count = (int64_t)B * p.T * p.C; return KWS_OK; }
-  if (p.style == LM_XCEPTION) {   // 6 = gate output, 7 = the GRU's saved steps [2][4: z, r, c, h][B, T, H], 8 = GRU output, 9 = attention BN table
-    if (what == 6) { *offset_floats = lo.xgy; *count = (int64_t)B * p.T * p.C; return KWS_OK; }
-    if (what == 7) {
-      KWS_REQUIRE(training, "lm_debug_view: view 7 exists in training only");
-      *offset_floats = lo.gsave; *count = kws_gru_save_floats(B, p.T, p.gH);
-      return KWS_OK;
-    }
-    if (what == 8) { *offset_floats = lo.gout; *count = (int64_t)B * 2 * p.gH; return KWS_OK; }
-    if (what == 9) { *offset_floats = lo.bn + lo.bn_stride * p.att_bn_idx; *count = 4; return KWS_OK; }
-  }
-  if (what == 0) {
-    if (p.style == LM_MFCC_AND_RAW && index <= 2) {
-      *offset_floats = lo.y0 + (index == 2 ? (int64_t)B * p.L0 * p.Cm : 0);
-      *count = (int64_t)B * p.L0 * (index == 2 ? p.Cr : p.Cm);
-      return KWS_OK;
-    }
-    if (index == 1) { *offset_floats = lo.y0; *count = (int64_t)B * p.L0 * p.C0; return KWS_OK; }
-    for (size_t j = 0; j < p.plain.size(); ++j)
-      if (index == p.plain[j].bn_idx) { *offset_floats = lo.py[j]; *count = (int64_t)B * p.plain[j].Lout * p.plain[j].cout; return KWS_OK; }
-    if (p.style == LM_STEFFE && index == p.ctx_bn_idx) { *offset_floats = lo.yc; *count = (int64_t)B * p.L0 * p.C0; return KWS_OK; }
-    for (int i = 0; i < nb; ++i) {
-      const LmBlock& b = p.blocks[i];
-      if (b.has_short && index == b.bns_idx) { *offset_floats = lo.ys[i]; *count = (int64_t)B * b.Lout * b.nf; return KWS_OK; }
-      if (index == b.bn1_idx) { *offset_floats = lo.y1[i]; *count = (int64_t)B * b.Lmid * b.nf; return KWS_OK; }
-      if (index == b.bn2_idx) { *offset_floats = lo.y2[i]; *count = (int64_t)B * b.Lmid * b.nf; return KWS_OK; }
-    }
-  }
-  kws_set_error("lm_debug_view: unknown view %d/%d", what, index);
-  return KWS_E_INVALID;
-}
-
-int LmProgram::predict(const float* params, const float* state, const float* x, int B, float* probs, float* ws, int64_t ws_bytes,
-                       hipStream_t st) const {
-  Ctx c;
-  c.p = this; c.params = params; c.state = const_cast<float*>(state); c.ws = ws; c.B = B;
-  c.training = false; c.st = st;
-  lm_layout(*this, B, &c.lo);
-  KWS_TRY(kws_workspace_check("net_predict", c.lo.total, ws_bytes, B));
-  kws_lm_tail_args t;
-  KWS_TRY(forward(c, x, &t));
-  if (c.p->style == LM_XCEPTION) {
-    KWS_TRY(xc_gate_gru_fwd(c, t.x, 0, 0, 0));
-    const kws_flat_tail_args f = xc_tail_args(c, probs);
-    return kws_flat_tail_launch(&f, 0, st);
-  }
-  if (c.p->style != LM_ATTENTION) {
-    const kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
-    return kws_gp_tail_launch(&g, 0, st);
-  }
-  t.probs = probs;
-  return kws_lm_tail_fwd(&t, 0, st);
-}
-
-int LmProgram::train(const float* params, float* state, const float* x, const float* y_onehot, int B, float* grads, float* probs,
-                     float* metrics, uint64_t seed, uint32_t step, int64_t row_offset, int loss_batch, float* ws, int64_t ws_bytes,
-                     hipStream_t st) const {
-  Ctx c;
-  c.p = this; c.params = params; c.state = state; c.ws = ws; c.B = B; c.training = true; c.st = st;
-  lm_layout(*this, B, &c.lo);
-  KWS_TRY(kws_workspace_check("net_train_fwd_bwd", c.lo.total, ws_bytes, B));
-  const LmProgram& p = *c.p;
-  const LmLayout& lo = c.lo;
-  KWS_HIP(hipMemsetAsync(grads, 0, (size_t)net->n_params * 4, st));
-  kws_lm_tail_args t;
-  KWS_TRY(forward(c, x, &t));
-  {  // every pointwise kernel transposed for its dgrad GEMM, KWS_TRANSPOSE_BATCH matrices per launch
-    std::vector<const float*> tin;
-    std::vector<float*> tout;
-    std::vector<int> trows, tcols;
-    auto add = [&](int64_t src, int64_t dst, int rows, int cols) {
-      tin.push_back(params + src); tout.push_back(ws + dst); trows.push_back(rows); tcols.push_back(cols);
-    };
-    for (size_t i = 0; i < p.blocks.size(); ++i) {
-      const LmBlock& b = p.blocks[i];
-      add(b.pw1, lo.wt_pw1[i], b.cin, b.nf);
-      add(b.pw2, lo.wt_pw2[i], b.nf, b.nf);
-      if (b.has_short) add(b.ws, lo.wt_ws[i], b.cin, b.nf);
-    }
-    for (size_t j = 0; j < p.plain.size(); ++j) add(p.plain[j].pw, lo.wt_plain[j], p.plain[j].cin, p.plain[j].cout);
-    if (p.style == LM_STEFFE) add(p.ctx_pw, lo.wt_ctx, p.C0, p.C0);
-    for (size_t o = 0; o < tin.size(); o += KWS_TRANSPOSE_BATCH) {
-      const int nbat = (int)std::min<size_t>(KWS_TRANSPOSE_BATCH, tin.size() - o);
-      KWS_TRY(kws_transpose_batch_f32(tin.data() + o, tout.data() + o, trows.data() + o, tcols.data() + o, nbat, st));
-    }
-  }
-  float* part = ws + lo.part;
-  float* red = ws + lo.red;
-  float* coef = ws + lo.coef;
-  float* G = ws + lo.G;
-  float* DZ = ws + lo.DZ;
-  float* dO = ws + lo.dOa;
-  float* dX = ws + lo.dOb;
-  KwsSlabQueue sq;
-  sq.base = ws + lo.tnq; sq.cap = lo.tnq_floats;
-  sq.allow_pair = kws_net_get_gemm_mode(net) != 1;    // mode 1: the A/B reference schedule (separate input- / weight-gradient launches)
-  DwFinQueue dq;
-  dq.base = ws + lo.dwq; dq.cap = lo.dwq_floats; dq.st = st;
-  // join backward + BatchNorm backward in two passes (round 4): reductions, fold (dgamma, dbeta, c1 | c2), then the masked /
-  // pool-routed gradient is recomputed and dy written directly - 5 tensor passes instead of the 6 of "kws_block_out_bwd,
-  // fold, kws_bn_bwd_apply", <= 256 partial rows (no slice fold), one launch less per join.  `outp` may be `dOin` (pool 1).
-  auto join_bwd = [&](const float* dOin, const float* yv, const BnRef& r, int bn_idx, float* outp, int L, int C, int pool,
-                      int relu) -> int {
-    KWS_TRY(kws_block_join_bwd(dOin, yv, c.bn_at(bn_idx), nullptr, nullptr, nullptr, part, 1, B, L, C, pool, relu, st));
-    KWS_TRY(kws_dw_bwd_finalize(part, kws_block_join_bwd_parts(B, L, C, pool), (int64_t)B * L, C, nullptr, grads + r.gamma,
-                                grads + r.beta, coef, red, st));
-    return kws_block_join_bwd(dOin, yv, c.bn_at(bn_idx), params + r.gamma, coef, outp, nullptr, 2, B, L, C, pool, relu, st);
-  };
-  // a strided block's shortcut branch: its BN (no mask, in place), the 1 x 1 convolution's weight gradient (slabs queued: summed
-  // with the pass's other weight gradients) and its input gradient on the Lout strided rows, left in DXS
-  auto short_bwd = [&](int i, const float* xin) -> int {
-    const LmBlock& b = p.blocks[i];
-    KWS_TRY(join_bwd(dO, ws + lo.ys[i], b.bns, b.bns_idx, dO, b.Lout, b.nf, 1, 0));
-    KWS_TRY(sq.gemm_gather(xin, &b.gs, dO, grads + b.ws, B, b.nf, st));
-    return kws_gemm_nn_f32(dO, ws + lo.wt_ws[i], ws + lo.DXS, (int64_t)B * b.Lout, b.nf, b.cin, nullptr, st);
-  };
-  // ---- tail forward + backward ----
-  if (p.style == LM_XCEPTION) {   // gate -> GRU -> Dense + softmax + CE, and back: the GRU's dx is the gate's dy, the gate's dx the last block's dO
-    const int H = p.gH;
-    KWS_TRY(xc_gate_gru_fwd(c, t.x, seed, step, row_offset));
-    kws_flat_tail_args f = xc_tail_args(c, probs);
-    KWS_TRY(kws_flat_tail_train(&f, y_onehot, ws + lo.fd, ws + lo.dl, ws + lo.gdout, ws + lo.per_loss, ws + lo.per_correct, seed, step,
-                                loss_batch, row_offset, metrics, st));
-    KWS_TRY(kws_small_wgrad_launch(ws + lo.fd, ws + lo.dl, grads + p.dk, grads + p.db, B, p.feat, p.NC, ws + lo.swg, st));
-    KWS_TRY(kws_gru_bwd_f32(ws + lo.gdout, ws + lo.xgy, params + p.gW[0], params + p.gU[0], params + p.gW[1], params + p.gU[1], ws + lo.gmx,
-                            ws + lo.gmh, ws + lo.gsave, G, grads + p.gW[0], grads + p.gU[0], grads + p.gb[0], grads + p.gW[1],
-                            grads + p.gU[1], grads + p.gb[1], ws + lo.gws, B, p.T, p.C, H, st));
-    KWS_TRY(kws_attn_gate_bwd_f32(G, t.x, ws + lo.u, ws + lo.att, c.bn_at(p.att_bn_idx), params + p.att_dw, params + p.att_pw,
-                                  params + p.att_bn.gamma, dO, grads + p.att_dw, grads + p.att_pw, grads + p.att_bn.gamma,
-                                  grads + p.att_bn.beta, ws + lo.xagb, B, p.T, p.C, XC_GATE_K, 1, st));
-  } else if (p.style != LM_ATTENTION) {
-    kws_gp_tail_args g = gp_tail_args(c, t.x, probs);
-    g.labels = y_onehot; g.dX = dO; g.fd = ws + lo.fd; g.dl = ws + lo.dl;
-    g.per_loss = ws + lo.per_loss; g.per_correct = ws + lo.per_correct;
-    g.seed = seed; g.step = step; g.keep_prob = p.drop_keep; g.loss_batch = loss_batch; g.row_offset = row_offset;
-    KWS_TRY(kws_gp_tail_launch(&g, 1, st));
-    KWS_TRY(kws_metrics_launch(g.per_loss, g.per_correct, B, metrics, st));
-    KWS_TRY(kws_small_wgrad_launch(g.fd, g.dl, grads + p.dk, p.has_bias ? grads + p.db : nullptr, B, p.feat, p.NC, ws + lo.swg,
-                                   st));
-    // ---- plain blocks after the residual stack, last to first: dO is the gradient wrt the materialised activation
-    for (int j = (int)p.plain.size() - 1; j >= 0; --j) {
-      const LmPlain& q = p.plain[j];
-      const int64_t M = (int64_t)B * q.Lout;
-      if (j == (int)p.plain.size() - 1) {
-        KWS_TRY(join_bwd(dO, ws + lo.py[j], q.bn, q.bn_idx, G, q.Lout, q.cout, 1, 1));
-      }  // else: G already holds dy of this block (pass 2 of the next block's depthwise backward)
-      KWS_TRY(sq.pair(G, ws + lo.wt_plain[j], DZ, ws + lo.pz[j], grads + q.pw, M, q.cin, q.cout, st));   // dgrad + wgrad: one launch
-      const int np = (int)(kws_dwconv_bwd_part_floats(B, q.Lin, q.cin) / (5 * q.cin));
-      if (j > 0) {
-        const LmPlain& r = p.plain[j - 1];
-        KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.py[j - 1], c.bn_at(r.bn_idx), params + q.dw, nullptr, nullptr, part, 1, B,
-                                      q.Lin, q.Lout, q.cin, q.stride, q.pad_l, st));
-        KWS_TRY(kws_dw_bwd_finalize(part, np, (int64_t)B * q.Lin, q.cin, grads + q.dw, grads + r.bn.gamma, grads + r.bn.beta,
-                                    coef, red, st));
-        KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.py[j - 1], c.bn_at(r.bn_idx), params + q.dw, coef, G, nullptr, 2, B, q.Lin,
-                                      q.Lout, q.cin, q.stride, q.pad_l, st));
-      } else {
-        const float* xin = ws + lo.o[p.blocks.size() - 1];
-        float* dpart;
-        KWS_TRY(dq.take(kws_dwconv_bwd_part_floats(B, q.Lin, q.cin), q.cin, grads + q.dw, &dpart));
-        KWS_TRY(kws_dwconv_bwd_f32(DZ, xin, nullptr, params + q.dw, dX, dpart, B, q.Lin, q.Lout, q.cin, q.stride, q.pad_l, st));
-        std::swap(dO, dX);
-      }
-    }
-  } else {
-  t.labels = y_onehot; t.probs = probs; t.dX = dO; t.fd = ws + lo.fd; t.dl = ws + lo.dl; t.gu = ws + lo.gu;
-  t.part = part; t.coef = ws + lo.coef2; t.d_gamma = grads + p.att_bn.gamma; t.d_beta = grads + p.att_bn.beta;
-  t.per_loss = ws + lo.per_loss; t.per_correct = ws + lo.per_correct; t.att = ws + lo.att;
-  t.seed = seed; t.step = step; t.loss_batch = loss_batch; t.row_offset = row_offset;
-  KWS_TRY(kws_lm_tail_fwd(&t, 1, st));
-  KWS_TRY(kws_metrics_launch(t.per_loss, t.per_correct, B, metrics, st));
-  KWS_TRY(kws_small_wgrad_launch(t.fd, t.dl, grads + p.dk, grads + p.db, B, p.C, p.NC, ws + lo.swg, st));
-  KWS_TRY(kws_lm_tail_bwd(&t, st));
-  KWS_TRY(kws_dw_bwd_finalize(part, B, 1, p.C, grads + p.att_dw, nullptr, grads + p.att_pw, nullptr, red, st));
-  }
-  // ---- residual blocks, last to first ----
-  for (int i = (int)p.blocks.size() - 1; i >= 0; --i) {
-    const LmBlock& b = p.blocks[i];
-    const int64_t M = (int64_t)B * b.Lmid;
-    const float* xin = i == 0 ? (p.style == LM_STEFFE ? ws + lo.ac : ws + lo.a0) : ws + lo.o[i - 1];
-    // main branch: join backward (maxpool routing + ReLU6 mask) -> BN2 -> pointwise 2
-    int np;
-    if (b.pool3) {   // the 3-wide SAME join keeps the one-pass form (an input position collects up to three windows)
-      KWS_TRY(kws_block_out3_bwd(dO, ws + lo.y2[i], c.bn_at(b.bn2_idx), G, part, B, b.Lmid, b.Lout, b.nf, b.stride, b.ppad, st));
-      np = (int)(kws_block_out3_bwd_part_floats(B, b.Lmid, b.nf) / (5 * b.nf));
-      KWS_TRY(kws_dw_bwd_finalize(part, np, M, b.nf, nullptr, grads + b.bn2.gamma, grads + b.bn2.beta, coef, red, st));
-      KWS_TRY(kws_bn_bwd_apply(G, ws + lo.y2[i], c.bn_at(b.bn2_idx), params + b.bn2.gamma, coef, M, b.nf, st));
-    } else {
-      KWS_TRY(join_bwd(dO, ws + lo.y2[i], b.bn2, b.bn2_idx, G, b.Lmid, b.nf, b.pool, 1));
-    }
-    KWS_TRY(sq.pair(G, ws + lo.wt_pw2[i], DZ, ws + lo.z2[i], grads + b.pw2, M, b.nf, b.nf, st));   // dgrad + wgrad: one launch where eligible
-    // depthwise 2 -> BN1 -> pointwise 1
-    // (two passes over dz and y1 instead of "store g, then kws_bn_bwd_apply": the masked gradient is never stored)
-    KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y1[i], c.bn_at(b.bn1_idx), params + b.dw2, nullptr, nullptr, part, 1, B,
-                                  b.Lmid, b.Lmid, b.nf, 1, 1, st));
-    np = (int)(kws_dwconv_bwd_part_floats(B, b.Lmid, b.nf) / (5 * b.nf));
-    KWS_TRY(kws_dw_bwd_finalize(part, np, M, b.nf, grads + b.dw2, grads + b.bn1.gamma, grads + b.bn1.beta, coef, red, st));
-    KWS_TRY(kws_dwconv_bwd_bn_f32(DZ, ws + lo.y1[i], c.bn_at(b.bn1_idx), params + b.dw2, coef, G, nullptr, 2, B, b.Lmid,
-                                  b.Lmid, b.nf, 1, 1, st));
-    KWS_TRY(sq.pair(G, ws + lo.wt_pw1[i], DZ, ws + lo.z1[i], grads + b.pw1, M, b.cin, b.nf, st));
-    // depthwise 1 on the (materialised) block input
-    float* dpart;      // only a weight gradient comes out of these rows: folded with the other blocks' at the end of the pass
-    KWS_TRY(dq.take(kws_dwconv_bwd_part_floats(B, b.Lin, b.cin), b.cin, grads + b.dw1, &dpart));
-    // round 6: with a strided shortcut whose rows sit at whole multiples of the stride, the shortcut branch runs FIRST and its input
-    // gradient joins the depthwise input gradient inside that kernel (same single addition per element: bit-identical) instead of an
-    // add_strided pass afterwards; gemm mode 1 (the A/B reference schedule) keeps the order and the launches of rounds 3 - 5
-    const bool short_first = b.has_short && sq.allow_pair && b.stride >= 2 && (int64_t)(b.Lout - 1) * b.stride < b.Lin;
-    if (b.has_short && short_first) {
-      KWS_TRY(short_bwd(i, xin));
-      KWS_TRY(kws_dwconv_bwd_acc_strided_f32(DZ, xin, params + b.dw1, ws + lo.DXS, b.stride, b.Lout, dX, dpart, B, b.Lin, b.Lmid, b.cin,
-                                             b.s1, b.pad1, st));
-    } else if (!b.has_short) {   // identity shortcut: the join's other gradient is added while the depthwise input gradient is written
-      KWS_TRY(kws_dwconv_bwd_acc_f32(DZ, xin, params + b.dw1, dO, dX, dpart, B, b.Lin, b.Lmid, b.cin, b.s1, b.pad1, st));
-    } else {
-      KWS_TRY(kws_dwconv_bwd_f32(DZ, xin, nullptr, params + b.dw1, dX, dpart, B, b.Lin, b.Lmid, b.cin, b.s1, b.pad1, st));
-      KWS_TRY(short_bwd(i, xin));   // residual branch
-      KWS_TRY(kws_add_strided_f32(dX, ws + lo.DXS, B, b.Lin, b.Lout, b.cin, b.stride, st));
-    }
-    std::swap(dO, dX);
-  }
-  if (p.style == LM_STEFFE) {  // ---- context block: dO is the gradient wrt its activated output ----
-    const int64_t M = (int64_t)B * p.L0;
-    KWS_TRY(join_bwd(dO, ws + lo.yc, p.ctx_bn, p.ctx_bn_idx, G, p.L0, p.C0, 1, 1));
-    KWS_TRY(sq.pair(G, ws + lo.wt_ctx, DZ, ws + lo.zc, grads + p.ctx_pw, M, p.C0, p.C0, st));
-    float* dpart;
-    KWS_TRY(dq.take(kws_dwconv_bwd_part_floats(B, p.L0, p.C0), p.C0, grads + p.ctx_dw, &dpart));
-    KWS_TRY(kws_dwconv_bwd_f32(DZ, ws + lo.a0, nullptr, params + p.ctx_dw, dX, dpart, B, p.L0, p.L0, p.C0, 1, 1, st));
-    std::swap(dO, dX);
-  }
-  if (p.style == LM_MFCC_AND_RAW) {  // ---- the two stems: split the gradient of the concatenation, then each like a first convolution
-    const int64_t M = (int64_t)B * p.L0;
-    float* dOm = dX;
-    float* dOr = dX + M * p.Cm;
-    KWS_TRY(copy_cols(dO, p.C0, dOm, p.Cm, M, p.Cm, st));
-    KWS_TRY(copy_cols(dO + p.Cm, p.C0, dOr, p.Cr, M, p.Cr, st));
-    struct Stem { float* d; const float* y; int idx; int C; const BnRef* bn; const kws_gather_t* g; int64_t w; };
-    const Stem stems[2] = {{dOm, ws + lo.y0, 1, p.Cm, &p.bn0, &p.g0, p.conv1},
-                           {dOr, ws + lo.y0 + M * p.Cm, 2, p.Cr, &p.bn0r, &p.g0r, p.conv1r}};
-    for (const Stem& sm : stems) {
-      KWS_TRY(join_bwd(sm.d, sm.y, *sm.bn, sm.idx, G, p.L0, sm.C, 1, 1));
-      KWS_TRY(sq.gemm_gather(x, sm.g, G, grads + sm.w, B, sm.C, st));
-    }
-    KWS_TRY(sq.flush(st));
-    KWS_TRY(dq.flush());
-    return KWS_OK;
-  }
-  KWS_TRY(dq.flush());     // the depthwise weight gradients whose rows were parked
-  // ---- first convolution ----
-  {
-    KWS_TRY(join_bwd(dO, ws + lo.y0, p.bn0, 1, G, p.L0, p.C0, 1, 1));
-    if (p.style != LM_STEFFE && p.Fp == p.F) {   // its gradient is written in place: the slabs join the pass's batched sum
-      KWS_TRY(sq.gemm_gather(x, &p.g0, G, grads + p.conv1, B, p.C0, st));
-      return sq.flush(st);
-    }
-    KWS_TRY(sq.flush(st));   // the pointwise weight gradients of the whole pass: one sum (two past 16 layers)
-    if (p.style == LM_STEFFE) {  // gradient of the zero-padded [76, C0] kernel; its first 75 rows are the kernel's
-      float* gw = ws + lo.gwpad;
-      KWS_TRY(kws_gemm_tn_gather_f32(x, &p.g0, G, gw, B, p.C0, ws + lo.tn, st));
-      KWS_HIP(hipMemcpyAsync(grads + p.conv1, gw, (size_t)p.K0 * p.C0 * 4, hipMemcpyDeviceToDevice, st));
-    } else {  // (Fp != F here: the unpadded case left above) the forward of this step left the padded input in xpad
-      float* gw = ws + lo.gwpad;
-      KWS_TRY(kws_gemm_tn_gather_f32(ws + lo.xpad, &p.g0, G, gw, B, p.C0, ws + lo.tn, st));
-      KWS_HIP(hipMemcpy2DAsync(grads + p.conv1, (size_t)p.F * p.C0 * 4, gw, (size_t)p.Fp * p.C0 * 4, (size_t)p.F * p.C0 * 4, 3,
-                               hipMemcpyDeviceToDevice, st));
-    }
-  }
-  return KWS_OK;
-}
-
-}  // namespace

@@ -76,7 +76,7 @@ def test_predict_matches_oracle(nc, F):
 
 # F = 257, 12 classes: conv_1d_spectrogram (model.py:1482-1561) - the same program on the
 # generator's 'spec' output; 257 is not a multiple of the gathered GEMM's 16-byte vectors, so the first
-# convolution runs on re-pitched copies (net_logmfcc.hip: pad_first_conv)
+# convolution runs on re-pitched copies (net_logmfcc.hip: LmPaddedStem)
 @pytest.mark.parametrize("B,nc,F", [(4, 32, 40), (19, 32, 40), (5, 12, 257)])
 def test_train_fwd_bwd_matches_oracle(B, nc, F):
     ora, net = _pair(nc, F=F)
@@ -202,4 +202,47 @@ def test_paired_backward_launches_are_bit_identical_for_the_residual_program():
         net.set_gemm_mode(mode0)
     for a, b in zip(out[0], out[1]):
         assert torch.equal(a, b)
+    assert float(out[0][1].abs().max()) > 0
+
+
+# kind, input_size, spectrogram_length, num_features: the reference functions' default input sizes
+_OTHER_RESIDUAL_MODELS = {
+    'steffeNet': (_lib.KWS_NET_STEFFE, 16000, 0, 0),
+    'conv_1d_residual': (_lib.KWS_NET_RESIDUAL, 16000, 0, 0),
+    'conv_1d_mfcc_and_raw': (_lib.KWS_NET_MFCC_AND_RAW, 98 * 40 + 16000, 98, 40),
+    'xception_with_attention': (_lib.KWS_NET_XCEPTION_ATTENTION, 16000, 0, 0),
+}
+
+
+@pytest.mark.parametrize("model", sorted(_OTHER_RESIDUAL_MODELS))
+def test_reference_schedule_is_bit_identical_for_the_other_residual_models(model):
+    """The other four models of the residual-block program under gemm modes 0 and 1 from the same weights and state: mode 1 makes
+    separate input-gradient / weight-gradient launches, runs a strided block's shortcut branch after the depthwise backward
+    (kws_add_strided_f32) and keeps the joins unfused.  Same arithmetic in the same order: probs, grads, metrics and state agree
+    bit for bit.  Not vacuous at batch 8, by the kernel trace of one mode-0 step per model at that batch
+    (profiles/residual_step_times.json, batch8_mode0): 15 - 23 paired launches (gemm_dgrad_wgrad_kernel) per model, every strided
+    block's depthwise backward in the shortcut-first form (6, 5, 4 and 3 launches) and no kws_add_strided_f32 launch."""
+    kind, size, T, F = _OTHER_RESIDUAL_MODELS[model]
+    nc, B = 12, 8
+    net = DeviceNet(kind, nc, input_size=size, spectrogram_length=T, num_features=F)
+    net.initialize(seed=5)
+    w0, s0 = net.params.clone(), net.state.clone()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(8)
+    x = (torch.randn((B, size), generator=g, device="cuda") * 0.3).contiguous()
+    y = torch.eye(nc, device="cuda")[torch.randint(0, nc, (B,), generator=g, device="cuda")].contiguous()
+    mode0 = net.gemm_mode
+    out = {}
+    try:
+        for mode in (0, 1):
+            net.set_gemm_mode(mode)
+            net.params.copy_(w0)
+            net.state.copy_(s0)
+            p = net.train_fwd_bwd(x, y, seed=3, step=1).clone()
+            torch.cuda.synchronize()
+            out[mode] = (p, net.grads.clone(), net.metrics.clone(), net.state.clone())
+    finally:
+        net.set_gemm_mode(mode0)
+    for name, a, b in zip(("probs", "grads", "metrics", "state"), out[0], out[1]):
+        assert torch.equal(a, b), name
     assert float(out[0][1].abs().max()) > 0
