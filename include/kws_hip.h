@@ -165,6 +165,25 @@ int kws_resample_i16(const kws_resample_plan_t* plan, const int16_t* x, int64_t 
 int kws_resample_f32(const kws_resample_plan_t* plan, const float* x, int64_t x_pitch, const int32_t* n_valid, int n_in,
                      float* out, int B, int keep, void* stream);
 
+/* Keyword spotting in a recording of any length (csrc/stream.hip; not in the reference, which infers one-second clips only).
+ * The window gather: W overlapping windows of `win` samples, `hop` samples apart, the first one starting at sample `start`,
+ *   out[w * win + i] = scale * (float)src[s],  s = start + (int64)w * hop + i,  an exact 0.0f where s is outside [0, n)
+ * (one float multiply: the bits are defined).  start may be negative, hop may exceed win, n may be 0 or smaller than win; all
+ * index arithmetic is 64-bit.  Nothing outside src[0, n) is read, nothing outside out[0, W * win) is written.
+ * KWS_E_INVALID unless win % 4 == 0, win >= 4, hop >= 1, W >= 1, out is 16-byte aligned, src aligned to its element size and
+ * 0 <= n <= 2^61, |start| <= 2^61 (the index above then fits int64 for every w).
+ * scale: 1 / 32768 gives DecodeWav's floats from int16 samples. */
+int kws_stream_frames_i16(const int16_t* src, int64_t n, int64_t start, int hop, int win, float scale, float* out, int W,
+                          void* stream);
+int kws_stream_frames_f32(const float* src, int64_t n, int64_t start, int hop, int win, float scale, float* out, int W,
+                          void* stream);
+/* Posterior smoothing and top-1 over a whole track probs [W, NC]:  lo = max(0, w - A + 1),
+ *   smoothed[w, c] = (probs[lo, c] + ... + probs[w, c]) / (float)(w - lo + 1)
+ * summed in ascending row order in float32, one correctly rounded float32 division; top[w] = the lowest c that attains the
+ * maximum of smoothed[w, :], top_score[w] = that maximum.  smoothed may be NULL.  1 <= A <= 4096, 1 <= NC <= 256, W >= 1.
+ * Every output is the direct A-term sum (no carried running sum), no atomics: a row's bits depend only on the rows under it. */
+int kws_stream_smooth_f32(const float* probs, int W, int NC, int A, float* smoothed, int* top, float* top_score, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Stand-alone forms of the classifier-tail ops (the network programs below run them fused in one
  * kernel; these bind ONE reference call site each).
