@@ -177,6 +177,16 @@ int kws_stream_frames_i16(const int16_t* src, int64_t n, int64_t start, int hop,
                           void* stream);
 int kws_stream_frames_f32(const float* src, int64_t n, int64_t start, int hop, int win, float scale, float* out, int W,
                           void* stream);
+/* The same gather as a copy of bits into rows `out_pitch` floats apart (the windows of a feature track that overlapping
+ * windows share; two calls with one out_pitch assemble composite rows):
+ *   out[w * out_pitch + i] = src[start + w * hop + i]  for 0 <= w < W, 0 <= i < win,  an exact +0.0f where that index is
+ * outside [0, n).  No arithmetic: NaN payloads, -0.0 and denormals arrive unchanged.  Nothing outside src[0, n) is read;
+ * nothing outside the W segments [w * out_pitch, w * out_pitch + win) is written - the out_pitch - win floats between the
+ * rows stay the caller's.  Any win >= 1, hop >= 1, out_pitch >= win, W >= 1, 0 <= n <= 2^61, |start| <= 2^61; src and out
+ * need float alignment only (16-byte stores are used wherever a row's own alignment allows).  KWS_E_INVALID otherwise, and
+ * for an output of more than 2^61 floats ((W - 1) * out_pitch + win), which has no address.  All index arithmetic is 64-bit. */
+int kws_stream_gather_f32(const float* src, int64_t n, int64_t start, int64_t hop, int win, float* out, int64_t out_pitch,
+                          int W, void* stream);
 /* Posterior smoothing and top-1 over a whole track probs [W, NC]:  lo = max(0, w - A + 1),
  *   smoothed[w, c] = (probs[lo, c] + ... + probs[w, c]) / (float)(w - lo + 1)
  * summed in ascending row order in float32, one correctly rounded float32 division; top[w] = the lowest c that attains the

@@ -175,6 +175,7 @@ SIGNATURES = {
     "kws_resample_f32": (_I, [_P, _P, _I64, _P, _I, _P, _I, _I, _P]),
     "kws_stream_frames_i16": (_I, [_P, _I64, _I64, _I, _I, _F, _P, _I, _P]),
     "kws_stream_frames_f32": (_I, [_P, _I64, _I64, _I, _I, _F, _P, _I, _P]),
+    "kws_stream_gather_f32": (_I, [_P, _I64, _I64, _I64, _I, _P, _I64, _I, _P]),
     "kws_stream_smooth_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "kws_stft_plan_create": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _F, _F, ctypes.POINTER(_P)]),
     "kws_stft_plan_destroy": (_I, [_P]),

@@ -14,6 +14,10 @@
 // for bit.  The windows overlap win / hop times; the re-reads come from L2 / Infinity Cache and the kernel is bound by
 // its W win 4 bytes of stores.
 //
+// gather_kernel: the same gather as a copy of bits into rows of any pitch, out[w pitch + i] = src[start + w hop + i], for
+// any win and any float alignment on either side (the windows of a shared feature track, stream.py; the comment at the
+// kernel has the chunking).
+//
 // smooth_kernel: smoothed[w, c] = (probs[lo, c] + ... + probs[w, c]) / (float)(w - lo + 1), lo = max(0, w - A + 1), summed
 // in ascending row order in float32 and divided once (the correctly rounded division: no fast-math), top[w] = the lowest
 // class that attains the row's maximum, top_score[w] = that maximum.  A row belongs to P = the power of two >= NC (64 at
@@ -132,6 +136,76 @@ int frames_launch(const T* src, int64_t n, int64_t start, int hop, int win, floa
   return KWS_OK;
 }
 
+struct GatherArgs {
+  const unsigned* src;       // the floats as their 32-bit patterns: the kernel moves bits
+  unsigned* out;
+  int64_t n, start, hop, pitch;
+  int64_t live;              // rows w >= live start at or past n: start + w hop is formed for w < live only
+  int win, W, cpr;           // cpr = (win + 6) / 4: the most aligned 16-byte chunks one row's destination touches
+  unsigned smis, dmis;       // (src / 4) mod 4 and (out / 4) mod 4
+  unsigned dw, dc;           // the grid's stride as (rows, chunks): gridDim * NT = dw * cpr + dc
+};
+
+// load4_fast on bit patterns
+__device__ __forceinline__ uint4 load4_bits(const unsigned* src, int64_t sA, unsigned a) {
+  const uint4 q0 = *reinterpret_cast<const uint4*>(src + sA);
+  uint4 q1 = q0;
+  if (a) q1 = *reinterpret_cast<const uint4*>(src + sA + 4);
+  uint4 v;
+  v.x = a == 0 ? q0.x : a == 1 ? q0.y : a == 2 ? q0.z : q0.w;
+  v.y = a == 0 ? q0.y : a == 1 ? q0.z : a == 2 ? q0.w : q1.x;
+  v.z = a == 0 ? q0.z : a == 1 ? q0.w : a == 2 ? q1.x : q1.y;
+  v.w = a == 0 ? q0.w : a == 1 ? q1.x : a == 2 ? q1.y : q1.z;
+  return v;
+}
+
+// out[w pitch + i] = src[start + w hop + i].  One work item is one ALIGNED 16-byte chunk of the destination: chunk c of row w
+// holds the row's elements i = 4 c - d .. 4 c - d + 3, d = (out / 4 + w pitch) mod 4 the row's own misalignment (it changes
+// from row to row when pitch % 4 != 0).  A chunk wholly inside the row is one 16-byte store; the row's first and last chunk,
+// when the row's edge cuts them, store their 1 ... 3 elements one by one - the floats between the rows are never written,
+// and never read.  The source side is frames_kernel's: the aligned chunk pair and a shift, sample by sample where a chunk
+// is not wholly inside [0, n).
+__global__ __launch_bounds__(NT) void gather_kernel(GatherArgs a) {
+  const unsigned i0 = blockIdx.x * NT + threadIdx.x;      // < MAX_BLOCKS * NT
+  int64_t w = i0 / (unsigned)a.cpr;
+  unsigned c = i0 - (unsigned)w * (unsigned)a.cpr;
+  while (w < a.W) {
+    const unsigned d = (a.dmis + ((unsigned)w & 3u) * ((unsigned)a.pitch & 3u)) & 3u;
+    const int64_t i = 4 * (int64_t)c - d;                 // >= -3; the last chunks of a well-aligned row lie behind it
+    if (i < a.win) {
+      unsigned* o = a.out + w * a.pitch + i;
+      const bool live = w < a.live;
+      const int64_t s = live ? a.start + w * a.hop + i : 0;
+      if (i >= 0 && i + 4 <= a.win) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (live) {
+          const unsigned al = (unsigned)((int64_t)a.smis + s) & 3u;
+          const int64_t sA = s - al;
+          if (sA >= 0 && sA + (al ? 8 : 4) <= a.n) {
+            v = load4_bits(a.src, sA, al);
+          } else {
+            if (s >= 0 && s < a.n) v.x = a.src[s];
+            if (s + 1 >= 0 && s + 1 < a.n) v.y = a.src[s + 1];
+            if (s + 2 >= 0 && s + 2 < a.n) v.z = a.src[s + 2];
+            if (s + 3 >= 0 && s + 3 < a.n) v.w = a.src[s + 3];
+          }
+        }
+        *reinterpret_cast<uint4*>(o) = v;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (i + k >= 0 && i + k < a.win) o[k] = (live && s + k >= 0 && s + k < a.n) ? a.src[s + k] : 0u;
+      }
+    }
+    w += a.dw;
+    c += a.dc;
+    if (c >= (unsigned)a.cpr) {
+      c -= (unsigned)a.cpr;
+      ++w;
+    }
+  }
+}
+
 // P lanes per row (a power of two, 1 ... 64), NT / P rows per workgroup
 __global__ __launch_bounds__(NT) void smooth_kernel(const float* __restrict__ probs, int W, int NC, int A, int P, float* __restrict__ smoothed,
                                                      int* __restrict__ top, float* __restrict__ top_score) {
@@ -185,6 +259,42 @@ int kws_stream_frames_i16(const int16_t* src, int64_t n, int64_t start, int hop,
 int kws_stream_frames_f32(const float* src, int64_t n, int64_t start, int hop, int win, float scale, float* out, int W,
                           void* stream) {
   return frames_launch<float>(src, n, start, hop, win, scale, out, W, stream);
+}
+
+int kws_stream_gather_f32(const float* src, int64_t n, int64_t start, int64_t hop, int win, float* out, int64_t out_pitch, int W,
+                          void* stream) {
+  KWS_REQUIRE(out && (src || n == 0), "stream_gather: NULL pointer");
+  KWS_REQUIRE(win >= 1 && hop >= 1 && W >= 1 && out_pitch >= win, "stream_gather: win=%d (>= 1) hop=%lld (>= 1) W=%d (>= 1) out_pitch=%lld (>= win)",
+              win, (long long)hop, W, (long long)out_pitch);
+  KWS_REQUIRE(n >= 0 && n <= MAX_SAMPLES && start >= -MAX_SAMPLES && start <= MAX_SAMPLES, "stream_gather: n=%lld start=%lld",
+              (long long)n, (long long)start);
+  // (W - 1) out_pitch + win floats of output: more than 2^61 of them have no address
+  KWS_REQUIRE(W == 1 || out_pitch <= (MAX_SAMPLES - win) / (W - 1), "stream_gather: W=%d rows of pitch %lld exceed 2^61 floats", W,
+              (long long)out_pitch);
+  KWS_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)src & 3) == 0, "stream_gather: src and out must be aligned to their 4-byte elements");
+  hipStream_t st = (hipStream_t)stream;
+  GatherArgs a;
+  a.src = reinterpret_cast<const unsigned*>(src); a.out = reinterpret_cast<unsigned*>(out);
+  a.n = n; a.start = start; a.hop = hop; a.pitch = out_pitch; a.win = win; a.W = W;
+  // rows that start before n: w hop < n - start <= 2^62, whatever hop is
+  const int64_t ahead = n - start;
+  a.live = ahead <= 0 ? 0 : (ahead - 1) / hop + 1;
+  if (a.live > W) a.live = W;
+  a.cpr = (int)(((int64_t)win + 6) / 4);
+  a.smis = (unsigned)(((uintptr_t)src / 4) & 3);
+  a.dmis = (unsigned)(((uintptr_t)out / 4) & 3);
+  const int64_t items = (int64_t)W * a.cpr;
+  const int64_t blocks = ceil_div64(items, NT);
+  const unsigned grid = (unsigned)(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS);
+  const unsigned stride = grid * NT;
+  a.dw = stride / (unsigned)a.cpr;
+  a.dc = stride % (unsigned)a.cpr;
+  // every source float under the live rows once (overlaps are cache hits) + every row segment stored
+  const double span = a.live > 0 ? (double)(a.live - 1) * (double)hop + win : 0.0;
+  KwsProfScope prof("stream_gather", 0.0, 4.0 * ((span < (double)n ? span : (double)n) + (double)W * win), st);
+  hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(NT), 0, st, a);
+  KWS_LAUNCH_CHECK("gather_kernel");
+  return KWS_OK;
 }
 
 int kws_stream_smooth_f32(const float* probs, int W, int NC, int A, float* smoothed, int* top, float* top_score, void* stream) {

@@ -43,6 +43,24 @@ def path_b_tables(window_size, num_mel_bins, num_keep, sample_rate=16000, lower_
                 dct=np.ascontiguousarray(dct, dtype=F32), log_offset=1e-6, log_floor=0.0)
 
 
+def path_b_plan(model_settings):
+    """A kws_stft_plan (a ctypes handle the caller destroys with kws_stft_plan_destroy) for the path-B features of
+    model.prepare_model_settings' dict: n_mel = dct_coefficient_count bands, n_out = num_log_mel_features coefficients -
+    the plan of AudioProcessor and of stream.Features."""
+    import ctypes
+    from . import _lib
+    t = path_b_tables(model_settings['window_size_samples'], model_settings['dct_coefficient_count'],
+                      model_settings['num_log_mel_features'], model_settings['sample_rate'])
+    plan = ctypes.c_void_p()
+    _lib.check(_lib.load().kws_stft_plan_create(
+        model_settings['window_size_samples'], model_settings['window_stride_samples'], t['fft_length'],
+        model_settings['dct_coefficient_count'], model_settings['num_log_mel_features'],
+        t['window'].ctypes.data_as(ctypes.c_void_p), t['mel'].ctypes.data_as(ctypes.c_void_p),
+        t['dct'].ctypes.data_as(ctypes.c_void_p), t['log_offset'], t['log_floor'], ctypes.byref(plan)),
+        "kws_stft_plan_create")
+    return plan
+
+
 def path_a_tables(window_size=480, sample_rate=16000, dct_coefficient_count=40, filterbank_channel_count=40,
                   lower=20.0, upper=4000.0):
     fft_len = _pow2_at_least(window_size)

@@ -13,7 +13,6 @@ error behaviour; reference input_data.py:49-610) for the accelerated path:
 """
 from __future__ import absolute_import, division, print_function
 
-import ctypes
 import glob
 import hashlib
 import math
@@ -363,17 +362,10 @@ class AudioProcessor(object):
         self.background_clamp_ = _Fetch(self, 'raw')
         self.spectrogram_ = _Fetch(self, 'spec')
         self.mfcc_ = _Fetch(self, 'mfcc')
-        from .features import path_b_tables
-        t = path_b_tables(model_settings['window_size_samples'], model_settings['dct_coefficient_count'],
-                          model_settings['num_log_mel_features'], model_settings['sample_rate'])
+        from .features import path_b_plan
         self._n_mel = model_settings['dct_coefficient_count']
         self._n_out = model_settings['num_log_mel_features']
-        plan = ctypes.c_void_p()
-        _lib.check(self.lib.kws_stft_plan_create(
-            model_settings['window_size_samples'], model_settings['window_stride_samples'], t['fft_length'],
-            self._n_mel, self._n_out, t['window'].ctypes.data_as(ctypes.c_void_p),
-            t['mel'].ctypes.data_as(ctypes.c_void_p), t['dct'].ctypes.data_as(ctypes.c_void_p),
-            t['log_offset'], t['log_floor'], ctypes.byref(plan)), "kws_stft_plan_create")
+        plan = path_b_plan(model_settings)
         self._plan = plan
         self._n_frames = self.lib.kws_stft_num_frames(plan, model_settings['desired_samples'])
 

@@ -7,9 +7,17 @@ window in one launch (`smooth`), and a host-side state machine (`detect`: thresh
 two per-window tracks into detections.  `spot` is the whole chain, `spot_wav` the same from a wav file of any sample rate,
 `score` counts detections against a ground truth.
 
-Out of scope: sharing STFT frames between overlapping windows of the feature-input models (a `transform` runs on every
-window), data-parallel sharding of one recording, peak picking inside a run of eligible windows (the first eligible window
-fires), carrying convolution state from window to window."""
+The feature-input models ('mfcc', 'spec', 'mfcc_and_raw') take `spot(..., features=Features(model_settings))`: every chunk
+of windows is one signal to the STFT, and window w is frames w r .. w r + F - 1 of the chunk's feature track, cut out by
+kws_stream_gather_f32 (`Features.rows`) - a frame depends on its own samples only, so the rows are those of the per-window
+feature step (`Features.windows`) bit for bit.
+
+Out of scope: shared STFT frames for a hop that is no multiple of the frame step (`share_frames=False` computes every
+window's own) and across chunk seams (the F - r frames two neighbouring chunks have in common are computed by both: 96 of
+2144 at hop 320, batch 1024), data-parallel sharding of one recording, peak picking inside a run of eligible windows (the
+first eligible window fires), carrying convolution state from window to window."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -72,6 +80,162 @@ def frames(x, win, hop, start=0, first=0, count=None, scale=None, out=None):
     return out.reshape(-1)[:count * win].reshape(count, win)
 
 
+def gather(src, n, start, hop, win, out, out_pitch, count, out_offset=0):
+    """kws_stream_gather_f32 on device float32 tensors: out.flat[out_offset + w out_pitch + i] = src.flat[start + w hop + i]
+    for w < count, i < win, +0.0 where that index is outside [0, n); a copy of bits, nothing else of `out` is written."""
+    if not (src.is_cuda and out.is_cuda and src.dtype == torch.float32 and out.dtype == torch.float32
+            and src.is_contiguous() and out.is_contiguous()):
+        raise ValueError("gather: src and out must be contiguous float32 device tensors")
+    n, count, win, out_pitch, out_offset = int(n), int(count), int(win), int(out_pitch), int(out_offset)
+    if n > src.numel() or out_offset < 0 or (count >= 1 and out_offset + (count - 1) * out_pitch + win > out.numel()):
+        raise ValueError("gather: n=%d of %d source floats, rows up to %d of %d output floats" %
+                         (n, src.numel(), out_offset + (count - 1) * out_pitch + win, out.numel()))
+    with torch.cuda.device(out.device):
+        _lib.call("kws_stream_gather_f32", _lib.ptr(src) if n else None, n, int(start), int(hop), win,
+                  ctypes.c_void_p(out.data_ptr() + 4 * out_offset), out_pitch, count, _lib.stream_ptr())
+    return out
+
+
+def plan_rows(count, hop, win, frame_len, step):
+    """The chunk of `count` windows, `hop` apart, as ONE signal for the STFT (host only) -> (Lc, J, r): Lc samples =
+    (count - 1) hop + win rounded up to a multiple of 4, r = hop / step frames between two windows, J = (count - 1) r + F
+    frames of which window w takes w r .. w r + F - 1, F = 1 + (win - frame_len) // step.  Frame w r + k of the signal
+    starts at sample w hop + k step, where frame k of window w starts: the same frame_len samples."""
+    count, hop, win, frame_len, step = int(count), int(hop), int(win), int(frame_len), int(step)
+    if count < 1 or hop < 1 or step < 1 or frame_len < 1 or win < frame_len:
+        raise ValueError("plan_rows: count=%d hop=%d win=%d frame_len=%d step=%d" % (count, hop, win, frame_len, step))
+    if hop % step:
+        raise ValueError("plan_rows: hop=%d is not a multiple of the frame step=%d, so overlapping windows share no STFT "
+                         "frames (spot(..., share_frames=False) computes every window's own)" % (hop, step))
+    r = hop // step
+    F = 1 + (win - frame_len) // step
+    return -(-((count - 1) * hop + win) // 4) * 4, (count - 1) * r + F, r
+
+
+class Features(object):
+    """The feature step of the feature-input models for `spot`: the path-B STFT / mel / DCT features AudioProcessor feeds
+    them (the same plan: features.path_b_plan), per window (`windows`) or once per chunk on a track the overlapping windows
+    share (`rows`).  model_settings: model.prepare_model_settings' dict; the representation - 'mfcc', 'spec' or
+    'mfcc_and_raw' - is its 'output_representation' entry or the keyword (prepare_model_settings takes it and does not
+    return it).  win = desired_samples, frame_len / step = the framing, F frames per window of `width` values, row = the
+    model's input size: F width, and the window's win samples behind them for 'mfcc_and_raw'.
+    The plan and the reused chunk buffers belong to one stream at a time; close() frees the plan."""
+    OUT_KINDS = {'mfcc': 0, 'spec': 1, 'mfcc_and_raw': 0}        # kws_stft_mel_f32's out_kind, as AudioProcessor.get_data
+    _KEYS = ('desired_samples', 'window_size_samples', 'window_stride_samples', 'dct_coefficient_count',
+             'num_log_mel_features', 'sample_rate')
+
+    def __init__(self, model_settings, device=None, output_representation=None):
+        self._plan = None
+        rep = output_representation if output_representation is not None else model_settings.get('output_representation')
+        if rep is None:
+            raise ValueError("Features: model_settings has no 'output_representation' (one of %s)" % sorted(self.OUT_KINDS))
+        if rep not in self.OUT_KINDS:
+            raise ValueError("Features: output_representation=%r - the raw-waveform models take the windows themselves; "
+                             "one of %s" % (rep, sorted(self.OUT_KINDS)))
+        for k in self._KEYS:
+            if k not in model_settings:
+                raise ValueError("Features: model_settings has no %r" % k)
+        self.representation = rep
+        self.out_kind = self.OUT_KINDS[rep]
+        self.win = int(model_settings['desired_samples'])
+        self.frame_len = int(model_settings['window_size_samples'])
+        self.step = int(model_settings['window_stride_samples'])
+        self.width = 257 if rep == 'spec' else int(model_settings['num_log_mel_features'])
+        if self.step < 1 or self.win < self.frame_len or self.frame_len < 1:
+            raise ValueError("Features: a window of %d samples holds no frame of %d (step %d)" % (self.win, self.frame_len, self.step))
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.lib = _lib.load()
+        from .features import path_b_plan
+        with torch.cuda.device(self.device):
+            self._plan = path_b_plan(model_settings)
+        self.F = self.lib.kws_stft_num_frames(self._plan, self.win)
+        self.row = self.F * self.width + (self.win if rep == 'mfcc_and_raw' else 0)
+        self._P = self._track = None
+
+    def close(self):
+        if getattr(self, '_plan', None):
+            self.lib.kws_stft_plan_destroy(self._plan)
+            self._plan = None
+        self._P = self._track = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def kernel_code(self, L, x=None):
+        """kws_stft_mel_kernel: which kernel the feature launch over signals of L samples at x (default: a 16-byte aligned
+        buffer, as every buffer of this class is) answers to."""
+        return self.lib.kws_stft_mel_kernel(self._plan, _lib.ptr(x) if x is not None else ctypes.c_void_p(16), int(L), self.out_kind)
+
+    def _stft(self, x, B, L, out):
+        if self._plan is None:
+            raise _lib.KwsError("Features is closed: its STFT plan is gone")
+        _lib.call("kws_stft_mel_f32", self._plan, _lib.ptr(x), B, L, _lib.ptr(out), self.out_kind, _lib.stream_ptr())
+
+    def _out(self, out, count):
+        if out is None:
+            return torch.empty((count, self.row), dtype=torch.float32, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and out.numel() >= count * self.row):
+            raise ValueError("Features: out must be a contiguous float32 device tensor of at least count * row elements")
+        return out
+
+    def windows(self, chunk, out=None):
+        """The per-window definition: device float32 windows [count, win] -> model input [count, row] by one
+        kws_stft_mel_f32 over the count windows (what AudioProcessor feeds the model); for 'mfcc_and_raw' the features land
+        in a dense buffer and two gathers lay them and the window's samples into the composite rows."""
+        if not (torch.is_tensor(chunk) and chunk.is_cuda and chunk.dtype == torch.float32 and chunk.dim() == 2
+                and chunk.shape[1] == self.win):
+            raise ValueError("Features.windows: a float32 device tensor [count, %d] is needed" % self.win)
+        chunk = chunk.contiguous()
+        count, fw = chunk.shape[0], self.F * self.width
+        out = self._out(out, count)
+        with torch.cuda.device(self.device):
+            if self.row == fw:
+                self._stft(chunk, count, self.win, out)
+            else:
+                dense = torch.empty((count, fw), dtype=torch.float32, device=self.device)
+                self._stft(chunk, count, self.win, dense)
+                gather(dense, count * fw, 0, fw, fw, out, self.row, count)
+                gather(chunk, count * self.win, 0, self.win, self.win, out, self.row, count, out_offset=fw)
+        return out.reshape(-1)[:count * self.row].reshape(count, self.row)
+
+    def rows(self, x, hop, start, first, count, out=None):
+        """The shared path: the model input [count, row] of windows first .. first + count - 1 (window w starts at sample
+        start + w hop of the recording x; zeros outside it), bit for bit windows(frames(...)) of them, with every STFT frame
+        of the chunk computed once.  hop must be a multiple of the frame step.  The chunk's Lc samples (plan_rows) are
+        gathered as one window into a reused buffer (the per-window gather's own multiply and zero fill), one
+        kws_stft_mel_f32 turns them into a reused track [J', width], J' >= J, and kws_stream_gather_f32 cuts window w's F
+        frames out of it from frame w r on; for 'mfcc_and_raw' a second gather puts the window's samples behind them."""
+        hop, start, first, count = int(hop), int(start), int(first), int(count)
+        if hop % self.step:
+            raise ValueError("Features.rows: hop=%d is not a multiple of the frame step=%d, so overlapping windows share no "
+                             "STFT frames (share_frames=False computes every window's own)" % (hop, self.step))
+        if first < 0:
+            raise ValueError("Features.rows: first=%d count=%d" % (first, count))
+        Lc, J, r = plan_rows(count, hop, self.win, self.frame_len, self.step)
+        if Lc >= 1 << 31:
+            raise ValueError("Features.rows: a chunk of %d windows is %d samples, more than one STFT launch takes" % (count, Lc))
+        xd = _device_samples(x, self.device)
+        out = self._out(out, count)
+        with torch.cuda.device(self.device):
+            Jt = self.lib.kws_stft_num_frames(self._plan, Lc)       # >= J: the rounding of Lc may add a frame
+            if self._P is None or self._P.numel() < Lc:
+                self._P = torch.empty(Lc, dtype=torch.float32, device=self.device)
+            if self._track is None or self._track.numel() < Jt * self.width:
+                self._track = torch.empty(Jt * self.width, dtype=torch.float32, device=self.device)
+            P, track = self._P, self._track
+            frames(xd, Lc, Lc, start=start + first * hop, first=0, count=1, out=P)
+            self._stft(P, 1, Lc, track)
+            fw = self.F * self.width
+            gather(track, J * self.width, 0, r * self.width, fw, out, self.row, count)
+            if self.row != fw:
+                gather(P, Lc, 0, hop, self.win, out, self.row, count, out_offset=fw)
+        return out.reshape(-1)[:count * self.row].reshape(count, self.row)
+
+
 def smooth(probs, average_windows):
     """probs [W, NC] (float32; uploaded if on the host) -> (smoothed [W, NC] f32, top [W] int32, top_score [W] f32) as device
     tensors: the mean of the last min(w + 1, average_windows) rows, its lowest-index maximum and that maximum's value."""
@@ -132,15 +296,32 @@ class Spotted(object):
 
 
 def spot(model, audio, labels=None, hop=320, average_ms=500, threshold=0.7, suppression_ms=1000, minimum_count=3, ignore=(0, 1),
-         batch=1024, start=0, transform=None, sample_rate=16000, win=None):
+         batch=1024, start=0, transform=None, sample_rate=16000, win=None, features=None, share_frames=True):
     """Keywords in a recording.  audio: 1-D int16 or float32 samples at `sample_rate` (tensor or array; int16 is scaled by
     1 / 32768 like DecodeWav).  The windows (win = the net's input size; with `transform`, a callable from device windows
     [count, win] to model input [count, input_size] such as an AudioProcessor's feature step, `win` is given) are hop samples
     apart and go through the net in chunks of `batch` on one stream without a host synchronisation; the posteriors are averaged
     over A = max(1, average_ms sample_rate // (1000 hop)) windows.  ignore: class indices that never fire - by default
-    _silence_ and _unknown_, positions 0 and 1 of input_data.prepare_words_list.  See `detect` for the decision."""
+    _silence_ and _unknown_, positions 0 and 1 of input_data.prepare_words_list.  See `detect` for the decision.
+    features: a `Features` for a feature-input model (win = features.win).  With share_frames (the default; hop must be a
+    multiple of the frame step) every chunk is features.rows - each STFT frame of the chunk computed once - otherwise
+    features.windows runs on every window as a transform would; the posteriors are the same bit for bit."""
     net = model.net
-    if transform is None:
+    shared = False
+    if features is not None:
+        if transform is not None:
+            raise ValueError("spot: features and transform are two ways to say the same thing - pass one")
+        if features.row != net.input_size:
+            raise ValueError("spot: features.row=%d but the model takes rows of %d" % (features.row, net.input_size))
+        if win is not None and int(win) != features.win:
+            raise ValueError("spot: win=%d but features.win=%d" % (int(win), features.win))
+        win = features.win
+        shared = bool(share_frames)
+        if shared:
+            plan_rows(1, hop, features.win, features.frame_len, features.step)      # refuses a hop that shares no frames
+        else:
+            transform = features.windows
+    if transform is None and not shared:
         win = net.input_size if win is None else int(win)
         if win != net.input_size:
             raise ValueError("spot: win=%d but the model takes %d samples (pass a transform)" % (win, net.input_size))
@@ -154,10 +335,13 @@ def spot(model, audio, labels=None, hop=320, average_ms=500, threshold=0.7, supp
     with torch.cuda.device(net.device):
         xd = _device_samples(audio, net.device)
         W = plan_windows(xd.shape[0], win, hop, start)
-        buf = torch.empty((min(batch, W), win), dtype=torch.float32, device=net.device)
+        buf = torch.empty((min(batch, W), features.row if shared else win), dtype=torch.float32, device=net.device)
         probs = torch.empty((W, net.num_classes), dtype=torch.float32, device=net.device)
         for w0 in range(0, W, batch):
             w1 = min(w0 + batch, W)
+            if shared:
+                net.predict(features.rows(xd, hop, start, w0, w1 - w0, out=buf), out=probs[w0:w1])
+                continue
             chunk = frames(xd, win, hop, start=start, first=w0, count=w1 - w0, out=buf)
             if transform is not None:
                 chunk = transform(chunk)
