@@ -73,6 +73,10 @@ int kws_profiler_get(kws_profiler_t* p, int idx, char* name, int cap, double* ms
  * bank: [n_clips, L] resident clip bank (f32, or int16 PCM scaled by 1/32768 like DecodeWav).
  * noise: 1-D concatenation of the background recordings (input_data.py:274-309); noise_off are
  * absolute start samples (input_data.py:484-487); noise may be NULL when every bg_vol is 0.
+ * A noise sample whose index noise_off[b] + t lies outside [0, noise_len) reads as 0 (a slice that starts before the
+ * recording, runs off its end or misses it entirely is defined, and nothing outside noise[0, noise_len) is read).
+ * shift may be any int32 (taken mod L).  out [B, L] must be 16-byte aligned when L % 4 == 0 (its rows are then written
+ * with 16-byte stores; KWS_E_INVALID before any launch otherwise); any float alignment serves for other L.
  * ---------------------------------------------------------------------------------------- */
 int kws_augment_f32(const float* bank, int64_t n_clips, int L, const int32_t* clip_idx,
                     const float* fg_vol, const int32_t* shift, const float* noise,
@@ -114,7 +118,10 @@ int kws_sampler_draw(uint32_t* mt_key, int* mt_pos, const kws_sampler_set_t* can
 /* a17 TTA transforms, reference make_submission.py:125-134.
  * kind: 0 copy, 1 np.roll(X,-1500,axis=1), 2 1.2*X, 3 clip(1.1*X,-1,1), 4 0.9*X */
 int kws_tta_transform(const float* x, float* out, int B, int L, int kind, void* stream);
-/* mean of n_terms probability tensors / divisor, argmax; make_submission.py:137-146 */
+/* mean of n_terms probability tensors / divisor, argmax; make_submission.py:137-146.
+ * out_probs[b,c] = (((probs[0] + probs[1]) + probs[2]) + ...)[b,c] / divisor in float32, in that order (the bits of an f32
+ * NumPy evaluation); out_argmax[b] (may be NULL) is the FIRST index of the row's largest value, as np.argmax returns it.
+ * 1 <= n_terms <= 8, divisor != 0. */
 int kws_tta_combine(const float* const* probs, int n_terms, float divisor, float* out_probs,
                     int32_t* out_argmax, int B, int C, void* stream);
 
@@ -798,6 +805,9 @@ int kws_attn_gate_bwd_f32(const float* dy, const float* x, const float* u, const
  * a14  optimizers on one flat parameter buffer, reference model.py:834 (RMSprop(lr=1e-3)) and
  *      model.py:96,110 (SGD momentum); constants SURVEY D.5.  g_eff = grad*grad_scale + 2*l2[i]*p
  *      (l2[i] = per-element kernel_regularizer coefficient, 0 for BN/bias).
+ *      kws_rmsprop_step and kws_adam_step move four elements per 16-byte access: p, grad, acc / m / v and l2 must be
+ *      16-byte aligned (whole allocations are), any n; a misaligned pointer is KWS_E_INVALID before any launch.
+ *      kws_sgd_momentum_step and kws_l2_loss take any float-aligned pointers.
  * ---------------------------------------------------------------------------------------- */
 int kws_rmsprop_step(float* p, const float* grad, float* acc, const float* l2, int64_t n, float lr,
                      float rho, float eps, float grad_scale, void* stream);

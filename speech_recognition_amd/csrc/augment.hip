@@ -169,6 +169,9 @@ int launch_augment(const BankT* bank, int64_t n_clips, int L, const int32_t* cli
   KWS_REQUIRE(bank && clip_idx && fg_vol && shift && bg_vol && out, "augment: NULL pointer");
   KWS_REQUIRE(n_clips > 0 && L > 0 && B > 0, "augment: bad sizes n_clips=%lld L=%d B=%d", (long long)n_clips, L, B);
   KWS_REQUIRE(noise == nullptr || (noise_off != nullptr && noise_len > 0), "augment: noise given without offsets");
+  // rows of L % 4 == 0 floats are written with 16-byte stores
+  KWS_REQUIRE((L & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+              "augment: out must be 16-byte aligned when L %% 4 == 0 (L=%d)", L);
   const int L4 = ceil_div(L, 4);
   KwsProfScope prof("augment", 3.0 * B * L, (double)B * L * (sizeof(BankT) + 8.0), (hipStream_t)stream);
   // grid.y carries the clip and is capped at 65535: a whole partition at once (get_data(how_many=-1),

@@ -114,6 +114,12 @@ __global__ __launch_bounds__(1024) void l2_loss_kernel(const float* __restrict__
   if (threadIdx.x == 0) out[0] = (float)red[0];
 }
 
+// rmsprop_kernel and adam_kernel move four elements per 16-byte access
+inline bool aligned16(const void* a, const void* b, const void* c, const void* d, const void* e = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(e)) & 15) == 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -121,6 +127,7 @@ extern "C" {
 int kws_rmsprop_step(float* p, const float* grad, float* acc, const float* l2, int64_t n, float lr, float rho,
                      float eps, float grad_scale, void* stream) {
   KWS_REQUIRE(p && grad && acc && l2 && n > 0, "rmsprop: bad arguments");
+  KWS_REQUIRE(aligned16(p, grad, acc, l2), "rmsprop: p, grad, acc and l2 must be 16-byte aligned");
   const int64_t n4 = ceil_div64(n, 4);
   KwsProfScope prof("optimizer", 8.0 * n, 24.0 * n, (hipStream_t)stream);
   hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)ceil_div64(n4, 256)), dim3(256), 0, (hipStream_t)stream, p, grad,
@@ -142,6 +149,7 @@ int kws_sgd_momentum_step(float* p, const float* grad, float* vel, const float* 
 int kws_adam_step(float* p, const float* grad, float* m, float* v, const float* l2, int64_t n, float lr_t, float beta1,
                   float beta2, float eps, float grad_scale, void* stream) {
   KWS_REQUIRE(p && grad && m && v && l2 && n > 0 && m != v, "adam: bad arguments");
+  KWS_REQUIRE(aligned16(p, grad, m, v, l2), "adam: p, grad, m, v and l2 must be 16-byte aligned");
   const int64_t n4 = ceil_div64(n, 4);
   KwsProfScope prof("optimizer", 12.0 * n, 32.0 * n, (hipStream_t)stream);
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ceil_div64(n4, 256)), dim3(256), 0, (hipStream_t)stream, p, grad, m, v,
